@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- Lambda-solve throughput of the MI355X path on a Venice-871-shaped synthetic BA.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload venice871] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload venice871] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value, unit, ms_per_step, ...).
+--dump-outputs DIR writes what the last timed step computed (the solution dx of the Lambda-solve) as DIR/dx.npy.
+--full adds everything else below (profiled phase pass, GN loops, roofline and microbenchmarks, drop-in timing,
+CPU baseline, the weak-scaling extra of N > 1), each of them measured in passes of its own after the timed steps.
 
 One "step" = one numeric Lambda-solve of the hot path (reference: CNonlinearSolver_Lambda::Optimize's
 linear solve, include/slam/NonlinearSolver_Lambda.h:605-626, through CLinearSolver_Schur
@@ -25,8 +30,8 @@ sums it, every rank factors S and back-substitutes its own landmarks. All of it 
     cameras -- one bundle adjustment with N x 530 304 landmarks, per-GPU work fixed. --scaling weak makes
     that variant the headline instead (labelled so).
 
-Extra fields: gn_iters_per_s (assembly + solve = one Gauss-Newton/LM iteration of device work),
-phase_ms, analyze_s, roofline (dominant kernel = MFMA f64 trailing update of the dense factor),
+Extra fields (--full): gn_iters_per_s (assembly + solve = one Gauss-Newton/LM iteration of device work),
+phase_ms, roofline (dominant kernel = MFMA f64 trailing update of the dense factor),
 cpu_baseline (the REFERENCE's own solvers compiled from /root/reference into oracle/_ref, timed on this box's
 host cores: headline = its fastest path on the same Lambda (CLinearSolver_Schur + dense LLT for BA), `cholmod` =
 north_star's CLinearSolver_CholMod on a bounded sample), dropin_ms (the host-pointer entry of the boundary).
@@ -45,6 +50,22 @@ import numpy as np  # noqa: E402
 METRIC = "Λ-solve block-nnz/sec + batch GN iters/sec, Venice BA, 1→8 MI355X"
 PEAK_FP64_MFMA_TFLOPS = 78.6   # MI355X fp64 matrix peak (vendor datasheet; MI355X_MICROARCH.md lists no fp64 row)
 PEAK_HBM_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (6.3 TB/s achievable)
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays {name: float64 vector} -> out_dir/<name>.npy. Beyond DUMP_LIMIT_BYTES in all, every array is cut to the same
+    fixed, seeded sample of its entries (sorted indices, written beside it as <name>_index.npy in float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, a.size * (DUMP_LIMIT_BYTES // 2) // total)   # half the budget for the values, half for the indices
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def main():
@@ -53,6 +74,12 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="venice871")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and report everything beyond the headline: phase times, GN loops, roofline, drop-in "
+                         "timing, CPU baseline (the --cpu-* options), weak-scaling extra")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the solution of the last timed Lambda-solve as DIR/dx.npy (float64; a fixed seeded sample "
+                         "with DIR/dx_index.npy beyond 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-solves", type=int, default=2)
     ap.add_argument("--cpu-backend", default="auto", choices=["auto", "schur", "cholmod", "csparse", "uberblock"],
@@ -218,7 +245,50 @@ def main():
     # ---- timed region: exactly K Lambda-solves, profiling instrumentation OFF (the hipEvents around
     # the phases and around every trailing-update launch cost a barrier packet each)
     dt = job.timed(args.steps, args.warmup, "step")
-    # ---- separate profiled pass: phase breakdown and the hipEvent-timed dominant kernel (last solve)
+    x_solve = d_rhs.download()   # what the timed path hands its caller: the solution dx of the last timed Lambda-solve
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"dx": x_solve})
+
+    total_nnzb = nnzb * world if weak else nnzb
+    mode_name = {api.MODE_SCHUR: "schur+dense", api.MODE_SCHUR_SPARSE: "schur+sparse reduced system",
+                 api.MODE_SPARSE: "sparse multifrontal"}[mode]
+
+    def headline(parallelism):
+        """the result line's fields that a plain run measures"""
+        return {
+            "metric": METRIC, "value": total_nnzb * args.steps / dt, "unit": "block-nnz/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
+            "higher_is_better": True, "scaling": "weak" if weak else "strong", "vs_baseline": None, "dtype": "f64",
+            "data": "graph file" if args.graph else "synthetic",
+            "config": {"workload": graph_note if graph_note else ("%s-shaped synthetic BA (%d cams, %d points, %d observations, LM-damped)" % (
+                args.workload, prob.get("nc", 0), prob.get("npts", 0), prob.v0.size) if "nc" in prob else args.workload),
+                "nnzb": int(nnzb), "n": int(st.n), "mode": mode_name,
+                "n_reduced": int(ctx.info("N_REDUCED")), "schur_pairs": int(ctx.info("SCHUR_PAIRS")),
+                "parallelism": parallelism},
+            "analyze_s": round(analyze_s, 3), "generate_s": round(gen_s, 2), "solution_norm": float(np.linalg.norm(x_solve)),
+        }
+
+    if not args.full:
+        if rank == 0:
+            parallelism = "single GPU"
+            if world > 1 and schur:
+                parallelism = ("%s: landmark shards x%d + one RCCL all-reduce of the packed reduced camera system (%.0f MB) on the "
+                               "ctx stream; the split into replicated and sharded work is reported by --full" % (
+                                   "weak (871 cameras, 530304 landmarks per GPU)" if weak else "strong (the one Venice problem)",
+                                   world, 8e-6 * ctx.schur_packed_size()))
+            elif world > 1:
+                parallelism = "replicas only: a pose graph of this size does not shard (DESIGN.md 6); every rank solves the same problem"
+            out = headline(parallelism)
+            if world == 1:
+                out["scaling_note"] = "one GPU: the whole problem (strong and weak coincide)"
+            if world > 1 and job.S is not None:
+                out["config"]["collective"] = " / ".join([job.xch.mode] + job.xch.notes)
+            print(json.dumps(out))
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: separate profiled pass: phase breakdown and the hipEvent-timed dominant kernel (last solve)
     ctx.set_profiling(True)
     for _ in range(3):
         solve()
@@ -226,8 +296,6 @@ def main():
     phase = ctx.phase_ms()
     dom_ms, dom_n, dom_flops = ctx.dominant_kernel()
     ctx.set_profiling(False)
-
-    x_solve = d_rhs.download()   # solution of the timed Lambda-solves (the later loops reuse the buffers)
 
     # ---- second loop: full GN iteration of device work (assembly + eta + solve)
     gn_steps = max(3, args.steps // 2)
@@ -381,9 +449,6 @@ def main():
         return
 
     x = x_solve
-    total_nnzb = nnzb * world if weak else nnzb
-    mode_name = {api.MODE_SCHUR: "schur+dense", api.MODE_SCHUR_SPARSE: "schur+sparse reduced system",
-                 api.MODE_SPARSE: "sparse multifrontal"}[mode]
     parallelism = "single GPU"
     if world > 1 and schur:
         rep = phase["factor"] + phase["trisolve"]                      # replicated on every rank
@@ -396,21 +461,12 @@ def main():
                            (rep + shard * world) / max(rep, 1e-9)))
     elif world > 1:
         parallelism = "replicas only: a pose graph of this size does not shard (DESIGN.md 6); every rank solves the same problem"
-    out = {
-        "metric": METRIC, "value": total_nnzb * args.steps / dt, "unit": "block-nnz/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
-        "higher_is_better": True, "scaling": "weak" if weak else "strong", "vs_baseline": None, "dtype": "f64",
-        "data": "graph file" if args.graph else "synthetic",
-        "config": {"workload": graph_note if graph_note else ("%s-shaped synthetic BA (%d cams, %d points, %d observations, LM-damped)" % (
-            args.workload, prob.get("nc", 0), prob.get("npts", 0), prob.v0.size) if "nc" in prob else args.workload),
-            "nnzb": int(nnzb), "n": int(st.n), "mode": mode_name,
-            "n_reduced": int(ctx.info("N_REDUCED")), "schur_pairs": int(ctx.info("SCHUR_PAIRS")),
-            "parallelism": parallelism},
+    out = headline(parallelism)
+    out.update({
         "gn_iters_per_s": gn_steps / dt_gn, "ms_per_gn_iter": 1e3 * dt_gn / gn_steps, "assemble_ms": assemble_ms,
         "phase_ms": {k: round(v, 4) for k, v in phase.items()},
-        "phase_ms_note": "separate pass with SPP_FLAG_PROFILE on (hipEvents per phase and per trailing-update launch); ms_per_step is timed with profiling off", "analyze_s": round(analyze_s, 3),
-        "generate_s": round(gen_s, 2), "solution_norm": float(np.linalg.norm(x)),
-    }
+        "phase_ms_note": "separate pass with SPP_FLAG_PROFILE on (hipEvents per phase and per trailing-update launch); ms_per_step is timed with profiling off",
+    })
     if world == 1:
         out["scaling_note"] = "one GPU: the whole problem (strong and weak coincide)"
     if schur:
