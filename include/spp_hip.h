@@ -303,6 +303,15 @@ int spp_dense_posv(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, double *d_b
 /* C (m x n, ldc) -= A^T B with A: k x m (lda), B: k x n (ldb): the MFMA trailing-update kernel */
 int spp_dense_gemm_tn_sub(spp_ctx *ctx, int64_t m, int64_t n, int64_t k,
 	const double *d_A, int64_t lda, const double *d_B, int64_t ldb, double *d_C, int64_t ldc);
+/* the same update as the factorization makes it: only the 128 x 128 tiles of C that reach the diagonal or lie above it
+ * are written (whole: their entries below the diagonal may change); tiles below them and rows >= m keep what they held */
+int spp_dense_gemm_tn_sub_upper(spp_ctx *ctx, int64_t m, int64_t n, int64_t k,
+	const double *d_A, int64_t lda, const double *d_B, int64_t ldb, double *d_C, int64_t ldc);
+/* the partial factorization of a big front of the sparse path: F (h x h, ld, upper triangle read) is laid out with
+ * pad = roundup(w, 128) - w identity rows / columns after its w pivots, as the sparse path lays out a front, and factored by
+ * the same call: R11, R12 and the contribution block S = A22 - R12^T R12 (upper triangle) come back in F. d_image (may be
+ * NULL) receives the padded image, hp = h + pad columns of (hp + 1) & ~1 doubles. SPP_NOT_POSDEF: a pivot of A11 failed. */
+int spp_dense_front_factor(spp_ctx *ctx, double *d_F, int64_t ld, int64_t w, int64_t h, double *d_image);
 
 const char *spp_version(void);
 

@@ -34,7 +34,7 @@ EXPORTS = [
     "spp_device_free", "spp_memcpy_h2d", "spp_memcpy_d2h", "spp_memcpy_d2d", "spp_get_phase_ms", "spp_get_dominant_kernel",
     "spp_microbench_copy", "spp_microbench_mfma_f64", "spp_microbench_ctile", "spp_microbench_update", "spp_block_ordering", "spp_schur_plan_host", "spp_set_profiling", "spp_se2_linearize_device", "spp_se2_update_device", "spp_ba_linearize_device", "spp_ba_update_device", "spp_se3_linearize_device", "spp_se3_update_device", "spp_edge_chi2_device", "spp_edge_robust_weights_device", "spp_edge_hessian_maxdiag_device",
     "spp_lm_gain_denominator_device", "spp_dense_potrf_upper", "spp_dense_posv",
-    "spp_dense_gemm_tn_sub", "spp_version",
+    "spp_dense_gemm_tn_sub", "spp_dense_gemm_tn_sub_upper", "spp_dense_front_factor", "spp_version",
 ]
 
 _lib = None
@@ -107,6 +107,8 @@ def load_library():
         "spp_dense_potrf_upper": (cint, [vp, vp, i64, i64]),
         "spp_dense_posv": (cint, [vp, vp, i64, i64, vp]),
         "spp_dense_gemm_tn_sub": (cint, [vp, i64, i64, i64, vp, i64, vp, i64, vp, i64]),
+        "spp_dense_gemm_tn_sub_upper": (cint, [vp, i64, i64, i64, vp, i64, vp, i64, vp, i64]),
+        "spp_dense_front_factor": (cint, [vp, vp, i64, i64, i64, vp]),
         "spp_version": (ctypes.c_char_p, []),
     }
     for name, (res, args) in sig.items():

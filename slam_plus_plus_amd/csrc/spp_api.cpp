@@ -373,7 +373,7 @@ int spp_get_info(const spp_ctx *ctx, int what, int64_t *out)
 {
 	if(!ctx || !out)
 		return SPP_E_BADARG;
-	if(ctx->mode < 0 && what != SPP_INFO_NNZB && what != SPP_INFO_NVALS && what != SPP_INFO_N)
+	if(ctx->mode < 0 && what != SPP_INFO_NNZB && what != SPP_INFO_NVALS && what != SPP_INFO_N && what != SPP_INFO_DENSE_STREAMED)
 		return SPP_E_STATE;
 	switch(what) {
 	case SPP_INFO_MODE: *out = (ctx->mode != SPP_MODE_SCHUR) ? ctx->mode : ctx->schur.mis ? SPP_MODE_SCHUR_MIS :
@@ -971,6 +971,30 @@ int spp_dense_gemm_tn_sub(spp_ctx *ctx, int64_t m, int64_t n, int64_t k, const d
 	dense_gemm_tn_sub(ctx, m, n, k, d_A, lda, d_B, ldb, d_C, ldc, false);
 	SPP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
 	return SPP_OK;
+	SPP_CATCH(ctx)
+}
+
+int spp_dense_gemm_tn_sub_upper(spp_ctx *ctx, int64_t m, int64_t n, int64_t k, const double *d_A, int64_t lda,
+	const double *d_B, int64_t ldb, double *d_C, int64_t ldc)
+{
+	if(!ctx || !d_A || !d_B || !d_C)
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	SPP_REQUIRE((lda % 2) == 0 && (ldb % 2) == 0, SPP_E_BADARG, "gemm_tn_sub: lda/ldb must be even (16-byte loads)");
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	dense_gemm_tn_sub(ctx, m, n, k, d_A, lda, d_B, ldb, d_C, ldc, true);
+	SPP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+	return SPP_OK;
+	SPP_CATCH(ctx)
+}
+
+int spp_dense_front_factor(spp_ctx *ctx, double *d_F, int64_t ld, int64_t w, int64_t h, double *d_image)
+{
+	if(!ctx || !d_F)
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	return dense_front_factor(ctx, d_F, ld, w, h, d_image);
 	SPP_CATCH(ctx)
 }
 

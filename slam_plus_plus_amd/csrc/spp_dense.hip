@@ -1146,7 +1146,8 @@ void dense_set_padding(spp_ctx *ctx, double *d_A, int64_t ld, int64_t n)
 // host drivers
 // --------------------------------------------------------------------------------------------------
 // info[0]: first failing pivot + 1, info[1]: timeout of the backward-substitution chain, info[2]: abort flag of
-// the device-flag hand-offs (stays set until the host has seen it), info[3]: abort flag of the sparse path's
+// the device-flag hand-offs and the streamed launch (stays set until the host has seen it; TAIL_ABORT_TIMEOUT: a wait of
+// the streamed launch gave up), info[3]: abort flag of the sparse path's
 // dependency-driven launches -- zeroed once, when the buffer is created
 static void ensure_info(spp_ctx *ctx)
 {
@@ -1543,7 +1544,7 @@ static int dense_tail_rows()
 // the streamed tail only takes over a full factorization (every tile row a pivot block, no identity-padded pivots)
 static bool dense_tail_applies(spp_ctx *ctx, int64_t rows, int64_t nsteps)
 {
-	return nsteps * NB >= rows && !(ctx->dense.ident_from >= 0 && ctx->dense.ident_from < rows);
+	return !ctx->dense.tail_disabled && nsteps * NB >= rows && !(ctx->dense.ident_from >= 0 && ctx->dense.ident_from < rows);
 }
 
 // The streamed tail (spp_dense_tail.h): everything behind row panel k -- the update of step k, then steps k + 1 .. --
@@ -1558,7 +1559,7 @@ static bool launch_dense_tail(spp_ctx *ctx, double *d_A, int64_t ld, int64_t row
 	}
 	DenseWork &dw = ctx->dense;
 	const int64_t c1 = (k + 1) * NB; // (k = -1: the whole factorization, no row panel in front of it)
-	if(!enabled || k + 1 >= nsteps || nsteps * NB < rows || (dw.ident_from >= 0 && dw.ident_from < rows))
+	if(!enabled || dw.tail_disabled || k + 1 >= nsteps || nsteps * NB < rows || (dw.ident_from >= 0 && dw.ident_from < rows))
 		return false;
 	const int Tr = (int)(nsteps - (k + 1)), Tc = (int)((ncols - c1 + NB - 1) / NB);
 	if(Tr < 1 || Tc < Tr || Tc > Tr + 1)
@@ -1604,7 +1605,8 @@ static bool launch_dense_tail(spp_ctx *ctx, double *d_A, int64_t ld, int64_t row
 			for(int j = i; j < Tc; ++ j)
 				key.push_back(std::make_pair((double)i + beta * (double)j, (i << 16) | j));
 		std::stable_sort(key.begin(), key.end(), [](const std::pair<double, int> &x, const std::pair<double, int> &y) { return x.first < y.first; });
-		std::vector<int> order(key.size());
+		std::vector<int> &order = dw.tail_order_host; // (the asynchronous upload reads it after this call returns)
+		order.resize(key.size());
 		for(size_t q = 0; q < key.size(); ++ q)
 			order[q] = key[q].second;
 		dw.tail_order.upload(order, s);
@@ -1628,7 +1630,12 @@ static bool launch_dense_tail(spp_ctx *ctx, double *d_A, int64_t ld, int64_t row
 	a.epoch = dw.tail_epoch;
 	a.info = dw.info.p;
 	a.abort = dw.info.p + 2;
-	a.timeout_ticks = (long long)(500.0 * 1e5);
+	static long long tail_timeout = -1;
+	if(tail_timeout < 0) {
+		const char *e = getenv("SPP_TAIL_TIMEOUT_TICKS"); // tests: a tiny value forces the timeout and the per-step fallback
+		tail_timeout = e ? atoll(e) : (long long)(500.0 * 1e5); // 500 ms of the 100 MHz wall clock
+	}
+	a.timeout_ticks = tail_timeout;
 	static int trace_env = -1;
 	if(trace_env < 0) {
 		const char *e = getenv("SPP_TAIL_TRACE"); // n: the n-th launch prints per tile row when its diagonal tile had all updates, was factored, and when the first panel tile started / ended
@@ -1957,6 +1964,13 @@ int dense_info_fetch(spp_ctx *ctx, bool *dag_aborted)
 		SPP_HIP_CHECK(hipMemset(ctx->dense.info.p + 2, 0, sizeof(int)));
 		return h_info[0];
 	}
+	if(h_info[2] == TAIL_ABORT_TIMEOUT) { // a wait of the streamed launch gave up: the result is garbage, streamed launches stay off
+		SPP_HIP_CHECK(hipMemset(ctx->dense.info.p + 2, 0, sizeof(int)));
+		ctx->dense.tail_disabled = true;
+		ctx->dense.fuse_dirty = true; // (a per-step schedule in front of the launch may have left its counters behind too)
+		throw Error(SPP_E_HIP, "dense factorization: the streamed launch (spp_dense_tail.h) timed out waiting for a tile; "
+			"the following calls use the per-step schedule");
+	}
 	if(h_info[2]) { // a cross-stream flag wait timed out: the result is garbage, the flag hand-offs stay off
 		SPP_HIP_CHECK(hipMemset(ctx->dense.info.p + 2, 0, sizeof(int)));
 		ctx->dense.sync_state = -1;
@@ -1983,6 +1997,57 @@ int dense_potrf_upper(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, bool /*k
 	dense_info_reset(ctx);
 	dense_factor_steps(ctx, d_A, ld, n, n, n + 1, (n + NB - 1) / NB, true);
 	return dense_info_fetch(ctx) ? SPP_NOT_POSDEF : SPP_OK;
+}
+
+// An h x h front (unpadded, leading dimension ld) <-> its image in the layout of the sparse path's big fronts
+// (spp_sparse.hip, bigfront_assemble_kernel): `pad` identity rows / columns inserted after the w pivots, leading dimension
+// ldp. One workgroup per column of the image. To the image: the upper triangle, zeros below it; back: every entry.
+__global__ __launch_bounds__(256)
+void front_image_kernel(double *F, int64_t ld, double *P, int64_t ldp, int w, int pad, int h, int to_image)
+{
+	const int c = (int)blockIdx.x, hp = h + pad;
+	const bool cpad = c >= w && c < w + pad;
+	const int cu = c < w ? c : c - pad;
+	for(int r = threadIdx.x; r < hp; r += 256) {
+		const bool rpad = r >= w && r < w + pad;
+		const int ru = r < w ? r : r - pad;
+		if(to_image)
+			P[r + (int64_t)c * ldp] = (cpad || rpad) ? (r == c ? 1.0 : 0.0) : (r <= c ? F[ru + (int64_t)cu * ld] : 0.0);
+		else if(!cpad && !rpad)
+			F[ru + (int64_t)cu * ld] = P[r + (int64_t)c * ldp];
+	}
+}
+
+int dense_front_factor(spp_ctx *ctx, double *d_F, int64_t ld, int64_t w, int64_t h, double *d_image)
+{
+	SPP_REQUIRE(w > 0 && h >= w && ld >= h && h < (1 << 20), SPP_E_BADARG, "front factor: need 0 < w <= h <= ld");
+	hipStream_t s = ctx->stream;
+	const int64_t pad = ((w + NB - 1) / NB) * NB - w, hp = h + pad, ldp = (hp + 1) & ~int64_t(1);
+	// (the image is followed by a band of sentinels: a write past the front's last column would change them)
+	const size_t img = (size_t)ldp * hp, band = (size_t)ldp * NB;
+	DevBuf<double> P;
+	P.reserve(img + band);
+	SPP_HIP_CHECK(hipMemsetAsync(P.p + img, 0xff, band * sizeof(double), s));
+	hipLaunchKernelGGL(front_image_kernel, dim3((unsigned)hp), dim3(256), 0, s, d_F, ld, P.p, ldp, (int)w, (int)pad, (int)h, 1);
+	dense_info_reset(ctx);
+	{
+		struct IdentGuard { // as the sparse path: pivots [w, w + pad) are identity padding
+			DenseWork &d;
+			IdentGuard(DenseWork &dw, int64_t from) : d(dw) { d.ident_from = from; }
+			~IdentGuard() { d.ident_from = -1; }
+		} guard(ctx->dense, w);
+		dense_factor_steps(ctx, P.p, ldp, w + pad, hp, hp, (w + pad) / NB, false);
+	}
+	const int info = dense_info_fetch(ctx);
+	hipLaunchKernelGGL(front_image_kernel, dim3((unsigned)hp), dim3(256), 0, s, d_F, ld, P.p, ldp, (int)w, (int)pad, (int)h, 0);
+	if(d_image)
+		SPP_HIP_CHECK(hipMemcpyAsync(d_image, P.p, (size_t)hp * ldp * sizeof(double), hipMemcpyDeviceToDevice, s));
+	std::vector<unsigned long long> hb(band);
+	SPP_HIP_CHECK(hipMemcpyAsync(hb.data(), P.p + img, band * sizeof(double), hipMemcpyDeviceToHost, s));
+	SPP_HIP_CHECK(hipStreamSynchronize(s));
+	for(size_t q = 0; q < band; ++ q)
+		SPP_REQUIRE(hb[q] == ~0ull, SPP_E_HIP, "front factor: a write past the end of the front's image");
+	return info ? SPP_NOT_POSDEF : SPP_OK;
 }
 
 // back substitution R x = y with y in d_b (n entries); uses the block inverses of the last potrf.
@@ -2020,8 +2085,9 @@ void dense_potrs_upper(spp_ctx *ctx, const double *d_R, int64_t n, int64_t ld, d
 			*dw.h_chain_err = 0;
 		}
 		++ dw.epoch;
-		// the check constant of this solve: odd multiples of a 64-bit odd constant are distinct and non-zero for 2^63 solves
-		const unsigned long long K = (2ull * (unsigned long long)(unsigned)dw.epoch + 1ull) * 0x9E3779B97F4A7C15ull;
+		// the check constant of this solve: odd multiples of a 64-bit odd constant are distinct and non-zero modulo 2^64, so
+		// K repeats only after 2^63 solves (epoch is 64-bit)
+		const unsigned long long K = (2ull * (unsigned long long)dw.epoch + 1ull) * 0x9E3779B97F4A7C15ull;
 		TrsvPay *xpay = (TrsvPay*)dw.trsv_pay.p, *wpay = xpay + (size_t)nblk * NB;
 		static int mform = -1;
 		if(mform < 0) {
@@ -2058,7 +2124,7 @@ void dense_potrs_upper(spp_ctx *ctx, const double *d_R, int64_t n, int64_t ld, d
 		}
 		++ dw.epoch;
 		hipLaunchKernelGGL(trsv_back_chain_kernel, dim3((unsigned)nblk), dim3(256), 0, s, d_R, ld, n, (int)nblk,
-			dw.tinv_all.p, d_b, dw.xtmp.p, dw.flags.p, dw.epoch, dw.info.p + 1);
+			dw.tinv_all.p, d_b, dw.xtmp.p, dw.flags.p, (int)dw.epoch, dw.info.p + 1);
 		SPP_HIP_CHECK(hipGetLastError());
 		SPP_HIP_CHECK(hipMemcpyAsync(d_b, dw.xtmp.p, n * sizeof(double), hipMemcpyDeviceToDevice, s));
 		// the timeout flag travels to pinned host memory; dense_chain_check() looks at it after the

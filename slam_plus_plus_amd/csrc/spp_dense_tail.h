@@ -40,11 +40,15 @@ struct TailArgs {
 	double *dbuf;        // [Tr][8][256]: inverse 16 x 16 diagonal tiles as they are published
 	int *pub;            // [Tr][Tc]: (epoch << 4) | row tiles published
 	int epoch;
-	int *info, *abort;
+	int *info, *abort;   // abort word: 1 = a diagonal block is not positive definite (info[0] says which), TAIL_ABORT_TIMEOUT = a wait gave up
 	long long timeout_ticks;
 	long long *trace;    // debugging (SPP_TAIL_TRACE): per tile row 8 wall-clock stamps
 	const int *order;    // workgroup -> tile (i << 16 | j), a topological order of the tiles (see the host side)
 };
+
+// the value a timed-out wait of the streamed launch leaves in the abort word (the host tells it from the other raisers:
+// a non-positive pivot, a cross-stream flag wait of the per-step schedule in front of it, both store 1)
+constexpr int TAIL_ABORT_TIMEOUT = 2;
 
 constexpr int TAIL_LDS_DOUBLES = POTRF_LDS_DOUBLES_INV2 + 16;
 
@@ -126,7 +130,7 @@ void dense_tail_kernel(const TailArgs a)
 				if(__hip_atomic_load(a.abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
 					break;
 				if(wall_clock64() - t0 > a.timeout_ticks) {
-					__hip_atomic_store(a.abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+					__hip_atomic_store(a.abort, TAIL_ABORT_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 					break;
 				}
 				__builtin_amdgcn_s_sleep(1);

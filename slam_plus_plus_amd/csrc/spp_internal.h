@@ -280,11 +280,13 @@ struct DenseWork {
 	DevBuf<double> tail_dinv;      // ... and the inverse 16 x 16 diagonal tiles it publishes
 	int tail_epoch = 0;
 	DevBuf<int> tail_order;        // workgroup -> tile of the streamed launch, for tail_order_tr x tail_order_tc tiles
+	std::vector<int> tail_order_host; // its host image (the upload is asynchronous: it lives as long as the table)
 	int tail_order_tr = 0, tail_order_tc = 0;
 	int tail_rows_last = 0;        // tile rows the last factorization streamed (diagnostics: SPP_INFO_DENSE_STREAMED)
+	bool tail_disabled = false;    // a streamed launch timed out on this ctx: later factorizations take the per-step schedule
 	DevBuf<double> trsv_m;         // M_b = Tinv_b R_{b, b+1} per block row (M form of the backward substitution)
 	DevBuf<double> trsv_pay;       // hand-over pairs {value, check word} of the one-workgroup chain: x (nblk x 128) and w (nblk x 128)
-	int epoch = 0;
+	uint64_t epoch = 0;            // solves so far (backward-substitution chains tell one solve from the next by it)
 	int *h_chain_err = nullptr;
 	hipStream_t aux = nullptr;     // lookahead stream: potrf_diag + trsm of the next panel
 	hipEvent_t ev[2] = {nullptr, nullptr};
@@ -410,6 +412,10 @@ void dense_reserve(spp_ctx *ctx, int64_t nblk); // workspaces for nblk diagonal 
 
 void dense_chain_check(spp_ctx *ctx); // call after the stream was synchronized
 void dense_set_padding(spp_ctx *ctx, double *d_A, int64_t ld, int64_t n);
+// unit tests: the partial factorization of a big sparse front, laid out (identity padding after the w pivots) and
+// factored as the sparse path does; d_F (h x h, ld) <- the result in the unpadded layout, d_image (optional, ldp x hp with
+// ldp = (hp + 1) & ~1, hp = h + pad) <- the padded image
+int dense_front_factor(spp_ctx *ctx, double *d_F, int64_t ld, int64_t w, int64_t h, double *d_image);
 bool dense_gemm_tn_sub(spp_ctx *ctx, int64_t m, int64_t n, int64_t k, const double *A, int64_t lda,
 	const double *B, int64_t ldb, double *C, int64_t ldc, bool upper_only);
 double microbench_copy(spp_ctx *ctx, size_t bytes, int iters);
