@@ -134,7 +134,8 @@ int spp_block_ordering(int64_t nb, const int64_t *col_ptr, const int64_t *row_id
  * observation lists, the block pattern of S and its per-block lists of block products. Runs on up to 16 host threads
  * (SPP_PLAN_THREADS); the result does not depend on their number. out[0..7] = poses, landmarks of this shard,
  * observations, block products, blocks of S, work items, split blocks, a 64-bit checksum of the lists; *seconds = wall
- * clock of the plan. For tests and for timing the analysis phase without a device. */
+ * clock of the plan. sparse_S: bit 0 = sparse reduced system, bit 1 = the MIS cut of SPP_MODE_SCHUR_MIS (one block
+ * width; its reduced system is always sparse). For tests and for timing the analysis phase without a device. */
 int spp_schur_plan_host(int64_t nb, const int32_t *dim, const int64_t *col_ptr, const int64_t *row_idx, int shard_rank,
 	int shard_world, int sparse_S, int64_t *out, double *seconds);
 

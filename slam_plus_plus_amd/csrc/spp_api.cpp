@@ -461,7 +461,7 @@ int spp_schur_plan_host(int64_t nb, const int32_t *dim, const int64_t *col_ptr, 
 				off += (int64_t)dim[row_idx[p]] * dim[j];
 			}
 		st.nvals = off;
-		const double sec = schur_plan_host_probe(st, shard_rank, shard_world, sparse_S != 0, out);
+		const double sec = schur_plan_host_probe(st, shard_rank, shard_world, (sparse_S & 1) != 0, (sparse_S & 2) != 0, out);
 		if(seconds)
 			*seconds = sec;
 		return SPP_OK;

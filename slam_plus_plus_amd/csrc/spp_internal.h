@@ -384,7 +384,7 @@ void nested_dissection_order(int64_t nb, const int64_t *col_ptr, const int64_t *
 void build_schur_plan(spp_ctx *ctx, bool sparse_S, bool mis = false);
 int64_t schur_buffer_doubles(const spp_ctx *ctx); // S | rhs buffer the Schur entry points work on
 bool schur_applicable(const Structure &st, int *dp, int *dl);
-double schur_plan_host_probe(const Structure &st, int shard_rank, int shard_world, bool sparse_S, int64_t *out); // host only: plan + checksum, seconds
+double schur_plan_host_probe(const Structure &st, int shard_rank, int shard_world, bool sparse_S, bool mis, int64_t *out); // host only: plan + checksum, seconds
 
 // ---- spp_sparse (symbolic on host + numeric on device) ----
 void sparse_analyze(spp_ctx *ctx, const Structure &st); // plan for `st` (Lambda, or the sparse reduced system)

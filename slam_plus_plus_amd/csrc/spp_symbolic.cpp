@@ -901,12 +901,13 @@ void build_schur_plan(spp_ctx *ctx, bool sparse_S, bool mis)
 }
 
 // host-only: the symbolic Schur plan of a structure, timed; out[0..7] = nc, nl, no, n_pairs, n_sblk, n_items, n_multi,
-// a checksum of the pair lists and block list (tests compare thread counts against each other)
-double schur_plan_host_probe(const Structure &st, int shard_rank, int shard_world, bool sparse_S, int64_t *out)
+// a checksum of the pair lists and block list (tests compare thread counts against each other); mis: the MIS cut of a
+// graph of one block width instead of the guided one
+double schur_plan_host_probe(const Structure &st, int shard_rank, int shard_world, bool sparse_S, bool mis, int64_t *out)
 {
 	const auto t0 = std::chrono::steady_clock::now();
 	SchurPlanHost h;
-	schur_plan_host(st, shard_rank, shard_world, sparse_S, false, h);
+	schur_plan_host(st, shard_rank, shard_world, sparse_S || mis, mis, h);
 	const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 	uint64_t sum = 1469598103934665603ull;
 	auto mix = [&](uint64_t v) { sum = (sum ^ v) * 1099511628211ull; };
