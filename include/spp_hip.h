@@ -301,6 +301,23 @@ int spp_microbench_update(spp_ctx *ctx, int64_t m, int iters, double *ms_per_lau
 int spp_dense_potrf_upper(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld);
 /* A x = b by the dense path (upper triangle of A read; A <- R, b <- x) */
 int spp_dense_posv(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, double *d_b);
+/* the same with the tile structure of A given: words[i], bit j set = the 128 x 128 tile (i, j), i <= j, of A may be nonzero
+ * (nwords = ceil(n / 128); nwords = 0: every tile). The call adds the diagonal tiles and the right-hand side's tile column
+ * and closes the pattern under elimination; the streamed factorization then skips the tiles that stay zero. A tile
+ * outside the closed pattern must hold exact zeros. Results equal those of spp_dense_posv. */
+int spp_dense_posv_masked(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, double *d_b, const uint64_t *words, int64_t nwords);
+/* host only: the tile mask of an n x n matrix of bs x bs blocks (i1[q], i2[q]), q < nblk, at rows / columns bs * index:
+ * words[i], bit j = tile (i, j) of 128 x 128 touched by a block (upper triangle); diagonal tiles always, with has_rhs the
+ * tile column of column n in every row; with fill the pattern is closed under elimination. *n_updates (may be NULL):
+ * rank-128 tile updates of a factorization on the pattern. Returns the number of words written (tile rows, at most 64),
+ * 0 when the matrix has more than 64 tile columns (no mask: every tile), or a negative error. */
+int spp_tile_mask_host(int64_t n, int bs, int64_t nblk, const int32_t *i1, const int32_t *i2, int has_rhs, int fill,
+	uint64_t *words, int64_t *n_updates);
+/* host only: the filled tile mask the dense Schur plan of a block pattern (as spp_schur_plan_host takes it) hands to the
+ * factorization of S; it covers the landmarks of every shard whatever shard_rank is. Returns the number of words, 0 for
+ * "every tile", or a negative error. */
+int spp_schur_tile_mask_host(int64_t nb, const int32_t *dim, const int64_t *col_ptr, const int64_t *row_idx, int shard_rank,
+	int shard_world, uint64_t *words);
 /* C (m x n, ldc) -= A^T B with A: k x m (lda), B: k x n (ldb): the MFMA trailing-update kernel */
 int spp_dense_gemm_tn_sub(spp_ctx *ctx, int64_t m, int64_t n, int64_t k,
 	const double *d_A, int64_t lda, const double *d_B, int64_t ldb, double *d_C, int64_t ldc);

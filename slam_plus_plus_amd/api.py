@@ -34,6 +34,7 @@ EXPORTS = [
     "spp_device_free", "spp_memcpy_h2d", "spp_memcpy_d2h", "spp_memcpy_d2d", "spp_get_phase_ms", "spp_get_dominant_kernel",
     "spp_microbench_copy", "spp_microbench_mfma_f64", "spp_microbench_ctile", "spp_microbench_update", "spp_block_ordering", "spp_schur_plan_host", "spp_set_profiling", "spp_se2_linearize_device", "spp_se2_update_device", "spp_ba_linearize_device", "spp_ba_update_device", "spp_se3_linearize_device", "spp_se3_update_device", "spp_edge_chi2_device", "spp_edge_robust_weights_device", "spp_edge_hessian_maxdiag_device",
     "spp_lm_gain_denominator_device", "spp_dense_potrf_upper", "spp_dense_posv",
+    "spp_dense_posv_masked", "spp_tile_mask_host", "spp_schur_tile_mask_host",
     "spp_dense_gemm_tn_sub", "spp_dense_gemm_tn_sub_upper", "spp_dense_front_factor", "spp_version",
 ]
 
@@ -106,6 +107,9 @@ def load_library():
         "spp_ba_update_device": (cint, [vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, vp, vp, ctypes.c_int64, cint, _c_f64p]),
         "spp_dense_potrf_upper": (cint, [vp, vp, i64, i64]),
         "spp_dense_posv": (cint, [vp, vp, i64, i64, vp]),
+        "spp_dense_posv_masked": (cint, [vp, vp, i64, i64, vp, vp, i64]),
+        "spp_tile_mask_host": (cint, [i64, cint, i64, vp, vp, cint, cint, vp, vp]),
+        "spp_schur_tile_mask_host": (cint, [i64, vp, vp, vp, cint, cint, vp]),
         "spp_dense_gemm_tn_sub": (cint, [vp, i64, i64, i64, vp, i64, vp, i64, vp, i64]),
         "spp_dense_gemm_tn_sub_upper": (cint, [vp, i64, i64, i64, vp, i64, vp, i64, vp, i64]),
         "spp_dense_front_factor": (cint, [vp, vp, i64, i64, i64, vp]),
@@ -157,6 +161,36 @@ def schur_plan_host(lam, shard_rank=0, shard_world=1, sparse_S=False, mis=False)
     d = dict(zip(keys, (int(v) for v in out)))
     d["seconds"] = sec.value
     return d
+
+
+def tile_mask_host(n, bs, i1, i2, has_rhs=True, fill=True):
+    """Host-only tile mask of an n x n matrix of bs x bs blocks (i1[q], i2[q]) in 128 x 128 tiles (spp_tile_mask_host):
+    returns (words, updates) -- one uint64 per tile row, bit j = tile (i, j) nonzero, and the rank-128 tile updates of a
+    factorization on that pattern. words is empty when the matrix has more than 64 tile columns. No GPU needed."""
+    lib = load_library()
+    i1 = np.ascontiguousarray(i1, dtype=np.int32)
+    i2 = np.ascontiguousarray(i2, dtype=np.int32)
+    words = np.zeros(64, dtype=np.uint64)
+    upd = ctypes.c_int64(0)
+    code = lib.spp_tile_mask_host(n, bs, i1.size, _ptr(i1), _ptr(i2), 1 if has_rhs else 0, 1 if fill else 0, _ptr(words),
+                                  ctypes.byref(upd))
+    if code < 0:
+        raise SppError("spp_tile_mask_host failed: %d" % code)
+    return words[:code].copy(), upd.value
+
+
+def schur_tile_mask_host(lam, shard_rank=0, shard_world=1):
+    """Host-only: the filled tile mask the dense Schur plan of a BlockCSC pattern hands to the factorization of S
+    (spp_schur_tile_mask_host); empty: every tile. No GPU needed."""
+    lib = load_library()
+    col_ptr = np.ascontiguousarray(lam.col_ptr, dtype=np.int64)
+    row_idx = np.ascontiguousarray(lam.row_idx, dtype=np.int64)
+    dim = np.ascontiguousarray(lam.dim, dtype=np.int32)
+    words = np.zeros(64, dtype=np.uint64)
+    code = lib.spp_schur_tile_mask_host(lam.nb, _ptr(dim), _ptr(col_ptr), _ptr(row_idx), shard_rank, shard_world, _ptr(words))
+    if code < 0:
+        raise SppError("spp_schur_tile_mask_host failed: %d" % code)
+    return words[:code].copy()
 
 
 class DeviceArray:

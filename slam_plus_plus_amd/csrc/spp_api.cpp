@@ -134,6 +134,7 @@ int spp_free_memory(spp_ctx *ctx)
 	ctx->dense.tail_pub.release();
 	ctx->dense.tail_order.release();
 	ctx->dense.tail_order_tr = ctx->dense.tail_order_tc = 0;
+	ctx->dense.tail_order_bits.clear();
 	ctx->dense.tail_dinv.release();
 	ctx->dense.tail_epoch = 0;
 	ctx->dense.epoch = 0;
@@ -434,6 +435,32 @@ int spp_block_ordering(int64_t nb, const int64_t *col_ptr, const int64_t *row_id
 	}
 }
 
+// the Structure of a bare block pattern (upper triangle), values laid out block after block; false: a block below the diagonal
+static bool structure_of_pattern(int64_t nb, const int32_t *dim, const int64_t *col_ptr, const int64_t *row_idx, Structure &st)
+{
+	st.nb = nb;
+	st.nnzb = col_ptr[nb];
+	st.col_ptr.assign(col_ptr, col_ptr + nb + 1);
+	st.row_idx.assign(row_idx, row_idx + st.nnzb);
+	st.dim.assign(dim, dim + nb);
+	st.base.resize(nb + 1);
+	st.base[0] = 0;
+	for(int64_t j = 0; j < nb; ++ j)
+		st.base[j + 1] = st.base[j] + dim[j];
+	st.n = st.base[nb];
+	st.blk_off.resize(st.nnzb);
+	int64_t off = 0;
+	for(int64_t j = 0; j < nb; ++ j)
+		for(int64_t p = col_ptr[j]; p < col_ptr[j + 1]; ++ p) {
+			if(row_idx[p] < 0 || row_idx[p] > j)
+				return false; // upper triangle only
+			st.blk_off[p] = off;
+			off += (int64_t)dim[row_idx[p]] * dim[j];
+		}
+	st.nvals = off;
+	return true;
+}
+
 int spp_schur_plan_host(int64_t nb, const int32_t *dim, const int64_t *col_ptr, const int64_t *row_idx, int shard_rank,
 	int shard_world, int sparse_S, int64_t *out, double *seconds)
 {
@@ -441,30 +468,35 @@ int spp_schur_plan_host(int64_t nb, const int32_t *dim, const int64_t *col_ptr, 
 		return SPP_E_BADARG;
 	try {
 		Structure st;
-		st.nb = nb;
-		st.nnzb = col_ptr[nb];
-		st.col_ptr.assign(col_ptr, col_ptr + nb + 1);
-		st.row_idx.assign(row_idx, row_idx + st.nnzb);
-		st.dim.assign(dim, dim + nb);
-		st.base.resize(nb + 1);
-		st.base[0] = 0;
-		for(int64_t j = 0; j < nb; ++ j)
-			st.base[j + 1] = st.base[j] + dim[j];
-		st.n = st.base[nb];
-		st.blk_off.resize(st.nnzb);
-		int64_t off = 0;
-		for(int64_t j = 0; j < nb; ++ j)
-			for(int64_t p = col_ptr[j]; p < col_ptr[j + 1]; ++ p) {
-				if(row_idx[p] < 0 || row_idx[p] > j)
-					return SPP_E_BADARG; // upper triangle only
-				st.blk_off[p] = off;
-				off += (int64_t)dim[row_idx[p]] * dim[j];
-			}
-		st.nvals = off;
+		if(!structure_of_pattern(nb, dim, col_ptr, row_idx, st))
+			return SPP_E_BADARG;
 		const double sec = schur_plan_host_probe(st, shard_rank, shard_world, (sparse_S & 1) != 0, (sparse_S & 2) != 0, out);
 		if(seconds)
 			*seconds = sec;
 		return SPP_OK;
+	} catch(const Error &e) {
+		return e.code;
+	} catch(const std::bad_alloc &) {
+		return SPP_E_NOMEM;
+	} catch(...) {
+		return SPP_E_HIP;
+	}
+}
+
+int spp_schur_tile_mask_host(int64_t nb, const int32_t *dim, const int64_t *col_ptr, const int64_t *row_idx, int shard_rank,
+	int shard_world, uint64_t *words)
+{
+	if(nb <= 0 || !dim || !col_ptr || !row_idx || !words || shard_world < 1 || shard_rank < 0 || shard_rank >= shard_world)
+		return SPP_E_BADARG;
+	try {
+		Structure st;
+		if(!structure_of_pattern(nb, dim, col_ptr, row_idx, st))
+			return SPP_E_BADARG;
+		std::vector<uint64_t> w;
+		schur_tile_mask_host_probe(st, shard_rank, shard_world, w);
+		for(size_t q = 0; q < w.size(); ++ q)
+			words[q] = w[q];
+		return (int)w.size();
 	} catch(const Error &e) {
 		return e.code;
 	} catch(const std::bad_alloc &) {
@@ -935,10 +967,40 @@ int spp_dense_potrf_upper(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld)
 
 int spp_dense_posv(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, double *d_b)
 {
-	if(!ctx || !d_A || !d_b || n <= 0 || ld < n)
+	return spp_dense_posv_masked(ctx, d_A, n, ld, d_b, nullptr, 0);
+}
+
+int spp_tile_mask_host(int64_t n, int bs, int64_t nblk, const int32_t *i1, const int32_t *i2, int has_rhs, int fill,
+	uint64_t *words, int64_t *n_updates)
+{
+	if(n <= 0 || bs <= 0 || nblk < 0 || (nblk && (!i1 || !i2)) || !words)
+		return SPP_E_BADARG;
+	try {
+		std::vector<uint64_t> w;
+		tile_mask_mark(n, bs, nblk, i1, i2, w);
+		const int64_t upd = tile_mask_close(n, has_rhs != 0, fill != 0, w);
+		if(n_updates)
+			*n_updates = upd;
+		for(size_t q = 0; q < w.size(); ++ q)
+			words[q] = w[q];
+		return (int)w.size();
+	} catch(...) {
+		return SPP_E_NOMEM;
+	}
+}
+
+int spp_dense_posv_masked(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, double *d_b, const uint64_t *words, int64_t nwords)
+{
+	if(!ctx || !d_A || !d_b || n <= 0 || ld < n || nwords < 0 || (nwords && !words))
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	std::vector<uint64_t> mask(words, words + nwords);
+	if(nwords) {
+		SPP_REQUIRE(nwords == (n + DENSE_NB - 1) / DENSE_NB, SPP_E_BADARG, "posv: one mask word per tile row of 128");
+		tile_mask_close(n, true, true, mask);
+	}
+	TileMaskGuard guard(ctx->dense, &mask);
 	const int64_t ldp = ((n + 1 + DENSE_NB - 1) / DENSE_NB) * DENSE_NB;
 	DevBuf<double> tmp;
 	tmp.reserve((size_t)ldp * ldp);

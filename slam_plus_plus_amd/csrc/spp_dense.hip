@@ -1562,11 +1562,28 @@ static bool launch_dense_tail(spp_ctx *ctx, double *d_A, int64_t ld, int64_t row
 	if(!enabled || dw.tail_disabled || k + 1 >= nsteps || nsteps * NB < rows || (dw.ident_from >= 0 && dw.ident_from < rows))
 		return false;
 	const int Tr = (int)(nsteps - (k + 1)), Tc = (int)((ncols - c1 + NB - 1) / NB);
-	if(Tr < 1 || Tc < Tr || Tc > Tr + 1)
+	if(Tr < 1 || Tc < Tr || Tc > Tr + 1 || Tc > TAIL_MAX_ROWS)
 		return false;
 	// (more tiles than CUs are fine: workgroups are dispatched row by row and leave after their own step, a workgroup that
 	// starts late finds the row tiles of the steps it missed in memory and catches up at the speed of its matrix cores)
-	const int ntile = Tr * Tc - Tr * (Tr - 1) / 2;
+	// The step words of the region: bit j of bits[i + 1] = tile (i, j) of the region is nonzero, bits[0] = the row panel
+	// in front of it. From the caller's filled mask of the whole matrix (global tile indices, one word per tile row) --
+	// a sub-pattern of a filled pattern that starts at a later step is filled too --, or every tile.
+	static int use_mask = -1;
+	if(use_mask < 0) {
+		const char *e = getenv("SPP_TAIL_MASK"); // 0: every tile, whatever structure the caller knows (A/B timing, tests)
+		use_mask = e ? atoi(e) : 1;
+	}
+	const std::vector<uint64_t> *mask = (use_mask && dw.tile_mask && (int64_t)dw.tile_mask->size() == nsteps) ? dw.tile_mask : nullptr;
+	std::vector<uint64_t> bits((size_t)Tr + 1);
+	const uint64_t all_cols = Tc == 64 ? ~0ull : (1ull << Tc) - 1;
+	for(int i = -1; i < Tr; ++ i) {
+		const int64_t g = k + 1 + i; // global tile row
+		uint64_t w = (mask && g >= 0) ? ((*mask)[(size_t)g] >> (k + 1)) : all_cols;
+		if(i >= 0)
+			w = (w | (1ull << i)) & ~((1ull << i) - 1); // the diagonal tile always, nothing below it
+		bits[(size_t)i + 1] = w & all_cols;
+	}
 	static int max_rows = -1;
 	if(max_rows < 0) {
 		const char *e = getenv("SPP_TAIL_ROWS"); // tile rows from which on the factorization is streamed
@@ -1594,7 +1611,9 @@ static bool launch_dense_tail(spp_ctx *ctx, double *d_A, int64_t ld, int64_t row
 	// beta >= 0 sorts the tiles topologically (producers before consumers: progress whatever is resident). Row by row
 	// (beta = 0) the 256 CUs start on the first ~6 rows, far tiles included, and the near-diagonal tiles of the rows
 	// behind them start late; beta > 0 holds the far columns back a little in favour of those.
-	if(dw.tail_order_tr != Tr || dw.tail_order_tc != Tc) {
+	if(dw.tail_order_tr != Tr || dw.tail_order_tc != Tc || dw.tail_order_bits != bits) {
+		if(!dw.tail_order_host.empty())
+			SPP_HIP_CHECK(hipStreamSynchronize(s)); // (an upload of the table's former host image may still be reading it)
 		static double beta = -1;
 		if(beta < 0) {
 			const char *e = getenv("SPP_TAIL_ORDER_BETA");
@@ -1603,7 +1622,8 @@ static bool launch_dense_tail(spp_ctx *ctx, double *d_A, int64_t ld, int64_t row
 		std::vector<std::pair<double, int> > key;
 		for(int i = 0; i < Tr; ++ i)
 			for(int j = i; j < Tc; ++ j)
-				key.push_back(std::make_pair((double)i + beta * (double)j, (i << 16) | j));
+				if((bits[(size_t)i + 1] >> j) & 1) // (only nonzero tiles get a workgroup)
+					key.push_back(std::make_pair((double)i + beta * (double)j, (i << 16) | j));
 		std::stable_sort(key.begin(), key.end(), [](const std::pair<double, int> &x, const std::pair<double, int> &y) { return x.first < y.first; });
 		std::vector<int> &order = dw.tail_order_host; // (the asynchronous upload reads it after this call returns)
 		order.resize(key.size());
@@ -1612,9 +1632,14 @@ static bool launch_dense_tail(spp_ctx *ctx, double *d_A, int64_t ld, int64_t row
 		dw.tail_order.upload(order, s);
 		dw.tail_order_tr = Tr;
 		dw.tail_order_tc = Tc;
+		dw.tail_order_bits = bits;
 	}
+	const int ntile = (int)dw.tail_order_host.size();
 	TailArgs a;
 	a.order = dw.tail_order.p;
+	memset(a.rowbits, 0, sizeof(a.rowbits));
+	for(size_t q = 0; q < bits.size(); ++ q)
+		a.rowbits[q] = bits[q];
 	a.A = d_A;
 	a.ld = ld;
 	a.rows = rows;
@@ -1663,7 +1688,7 @@ static bool launch_dense_tail(spp_ctx *ctx, double *d_A, int64_t ld, int64_t row
 		std::vector<long long> h((size_t)Tr * 8);
 		SPP_HIP_CHECK(hipStreamSynchronize(s));
 		SPP_HIP_CHECK(hipMemcpy(h.data(), trace.p, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
-		fprintf(stderr, "[spp] streamed tail, %d tile rows (us from the launch's first stamp): diagonal tile: updates complete / factored+inverted | first panel tile: first row tile seen / last seen / last published\n", Tr);
+		fprintf(stderr, "[spp] streamed tail, %d tile rows, %d of %d tiles launched (us from the launch's first stamp): diagonal tile: updates complete / factored+inverted | first panel tile: first row tile seen / last seen / last published\n", Tr, ntile, Tr * Tc - Tr * (Tr - 1) / 2);
 		const long long t0 = h[0];
 		for(int i = 0; i < Tr; ++ i)
 			fprintf(stderr, "  row %2d  start %7.1f  updated %7.1f  done %7.1f | %7.1f %7.1f %7.1f\n", i, (h[8 * i] - t0) * 0.01, (h[8 * i + 1] - t0) * 0.01,

@@ -22,10 +22,17 @@
 // Workgroups are numbered row by row: whatever a workgroup waits for is produced by a workgroup
 // with a smaller index, which never waits for a larger one -- progress does not depend on residency. Every wait is bounded (abort word).
 // Summation order per tile: steps ascending, row tiles ascending -- fixed, bit-reproducible.
+// Structure: the launch takes one 64-bit word per step (bit j of word k = tile (k, j) of the FILLED pattern is nonzero,
+// spp_symbolic.cpp: tile_mask_close). Only tiles with their bit set have a workgroup; tile (i, j) applies step k only if
+// bits i and j of word k are both set, and neither waits for nor fetches a row tile of a step it skips -- such an update
+// subtracts a product with an all-zero row tile, a tile without a workgroup is zero before and after and is never
+// written. With every bit set the launch is the dense one, workgroup for workgroup.
 #pragma once
 #include "spp_dense_dev.h"
 
 namespace spp {
+
+constexpr int TAIL_MAX_ROWS = 64; // tile columns of a region: one bit each in a step's word
 
 struct TailArgs {
 	double *A;           // the matrix (column-major, leading dimension ld)
@@ -43,7 +50,10 @@ struct TailArgs {
 	int *info, *abort;   // abort word: 1 = a diagonal block is not positive definite (info[0] says which), TAIL_ABORT_TIMEOUT = a wait gave up
 	long long timeout_ticks;
 	long long *trace;    // debugging (SPP_TAIL_TRACE): per tile row 8 wall-clock stamps
-	const int *order;    // workgroup -> tile (i << 16 | j), a topological order of the tiles (see the host side)
+	const int *order;    // workgroup -> tile (i << 16 | j), a topological order of the nonzero tiles (see the host side)
+	// rowbits[k + 1], bit j: tile (k, j) of the region is nonzero after symbolic fill (region tile indices); rowbits[0]
+	// is the row panel in front of the region (have_pre)
+	unsigned long long rowbits[TAIL_MAX_ROWS + 1];
 };
 
 // the value a timed-out wait of the streamed launch leaves in the abort word (the host tells it from the other raisers:
@@ -200,10 +210,17 @@ void dense_tail_kernel(const TailArgs a)
 		const int ek = tid & 15, ec = tid >> 4; // this thread's elements: (ek, ec) and (ek, ec + 64) of a row tile
 		constexpr int PS = 18;                  // column stride of a row tile's LDS image (even: 16-byte aligned columns)
 		const int ekp = 4 * (ek & 3) + (ek >> 2);
-		const int kfirst = a.have_pre ? -1 : 0, nst = 8 * (ti - kfirst);
+		const int kfirst = a.have_pre ? -1 : 0;
+		// the steps this tile applies (bit k - kfirst): both row tiles (k, ti) and (k, tj) nonzero
+		unsigned long long steps = 0;
+		for(int k = kfirst; k < ti; ++ k) {
+			const unsigned long long w = a.rowbits[k + 1];
+			if(((w >> ti) & (w >> tj) & 1) != 0)
+				steps |= 1ull << (k - kfirst);
+		}
+		const int nst = 8 * __builtin_popcountll(steps);
 		double va[2], vb[2];
-		auto fetch = [&](const int sidx) {
-			const int k = kfirst + (sidx >> 3), J = sidx & 7;
+		auto fetch = [&](const int k, const int J) {
 			const double *rowp = a.A + (a.c0 + (int64_t)NB * k) + 16 * J + ek;
 #pragma unroll
 			for(int h = 0; h < 2; ++ h) {
@@ -217,8 +234,13 @@ void dense_tail_kernel(const TailArgs a)
 		int avail = a.have_pre ? 8 : 0; // row tiles of the current step known to be out
 		pre_first = diag && nst > 0 && (nst & 1) == 0 && a.rows - i0 >= 16; // (the last round's images are the second pair; the right-hand side column is not in the first tile)
 		bool inflight = false;
+		int k = kfirst;
 		for(int sidx = 0; sidx < nst; ++ sidx) {
-			const int k = kfirst + (sidx >> 3), J = sidx & 7;
+			const int J = sidx & 7;
+			if(J == 0) { // the next step this tile applies
+				k = kfirst + __builtin_ctzll(steps);
+				steps &= steps - 1;
+			}
 			if(J == 0 && k >= 0)
 				avail = 0;
 			if(!inflight) {
@@ -227,7 +249,7 @@ void dense_tail_kernel(const TailArgs a)
 					if(avail < 0)
 						return;
 				}
-				fetch(sidx);
+				fetch(k, J);
 			}
 			// a look at the counters for the NEXT row tile of this step, by one lane, without waiting: the answer travels
 			// with the barrier below. (A workgroup that keeps up only ever learns of one row tile per wait; one that lags
@@ -257,7 +279,7 @@ void dense_tail_kernel(const TailArgs a)
 			// the next row tile, if it is out already (same step; the next step's counters are other words)
 			inflight = (sidx + 1 < nst) && (J + 1 < 8) && (J + 1 < avail);
 			if(inflight)
-				fetch(sidx + 1);
+				fetch(k, J + 1);
 			double fa[4]; // (an off-diagonal tile: the four tiles of a wave share their rows -- ONE A fragment for all four)
 #pragma unroll
 			for(int u = 0; u < 4; ++ u) {

@@ -232,6 +232,7 @@ struct SchurPlan {
 	std::vector<int64_t> pose_block; // reduced pose index -> original block column
 	std::vector<int64_t> lm_block;   // owned landmark index -> original block column
 	std::vector<uint8_t> is_lm;      // per block column: eliminated by the Schur complement (any shard)
+	std::vector<uint64_t> tile_mask; // dense S: its filled 128 x 128 tile pattern over ALL shards (tile_mask_close); empty: every tile
 	// device arrays
 	DevBuf<int32_t> lm_ptr;        // [nl+1] first obs of landmark
 	DevBuf<int32_t> bs_ptr;        // [n_bs+1] landmark ranges of the fused back-substitution (at most 256 observations each); n_bs = 0: two launches
@@ -282,6 +283,11 @@ struct DenseWork {
 	DevBuf<int> tail_order;        // workgroup -> tile of the streamed launch, for tail_order_tr x tail_order_tc tiles
 	std::vector<int> tail_order_host; // its host image (the upload is asynchronous: it lives as long as the table)
 	int tail_order_tr = 0, tail_order_tc = 0;
+	std::vector<uint64_t> tail_order_bits; // ... and for these step words (the table is keyed by the tile mask as well)
+	// Tile structure of the matrix the next factorization gets (set by the caller for that one call, TileMaskGuard): one
+	// word per tile row of 128, bit j = tile (i, j) is nonzero after symbolic fill (tile_mask_close). nullptr or a size
+	// that does not match the factorization's tile rows: every tile is nonzero.
+	const std::vector<uint64_t> *tile_mask = nullptr;
 	int tail_rows_last = 0;        // tile rows the last factorization streamed (diagnostics: SPP_INFO_DENSE_STREAMED)
 	bool tail_disabled = false;    // a streamed launch timed out on this ctx: later factorizations take the per-step schedule
 	DevBuf<double> trsv_m;         // M_b = Tinv_b R_{b, b+1} per block row (M form of the backward substitution)
@@ -412,6 +418,20 @@ void dense_reserve(spp_ctx *ctx, int64_t nblk); // workspaces for nblk diagonal 
 
 void dense_chain_check(spp_ctx *ctx); // call after the stream was synchronized
 void dense_set_padding(spp_ctx *ctx, double *d_A, int64_t ld, int64_t n);
+struct TileMaskGuard { // hands a tile mask to the factorizations enqueued while it lives
+	DenseWork &d;
+	TileMaskGuard(DenseWork &dw, const std::vector<uint64_t> *m) : d(dw) { d.tile_mask = (m && !m->empty()) ? m : nullptr; }
+	~TileMaskGuard() { d.tile_mask = nullptr; }
+};
+// Tile masks of an n x n matrix (+ right-hand side column n) in 128 x 128 tiles (host only, spp_symbolic.cpp).
+// tile_mask_mark: the tiles the bs x bs blocks (i1[q], i2[q]) at rows / columns bs * index touch (either triangle given,
+// the upper one marked); words is resized to the tile rows, or left EMPTY (= every tile) with more than 64 tile columns.
+// tile_mask_close: diagonal tiles and the right-hand side's tile column set, nothing below the diagonal, then symbolic
+// elimination (for k ascending every pair of nonzero tiles (k, a), (k, b), k < a <= b, fills (a, b)); returns the
+// number of rank-128 tile updates of the filled pattern.
+void tile_mask_mark(int64_t n, int bs, int64_t nblk, const int32_t *i1, const int32_t *i2, std::vector<uint64_t> &words);
+int64_t tile_mask_close(int64_t n, bool has_rhs, bool fill, std::vector<uint64_t> &words);
+void schur_tile_mask_host_probe(const Structure &st, int shard_rank, int shard_world, std::vector<uint64_t> &words); // the mask a dense Schur plan carries
 // unit tests: the partial factorization of a big sparse front, laid out (identity padding after the w pivots) and
 // factored as the sparse path does; d_F (h x h, ld) <- the result in the unpadded layout, d_image (optional, ldp x hp with
 // ldp = (hp + 1) & ~1, hp = h + pad) <- the padded image

@@ -978,7 +978,12 @@ static int schur_finish_t(spp_ctx *ctx, const double *d_vals, double *S, double 
 		dense_set_padding(ctx, S, ld, sp.n_red);
 		// the status of the factorization is fetched at the very end: a host round trip here would leave the GPU
 		// idle for ~40 us before the solves (after a failure they run on garbage and the result is discarded)
-		dense_potrf_upper_enqueue(ctx, S, sp.n_red, ld);
+		{
+			// S is a band plus what elimination fills: the streamed launch skips the tiles that stay zero. The mask covers the
+			// landmarks of every shard, so it also holds for an S summed over the ranks.
+			TileMaskGuard guard(ctx->dense, &sp.tile_mask);
+			dense_potrf_upper_enqueue(ctx, S, sp.n_red, ld);
+		}
 		phase_end(ctx, SPP_PHASE_FACTOR);
 		xcol = S + sp.n_red * ld;
 		phase_begin(ctx, SPP_PHASE_TRISOLVE);

@@ -35,7 +35,7 @@ void SchurPlan::release_all()
 	sblk_voff.release(); s_st = Structure(); sparse_S = false; mis = false;
 	pair_a.release(); pair_b.release(); multi_blk.release(); multi_ptr.release(); cinv.release(); lfac.release();
 	W.release(); Up.release(); xw.release(); partial.release(); S.release();
-	pose_block.clear(); lm_block.clear(); is_lm.clear();
+	pose_block.clear(); lm_block.clear(); is_lm.clear(); tile_mask.clear();
 }
 
 // Guided ordering is possible when there are exactly two block widths and the blocks of the
@@ -160,6 +160,96 @@ struct RawBuf {
 	const T &operator[](size_t i) const { return p[i]; }
 };
 
+// --------------------------------------------------------------------------------------------------
+// Tile structure of a dense reduced system (the streamed dense factor, spp_dense_tail.h, skips structurally zero tiles).
+// A word per tile row of DENSE_NB rows, bit j = tile (i, j); the layout is the factor's: n pivots, the right-hand side
+// in column n, identity padding behind it (diagonal tiles only).
+// --------------------------------------------------------------------------------------------------
+void tile_mask_mark(int64_t n, int bs, int64_t nblk, const int32_t *i1, const int32_t *i2, std::vector<uint64_t> &words)
+{
+	words.clear();
+	const int64_t Tr = (n + DENSE_NB - 1) / DENSE_NB, Tc = n / DENSE_NB + 1;
+	if(Tr < 1 || Tc > 64)
+		return; // (empty: every tile)
+	words.assign((size_t)Tr, 0);
+	for(int64_t q = 0; q < nblk; ++ q) {
+		const int64_t a = std::min(i1[q], i2[q]), b = std::max(i1[q], i2[q]);
+		// a bs x bs block may straddle two tiles in either direction
+		const int64_t r0 = a * bs / DENSE_NB, r1 = std::min<int64_t>(a * bs + bs - 1, n - 1) / DENSE_NB;
+		const int64_t c0 = b * bs / DENSE_NB, c1 = std::min<int64_t>(b * bs + bs - 1, n - 1) / DENSE_NB;
+		if(a < 0 || r0 >= Tr || c0 >= Tr)
+			continue;
+		words[r0] |= (1ull << c0) | (1ull << c1);
+		words[r1] |= (1ull << c0) | (1ull << c1);
+	}
+}
+
+int64_t tile_mask_close(int64_t n, bool has_rhs, bool fill, std::vector<uint64_t> &words)
+{
+	const int64_t Tr = (n + DENSE_NB - 1) / DENSE_NB, Tc = has_rhs ? n / DENSE_NB + 1 : Tr;
+	if(Tr < 1 || Tc > 64 || (int64_t)words.size() != Tr) {
+		words.clear();
+		return -1;
+	}
+	const uint64_t cols = Tc == 64 ? ~0ull : (1ull << Tc) - 1;
+	for(int64_t i = 0; i < Tr; ++ i) {
+		words[i] |= 1ull << i;
+		if(has_rhs)
+			words[i] |= 1ull << (n / DENSE_NB); // the tile column of the right-hand side is nonzero in every row
+		words[i] &= cols & ~((1ull << i) - 1);
+	}
+	int64_t updates = 0;
+	for(int64_t k = 0; k < Tr; ++ k) {
+		const uint64_t r = words[k] & ~((2ull << k) - 1); // nonzero tiles right of the diagonal
+		for(uint64_t m = r; m; m &= m - 1) {
+			const int a = __builtin_ctzll(m);
+			if(a >= Tr)
+				break;
+			const uint64_t f = r & ~((1ull << a) - 1);
+			if(fill)
+				words[a] |= f;
+			updates += __builtin_popcountll(words[a] & f);
+		}
+	}
+	return updates;
+}
+
+// the tiles of S = A - sum over landmarks of U C^-1 U^T, over the landmarks of ALL shards (the exchanged S is the sum
+// over the ranks): every camera-camera block of the structure and, per eliminated block, every pair of its observers
+static void schur_tile_mask(const Structure &st, const std::vector<uint8_t> &is_lm, const std::vector<int32_t> &pose_of,
+	int dp, int64_t n_red, std::vector<uint64_t> &words)
+{
+	tile_mask_mark(n_red, dp, 0, nullptr, nullptr, words);
+	if(words.empty())
+		return;
+	const int64_t Tr = (int64_t)words.size();
+	auto tiles_of = [&](int32_t pose) -> uint64_t {
+		return (1ull << ((int64_t)pose * dp / DENSE_NB)) | (1ull << (((int64_t)pose * dp + dp - 1) / DENSE_NB));
+	};
+	auto mark = [&](uint64_t rows, const uint64_t cols) {
+		for(; rows; rows &= rows - 1) {
+			const int a = __builtin_ctzll(rows);
+			if(a < Tr)
+				words[a] |= cols;
+		}
+	};
+	std::vector<uint64_t> seen(st.nb, 0); // per eliminated block: the tiles of its observers
+	for(int64_t j = 0; j < st.nb; ++ j)
+		for(int64_t p = st.col_ptr[j]; p < st.col_ptr[j + 1]; ++ p) {
+			const int64_t i = st.row_idx[p];
+			if(!is_lm[i] && !is_lm[j])
+				mark(tiles_of(pose_of[i]), tiles_of(pose_of[j])); // (i <= j and the stable partition: upper)
+			else if(!is_lm[i])
+				seen[j] |= tiles_of(pose_of[i]);
+			else if(!is_lm[j])
+				seen[i] |= tiles_of(pose_of[j]);
+		}
+	for(int64_t j = 0; j < st.nb; ++ j)
+		if(seen[j])
+			mark(seen[j], seen[j]);
+	tile_mask_close(n_red, true, true, words);
+}
+
 // Everything build_schur_plan() derives from the block structure, in host memory: the pure symbolic part (no device,
 // no ctx), also reachable through spp_schur_plan_host() for host-only tests and timing.
 struct SchurPlanHost {
@@ -177,6 +267,7 @@ struct SchurPlanHost {
 	std::vector<int64_t> sblk_aoff, sblk_voff, pose_rbase;
 	std::vector<SaccItem> recs;
 	Structure s_st;
+	std::vector<uint64_t> tile_mask; // dense S: filled tile pattern (schur_tile_mask); empty: every tile
 };
 
 static void schur_plan_host(const Structure &st, int shard_rank, int shard_world, bool sparse_S, bool mis, SchurPlanHost &h)
@@ -222,6 +313,8 @@ static void schur_plan_host(const Structure &st, int shard_rank, int shard_world
 	h.ld = ((h.n_red + 1 + DENSE_NB - 1) / DENSE_NB) * DENSE_NB; // at least one padding column (rhs)
 	SPP_REQUIRE(sparse_S || h.ld <= 65536, SPP_E_UNSUPPORTED,
 		"reduced camera system too large for the dense path (use SPP_MODE_SCHUR_SPARSE)");
+	if(!sparse_S)
+		schur_tile_mask(st, is_lm, pose_of, dp, h.n_red, h.tile_mask);
 
 	// ---- observations: every pose-landmark block, sorted by (landmark, pose). Two passes over ranges of columns on host
 	// threads: counts per range, then every range writes its observations / camera-camera blocks at its offset.
@@ -821,6 +914,7 @@ void build_schur_plan(spp_ctx *ctx, bool sparse_S, bool mis)
 	sp.add_A = (ctx->shard_rank == 0);
 	sp.n_red = h.n_red;
 	sp.ld = h.ld;
+	sp.tile_mask.swap(h.tile_mask);
 	sp.no = no;
 	sp.n_pairs = h.n_pairs;
 	sp.n_sblk = h.n_sblk;
@@ -927,6 +1021,14 @@ double schur_plan_host_probe(const Structure &st, int shard_rank, int shard_worl
 	out[0] = h.nc; out[1] = h.nl; out[2] = h.no; out[3] = h.n_pairs; out[4] = h.n_sblk; out[5] = h.n_items; out[6] = h.n_multi;
 	out[7] = (int64_t)sum;
 	return sec;
+}
+
+// host-only: the filled tile mask the dense Schur plan of a structure would carry (every shard's is the same)
+void schur_tile_mask_host_probe(const Structure &st, int shard_rank, int shard_world, std::vector<uint64_t> &words)
+{
+	SchurPlanHost h;
+	schur_plan_host(st, shard_rank, shard_world, false, false, h);
+	words.swap(h.tile_mask);
 }
 
 // --------------------------------------------------------------------------------------------------
