@@ -269,11 +269,7 @@ static bool launch_gemm_mixed(hipStream_t s, int64_t M, int64_t N, int K, const 
 	const int64_t T = nt * (nt + 1) / 2 + (ntc - nt) * nt;
 	const int64_t n128 = (T / slots) * slots;
 	const int64_t grid = n128 + 4 * (T - n128);
-	static int use444 = -1;
-	if(use444 < 0) {
-		const char *e = getenv("SPP_TILE_444"); // whole 128 x 128 tiles: 0 register-staged 16x16x4 tile (rounds 1-2, default), 1 LDS-DMA 16x16x4 tile, 2 LDS-DMA 4x4x4_4b tile
-		use444 = e ? atoi(e) : 0;
-	}
+	const int use444 = switches().tile_444;
 	static uint64_t mixed_attr_seen = 0;
 	if(first_on_this_device(mixed_attr_seen))
 		SPP_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_tn_mixed_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1223,8 +1219,7 @@ static void ensure_dense_work(spp_ctx *ctx, int64_t nblk)
 		// to the chain: under a running bulk update every wave slot of the chip is taken, potrf_diag and the
 		// tile-row workgroups otherwise wait for bulk workgroups to retire (measured: potrf_diag 33 -> 50..100 us,
 		// tile row 10 -> 55 us). 8 CUs already help, 32..64 are best; beyond that the bulk update itself suffers.
-		const char *r = getenv("SPP_AUX_RESERVE_CUS");
-		const int reserve = r ? atoi(r) : 32;
+		const int reserve = switches().aux_reserve_cus;
 		if(reserve > 0) {
 			int ncu = 0; // (one attribute: hipGetDeviceProperties fills a 1.5 KB record through dozens of driver queries, milliseconds)
 			SPP_HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device));
@@ -1273,7 +1268,15 @@ static void dense_factor_steps_enqueue(spp_ctx *ctx, double *d_A, int64_t ld, in
 	int64_t nsteps, bool has_rhs, bool use_flags = false, bool allow_fused = true);
 static bool flag_schedule_usable(spp_ctx *ctx);
 static void flag_signal(hipStream_t st, int *flag, int value);
-static void flag_wait(spp_ctx *ctx, hipStream_t st, const int *flag, int value, double timeout_ms = 500.0);
+static void flag_wait(spp_ctx *ctx, hipStream_t st, const int *flag, int value, long long timeout_ticks = WAIT_TICKS_DEFAULT);
+static bool streams_concurrent(spp_ctx *ctx, hipStream_t a, hipStream_t b, int slot);
+
+// (an error of the query counts as capturing: the schedules that cannot be captured stay off)
+static bool capturing(hipStream_t s)
+{
+	hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+	return hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+}
 
 // ---- lookahead schedule (spp_dense_la.h): host side -------------------------------------------------------------------
 // Streams: the chain kernel runs on a stream of its own that is CU-masked to the `reserve` CUs the bulk stream's mask
@@ -1286,46 +1289,29 @@ static void la_setup_streams(spp_ctx *ctx)
 	if(dw.la_state != 0)
 		return;
 	dw.la_state = -1;
-	const char *e = getenv("SPP_DENSE_LA"); // 1: the lookahead schedule (spp_dense_la.h); default: the two-stream schedule of rounds 1-2
-	if(!e || !atoi(e))
+	if(!switches().dense_la)
 		return;
 	hipDeviceProp_t prop;
 	SPP_HIP_CHECK(hipGetDeviceProperties(&prop, ctx->device));
 	const int ncu = prop.multiProcessorCount;
-	const char *r = getenv("SPP_AUX_RESERVE_CUS");
-	const int reserve = r ? atoi(r) : 32;
+	const int reserve = switches().aux_reserve_cus;
 	if(ncu < 128 || reserve < 1 + LA_G1 + 1 || reserve > ncu / 2 || !dw.aux)
 		return; // a small partition: the chain kernel's workgroups + a useful bulk side do not fit
 	dw.la_ncu = ncu;
 	dw.la_reserve = reserve;
-	const char *m = getenv("SPP_LA_CHAIN_MASK"); // 0: the chain kernel on an unmasked stream
 	const int nw = (ncu + 31) / 32;
 	std::vector<uint32_t> mask((size_t)nw, 0u);
 	for(int c = 0; c < reserve; ++ c)
 		mask[(size_t)c / 32] |= 1u << (c % 32);
-	if((m && !atoi(m)) || hipExtStreamCreateWithCUMask(&dw.chain, (uint32_t)nw, mask.data()) != hipSuccess) {
+	if(!switches().la_chain_mask || hipExtStreamCreateWithCUMask(&dw.chain, (uint32_t)nw, mask.data()) != hipSuccess) {
 		(void)hipGetLastError();
 		SPP_HIP_CHECK(hipStreamCreateWithFlags(&dw.chain, hipStreamNonBlocking));
 	}
 	SPP_HIP_CHECK(hipEventCreateWithFlags(&dw.ev_chain, hipEventDisableTiming));
 	// the chain stream and the bulk stream must run CONCURRENTLY (two streams that share a hardware queue would make the
 	// bulk launches wait for the end of the chain kernel, which waits for them): wait enqueued first, both directions
-	dw.sync.reserve(16);
-	SPP_HIP_CHECK(hipMemsetAsync(dw.sync.p, 0, 16 * sizeof(int), ctx->stream));
-	SPP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-	hipStream_t st[2] = {dw.chain, dw.aux};
-	for(int p = 0; p < 2; ++ p) {
-		flag_wait(ctx, st[p], dw.sync.p + 8 + p, 1, 20.0);
-		flag_signal(st[1 - p], dw.sync.p + 8 + p, 1);
-	}
-	for(int i = 0; i < 2; ++ i)
-		SPP_HIP_CHECK(hipStreamSynchronize(st[i]));
-	int h_abort = 0;
-	SPP_HIP_CHECK(hipMemcpy(&h_abort, dw.info.p + 2, sizeof(int), hipMemcpyDeviceToHost));
-	if(h_abort) {
-		SPP_HIP_CHECK(hipMemset(dw.info.p + 2, 0, sizeof(int)));
+	if(!streams_concurrent(ctx, dw.chain, dw.aux, 8))
 		return;
-	}
 	static uint64_t attr_seen = 0;
 	if(first_on_this_device(attr_seen)) {
 		SPP_HIP_CHECK(hipFuncSetAttribute((const void*)la_chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1339,8 +1325,7 @@ static bool la_usable(spp_ctx *ctx, int64_t nsteps)
 	DenseWork &dw = ctx->dense;
 	if(nsteps < 6 || dw.sync_state < 0)
 		return false;
-	hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-	if(hipStreamIsCapturing(ctx->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)
+	if(capturing(ctx->stream))
 		return false; // counters are zeroed and polled inside one call: not for a captured graph
 	la_setup_streams(ctx);
 	return dw.la_state == 1;
@@ -1361,42 +1346,24 @@ static void dense_factor_lookahead(spp_ctx *ctx, double *d_A, int64_t ld, int64_
 	a.nt = (int)((ncols + NB - 1) / NB);
 	a.has_rhs = has_rhs ? 1 : 0;
 	a.g1 = LA_G1;
-	static int g2_env = -1, acq = -1, trace_n = -1;
-	static int64_t slots_env = -1;
-	if(g2_env < 0) {
-		const char *e = getenv("SPP_LA_G2");
-		g2_env = e ? atoi(e) : 0;
-		e = getenv("SPP_LA_BULK_ACQUIRE");
-		acq = e ? atoi(e) : 1;
-		e = getenv("SPP_LA_SLOTS");
-		slots_env = e ? atol(e) : 0;
-		e = getenv("SPP_LA_TRACE"); // n: the n-th factorization prints when its diagonal blocks started / ended
-		trace_n = e ? atoi(e) : 0;
-	}
-	a.g2 = g2_env > 0 ? std::min(g2_env, dw.la_reserve - 1 - LA_G1) : dw.la_reserve - 1 - LA_G1;
+	const Switches &sw = switches();
+	a.g2 = sw.la_g2 > 0 ? std::min(sw.la_g2, dw.la_reserve - 1 - LA_G1) : dw.la_reserve - 1 - LA_G1;
 	a.tinv_all = dw.tinv_all.p;
 	a.info = dw.info.p;
 	const size_t nints = (la_counter_ints(a.nsteps, a.nt) + 3) & ~(size_t)3;
 	dw.la_cnt.reserve(nints);
 	a.cnt = dw.la_cnt.p;
 	a.abort = dw.info.p + 2;
-	a.timeout_ticks = (long long)(500.0 * 1e5);
-	a.bulk_acquire = acq;
-	{
-		static int u = -1;
-		if(u < 0) {
-			const char *e = getenv("SPP_TILE_444");
-			u = e ? atoi(e) : 0;
-		}
-		static uint64_t bulk_attr_seen = 0;
-		if(first_on_this_device(bulk_attr_seen))
-			SPP_HIP_CHECK(hipFuncSetAttribute((const void*)la_bulk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-				LA_BULK_LDS_DOUBLES * (int)sizeof(double)));
-		a.use444 = u;
-	}
+	a.timeout_ticks = WAIT_TICKS_DEFAULT;
+	a.bulk_acquire = sw.la_bulk_acquire;
+	a.use444 = sw.tile_444;
+	static uint64_t bulk_attr_seen = 0;
+	if(first_on_this_device(bulk_attr_seen))
+		SPP_HIP_CHECK(hipFuncSetAttribute((const void*)la_bulk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+			LA_BULK_LDS_DOUBLES * (int)sizeof(double)));
 	a.trace = nullptr;
 	static int la_calls = 0;
-	const bool tracing = trace_n > 0 && ++ la_calls == trace_n;
+	const bool tracing = sw.la_trace > 0 && ++ la_calls == sw.la_trace;
 	if(tracing) {
 		const size_t nw = (size_t)12 * nsteps + 16;
 		dw.la_trace.reserve(nw);
@@ -1412,7 +1379,7 @@ static void dense_factor_lookahead(spp_ctx *ctx, double *d_A, int64_t ld, int64_
 	SPP_HIP_CHECK(hipStreamWaitEvent(sc, dw.ev[0], 0));
 	SPP_HIP_CHECK(hipStreamWaitEvent(sb, dw.ev[0], 0));
 	hipLaunchKernelGGL(la_chain_kernel, dim3((unsigned)(1 + LA_G1 + a.g2)), dim3(LA_THREADS), LA_LDS_DOUBLES * sizeof(double), sc, a);
-	const int64_t slots = slots_env > 0 ? slots_env : 512; // the first multiple of this many tiles of a launch go whole, the rest in quarters
+	const int64_t slots = sw.la_slots > 0 ? sw.la_slots : 512; // the first multiple of this many tiles of a launch go whole, the rest in quarters
 	for(int k = 0; k < a.nsteps; ++ k) {
 		const int64_t c1 = (int64_t)NB * (k + 1);
 		if(c1 >= ncols || rows - c1 <= 0)
@@ -1459,16 +1426,15 @@ void dense_factor_steps(spp_ctx *ctx, double *d_A, int64_t ld, int64_t n, int64_
 {
 	ensure_dense_work(ctx, nsteps);
 	ctx->dense.tail_rows_last = 0;
-	hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-	const bool capturing = hipStreamIsCapturing(ctx->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
-	if(!capturing && la_usable(ctx, nsteps)) { // lookahead: persistent chain kernel + one bulk launch per step
+	const bool captured = capturing(ctx->stream);
+	if(!captured && la_usable(ctx, nsteps)) { // lookahead: persistent chain kernel + one bulk launch per step
 		dense_factor_lookahead(ctx, d_A, ld, n, rows, ncols, nsteps, has_rhs);
 		ctx->dense.tinv_half = 0; // (its chain stores whole inverses)
 		return;
 	}
 	ctx->dense.tinv_half = nsteps;
-	const bool flags = !capturing && nsteps >= 4 && flag_schedule_usable(ctx); // cross-stream hand-offs through device flags instead of events
-	dense_factor_steps_enqueue(ctx, d_A, ld, n, rows, ncols, nsteps, has_rhs, flags, !capturing);
+	const bool flags = !captured && nsteps >= 4 && flag_schedule_usable(ctx); // cross-stream hand-offs through device flags instead of events
+	dense_factor_steps_enqueue(ctx, d_A, ld, n, rows, ncols, nsteps, has_rhs, flags, !captured);
 }
 
 static void flag_signal(hipStream_t st, int *flag, int value)
@@ -1476,29 +1442,30 @@ static void flag_signal(hipStream_t st, int *flag, int value)
 	hipLaunchKernelGGL(flag_signal_kernel, dim3(1), dim3(64), 0, st, flag, value);
 }
 
-static FlagWait make_flag_wait(spp_ctx *ctx, const int *flag, int value, double timeout_ms = 500.0)
+static FlagWait make_flag_wait(spp_ctx *ctx, const int *flag, int value, long long timeout_ticks = WAIT_TICKS_DEFAULT)
 {
-	return FlagWait{flag, value, ctx->dense.info.p + 2, (long long)(timeout_ms * 1e5)};
+	return FlagWait{flag, value, ctx->dense.info.p + 2, timeout_ticks};
 }
 
-static void flag_wait(spp_ctx *ctx, hipStream_t st, const int *flag, int value, double timeout_ms)
+static void flag_wait(spp_ctx *ctx, hipStream_t st, const int *flag, int value, long long timeout_ticks)
 {
-	hipLaunchKernelGGL(flag_wait_kernel, dim3(1), dim3(64), 0, st, make_flag_wait(ctx, flag, value, timeout_ms));
+	hipLaunchKernelGGL(flag_wait_kernel, dim3(1), dim3(64), 0, st, make_flag_wait(ctx, flag, value, timeout_ticks));
 }
 
-// Do the chain stream and the bulk stream run concurrently? Both directions are tried with the WAIT ENQUEUED
-// FIRST: two streams that share a hardware queue would make a waiter block its own signaller; such a pair times
-// out here (20 ms) and the event schedule stays in use for this ctx stream.
-static bool flag_schedule_selftest(spp_ctx *ctx)
+// Do two streams run concurrently? Both directions are tried with the WAIT ENQUEUED FIRST (flags sync[slot],
+// sync[slot + 1]): two streams that share a hardware queue would make a waiter block its own signaller; such a pair
+// times out here (20 ms) -- for the chain stream and the bulk stream the event schedule then stays in use for this
+// ctx stream, for the lookahead schedule's two streams that schedule stays off.
+static bool streams_concurrent(spp_ctx *ctx, hipStream_t a, hipStream_t b, int slot)
 {
 	DenseWork &dw = ctx->dense;
-	hipStream_t st[2] = {ctx->stream, dw.aux};
+	hipStream_t st[2] = {a, b};
 	dw.sync.reserve(16);
 	SPP_HIP_CHECK(hipMemsetAsync(dw.sync.p, 0, 16 * sizeof(int), ctx->stream));
 	SPP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
 	for(int p = 0; p < 2; ++ p) {
-		flag_wait(ctx, st[p], dw.sync.p + p, 1, 20.0);
-		flag_signal(st[1 - p], dw.sync.p + p, 1);
+		flag_wait(ctx, st[p], dw.sync.p + slot + p, 1, 20 * WAIT_TICKS_PER_MS);
+		flag_signal(st[1 - p], dw.sync.p + slot + p, 1);
 	}
 	for(int i = 0; i < 2; ++ i)
 		SPP_HIP_CHECK(hipStreamSynchronize(st[i]));
@@ -1513,32 +1480,16 @@ static bool flag_schedule_selftest(spp_ctx *ctx)
 
 static bool flag_schedule_usable(spp_ctx *ctx)
 {
-	static int sched = -1;
-	if(sched < 0) {
-		const char *e = getenv("SPP_DENSE_SCHED"); // 0: cross-stream events (round 1), 1: device flags
-		sched = e ? atoi(e) : 1;
-	}
-	if(!sched)
+	if(!switches().dense_sched)
 		return false;
 	DenseWork &dw = ctx->dense;
 	if(dw.sync_state == 0 || dw.sync_stream != ctx->stream) {
-		hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-		if(hipStreamIsCapturing(ctx->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)
+		if(capturing(ctx->stream))
 			return false; // no self-test (host synchronization) inside a capture
-		dw.sync_state = flag_schedule_selftest(ctx) ? 1 : -1;
+		dw.sync_state = streams_concurrent(ctx, ctx->stream, dw.aux, 0) ? 1 : -1;
 		dw.sync_stream = ctx->stream;
 	}
 	return dw.sync_state == 1;
-}
-
-static int dense_tail_rows()
-{
-	static int v = -1;
-	if(v < 0) {
-		const char *e = getenv("SPP_TAIL_ROWS"), *on = getenv("SPP_DENSE_TAIL");
-		v = (on && !atoi(on)) ? 0 : (e ? atoi(e) : 44);
-	}
-	return v;
 }
 
 // the streamed tail only takes over a full factorization (every tile row a pivot block, no identity-padded pivots)
@@ -1552,29 +1503,20 @@ static bool dense_tail_applies(spp_ctx *ctx, int64_t rows, int64_t nsteps)
 // for one workgroup per CU. Returns false when it does not apply (the per-step schedule goes on).
 static bool launch_dense_tail(spp_ctx *ctx, double *d_A, int64_t ld, int64_t rows, int64_t ncols, int64_t nsteps, int64_t k, bool has_rhs)
 {
-	static int enabled = -1;
-	if(enabled < 0) {
-		const char *e = getenv("SPP_DENSE_TAIL"); // 1: the streamed tail; 0: the per-step single-stream tail of round 2
-		enabled = e ? atoi(e) : 1;
-	}
+	const Switches &sw = switches();
 	DenseWork &dw = ctx->dense;
 	const int64_t c1 = (k + 1) * NB; // (k = -1: the whole factorization, no row panel in front of it)
-	if(!enabled || dw.tail_disabled || k + 1 >= nsteps || nsteps * NB < rows || (dw.ident_from >= 0 && dw.ident_from < rows))
+	if(!dense_tail_applies(ctx, rows, nsteps))
 		return false;
 	const int Tr = (int)(nsteps - (k + 1)), Tc = (int)((ncols - c1 + NB - 1) / NB);
-	if(Tr < 1 || Tc < Tr || Tc > Tr + 1 || Tc > TAIL_MAX_ROWS)
+	if(Tr < 1 || Tr > sw.tail_rows || Tc < Tr || Tc > Tr + 1 || Tc > TAIL_MAX_ROWS) // (tail_rows is 0 with the streamed tail switched off)
 		return false;
 	// (more tiles than CUs are fine: workgroups are dispatched row by row and leave after their own step, a workgroup that
 	// starts late finds the row tiles of the steps it missed in memory and catches up at the speed of its matrix cores)
 	// The step words of the region: bit j of bits[i + 1] = tile (i, j) of the region is nonzero, bits[0] = the row panel
 	// in front of it. From the caller's filled mask of the whole matrix (global tile indices, one word per tile row) --
 	// a sub-pattern of a filled pattern that starts at a later step is filled too --, or every tile.
-	static int use_mask = -1;
-	if(use_mask < 0) {
-		const char *e = getenv("SPP_TAIL_MASK"); // 0: every tile, whatever structure the caller knows (A/B timing, tests)
-		use_mask = e ? atoi(e) : 1;
-	}
-	const std::vector<uint64_t> *mask = (use_mask && dw.tile_mask && (int64_t)dw.tile_mask->size() == nsteps) ? dw.tile_mask : nullptr;
+	const std::vector<uint64_t> *mask = (sw.tail_mask && dw.tile_mask && (int64_t)dw.tile_mask->size() == nsteps) ? dw.tile_mask : nullptr;
 	std::vector<uint64_t> bits((size_t)Tr + 1);
 	const uint64_t all_cols = Tc == 64 ? ~0ull : (1ull << Tc) - 1;
 	for(int i = -1; i < Tr; ++ i) {
@@ -1584,13 +1526,6 @@ static bool launch_dense_tail(spp_ctx *ctx, double *d_A, int64_t ld, int64_t row
 			w = (w | (1ull << i)) & ~((1ull << i) - 1); // the diagonal tile always, nothing below it
 		bits[(size_t)i + 1] = w & all_cols;
 	}
-	static int max_rows = -1;
-	if(max_rows < 0) {
-		const char *e = getenv("SPP_TAIL_ROWS"); // tile rows from which on the factorization is streamed
-		max_rows = e ? atoi(e) : 44;
-	}
-	if(Tr > max_rows)
-		return false;
 	hipStream_t s = ctx->stream;
 	static uint64_t attr_seen = 0;
 	if(first_on_this_device(attr_seen))
@@ -1614,11 +1549,7 @@ static bool launch_dense_tail(spp_ctx *ctx, double *d_A, int64_t ld, int64_t row
 	if(dw.tail_order_tr != Tr || dw.tail_order_tc != Tc || dw.tail_order_bits != bits) {
 		if(!dw.tail_order_host.empty())
 			SPP_HIP_CHECK(hipStreamSynchronize(s)); // (an upload of the table's former host image may still be reading it)
-		static double beta = -1;
-		if(beta < 0) {
-			const char *e = getenv("SPP_TAIL_ORDER_BETA");
-			beta = e ? atof(e) : 0.0;
-		}
+		const double beta = sw.tail_order_beta;
 		std::vector<std::pair<double, int> > key;
 		for(int i = 0; i < Tr; ++ i)
 			for(int j = i; j < Tc; ++ j)
@@ -1655,21 +1586,11 @@ static bool launch_dense_tail(spp_ctx *ctx, double *d_A, int64_t ld, int64_t row
 	a.epoch = dw.tail_epoch;
 	a.info = dw.info.p;
 	a.abort = dw.info.p + 2;
-	static long long tail_timeout = -1;
-	if(tail_timeout < 0) {
-		const char *e = getenv("SPP_TAIL_TIMEOUT_TICKS"); // tests: a tiny value forces the timeout and the per-step fallback
-		tail_timeout = e ? atoll(e) : (long long)(500.0 * 1e5); // 500 ms of the 100 MHz wall clock
-	}
-	a.timeout_ticks = tail_timeout;
-	static int trace_env = -1;
-	if(trace_env < 0) {
-		const char *e = getenv("SPP_TAIL_TRACE"); // n: the n-th launch prints per tile row when its diagonal tile had all updates, was factored, and when the first panel tile started / ended
-		trace_env = e ? atoi(e) : 0;
-	}
+	a.timeout_ticks = sw.tail_timeout_ticks;
 	static int launches = 0;
 	DevBuf<long long> trace;
 	a.trace = nullptr;
-	if(trace_env && ++ launches == trace_env) {
+	if(sw.tail_trace && ++ launches == sw.tail_trace) {
 		trace.reserve((size_t)Tr * 8);
 		SPP_HIP_CHECK(hipMemsetAsync(trace.p, 0, (size_t)Tr * 8 * sizeof(long long), s));
 		a.trace = trace.p;
@@ -1800,12 +1721,7 @@ static void dense_factor_steps_enqueue(spp_ctx *ctx, double *d_A, int64_t ld, in
 	bool bulk_pending = false;
 	// Fused chain kernel (update_potrf_kernel): the update of a row region from panel kp and the factorization of the
 	// region's first diagonal block (step kn) in one launch; the panel solve of step kn follows as its own launch.
-	static int fused_env = -1;
-	if(fused_env < 0) {
-		const char *e = getenv("SPP_FUSED"); // 0: tile row / update, potrf_diag and panel solve as three launches (round 1)
-		fused_env = e ? atoi(e) : 1;
-	}
-	const int fused = allow_fused ? fused_env : 0; // (its sub-tile counters are monotonic: not inside a stream capture)
+	const int fused = allow_fused ? switches().fused : 0; // (its sub-tile counters are monotonic: not inside a stream capture)
 	if(fused) {
 		static uint64_t fattr_seen = 0;
 		if(first_on_this_device(fattr_seen)) {
@@ -1841,7 +1757,7 @@ static void dense_factor_steps_enqueue(spp_ctx *ctx, double *d_A, int64_t ld, in
 		hipLaunchKernelGGL(update_potrf_kernel, dim3((unsigned)(nA + do_potrf + nbi * nbj)), dim3(POTRF_THREADS),
 			POTRF_LDS_DOUBLES * sizeof(double), s, m, N, d_A + kp0 + r0 * ld, ld, d_A + r0 + r0 * ld, nA, dw.fuse_expect[slot], do_potrf,
 			n_valid, (has_rhs && n_valid < NB) ? 1 : 0, dw.tinv_all.p + (size_t)(kn >= 0 ? kn : 0) * NB * NB, dw.info.p, kn0,
-			dw.fuse_cnt.p + slot, dw.info.p + 2, (long long)(500.0 * 1e5));
+			dw.fuse_cnt.p + slot, dw.info.p + 2, WAIT_TICKS_DEFAULT);
 		return true;
 	};
 	auto potrf_and_panel = [&](int64_t k, bool potrf_done = false) {
@@ -1863,7 +1779,7 @@ static void dense_factor_steps_enqueue(spp_ctx *ctx, double *d_A, int64_t ld, in
 		flush_wait_b();
 		launch_gemm_staged<32, 32, 16, 16, 0>(s, m, ncols - r0, NB, P, ld, P, ld, d_A + r0 + r0 * ld, ld, true);
 	};
-	if(allow_fused && nsteps >= 2 && dense_tail_rows() * NB >= rows && dense_tail_applies(ctx, rows, nsteps) &&
+	if(allow_fused && nsteps >= 2 && switches().tail_rows * NB >= rows && dense_tail_applies(ctx, rows, nsteps) &&
 		launch_dense_tail(ctx, d_A, ld, rows, ncols, nsteps, -1, has_rhs)) {
 		dw.tinv_half = 0; // the whole factorization streamed: every block inverse is complete
 		SPP_HIP_CHECK(hipGetLastError());
@@ -1875,7 +1791,7 @@ static void dense_factor_steps_enqueue(spp_ctx *ctx, double *d_A, int64_t ld, in
 		const int64_t k0 = k * NB, c1 = k0 + NB, c2 = c1 + NB;
 		if(c1 >= ncols || rows - c1 <= 0)
 			break;
-		if(rows - c1 <= single_below || (allow_fused && dense_tail_rows() * NB >= rows - c1 && dense_tail_applies(ctx, rows, nsteps))) {
+		if(rows - c1 <= single_below || (allow_fused && switches().tail_rows * NB >= rows - c1 && dense_tail_applies(ctx, rows, nsteps))) {
 			// small trailing matrix: the whole update is shorter than a cross-stream hand-off plus the tile row
 			if(bulk_pending) {
 				wait_b_now();
@@ -2085,19 +2001,9 @@ void dense_potrs_upper(spp_ctx *ctx, const double *d_R, int64_t n, int64_t ld, d
 		hipLaunchKernelGGL(tinv_finish_kernel, dim3((unsigned)ctx->dense.tinv_half), dim3(1024), 0, s, ctx->dense.tinv_all.p);
 		ctx->dense.tinv_half = 0;
 	}
-	static int chain = -1;
-	if(chain < 0) {
-		const char *e = getenv("SPP_TRSV_CHAIN"); // 2: the chain inside one workgroup (default), 1: a workgroup per hop (round 2), 0: a launch per hop (round 1)
-		chain = e ? atoi(e) : 2;
-	}
-	int use_chain = chain;
-	{
-		// both chain kernels tell one solve from the next by a kernel argument (epoch / check constant): a captured
-		// launch would replay it stale -- inside a stream capture the substitution is a launch per block row
-		hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-		if(hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)
-			use_chain = 0;
-	}
+	// both chain kernels tell one solve from the next by a kernel argument (epoch / check constant): a captured
+	// launch would replay it stale -- inside a stream capture the substitution is a launch per block row
+	const int use_chain = capturing(s) ? 0 : switches().trsv_chain;
 	if(use_chain == 2 && nblk > 1 && nblk <= 4096) {
 		DenseWork &dw = ctx->dense;
 		const size_t need = (size_t)nblk * NB * 4; // x and w, two words per element
@@ -2114,12 +2020,7 @@ void dense_potrs_upper(spp_ctx *ctx, const double *d_R, int64_t n, int64_t ld, d
 		// K repeats only after 2^63 solves (epoch is 64-bit)
 		const unsigned long long K = (2ull * (unsigned long long)dw.epoch + 1ull) * 0x9E3779B97F4A7C15ull;
 		TrsvPay *xpay = (TrsvPay*)dw.trsv_pay.p, *wpay = xpay + (size_t)nblk * NB;
-		static int mform = -1;
-		if(mform < 0) {
-			const char *e = getenv("SPP_TRSV_MFORM"); // 0: the chain applies R_{b, b+1} and Tinv_b itself (two tiles per hop)
-			mform = e ? atoi(e) : 1;
-		}
-		if(mform) {
+		if(switches().trsv_mform) {
 			if(dw.trsv_m.cap < (size_t)nblk * NB * NB)
 				dw.trsv_m.reserve((size_t)nblk * NB * NB);
 			static uint64_t attr_seen = 0;

@@ -18,6 +18,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include "../../include/spp_hip.h"
+#include "spp_switches.h"
 
 namespace spp {
 
@@ -51,7 +52,7 @@ struct VClock {
 	const char *who;
 	std::chrono::steady_clock::time_point t;
 	bool on;
-	explicit VClock(const char *w) : who(w), t(std::chrono::steady_clock::now()), on(getenv("SPP_VERBOSE") != nullptr) {}
+	explicit VClock(const char *w) : who(w), t(std::chrono::steady_clock::now()), on(switches().verbose) {}
 	void lap(const char *what)
 	{
 		if(!on)
@@ -486,18 +487,9 @@ inline void run_threads(int nt, F fn)
 
 inline int plan_threads(int64_t work)
 {
-	static int env = -1;
-	if(env < 0) {
-		const char *e = getenv("SPP_PLAN_THREADS"); // host threads of the symbolic phase (default: up to 16)
-		env = e ? std::max(1, atoi(e)) : 0;
-	}
-	static int64_t min_work = -1;
-	if(min_work < 0) {
-		const char *e = getenv("SPP_PLAN_MIN_WORK"); // (tests: 1 cuts even the smallest problem among the threads)
-		min_work = e ? std::max<int64_t>(1, atoll(e)) : (int64_t(1) << 18);
-	}
+	const int env = switches().plan_threads; // 0: automatic
 	int nt = env ? env : (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency()));
-	if(work < min_work)
+	if(work < switches().plan_min_work)
 		nt = 1; // small problems: a thread costs more than it saves
 	return std::min(nt, 64);
 }

@@ -927,15 +927,7 @@ static void schur_form_t(spp_ctx *ctx, const double *d_vals, const double *d_rhs
 	phase_end(ctx, SPP_PHASE_SCHUR_INV);
 	phase_begin(ctx, SPP_PHASE_SCHUR_GEMM);
 	if(sp.n_items) {
-		static int chunk_env = -1;
-		if(chunk_env < 0) {
-			// items per wave (0 = one persistent set of workgroups). Measured on the Venice shape: 1 -> 0.86 ms, 4...16 ->
-			// 0.98 ms, persistent 1.5 ms: the hardware's dynamic dispatch of one-item waves balances the uneven items
-			// (1 ... 2048 pairs) better than the software pipeline across items hides latency
-			const char *e = getenv("SPP_SACC_CHUNK");
-			chunk_env = e ? atoi(e) : 1;
-		}
-		int chunk = chunk_env;
+		int chunk = switches().sacc_chunk; // items per wave
 		if(chunk <= 0) // persistent: two workgroups per CU (the LDS images of 8 waves fill a CU)
 			chunk = (int)((sp.xcd_max_items + SACC_WAVES * 64 - 1) / (SACC_WAVES * 64));
 		const int64_t per = (int64_t)SACC_WAVES * chunk;
@@ -992,11 +984,7 @@ static int schur_finish_t(spp_ctx *ctx, const double *d_vals, double *S, double 
 	}
 	phase_begin(ctx, SPP_PHASE_BACKSUBST);
 	static_assert(DL <= DP, "the products U^T dx reuse the W l buffer (DP doubles per observation)");
-	static int bs_fused = -1;
-	if(bs_fused < 0) {
-		const char *e = getenv("SPP_BACKSUBST_FUSED"); // 0: the products U^T dx through memory, two launches (rounds 1-3)
-		bs_fused = e ? atoi(e) : 1;
-	}
+	const int bs_fused = switches().backsubst_fused;
 	const double *cinv_arg = (sp.factored && DL <= 3) ? (const double*)nullptr : (const double*)sp.cinv.p;
 	if(bs_fused && sp.n_bs > 0)
 		hipLaunchKernelGGL((backsubst_fused_kernel<DP, DL>), dim3((unsigned)sp.n_bs), dim3(256), 0, s,

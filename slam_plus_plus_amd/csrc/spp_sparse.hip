@@ -193,17 +193,15 @@ static const int NCLS = 5;
 // big fronts inside the dependency-driven launch (bigfront_team_body): threads and LDS of a team member
 constexpr int TEAM_THREADS = 1024;
 constexpr size_t TEAM_LDS_DOUBLES = (size_t)(NB + 16) * FS_STRIDE > (size_t)POTRF_LDS_DOUBLES ? (size_t)(NB + 16) * FS_STRIDE : (size_t)POTRF_LDS_DOUBLES;
-static const int MID_FRONT_MAX = 640; // largest padded height the one-workgroup in-place (HBM image) kernel is built for
-static const int MID_FRONT_DEFAULT = 320; // default split: fronts above go to the dense MFMA kernels
+// (MID_FRONT_MAX, the largest padded height the one-workgroup in-place kernel is built for: spp_switches.h, beside its switch)
 
 void sparse_analyze(spp_ctx *ctx, const Structure &st)
 {
 	const int64_t nb = st.nb;
+	const Switches &sw = switches();
 	// fronts above this padded height go to the dense MFMA kernels (one after the other, many workgroups
-	// each) instead of the one-workgroup in-place kernel; SPP_MID_FRONT_MAX tunes the split (128 .. 640; with the single-stream dense steps 320 measured best on sphere2500, neutral on the other sparse workloads)
-	int mid_front_max = MID_FRONT_DEFAULT;
-	if(const char *e = getenv("SPP_MID_FRONT_MAX"))
-		mid_front_max = std::max(128, std::min(MID_FRONT_MAX, atoi(e)));
+	// each) instead of the one-workgroup in-place kernel
+	const int mid_front_max = sw.mid_front_max;
 	sparse_release(ctx);
 	SparsePlan *sp = new SparsePlan;
 	ctx->sparse = sp;
@@ -273,8 +271,8 @@ void sparse_analyze(spp_ctx *ctx, const Structure &st)
 		// than 3x the block-level flops, or when it is simply better on both counts.
 		// SPP_ORDERING = amd | nd forces one of them. The two candidates (ordering + symbolic factorization each) are
 		// independent: they run side by side on two host threads.
-		const char *force = getenv("SPP_ORDERING");
-		const bool want_nd = force ? !strcmp(force, "nd") : (nb >= 256);
+		const bool force = sw.ordering != ORDERING_AUTO;
+		const bool want_nd = force ? sw.ordering == ORDERING_ND : (nb >= 256);
 		Symbolic y_amd, y_nd;
 		std::exception_ptr err_nd;
 		std::thread t_nd;
@@ -305,7 +303,7 @@ void sparse_analyze(spp_ctx *ctx, const Structure &st)
 		if(want_nd) {
 			take = force ? true : ((4 * y_nd.height < y_amd.height && y_nd.flops <= 3.0 * y_amd.flops) ||
 				(y_nd.height < y_amd.height && y_nd.flops <= 1.02 * y_amd.flops));
-			if(getenv("SPP_VERBOSE"))
+			if(sw.verbose)
 				fprintf(stderr, "[spp] ordering: amd height %lld flops %.3g | nd height %lld flops %.3g -> %s\n",
 					(long long)y_amd.height, y_amd.flops, (long long)y_nd.height, y_nd.flops, take ? "nd" : "amd");
 		}
@@ -373,15 +371,7 @@ void sparse_analyze(spp_ctx *ctx, const Structure &st)
 			// rows of s beyond its pivot block are a subset of the parent's rows (incl. its pivot block)
 			const int64_t zeros = ws * (hp - hs_beyond);
 			const int64_t merged_panel = (ws + wp) * (ws + hp);
-			static int64_t small_w = -1;
-			static double zero_frac = 0.12;
-			if(small_w < 0) {
-				const char *e = getenv("SPP_AMALG_SMALL"); // merged pivot widths up to this are always accepted
-				small_w = e ? atol(e) : 32;
-				if(const char *z = getenv("SPP_AMALG_ZEROS"))
-					zero_frac = atof(z);
-			}
-			const bool small = (ws + wp) <= small_w;
+			const bool small = (ws + wp) <= sw.amalg_small;
 			// ALL explicit zeros of the merged supernode count (those bought by earlier merges included):
 			// along a chain -- the elimination tree of a banded system -- the newly added zeros alone
 			// always look small next to the growing panel, and the whole chain would collapse into one
@@ -389,15 +379,7 @@ void sparse_analyze(spp_ctx *ctx, const Structure &st)
 			const int64_t ztot = zeros + cur_zeros[s] + cur_zeros[s + 1];
 			// (the looser bound only while the merged front stays small: a front of up to ~100 rows costs its latency, ~13 us,
 			// whatever its size, so fewer levels pay; above that the explicit zeros cost flops on the critical path)
-			static int64_t relax_h = -1;
-			static double zero_frac_small = 0.2;
-			if(relax_h < 0) {
-				const char *e = getenv("SPP_AMALG_RELAX_H");
-				relax_h = e ? atol(e) : 96;
-				if(const char *z = getenv("SPP_AMALG_ZEROS_SMALL"))
-					zero_frac_small = atof(z);
-			}
-			const double zf = (ws + hp <= relax_h) ? std::max(zero_frac, zero_frac_small) : zero_frac;
+			const double zf = (ws + hp <= sw.amalg_relax_h) ? std::max(sw.amalg_zeros, sw.amalg_zeros_small) : sw.amalg_zeros;
 			if(zeros == 0 || small || (double)ztot <= zf * (double)merged_panel) {
 				merged_into_next[s] = 1;
 				cur_w[s + 1] = ws + wp; // the merged supernode takes the parent's slot
@@ -546,9 +528,7 @@ void sparse_analyze(spp_ctx *ctx, const Structure &st)
 	std::vector<int64_t> front_tinv(ns, 0);
 	int64_t tinv_doubles = 0;
 	{
-		bool teams = true;
-		if(const char *e = getenv("SPP_SPARSE_TEAMS"))
-			teams = atoi(e) != 0;
+		bool teams = sw.sparse_teams;
 		// a team's counter barrier needs ALL of its members resident at once (one 1024-thread workgroup with ~137 KB of LDS
 		// per CU): never more members than half the CUs of this device (a partitioned or CU-masked device), and no teams
 		// at all on one that cannot hold a team of two beside the rest of the launch
@@ -574,12 +554,8 @@ void sparse_analyze(spp_ctx *ctx, const Structure &st)
 		std::stable_sort(fronts_in.begin(), fronts_in.end(), [&](int32_t a, int32_t b) {
 			return level[a] != level[b] ? level[a] < level[b] : front_cls[a] > front_cls[b]; });
 		dag_list_bwd.assign(fronts_in.rbegin(), fronts_in.rend()); // parents first
-		int team_max = 40, team_cols = 16; // measured on sphere2500: 12 / 64 -> 1.55 ms, 24 / 32 -> 1.34, 32 / 16 -> 1.27, 48 / 16 -> 1.26, 64 / 8 -> 1.36
-		if(const char *e = getenv("SPP_SPARSE_TEAM_MAX"))
-			team_max = std::max(1, std::min(64, atoi(e)));
-		team_max = std::max(2, std::min(team_max, team_cap));
-		if(const char *e = getenv("SPP_SPARSE_TEAM_COLS")) // columns of the padded front per member
-			team_cols = std::max(8, std::min(256, atoi(e)));
+		// (defaults 40 / 16; measured on sphere2500: 12 / 64 -> 1.55 ms, 24 / 32 -> 1.34, 32 / 16 -> 1.27, 48 / 16 -> 1.26, 64 / 8 -> 1.36)
+		const int team_max = std::max(2, std::min(sw.sparse_team_max, team_cap)), team_cols = sw.sparse_team_cols;
 		for(size_t i = 0; i < fronts_in.size(); ++ i) {
 			const int32_t q = fronts_in[i];
 			int G = 1;
@@ -705,7 +681,7 @@ void sparse_analyze(spp_ctx *ctx, const Structure &st)
 		for(int32_t e = 0; e < pdim[k]; ++ e)
 			perm_scalar[pbase[k] + e] = (int32_t)(st.base[order[k]] + e);
 
-	if(getenv("SPP_VERBOSE")) {
+	if(sw.verbose) {
 		int64_t hist[8] = {0}; // h <= 16, 32, 64, 128, 256, 512, 1024, more
 		double fl_hist[8] = {0};
 		int32_t hmax = 0, wmax = 0;
@@ -1650,12 +1626,7 @@ static void sparse_enqueue(spp_ctx *ctx, const double *d_vals, double *d_rhs)
 	phase_begin(ctx, SPP_PHASE_FACTOR);
 	// P b: every front takes its pivot rows of it as its right-hand-side column
 	hipLaunchKernelGGL(gather_perm_kernel, dim3(gn), dim3(256), 0, s, sp->n, sp->perm_scalar.p, d_rhs, sp->xperm.p);
-	static int use_dag = -1;
-	if(use_dag < 0) {
-		const char *e = getenv("SPP_SPARSE_DAG"); // 0: one launch per level and size class (round 1 / 2 schedule)
-		use_dag = e ? atoi(e) : 1;
-	}
-	const bool dag = use_dag && sp->dag_ok && sp->dag_n > 0;
+	const bool dag = switches().sparse_dag && sp->dag_ok && sp->dag_n > 0;
 	const int32_t first_level = dag ? sp->dag_level_limit : 0;
 	DagArgs da;
 	da.front_cls = sp->front_cls.p;
@@ -1664,12 +1635,7 @@ static void sparse_enqueue(spp_ctx *ctx, const double *d_vals, double *d_rhs)
 	da.done = sp->dag_done.p;
 	da.level_limit = sp->dag_level_limit;
 	da.abort = ctx->dense.info.p + 3;
-	static long long dag_timeout = -1;
-	if(dag_timeout < 0) {
-		const char *e = getenv("SPP_DAG_TIMEOUT_TICKS"); // debugging / tests: a tiny value forces the timeout fallback
-		dag_timeout = e ? atoll(e) : (long long)(500.0 * 1e5); // 500 ms of the 100 MHz wall clock
-	}
-	da.timeout_ticks = dag_timeout;
+	da.timeout_ticks = switches().dag_timeout_ticks;
 	da.epoch = 0;
 	da.level_first = 0;
 	da.list = nullptr;
@@ -1701,18 +1667,14 @@ static void sparse_enqueue(spp_ctx *ctx, const double *d_vals, double *d_rhs)
 		const int32_t skip = 0;
 		da.list = sp->dag_list.p + skip;
 		da.rank = sp->dag_rank.p + skip;
-		static int trace_left = -1;
-		if(trace_left < 0)
-			trace_left = getenv("SPP_DAG_TRACE") ? atoi(getenv("SPP_DAG_TRACE")) : 0;
+		static int trace_left = switches().dag_trace; // (a countdown, not the switch: the n-th factorization prints)
 		DevBuf<long long> trace_buf;
 		if(trace_left > 0) {
 			trace_buf.reserve((size_t)8 * sp->dag_n);
 			SPP_HIP_CHECK(hipMemsetAsync(trace_buf.p, 0, (size_t)8 * sp->dag_n * sizeof(long long), s));
 			da.trace = trace_buf.p;
 		}
-		static int split_env = -1;
-		if(split_env < 0)
-			split_env = getenv("SPP_DAG_SPLIT") ? atoi(getenv("SPP_DAG_SPLIT")) : 1;
+		const int split_env = switches().dag_split;
 		if(sp->dag_n > skip) {
 			FrontArgs fa = make_front_args(ctx, sp, d_vals);
 			fa.trace = da.trace;

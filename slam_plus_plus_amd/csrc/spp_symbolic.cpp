@@ -553,12 +553,8 @@ static void schur_plan_host(const Structure &st, int shard_rank, int shard_world
 	const int64_t n_pairs = lm_pairs[nl];
 	SPP_REQUIRE(n_pairs < (int64_t(1) << 31), SPP_E_UNSUPPORTED, "too many block products for 32-bit pair indices");
 	h.n_pairs = n_pairs;
-	{
-		const char *e = getenv("SPP_SACC_ULM");
-		h.u_landmark_major = e ? atoi(e) != 0 : true;
-		e = getenv("SPP_SACC_FACTORED"); // 0: two packed blocks per observation (W and U), as in rounds 1-2
-		h.factored = e ? atoi(e) != 0 : true;
-	}
+	h.u_landmark_major = switches().sacc_ulm;
+	h.factored = switches().sacc_factored;
 	RawBuf<int32_t> &pair_a = h.pair_a, &pair_b = h.pair_b;
 	pair_a.resize(n_pairs);
 	pair_b.resize(n_pairs);
@@ -748,26 +744,12 @@ static void schur_plan_host(const Structure &st, int shard_rank, int shard_world
 	bool interleave = false;
 	std::vector<int32_t> xb_il;
 	{
-		static int64_t tb_env = -1;
-		if(tb_env < 0) {
-			const char *e = getenv("SPP_SACC_TILE"); // cameras per side of an item tile (1 = plain row-major block order)
-			tb_env = e ? std::max<int64_t>(1, atol(e)) : 4;
-		}
-		static int64_t tbc_env = -1;
-		if(tbc_env < 0) {
-			const char *e = getenv("SPP_SACC_TILE_COLS"); // cameras per tile along a row of S (0: the whole row)
-			tbc_env = e ? atol(e) : -2;
-		}
+		const int64_t tb_env = switches().sacc_tile, tbc_env = switches().sacc_tile_cols; // (-2: as the tile's side)
 		const int64_t TB = tb_env, TBC = (tbc_env == -2) ? TB : (tbc_env <= 0 ? nc : tbc_env), ntile = (nc + TBC - 1) / TBC;
 		std::vector<int32_t> perm(item_blk.size());
 		for(size_t q = 0; q < perm.size(); ++ q)
 			perm[q] = (int32_t)q;
-		static int il_env = -1;
-		if(il_env < 0) {
-			const char *e = getenv("SPP_SACC_XCD"); // 1: tiles dealt round-robin to the XCDs, 0: one contiguous range per XCD
-			il_env = e ? atoi(e) : 1;
-		}
-		interleave = il_env != 0;
+		interleave = switches().sacc_xcd != 0;
 		std::vector<int64_t> tile_of_item(item_blk.size());
 		for(size_t q = 0; q < tile_of_item.size(); ++ q)
 			tile_of_item[q] = (sblk_i1[item_blk[q]] / TB) * ntile + sblk_i2[item_blk[q]] / TBC;
