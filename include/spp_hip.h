@@ -318,6 +318,15 @@ int spp_tile_mask_host(int64_t n, int bs, int64_t nblk, const int32_t *i1, const
  * "every tile", or a negative error. */
 int spp_schur_tile_mask_host(int64_t nb, const int32_t *dim, const int64_t *col_ptr, const int64_t *row_idx, int shard_rank,
 	int shard_world, uint64_t *words);
+/* host only: the workgroup order of the streamed dense factor for an n x n matrix (+ right-hand side column with has_rhs)
+ * whose FILLED tile mask is words[0 .. nwords) (nwords = ceil(n / 128), or 0: no mask, every tile): table[q] = (i << 16) | j,
+ * the tile workgroup q owns (room for 64 * 65 / 2 + 64 entries). resident: workgroups the device holds at once; early:
+ * the value of SPP_TAIL_EARLY to apply; beta: the order key i + beta j (SPP_TAIL_ORDER_BETA, 0 = row by row). With a mask,
+ * early != 0 and the conditions of DESIGN section 11 met, the tiles of the trailing tile rows r* .. go first; otherwise
+ * the table is the sorted one. info (may be NULL, 5 entries): tiles in front, r* (tile rows when none), whole rows
+ * resident D, live demand of the other tiles, tiles of the widest row. Returns the number of entries or a negative error. */
+int spp_tail_order_host(int64_t n, int has_rhs, const uint64_t *words, int64_t nwords, int resident, int early, double beta,
+	int32_t *table, int32_t *info);
 /* C (m x n, ldc) -= A^T B with A: k x m (lda), B: k x n (ldb): the MFMA trailing-update kernel */
 int spp_dense_gemm_tn_sub(spp_ctx *ctx, int64_t m, int64_t n, int64_t k,
 	const double *d_A, int64_t lda, const double *d_B, int64_t ldb, double *d_C, int64_t ldc);

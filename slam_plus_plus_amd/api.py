@@ -34,7 +34,7 @@ EXPORTS = [
     "spp_device_free", "spp_memcpy_h2d", "spp_memcpy_d2h", "spp_memcpy_d2d", "spp_get_phase_ms", "spp_get_dominant_kernel",
     "spp_microbench_copy", "spp_microbench_mfma_f64", "spp_microbench_ctile", "spp_microbench_update", "spp_block_ordering", "spp_schur_plan_host", "spp_set_profiling", "spp_se2_linearize_device", "spp_se2_update_device", "spp_ba_linearize_device", "spp_ba_update_device", "spp_se3_linearize_device", "spp_se3_update_device", "spp_edge_chi2_device", "spp_edge_robust_weights_device", "spp_edge_hessian_maxdiag_device",
     "spp_lm_gain_denominator_device", "spp_dense_potrf_upper", "spp_dense_posv",
-    "spp_dense_posv_masked", "spp_tile_mask_host", "spp_schur_tile_mask_host",
+    "spp_dense_posv_masked", "spp_tile_mask_host", "spp_schur_tile_mask_host", "spp_tail_order_host",
     "spp_dense_gemm_tn_sub", "spp_dense_gemm_tn_sub_upper", "spp_dense_front_factor", "spp_version",
 ]
 
@@ -110,6 +110,7 @@ def load_library():
         "spp_dense_posv_masked": (cint, [vp, vp, i64, i64, vp, vp, i64]),
         "spp_tile_mask_host": (cint, [i64, cint, i64, vp, vp, cint, cint, vp, vp]),
         "spp_schur_tile_mask_host": (cint, [i64, vp, vp, vp, cint, cint, vp]),
+        "spp_tail_order_host": (cint, [i64, cint, vp, i64, cint, cint, dbl, vp, vp]),
         "spp_dense_gemm_tn_sub": (cint, [vp, i64, i64, i64, vp, i64, vp, i64, vp, i64]),
         "spp_dense_gemm_tn_sub_upper": (cint, [vp, i64, i64, i64, vp, i64, vp, i64, vp, i64]),
         "spp_dense_front_factor": (cint, [vp, vp, i64, i64, i64, vp]),
@@ -191,6 +192,24 @@ def schur_tile_mask_host(lam, shard_rank=0, shard_world=1):
     if code < 0:
         raise SppError("spp_schur_tile_mask_host failed: %d" % code)
     return words[:code].copy()
+
+
+def tail_order_host(n, words, has_rhs=True, resident=256, early=True, beta=0.0):
+    """Host-only: the workgroup -> tile table of the streamed dense factor for an n x n matrix with the filled tile mask
+    `words` (empty / None: no mask) on a device that holds `resident` workgroups (spp_tail_order_host). Returns
+    (tiles, info): tiles is a list of (i, j) in workgroup order, info a dict with n_early (tiles seated in front),
+    r_star (their first tile row; the number of tile rows when there are none), rows_resident (D), live_demand, widest.
+    No GPU needed."""
+    lib = load_library()
+    words = np.ascontiguousarray(words if words is not None else [], dtype=np.uint64)
+    table = np.zeros(64 * 65 // 2 + 64, dtype=np.int32)
+    info = np.zeros(5, dtype=np.int32)
+    code = lib.spp_tail_order_host(int(n), 1 if has_rhs else 0, _ptr(words) if words.size else None, words.size, int(resident),
+                                   1 if early else 0, float(beta), _ptr(table), _ptr(info))
+    if code < 0:
+        raise SppError("spp_tail_order_host failed: %d" % code)
+    tiles = [(int(t) >> 16, int(t) & 0xffff) for t in table[:code]]
+    return tiles, dict(zip(("n_early", "r_star", "rows_resident", "live_demand", "widest"), (int(v) for v in info)))
 
 
 class DeviceArray:

@@ -989,6 +989,34 @@ int spp_tile_mask_host(int64_t n, int bs, int64_t nblk, const int32_t *i1, const
 	}
 }
 
+int spp_tail_order_host(int64_t n, int has_rhs, const uint64_t *words, int64_t nwords, int resident, int early, double beta,
+	int32_t *table, int32_t *info)
+{
+	const int64_t Tr = (n + DENSE_NB - 1) / DENSE_NB, Tc = has_rhs ? n / DENSE_NB + 1 : Tr;
+	if(n <= 0 || Tr > 64 || Tc > 64 || nwords < 0 || (nwords && (!words || nwords != Tr)) || !table || !(beta >= 0))
+		return SPP_E_BADARG;
+	try {
+		// the step words as the streamed launch of a whole factorization forms them (launch_dense_tail, k = -1)
+		std::vector<uint64_t> bits((size_t)Tr + 1);
+		const uint64_t all_cols = Tc == 64 ? ~0ull : (1ull << Tc) - 1;
+		bits[0] = all_cols;
+		for(int64_t i = 0; i < Tr; ++ i)
+			bits[(size_t)i + 1] = (((nwords ? words[i] : all_cols) | (1ull << i)) & ~((1ull << i) - 1)) & all_cols;
+		std::vector<int> order;
+		int oinfo[5];
+		const bool use = nwords && early; // (as the launch: only with a mask in force)
+		tail_order_table(bits, (int)Tr, (int)Tc, false, beta, use ? resident : 0, use, order, oinfo);
+		for(size_t q = 0; q < order.size(); ++ q)
+			table[q] = order[q];
+		if(info)
+			for(int q = 0; q < 5; ++ q)
+				info[q] = oinfo[q];
+		return (int)order.size();
+	} catch(...) {
+		return SPP_E_NOMEM;
+	}
+}
+
 int spp_dense_posv_masked(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, double *d_b, const uint64_t *words, int64_t nwords)
 {
 	if(!ctx || !d_A || !d_b || n <= 0 || ld < n || nwords < 0 || (nwords && !words))

@@ -1546,24 +1546,38 @@ static bool launch_dense_tail(spp_ctx *ctx, double *d_A, int64_t ld, int64_t row
 	// beta >= 0 sorts the tiles topologically (producers before consumers: progress whatever is resident). Row by row
 	// (beta = 0) the 256 CUs start on the first ~6 rows, far tiles included, and the near-diagonal tiles of the rows
 	// behind them start late; beta > 0 holds the far columns back a little in favour of those.
-	if(dw.tail_order_tr != Tr || dw.tail_order_tc != Tc || dw.tail_order_bits != bits) {
+	// With a tile mask in force the tiles that every early step updates but that row by row get a CU many steps late (the
+	// trailing triangle of a bordered band) are seated first: tail_order_table() in spp_symbolic.cpp has the rule and the
+	// condition under which progress still holds -- it depends on how many workgroups the device holds at once. Without
+	// a mask the table is the sorted one.
+	const bool early = mask != nullptr && sw.tail_early != 0;
+	if(early && dw.tail_resident < 0) {
+		int per_cu = 0;
+		hipDeviceProp_t prop;
+		if(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)dense_tail_kernel, POTRF_THREADS,
+		   TAIL_LDS_DOUBLES * sizeof(double)) == hipSuccess && hipGetDeviceProperties(&prop, ctx->device) == hipSuccess)
+			dw.tail_resident = std::max(per_cu, 0) * prop.multiProcessorCount;
+		else {
+			(void)hipGetLastError();
+			dw.tail_resident = 0; // (unknown: nothing goes in front)
+		}
+	}
+	if(dw.tail_order_tr != Tr || dw.tail_order_tc != Tc || dw.tail_order_bits != bits || dw.tail_order_pre != (k >= 0) ||
+	   dw.tail_order_masked != early) {
 		if(!dw.tail_order_host.empty())
 			SPP_HIP_CHECK(hipStreamSynchronize(s)); // (an upload of the table's former host image may still be reading it)
-		const double beta = sw.tail_order_beta;
-		std::vector<std::pair<double, int> > key;
-		for(int i = 0; i < Tr; ++ i)
-			for(int j = i; j < Tc; ++ j)
-				if((bits[(size_t)i + 1] >> j) & 1) // (only nonzero tiles get a workgroup)
-					key.push_back(std::make_pair((double)i + beta * (double)j, (i << 16) | j));
-		std::stable_sort(key.begin(), key.end(), [](const std::pair<double, int> &x, const std::pair<double, int> &y) { return x.first < y.first; });
 		std::vector<int> &order = dw.tail_order_host; // (the asynchronous upload reads it after this call returns)
-		order.resize(key.size());
-		for(size_t q = 0; q < key.size(); ++ q)
-			order[q] = key[q].second;
+		int oinfo[5];
+		tail_order_table(bits, Tr, Tc, k >= 0, sw.tail_order_beta, early ? dw.tail_resident : 0, early, order, oinfo);
+		if(sw.verbose)
+			fprintf(stderr, "[spp] streamed tail: %d x %d tiles, %d listed, %d resident; %d tiles of rows %d.. seated first (whole rows resident %d, live demand %d)\n",
+				Tr, Tc, (int)order.size(), early ? dw.tail_resident : 0, oinfo[0], oinfo[1], oinfo[2], oinfo[3]);
 		dw.tail_order.upload(order, s);
 		dw.tail_order_tr = Tr;
 		dw.tail_order_tc = Tc;
 		dw.tail_order_bits = bits;
+		dw.tail_order_pre = k >= 0;
+		dw.tail_order_masked = early;
 	}
 	const int ntile = (int)dw.tail_order_host.size();
 	TailArgs a;

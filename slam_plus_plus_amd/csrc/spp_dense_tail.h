@@ -20,7 +20,10 @@
 // one lane (relaxed, agent scope) and reads the payload with agent-scope atomic loads (L2-bypassing on gfx950) -- no
 // fences. Counters carry the epoch of the factorization in their upper bits (no clearing between factorizations).
 // Workgroups are numbered row by row: whatever a workgroup waits for is produced by a workgroup
-// with a smaller index, which never waits for a larger one -- progress does not depend on residency. Every wait is bounded (abort word).
+// with a smaller index, which never waits for a larger one -- progress does not depend on residency. With a tile mask a
+// set E of trailing tile rows may be numbered in front of all others (tail_order_table, spp_symbolic.cpp): no tile outside
+// E waits for one of E, and the host uses E only when E and the live tiles outside it are resident together. Every wait
+// is bounded (abort word).
 // Summation order per tile: steps ascending, row tiles ascending -- fixed, bit-reproducible.
 // Structure: the launch takes one 64-bit word per step (bit j of word k = tile (k, j) of the FILLED pattern is nonzero,
 // spp_symbolic.cpp: tile_mask_close). Only tiles with their bit set have a workgroup; tile (i, j) applies step k only if

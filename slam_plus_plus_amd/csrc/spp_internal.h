@@ -285,6 +285,8 @@ struct DenseWork {
 	std::vector<int> tail_order_host; // its host image (the upload is asynchronous: it lives as long as the table)
 	int tail_order_tr = 0, tail_order_tc = 0;
 	std::vector<uint64_t> tail_order_bits; // ... and for these step words (the table is keyed by the tile mask as well)
+	bool tail_order_pre = false, tail_order_masked = false; // ... with / without a row panel in front, with / without a caller's mask
+	int tail_resident = -1;        // workgroups of the streamed launch the device holds at once (occupancy x CUs); -1: not asked yet
 	// Tile structure of the matrix the next factorization gets (set by the caller for that one call, TileMaskGuard): one
 	// word per tile row of 128, bit j = tile (i, j) is nonzero after symbolic fill (tile_mask_close). nullptr or a size
 	// that does not match the factorization's tile rows: every tile is nonzero.
@@ -433,6 +435,10 @@ struct TileMaskGuard { // hands a tile mask to the factorizations enqueued while
 void tile_mask_mark(int64_t n, int bs, int64_t nblk, const int32_t *i1, const int32_t *i2, std::vector<uint64_t> &words);
 int64_t tile_mask_close(int64_t n, bool has_rhs, bool fill, std::vector<uint64_t> &words);
 void schur_tile_mask_host_probe(const Structure &st, int shard_rank, int shard_world, std::vector<uint64_t> &words); // the mask a dense Schur plan carries
+// workgroup -> tile (i << 16 | j) of the streamed launch for the step words bits[0 .. Tr] of a region (host only,
+// spp_symbolic.cpp: the rule and the progress condition are stated there)
+void tail_order_table(const std::vector<uint64_t> &bits, int Tr, int Tc, bool have_pre, double beta, int resident, bool early,
+	std::vector<int> &order, int *info);
 // unit tests: the partial factorization of a big sparse front, laid out (identity padding after the w pivots) and
 // factored as the sparse path does; d_F (h x h, ld) <- the result in the unpadded layout, d_image (optional, ldp x hp with
 // ldp = (hp + 1) & ~1, hp = h + pad) <- the padded image

@@ -214,6 +214,93 @@ int64_t tile_mask_close(int64_t n, bool has_rhs, bool fill, std::vector<uint64_t
 	return updates;
 }
 
+// Workgroup -> tile of the streamed launch (spp_dense_tail.h). bits[k + 1], bit j: tile (k, j) of the region is listed,
+// bits[0]: the row panel in front of the region (step -1, applied only with have_pre).
+// Tile (i, j) needs row tiles of (k, i) and (k, j), k < i, so any key alpha i + beta j with alpha > 0, beta >= 0 sorts the
+// tiles topologically: that is the base order (beta = 0: row by row), and with !early the whole table.
+// early: a set E of tiles goes in front of it, those that the base order seats many steps after their first update is
+// out and that then run behind the chain until it has to wait for them.
+//   first(i, j) = the first step tile (i, j) applies (bits i and j of that step's word both set), its own row i if none;
+//   D = resident / (tiles of the widest listed row): whole rows the launch holds resident at its start;
+//   a tile lags if i - first(i, j) > D;
+//   E = the tiles of the longest run of trailing rows r* .. Tr - 1 in which every listed tile lags.
+// Consumers of a tile of row i lie in rows > i, so a trailing run of rows is closed under "consumer of": NO TILE OUTSIDE E
+// WAITS FOR A TILE OF E. The tiles outside E keep the base order among themselves -- topological --, so with E seated
+// they complete one after the other on whatever is left, and then E does (row by row inside E). Progress needs
+// resident > |E| instead of nothing at all; E is used only if
+//   |E| <= resident / 2   and   resident - |E| >= max over r of #{(i, j) outside E : first(i, j) <= r <= i}
+// (the live demand: tiles that have something to do while the chain is at row r), otherwise the table is the base
+// order, entry for entry. info (may be null): {|E|, r*, D, live demand, widest row} -- r* = Tr, |E| = 0 when E is not used.
+void tail_order_table(const std::vector<uint64_t> &bits, int Tr, int Tc, bool have_pre, double beta, int resident, bool early,
+	std::vector<int> &order, int *info)
+{
+	std::vector<std::pair<double, int> > key;
+	for(int i = 0; i < Tr; ++ i)
+		for(int j = i; j < Tc; ++ j)
+			if((bits[(size_t)i + 1] >> j) & 1) // (only nonzero tiles get a workgroup)
+				key.push_back(std::make_pair((double)i + beta * (double)j, (i << 16) | j));
+	std::stable_sort(key.begin(), key.end(), [](const std::pair<double, int> &x, const std::pair<double, int> &y) { return x.first < y.first; });
+	order.resize(key.size());
+	for(size_t q = 0; q < key.size(); ++ q)
+		order[q] = key[q].second;
+	int widest = 1;
+	for(int i = 0; i < Tr; ++ i)
+		widest = std::max(widest, (int)__builtin_popcountll(bits[(size_t)i + 1]));
+	const int D = std::max(resident, 0) / widest;
+	if(info) {
+		info[0] = 0;
+		info[1] = Tr;
+		info[2] = D;
+		info[3] = 0;
+		info[4] = widest;
+	}
+	if(!early || resident <= 0)
+		return;
+	auto first_step = [&](const int i, const int j) -> int {
+		for(int k = have_pre ? -1 : 0; k < i; ++ k) {
+			const uint64_t w = bits[(size_t)k + 1];
+			if((w >> i) & (w >> j) & 1)
+				return k;
+		}
+		return i;
+	};
+	int r_star = Tr;
+	for(int i = Tr - 1; i >= 0; -- i) {
+		bool all_lag = true;
+		for(int j = i; j < Tc && all_lag; ++ j)
+			if((bits[(size_t)i + 1] >> j) & 1)
+				all_lag = i - first_step(i, j) > D;
+		if(!all_lag)
+			break;
+		r_star = i;
+	}
+	int n_early = 0;
+	std::vector<int> live((size_t)Tr + 1, 0); // (as differences first: +1 at first(i, j), -1 behind row i)
+	for(size_t q = 0; q < order.size(); ++ q) {
+		const int i = order[q] >> 16, j = order[q] & 0xffff;
+		if(i >= r_star)
+			++ n_early;
+		else {
+			++ live[(size_t)std::max(first_step(i, j), 0)];
+			-- live[(size_t)i + 1];
+		}
+	}
+	int demand = 0;
+	for(int r = 0, run = 0; r < Tr; ++ r) {
+		run += live[(size_t)r];
+		demand = std::max(demand, run);
+	}
+	if(info)
+		info[3] = demand;
+	if(n_early == 0 || n_early > resident / 2 || resident - n_early < demand)
+		return;
+	std::stable_partition(order.begin(), order.end(), [r_star](const int t) { return (t >> 16) >= r_star; });
+	if(info) {
+		info[0] = n_early;
+		info[1] = r_star;
+	}
+}
+
 // the tiles of S = A - sum over landmarks of U C^-1 U^T, over the landmarks of ALL shards (the exchanged S is the sum
 // over the ranks): every camera-camera block of the structure and, per eliminated block, every pair of its observers
 static void schur_tile_mask(const Structure &st, const std::vector<uint8_t> &is_lm, const std::vector<int32_t> &pose_of,
