@@ -315,9 +315,18 @@ int spp_tile_mask_host(int64_t n, int bs, int64_t nblk, const int32_t *i1, const
 	uint64_t *words, int64_t *n_updates);
 /* host only: the filled tile mask the dense Schur plan of a block pattern (as spp_schur_plan_host takes it) hands to the
  * factorization of S; it covers the landmarks of every shard whatever shard_rank is. Returns the number of words, 0 for
- * "every tile", or a negative error. */
+ * "every tile", or a negative error. The mask is that of the natural camera order. */
 int spp_schur_tile_mask_host(int64_t nb, const int32_t *dim, const int64_t *col_ptr, const int64_t *row_idx, int shard_rank,
 	int shard_world, uint64_t *words);
+/* host only: the camera order the Schur plan of a block pattern uses for landmark shard shard_rank of shard_world (read
+ * back from that plan; every shard chooses the same) and the cost model of the streamed factor behind it. flags: 1 = sparse S, 2 = MIS (both keep the natural order). cam_order[position] = camera in
+ * natural numbering (room for every pose). figures (8 entries): listed tiles, rank-128 tile updates, critical path of
+ * diagonal tiles and modelled launch cost in microseconds of the NATURAL order, then the same four of the order used.
+ * order_in (may be NULL): a permutation of the cameras -- nothing is chosen, figures[4..7] are those of order_in.
+ * spp_schur_tile_mask_host keeps reporting the mask of the natural order. Returns 1 when the order used differs from the
+ * natural one, 0 when it does not, or a negative error. */
+int spp_schur_cam_order_host(int64_t nb, const int32_t *dim, const int64_t *col_ptr, const int64_t *row_idx, int shard_rank,
+	int shard_world, int flags, const int64_t *order_in, int64_t *cam_order, double *figures);
 /* host only: the workgroup order of the streamed dense factor for an n x n matrix (+ right-hand side column with has_rhs)
  * whose FILLED tile mask is words[0 .. nwords) (nwords = ceil(n / 128), or 0: no mask, every tile): table[q] = (i << 16) | j,
  * the tile workgroup q owns (room for 64 * 65 / 2 + 64 entries). resident: workgroups the device holds at once; early:

@@ -34,7 +34,7 @@ EXPORTS = [
     "spp_device_free", "spp_memcpy_h2d", "spp_memcpy_d2h", "spp_memcpy_d2d", "spp_get_phase_ms", "spp_get_dominant_kernel",
     "spp_microbench_copy", "spp_microbench_mfma_f64", "spp_microbench_ctile", "spp_microbench_update", "spp_block_ordering", "spp_schur_plan_host", "spp_set_profiling", "spp_se2_linearize_device", "spp_se2_update_device", "spp_ba_linearize_device", "spp_ba_update_device", "spp_se3_linearize_device", "spp_se3_update_device", "spp_edge_chi2_device", "spp_edge_robust_weights_device", "spp_edge_hessian_maxdiag_device",
     "spp_lm_gain_denominator_device", "spp_dense_potrf_upper", "spp_dense_posv",
-    "spp_dense_posv_masked", "spp_tile_mask_host", "spp_schur_tile_mask_host", "spp_tail_order_host",
+    "spp_dense_posv_masked", "spp_tile_mask_host", "spp_schur_tile_mask_host", "spp_tail_order_host", "spp_schur_cam_order_host",
     "spp_dense_gemm_tn_sub", "spp_dense_gemm_tn_sub_upper", "spp_dense_front_factor", "spp_version",
 ]
 
@@ -111,6 +111,7 @@ def load_library():
         "spp_tile_mask_host": (cint, [i64, cint, i64, vp, vp, cint, cint, vp, vp]),
         "spp_schur_tile_mask_host": (cint, [i64, vp, vp, vp, cint, cint, vp]),
         "spp_tail_order_host": (cint, [i64, cint, vp, i64, cint, cint, dbl, vp, vp]),
+        "spp_schur_cam_order_host": (cint, [i64, vp, vp, vp, cint, cint, cint, vp, vp, vp]),
         "spp_dense_gemm_tn_sub": (cint, [vp, i64, i64, i64, vp, i64, vp, i64, vp, i64]),
         "spp_dense_gemm_tn_sub_upper": (cint, [vp, i64, i64, i64, vp, i64, vp, i64, vp, i64]),
         "spp_dense_front_factor": (cint, [vp, vp, i64, i64, i64, vp]),
@@ -192,6 +193,34 @@ def schur_tile_mask_host(lam, shard_rank=0, shard_world=1):
     if code < 0:
         raise SppError("spp_schur_tile_mask_host failed: %d" % code)
     return words[:code].copy()
+
+
+def schur_cam_order_host(lam, order=None, sparse_S=False, mis=False, shard_rank=0, shard_world=1):
+    """Host-only: the camera order the dense Schur plan of a BlockCSC pattern uses and the tile-DAG cost model behind it
+    (spp_schur_cam_order_host); without `order` it is read back from the host plan of landmark shard shard_rank of
+    shard_world. Returns (cam_order, used, natural, chosen): cam_order[position] = camera in natural
+    numbering, used = it differs from the natural order, natural / chosen = dicts with tiles, updates, path (longest chain of
+    diagonal tiles) and cost_us of the two orders. With `order` (a permutation of the cameras) nothing is chosen and
+    `chosen` holds the model's figures of that order. No GPU needed."""
+    lib = load_library()
+    col_ptr = np.ascontiguousarray(lam.col_ptr, dtype=np.int64)
+    row_idx = np.ascontiguousarray(lam.row_idx, dtype=np.int64)
+    dim = np.ascontiguousarray(lam.dim, dtype=np.int32)
+    nc = int((dim == dim.max()).sum()) if not mis else int(dim.size)
+    out = np.full(max(nc, 1), -1, dtype=np.int64)   # (the MIS cut keeps fewer poses than blocks: trimmed below)
+    fig = np.zeros(8, dtype=np.float64)
+    oin = None if order is None else np.ascontiguousarray(order, dtype=np.int64)
+    if oin is not None and oin.size != nc:
+        raise SppError("schur_cam_order_host: order must list every camera once")
+    code = lib.spp_schur_cam_order_host(lam.nb, _ptr(dim), _ptr(col_ptr), _ptr(row_idx), shard_rank, shard_world,
+                                        (1 if sparse_S else 0) | (2 if mis else 0),
+                                        _ptr(oin) if oin is not None else None, _ptr(out), _ptr(fig))
+    if code < 0:
+        raise SppError("spp_schur_cam_order_host failed: %d" % code)
+    keys = ("tiles", "updates", "path", "cost_us")
+    natural = dict(zip(keys, (int(fig[0]), int(fig[1]), int(fig[2]), float(fig[3]))))
+    chosen = dict(zip(keys, (int(fig[4]), int(fig[5]), int(fig[6]), float(fig[7]))))
+    return out[out >= 0], bool(code), natural, chosen
 
 
 def tail_order_host(n, words, has_rhs=True, resident=256, early=True, beta=0.0):

@@ -506,6 +506,53 @@ int spp_schur_tile_mask_host(int64_t nb, const int32_t *dim, const int64_t *col_
 	}
 }
 
+// host only: the camera order the Schur plan of a structure and landmark shard uses, read back from that plan (flags: 1 sparse S, 2 MIS -- both keep the natural
+// order), cam_order[position] = camera in natural numbering; figures[0..3] = listed tiles, rank-128 updates, critical path
+// of diagonal tiles and modelled launch cost in us of the natural order, figures[4..7] the same of the order used. With
+// order_in (a permutation of the cameras) nothing is chosen: figures[4..7] are those of order_in. Returns 1 when the order
+// used is not the natural one, 0 when it is.
+int spp_schur_cam_order_host(int64_t nb, const int32_t *dim, const int64_t *col_ptr, const int64_t *row_idx, int shard_rank,
+	int shard_world, int flags, const int64_t *order_in, int64_t *cam_order, double *figures)
+{
+	if(nb <= 0 || !dim || !col_ptr || !row_idx || !cam_order || !figures || shard_world < 1 || shard_rank < 0 || shard_rank >= shard_world)
+		return SPP_E_BADARG;
+	try {
+		Structure st;
+		if(!structure_of_pattern(nb, dim, col_ptr, row_idx, st))
+			return SPP_E_BADARG;
+		if(order_in) {
+			int64_t nc = 0;
+			const int dmax = *std::max_element(dim, dim + nb);
+			for(int64_t j = 0; j < nb; ++ j)
+				nc += dim[j] == dmax;
+			std::vector<char> seen((size_t)nc, 0);
+			for(int64_t q = 0; q < nc; ++ q) {
+				if(order_in[q] < 0 || order_in[q] >= nc || seen[order_in[q]])
+					return SPP_E_BADARG;
+				seen[order_in[q]] = 1;
+			}
+		}
+		std::vector<int32_t> order;
+		TileDagCost cost[2];
+		const bool used = schur_cam_order_host_probe(st, shard_rank, shard_world, (flags & 1) != 0, (flags & 2) != 0, order_in, order, cost);
+		for(size_t q = 0; q < order.size(); ++ q)
+			cam_order[q] = order[q];
+		for(int side = 0; side < 2; ++ side) {
+			figures[4 * side] = (double)cost[side].tiles;
+			figures[4 * side + 1] = (double)cost[side].updates;
+			figures[4 * side + 2] = (double)cost[side].path;
+			figures[4 * side + 3] = cost[side].cost_us;
+		}
+		return used ? 1 : 0;
+	} catch(const Error &e) {
+		return e.code;
+	} catch(const std::bad_alloc &) {
+		return SPP_E_NOMEM;
+	} catch(...) {
+		return SPP_E_HIP;
+	}
+}
+
 int spp_schur_buffer_size(const spp_ctx *ctx, int64_t *n_doubles)
 {
 	if(!ctx || !n_doubles)

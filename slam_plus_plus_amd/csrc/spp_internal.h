@@ -206,7 +206,7 @@ struct SaccItem {
 	int32_t beg, end;  // pair range
 	int32_t kind;      // 0: dp x dp block of the dense S at element offset dst (leading dimension ld),
 	                   // 1: contiguous dp*dp values at S + dst (sparse reduced system), 2: partial slot at partial + dst
-	int32_t pad;
+	int32_t a_tr;      // 1: the A block is stored transposed (its cameras' positions are reversed by the camera order)
 	int64_t dst;
 	int64_t aoff;      // offset of the A block in vals that this item adds, or -1
 };
@@ -253,7 +253,7 @@ struct SchurPlan {
 	DevBuf<int32_t> xcd_beg;       // [9] item range of each XCD (equal work, not equal counts)
 	int32_t xcd_max_items = 0;     // longest of those ranges
 	DevBuf<int32_t> sblk_i1, sblk_i2; // [n_sblk]
-	DevBuf<int64_t> sblk_aoff;     // [n_sblk] offset of the A block in vals or -1
+	DevBuf<int64_t> sblk_aoff;     // [n_sblk] offset of the A block in vals or -1; -2 - offset: the block is stored transposed
 	DevBuf<int32_t> pair_a, pair_b; // [n_pairs]
 	DevBuf<int32_t> multi_blk;     // [n_multi] S block id of split blocks
 	DevBuf<int32_t> multi_ptr;     // [n_multi+1] slot range
@@ -434,7 +434,27 @@ struct TileMaskGuard { // hands a tile mask to the factorizations enqueued while
 // number of rank-128 tile updates of the filled pattern.
 void tile_mask_mark(int64_t n, int bs, int64_t nblk, const int32_t *i1, const int32_t *i2, std::vector<uint64_t> &words);
 int64_t tile_mask_close(int64_t n, bool has_rhs, bool fill, std::vector<uint64_t> &words);
-void schur_tile_mask_host_probe(const Structure &st, int shard_rank, int shard_world, std::vector<uint64_t> &words); // the mask a dense Schur plan carries
+void schur_tile_mask_host_probe(const Structure &st, int shard_rank, int shard_world, std::vector<uint64_t> &words); // the mask a dense Schur plan carries in the NATURAL camera order
+// Cost model of the streamed launch on a filled tile mask (host only, spp_symbolic.cpp: tile_dag_cost). The launch is
+// bound by its chain of diagonal tiles or by its tile updates, whichever is longer:
+//   cost = max(path * TAIL_MODEL_STEP_US, updates * TAIL_MODEL_UPDATE_US / resident) + TAIL_MODEL_START_US.
+// The constants are the measured ones of DESIGN sections 10 - 11 (profiles/r04_dense_tail_trace.txt, r06_dense_tail_trace.txt):
+// a step of the chain = 31 - 34 us of potrf_diag panels + 3 - 5 us of hand-over = 36.5 us; a tile applies a row tile
+// in 2.0 us when it only streams (2.6 us while it catches up, 4.6 us is the rate at which the chain emits them); the
+// launch starts 45 us before its first step ends; 256 resident workgroups (one per CU of an MI355X) -- a constant and
+// not the device's count, so that every rank and every host probe chooses the same camera order.
+constexpr double TAIL_MODEL_STEP_US = 36.5, TAIL_MODEL_UPDATE_US = 2.0, TAIL_MODEL_START_US = 45.0;
+constexpr int TAIL_MODEL_RESIDENT = 256;
+struct TileDagCost {
+	int64_t tiles = 0, updates = 0, path = 0; // listed tiles, rank-128 updates, longest chain of diagonal tiles
+	double cost_us = 0;
+};
+TileDagCost tile_dag_cost(int64_t n, const std::vector<uint64_t> &filled, int resident); // (filled: tile_mask_close(n, true, true))
+// host only: the camera order the Schur plan of a structure and shard uses, read back from that plan (cam_order[position] = camera in natural numbering)
+// and the model's figures of the natural order / of that order; order_in given: the figures of THAT order in cost[1],
+// nothing is chosen. Returns whether cam_order differs from the identity.
+bool schur_cam_order_host_probe(const Structure &st, int shard_rank, int shard_world, bool sparse_S, bool mis, const int64_t *order_in,
+	std::vector<int32_t> &cam_order, TileDagCost cost[2]);
 // workgroup -> tile (i << 16 | j) of the streamed launch for the step words bits[0 .. Tr] of a region (host only,
 // spp_symbolic.cpp: the rule and the progress condition are stated there)
 void tail_order_table(const std::vector<uint64_t> &bits, int Tr, int Tc, bool have_pre, double beta, int resident, bool early,

@@ -396,7 +396,7 @@ __device__ __forceinline__ SaccItem sacc_load_item(const SaccItem *__restrict__ 
 	SaccItem r;
 	r.beg = r.end = 0;
 	r.kind = -1;
-	r.pad = 0;
+	r.a_tr = 0;
 	r.dst = 0;
 	r.aoff = -1;
 	if(idx < lim)
@@ -479,9 +479,11 @@ void s_accum_kernel(const SaccItem *__restrict__ items, const int32_t *__restric
 		if(last) {
 			nn = sacc_load_item(items, (left > 2) ? idx + 2 * SACC_WAVES : lim, lim);
 			if(cur.aoff >= 0 && lane < NE2) {
-				aval0 = vals[cur.aoff + 2 * lane];
-				if(2 * lane + 1 < NE)
-					aval1 = vals[cur.aoff + 2 * lane + 1];
+				// (a block whose cameras the camera order reversed is stored transposed: element (r, c) of S reads (c, r))
+				const int e0 = 2 * lane, e1 = 2 * lane + 1;
+				aval0 = vals[cur.aoff + (cur.a_tr ? e0 / DP + (e0 % DP) * DP : e0)];
+				if(e1 < NE)
+					aval1 = vals[cur.aoff + (cur.a_tr ? e1 / DP + (e1 % DP) * DP : e1)];
 			}
 		}
 		// ---- cooperative fetch of up to 64 W and 64 U blocks into the LDS images
@@ -707,6 +709,8 @@ void s_multi_kernel(int64_t n_multi, const int32_t *__restrict__ multi_blk, cons
 	const int64_t aoff = sblk_aoff[b];
 	if(add_A && aoff >= 0)
 		acc = vals[aoff + lane] + acc;
+	else if(add_A && aoff < -1) // stored transposed (the camera order reversed its cameras)
+		acc = vals[(-2 - aoff) + lane / DP + (lane % DP) * DP] + acc;
 	if(sblk_voff) {
 		S[sblk_voff[b] + lane] = acc;
 		return;

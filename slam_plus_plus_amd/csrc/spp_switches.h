@@ -57,6 +57,7 @@ struct Switches {
 	int64_t sacc_tile_cols;   // SPP_SACC_TILE_COLS (-2 = as SPP_SACC_TILE): cameras per tile along a row of S (<= 0: the whole row)
 	int sacc_xcd;             // SPP_SACC_XCD (1): 1: tiles dealt round-robin to the XCDs, 0: one contiguous range per XCD
 	int sacc_chunk;           // SPP_SACC_CHUNK (1): items per wave (<= 0 = one persistent set of workgroups). Measured on the Venice shape: 1 -> 0.86 ms, 4...16 -> 0.98 ms, persistent 1.5 ms: the hardware's dynamic dispatch of one-item waves balances the uneven items (1 ... 2048 pairs) better than the software pipeline across items hides latency
+	int schur_cam_order;      // SPP_SCHUR_CAM_ORDER (1): dense S with a tile mask: the cameras of a closed loop are ordered arc, arc, separators (tile-aligned dissection, schur_cam_order) when the cost model of the streamed factor gains 10 %; 0: the natural order always
 	int backsubst_fused;      // SPP_BACKSUBST_FUSED (1): 0: the products U^T dx through memory, two launches (rounds 1-3)
 
 	// ---- sparse path (spp_sparse.hip)
@@ -126,6 +127,7 @@ inline Switches parse_switches()
 	w.sacc_tile_cols = env_i64("SPP_SACC_TILE_COLS", -2);
 	w.sacc_xcd = env_int("SPP_SACC_XCD", 1);
 	w.sacc_chunk = env_int("SPP_SACC_CHUNK", 1);
+	w.schur_cam_order = env_int("SPP_SCHUR_CAM_ORDER", 1);
 	w.backsubst_fused = env_int("SPP_BACKSUBST_FUSED", 1);
 
 	w.mid_front_max = std::max(128, std::min(MID_FRONT_MAX, env_int("SPP_MID_FRONT_MAX", 320)));

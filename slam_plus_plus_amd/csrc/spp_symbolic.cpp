@@ -325,7 +325,7 @@ static void schur_tile_mask(const Structure &st, const std::vector<uint8_t> &is_
 		for(int64_t p = st.col_ptr[j]; p < st.col_ptr[j + 1]; ++ p) {
 			const int64_t i = st.row_idx[p];
 			if(!is_lm[i] && !is_lm[j])
-				mark(tiles_of(pose_of[i]), tiles_of(pose_of[j])); // (i <= j and the stable partition: upper)
+				mark(tiles_of(pose_of[i]), tiles_of(pose_of[j])), mark(tiles_of(pose_of[j]), tiles_of(pose_of[i])); // (either sense: a camera order may reverse the two; tile_mask_close keeps the upper one)
 			else if(!is_lm[i])
 				seen[j] |= tiles_of(pose_of[i]);
 			else if(!is_lm[j])
@@ -335,6 +335,329 @@ static void schur_tile_mask(const Structure &st, const std::vector<uint8_t> &is_
 		if(seen[j])
 			mark(seen[j], seen[j]);
 	tile_mask_close(n_red, true, true, words);
+}
+
+// --------------------------------------------------------------------------------------------------
+// Camera order of a dense reduced system. The streamed dense factor is bound by its chain of
+// diagonal tiles; in the natural order of a closed camera loop (a band plus a wrap-around border) every tile row k has
+// tile (k - 1, k), so the chain is all tile rows. Ordered arc A, arc B, separators -- A and B not co-visible, B starting
+// on a tile boundary -- no listed tile couples the arcs and the shorter arc's diagonal tiles are factored beside the
+// longer one's.
+// --------------------------------------------------------------------------------------------------
+TileDagCost tile_dag_cost(int64_t n, const std::vector<uint64_t> &filled, int resident)
+{
+	TileDagCost c;
+	const int64_t Tr = (int64_t)filled.size();
+	std::vector<uint64_t> w(filled);
+	c.updates = tile_mask_close(n, true, true, w); // (closed already: counts the updates)
+	std::vector<int> depth((size_t)Tr, 1);
+	for(int64_t k = 0; k < Tr; ++ k) {
+		c.tiles += __builtin_popcountll(w[k]);
+		for(int64_t j = 0; j < k; ++ j)
+			if((w[j] >> k) & 1)
+				depth[k] = std::max(depth[k], depth[j] + 1);
+		c.path = std::max<int64_t>(c.path, depth[k]);
+	}
+	c.cost_us = std::max(c.path * TAIL_MODEL_STEP_US, c.updates * TAIL_MODEL_UPDATE_US / std::max(1, resident)) + TAIL_MODEL_START_US;
+	return c;
+}
+
+// co-visibility of the cameras in their natural numbering, a row of bits per camera (camera-camera blocks, pairs of
+// observers of an eliminated block, the camera itself); over the landmarks of ALL shards, like the tile mask
+struct CamGraph {
+	int64_t nc = 0, nw = 0;
+	std::vector<uint64_t> bits;
+	uint64_t *row(int64_t c) { return bits.data() + c * nw; }
+	const uint64_t *row(int64_t c) const { return bits.data() + c * nw; }
+};
+
+static void cam_graph(const Structure &st, const std::vector<uint8_t> &is_lm, const std::vector<int32_t> &cam_of, int64_t nc, CamGraph &g)
+{
+	g.nc = nc;
+	g.nw = (nc + 63) / 64;
+	g.bits.assign((size_t)(nc * g.nw), 0);
+	auto set = [&](int64_t a, int64_t b) { g.row(a)[b >> 6] |= 1ull << (b & 63); };
+	// observers per eliminated block (counting sort: an observation lies in the column of whichever of the two comes later)
+	std::vector<int64_t> ptr((size_t)st.nb + 1, 0);
+	for(int64_t j = 0; j < st.nb; ++ j)
+		for(int64_t p = st.col_ptr[j]; p < st.col_ptr[j + 1]; ++ p) {
+			const int64_t i = st.row_idx[p];
+			if(is_lm[i] != is_lm[j])
+				++ ptr[(is_lm[i] ? i : j) + 1];
+		}
+	for(int64_t j = 0; j < st.nb; ++ j)
+		ptr[j + 1] += ptr[j];
+	std::vector<int32_t> obs((size_t)ptr[st.nb]);
+	{
+		std::vector<int64_t> fill(ptr.begin(), ptr.end() - 1);
+		for(int64_t j = 0; j < st.nb; ++ j)
+			for(int64_t p = st.col_ptr[j]; p < st.col_ptr[j + 1]; ++ p) {
+				const int64_t i = st.row_idx[p];
+				if(!is_lm[i] && !is_lm[j]) {
+					set(cam_of[i], cam_of[j]);
+					set(cam_of[j], cam_of[i]);
+				} else if(is_lm[i] != is_lm[j])
+					obs[fill[is_lm[i] ? i : j] ++] = cam_of[is_lm[i] ? j : i];
+			}
+	}
+	// every observer's row takes the block's observer set (only the words it spans). Ranges of blocks on host threads, each
+	// into an image of its own (nc^2 bits: 93 KB at 871 cameras), the images are OR-ed afterwards
+	const int nt = plan_threads((int64_t)obs.size() * 4);
+	std::vector<int64_t> lcut;
+	balanced_cuts(ptr, nt, lcut);
+	std::vector<std::vector<uint64_t> > img((size_t)nt);
+	run_threads(nt, [&](int t) {
+		std::vector<uint64_t> &im = img[t];
+		im.assign(g.bits.size(), 0);
+		std::vector<uint64_t> tmp((size_t)g.nw, 0);
+		for(int64_t l = lcut[t]; l < lcut[t + 1]; ++ l) {
+			const int64_t b = ptr[l], e = ptr[l + 1];
+			if(b == e)
+				continue;
+			int64_t lo = g.nw, hi = -1;
+			for(int64_t q = b; q < e; ++ q) {
+				const int64_t w = obs[q] >> 6;
+				tmp[w] |= 1ull << (obs[q] & 63);
+				lo = std::min(lo, w);
+				hi = std::max(hi, w);
+			}
+			for(int64_t q = b; q < e; ++ q) {
+				uint64_t *r = im.data() + obs[q] * g.nw;
+				for(int64_t w = lo; w <= hi; ++ w)
+					r[w] |= tmp[w];
+			}
+			for(int64_t w = lo; w <= hi; ++ w)
+				tmp[w] = 0;
+		}
+	});
+	for(int t = 0; t < nt; ++ t)
+		for(size_t q = 0; q < g.bits.size(); ++ q)
+			g.bits[q] |= img[t][q];
+	for(int64_t c = 0; c < nc; ++ c)
+		set(c, c);
+}
+
+// the filled tile mask of the graph with camera c at position pos[c] (what schur_tile_mask gives for that order)
+static void cam_graph_mask(const CamGraph &g, const std::vector<int32_t> &pos, int dp, int64_t n_red, std::vector<uint64_t> &words)
+{
+	tile_mask_mark(n_red, dp, 0, nullptr, nullptr, words);
+	if(words.empty())
+		return;
+	const int64_t Tr = (int64_t)words.size();
+	std::vector<uint64_t> tl((size_t)g.nc);
+	for(int64_t c = 0; c < g.nc; ++ c)
+		tl[c] = (1ull << ((int64_t)pos[c] * dp / DENSE_NB)) | (1ull << (((int64_t)pos[c] * dp + dp - 1) / DENSE_NB));
+	for(int64_t c = 0; c < g.nc; ++ c) {
+		uint64_t cols = 0;
+		const uint64_t *r = g.row(c);
+		for(int64_t w = 0; w < g.nw; ++ w)
+			for(uint64_t m = r[w]; m; m &= m - 1)
+				cols |= tl[w * 64 + __builtin_ctzll(m)];
+		for(uint64_t rows = tl[c]; rows; rows &= rows - 1) {
+			const int a = __builtin_ctzll(rows);
+			if(a < Tr)
+				words[a] |= cols;
+		}
+	}
+	tile_mask_close(n_red, true, true, words);
+}
+
+// whether the streamed launch keeps its progress margin on this mask: the live-demand condition of tail_order_table
+static bool cam_order_live_ok(const std::vector<uint64_t> &filled, int64_t n_red)
+{
+	const int Tr = (int)filled.size(), Tc = (int)(n_red / DENSE_NB + 1);
+	std::vector<uint64_t> bits((size_t)Tr + 1);
+	bits[0] = Tc == 64 ? ~0ull : (1ull << Tc) - 1;
+	for(int i = 0; i < Tr; ++ i)
+		bits[(size_t)i + 1] = filled[i];
+	std::vector<int> order;
+	int info[5];
+	tail_order_table(bits, Tr, Tc, false, 0.0, TAIL_MODEL_RESIDENT, true, order, info);
+	return info[0] > 0 || info[3] <= TAIL_MODEL_RESIDENT; // the trailing rows are seated early, or everything live fits
+}
+
+// The rule. A LOOP is cut only: the first and the last camera of the natural order are co-visible (the natural order is
+// then a band plus a wrap-around border, and that border is a separator already). Candidates: arc A = the cameras
+// [a, a + m) of the natural order, m a multiple of the cameras between two tile boundaries; separator = the cameras A
+// sees -- on a loop, two runs --, B = all the others (so no block couples A and B), in one connected piece, cut down to a
+// whole number of tiles (its last cameras join the separator). An open chain, an arrow or two components keep the
+// natural order. The candidate that hides the most tile rows (the shorter of the two arcs is the longest) is taken, ties:
+// the smaller separator, B in one run of the natural order, the smaller m, a. Inside A, B and the separator the cameras
+// keep their natural order. Accepted only if the model's cost falls by a tenth and the live-demand condition holds;
+// otherwise order = identity. order[position] = camera.
+static bool cam_dissect(const CamGraph &g, int dp, int64_t n_red, std::vector<int32_t> &order, TileDagCost cost[2])
+{
+	const int64_t nc = g.nc, nw = g.nw;
+	order.resize((size_t)nc);
+	std::vector<int32_t> pos((size_t)nc);
+	for(int64_t c = 0; c < nc; ++ c)
+		order[c] = pos[c] = (int32_t)c;
+	std::vector<uint64_t> words;
+	cam_graph_mask(g, pos, dp, n_red, words);
+	if(words.empty())
+		return false;
+	cost[0] = cost[1] = tile_dag_cost(n_red, words, TAIL_MODEL_RESIDENT);
+	int64_t al = DENSE_NB;
+	for(int64_t x = dp, y = DENSE_NB; y; ) { // al = 128 / gcd(128, dp) cameras
+		const int64_t t = x % y;
+		x = y;
+		y = t;
+		if(!y)
+			al = DENSE_NB / x;
+	}
+	typedef std::vector<uint64_t> Set;
+	auto count = [&](const Set &x) { int64_t n = 0; for(int64_t w = 0; w < nw; ++ w) n += __builtin_popcountll(x[w]); return n; };
+	auto nbrs = [&](const Set &x, Set &out) { // union of the rows of x
+		out.assign((size_t)nw, 0);
+		for(int64_t w = 0; w < nw; ++ w)
+			for(uint64_t m = x[w]; m; m &= m - 1) {
+				const uint64_t *r = g.row(w * 64 + __builtin_ctzll(m));
+				for(int64_t v = 0; v < nw; ++ v)
+					out[v] |= r[v];
+			}
+	};
+	auto flood = [&](const Set &within, Set &comp) { // comp (a seed inside `within`) <- its connected piece of `within`
+		Set front(comp), nb;
+		for(;;) {
+			nbrs(front, nb);
+			bool grew = false;
+			for(int64_t w = 0; w < nw; ++ w) {
+				front[w] = nb[w] & within[w] & ~comp[w];
+				comp[w] |= front[w];
+				grew = grew || front[w];
+			}
+			if(!grew)
+				return;
+		}
+	};
+	auto first_bit = [&](const Set &x, Set &seed) {
+		seed.assign((size_t)nw, 0);
+		for(int64_t w = 0; w < nw; ++ w)
+			if(x[w]) {
+				seed[w] = x[w] & (~x[w] + 1);
+				return true;
+			}
+		return false;
+	};
+	Set all((size_t)nw, 0);
+	for(int64_t c = 0; c < nc; ++ c)
+		all[c >> 6] |= 1ull << (c & 63);
+	if(!((g.row(0)[(nc - 1) >> 6] >> ((nc - 1) & 63)) & 1))
+		return false; // the natural order does not close on itself: no loop
+	struct Cand { int64_t shorter = 0, sep = 0, runs = 0, a = 0, m = 0; } best;
+	Set A((size_t)nw), S, B((size_t)nw), bestA, bestB, comp;
+	const int64_t stride = std::max<int64_t>(1, al / 8);
+	for(int64_t m = al; 2 * m <= nc; m += al)
+		for(int64_t a = 0; a + m <= nc; a += stride) {
+			std::fill(A.begin(), A.end(), 0);
+			for(int64_t c = a; c < a + m; ++ c)
+				A[c >> 6] |= 1ull << (c & 63);
+			nbrs(A, S);
+			for(int64_t w = 0; w < nw; ++ w) {
+				S[w] &= ~A[w];
+				B[w] = all[w] & ~A[w] & ~S[w];
+			}
+			const int64_t nB = count(B), nBal = nB - nB % al;
+			if(nBal == 0)
+				continue;
+			Cand cd;
+			cd.shorter = std::min(m, nBal);
+			cd.sep = nc - m - nBal;
+			cd.a = a;
+			cd.m = m;
+			for(int64_t c = 0; c < nc; ++ c) // runs of consecutive cameras in B
+				cd.runs += ((B[c >> 6] >> (c & 63)) & 1) && !(c && ((B[(c - 1) >> 6] >> ((c - 1) & 63)) & 1));
+			if(best.m && !(cd.shorter > best.shorter || (cd.shorter == best.shorter && (cd.sep < best.sep ||
+			   (cd.sep == best.sep && cd.runs < best.runs)))))
+				continue; // (a and m ascend: the earlier candidate wins a full tie)
+			// B in one piece (an arrow or a second component would fall apart)
+			first_bit(B, comp);
+			flood(B, comp);
+			if(comp != B)
+				continue;
+			best = cd;
+			bestA = A;
+			bestB = B;
+		}
+	if(switches().verbose)
+		fprintf(stderr, "[spp] camera order: best arc a %lld m %lld shorter %lld sep %lld runs %lld\n", (long long)best.a,
+			(long long)best.m, (long long)best.shorter, (long long)best.sep, (long long)best.runs);
+	if(!best.m)
+		return false;
+	// positions: A, the first whole tiles of B, everything else; natural order inside each
+	const int64_t nBal = count(bestB) - count(bestB) % al;
+	std::vector<int32_t> cand_order;
+	cand_order.reserve((size_t)nc);
+	std::vector<uint8_t> placed((size_t)nc, 0);
+	for(int64_t c = 0; c < nc; ++ c)
+		if((bestA[c >> 6] >> (c & 63)) & 1) {
+			cand_order.push_back((int32_t)c);
+			placed[c] = 1;
+		}
+	for(int64_t c = 0, k = 0; c < nc && k < nBal; ++ c)
+		if((bestB[c >> 6] >> (c & 63)) & 1) {
+			cand_order.push_back((int32_t)c);
+			placed[c] = 1;
+			++ k;
+		}
+	for(int64_t c = 0; c < nc; ++ c)
+		if(!placed[c])
+			cand_order.push_back((int32_t)c);
+	for(int64_t q = 0; q < nc; ++ q)
+		pos[cand_order[q]] = (int32_t)q;
+	cam_graph_mask(g, pos, dp, n_red, words);
+	const TileDagCost c1 = tile_dag_cost(n_red, words, TAIL_MODEL_RESIDENT);
+	const bool live_ok = cam_order_live_ok(words, n_red);
+	if(switches().verbose)
+		fprintf(stderr, "[spp] camera order: candidate tiles %lld updates %lld chain %lld model %.0f us (natural %.0f), live ok %d\n",
+			(long long)c1.tiles, (long long)c1.updates, (long long)c1.path, c1.cost_us, cost[0].cost_us, (int)live_ok);
+	if(!(c1.cost_us <= 0.9 * cost[0].cost_us) || !live_ok)
+		return false;
+	cost[1] = c1;
+	order.swap(cand_order);
+	return true;
+}
+
+// the camera order of a plan: cam_order[position] = camera in natural numbering (cam_of[block column])
+static bool schur_cam_order(const Structure &st, const std::vector<uint8_t> &is_lm, const std::vector<int32_t> &cam_of, int64_t nc,
+	int dp, bool sparse_S, bool mis, const int64_t *order_in, std::vector<int32_t> &cam_order, TileDagCost cost[2])
+{
+	cam_order.resize((size_t)nc);
+	for(int64_t c = 0; c < nc; ++ c)
+		cam_order[c] = (int32_t)c;
+	cost[0] = cost[1] = TileDagCost();
+	const int64_t n_red = nc * dp;
+	// only where the streamed factor can work on a tile mask: dense S, at most 64 tile columns. (Not tied to SPP_TAIL_MASK:
+	// that switch promises the same bits with and without the mask, tests/test_gpu_dense_tilemask.py, so the order must
+	// not depend on it.)
+	if(sparse_S || mis || n_red / DENSE_NB + 1 > 64 || nc < 2 || (!order_in && !switches().schur_cam_order))
+		return false;
+	VClock clk("camera order");
+	CamGraph g;
+	cam_graph(st, is_lm, cam_of, nc, g);
+	clk.lap("co-visibility graph");
+	if(order_in) { // (probe: the model's figures of a given order)
+		std::vector<int32_t> pos((size_t)nc);
+		for(int64_t q = 0; q < nc; ++ q) {
+			cam_order[q] = (int32_t)order_in[q];
+			pos[order_in[q]] = (int32_t)q;
+		}
+		std::vector<uint64_t> words;
+		for(int side = 0; side < 2; ++ side) {
+			if(!side)
+				for(int64_t c = 0; c < nc; ++ c)
+					pos[c] = (int32_t)c;
+			else
+				for(int64_t q = 0; q < nc; ++ q)
+					pos[order_in[q]] = (int32_t)q;
+			cam_graph_mask(g, pos, dp, n_red, words);
+			cost[side] = tile_dag_cost(n_red, words, TAIL_MODEL_RESIDENT);
+		}
+		return false;
+	}
+	const bool used = cam_dissect(g, dp, n_red, cam_order, cost);
+	clk.lap("dissection + cost model");
+	return used;
 }
 
 // Everything build_schur_plan() derives from the block structure, in host memory: the pure symbolic part (no device,
@@ -355,6 +678,7 @@ struct SchurPlanHost {
 	std::vector<SaccItem> recs;
 	Structure s_st;
 	std::vector<uint64_t> tile_mask; // dense S: filled tile pattern (schur_tile_mask); empty: every tile
+	TileDagCost cam_cost[2];               // the model's figures of the natural order / of the order used
 };
 
 static void schur_plan_host(const Structure &st, int shard_rank, int shard_world, bool sparse_S, bool mis, SchurPlanHost &h)
@@ -377,6 +701,8 @@ static void schur_plan_host(const Structure &st, int shard_rank, int shard_world
 	h.dl = dl;
 
 	// ---- guided ordering: stable partition by width (LinearSolver_Schur.cpp:771-838)
+	// The cameras keep that (natural) order unless the camera order of a closed loop is accepted (schur_cam_order): from
+	// here on a pose is its POSITION, pose_of[] / pose_block[], and everything below goes through the two.
 	std::vector<int32_t> pose_of(st.nb, -1), lm_of(st.nb, -1);
 	int64_t nc = 0, nl_total = 0, nl = 0;
 	for(int64_t j = 0; j < st.nb; ++ j) {
@@ -395,6 +721,22 @@ static void schur_plan_host(const Structure &st, int shard_rank, int shard_world
 	h.nc = nc;
 	h.nl = nl;
 	h.nl_total = nl_total;
+	{
+		std::vector<int32_t> cam_order;
+		if(schur_cam_order(st, is_lm, pose_of, nc, dp, sparse_S, mis, nullptr, cam_order, h.cam_cost)) {
+			const std::vector<int64_t> natural(h.pose_block);
+			for(int64_t q = 0; q < nc; ++ q) {
+				h.pose_block[q] = natural[cam_order[q]];
+				pose_of[h.pose_block[q]] = (int32_t)q;
+			}
+			if(switches().verbose)
+				fprintf(stderr, "[spp] camera order: tiles %lld -> %lld, updates %lld -> %lld, chain %lld -> %lld, model %.0f -> %.0f us\n",
+					(long long)h.cam_cost[0].tiles, (long long)h.cam_cost[1].tiles, (long long)h.cam_cost[0].updates,
+					(long long)h.cam_cost[1].updates, (long long)h.cam_cost[0].path, (long long)h.cam_cost[1].path,
+					h.cam_cost[0].cost_us, h.cam_cost[1].cost_us);
+		}
+		clk.lap("camera order");
+	}
 	const bool add_A = (shard_rank == 0);
 	h.n_red = nc * dp;
 	h.ld = ((h.n_red + 1 + DENSE_NB - 1) / DENSE_NB) * DENSE_NB; // at least one padding column (rhs)
@@ -408,7 +750,7 @@ static void schur_plan_host(const Structure &st, int shard_rank, int shard_world
 	struct Obs { int32_t lm, pose; int64_t off; };
 	HVec<int64_t> &lm_coff = h.lm_coff;
 	lm_coff.assign(nl, -1);
-	struct ABlk { int32_t i1, i2; int64_t off; };
+	struct ABlk { int32_t i1, i2; int64_t off; }; // (off: -2 - offset when the block is stored transposed, i.e. its positions are reversed)
 	std::vector<ABlk> ablk;
 	HVec<int32_t> &lm_ptr = h.lm_ptr, &obs_pose = h.obs_pose, &obs_lm = h.obs_lm;
 	HVec<int64_t> &obs_off = h.obs_off;
@@ -467,8 +809,12 @@ static void schur_plan_host(const Structure &st, int shard_rank, int shard_world
 			for(int64_t j = jcut[t]; j < jcut[t + 1]; ++ j)
 				for(int64_t p = st.col_ptr[j]; p < st.col_ptr[j + 1]; ++ p) {
 					const int k = classify(j, p, o);
-					if(k == 0)
-						ablk[q ++] = {pose_of[st.row_idx[p]], pose_of[j], st.blk_off[p]}; // i <= j and stable partition keep i1 <= i2
+					if(k == 0) {
+						// i <= j: in the natural order i1 <= i2; a camera order may reverse the two, the block is then the
+						// transpose of the upper S block it is added to
+						const int32_t pi = pose_of[st.row_idx[p]], pj = pose_of[j];
+						ablk[q ++] = pi <= pj ? ABlk{pi, pj, st.blk_off[p]} : ABlk{pj, pi, -2 - st.blk_off[p]};
+					}
 					else if(k == 1) {
 						if(lm_of[j] >= 0)
 							lm_coff[lm_of[j]] = st.blk_off[p]; // diagonal C block
@@ -532,7 +878,34 @@ static void schur_plan_host(const Structure &st, int shard_rank, int shard_world
 	// (cameras before points, the usual numbering: the column scan above already emits the observations in order)
 	const int64_t no = (int64_t)obs_pose.size();
 	h.no = no;
-	if(!obs_sorted) {
+	bool lm_sorted = true;
+	for(int64_t a = 1; a < no && lm_sorted; ++ a)
+		lm_sorted = obs_lm[a - 1] <= obs_lm[a];
+	if(!obs_sorted && lm_sorted) {
+		// (a camera order: the landmarks still ascend, only the poses inside a landmark's run do not -- short runs, sorted in
+		// place on host threads)
+		const int nts2 = plan_threads(no);
+		run_threads(nts2, [&](int t) {
+			int64_t a = no * t / nts2, a1 = no * (t + 1) / nts2;
+			while(a > 0 && a < no && obs_lm[a] == obs_lm[a - 1])
+				++ a; // (a run belongs to the range it starts in)
+			std::vector<std::pair<int32_t, int64_t> > run;
+			while(a < a1) {
+				int64_t e = a + 1;
+				while(e < no && obs_lm[e] == obs_lm[a])
+					++ e;
+				run.clear();
+				for(int64_t q = a; q < e; ++ q)
+					run.push_back(std::make_pair(obs_pose[q], obs_off[q]));
+				std::sort(run.begin(), run.end());
+				for(int64_t q = a; q < e; ++ q) {
+					obs_pose[q] = run[q - a].first;
+					obs_off[q] = run[q - a].second;
+				}
+				a = e;
+			}
+		});
+	} else if(!obs_sorted) {
 		std::vector<Obs> obs(no);
 		for(int64_t a = 0; a < no; ++ a)
 			obs[a] = {obs_lm[a], obs_pose[a], obs_off[a]};
@@ -722,7 +1095,7 @@ static void schur_plan_host(const Structure &st, int shard_rank, int shard_world
 				int64_t out = b0;
 				for(int64_t c = i1; c < nc; ++ c) {
 					start[c] = out;
-					if(col_cnt[c + 1] || a_of_col[c] >= 0 || foreign[c]) {
+					if(col_cnt[c + 1] || a_of_col[c] != -1 || foreign[c]) {
 						ro.i1.push_back((int32_t)i1);
 						ro.i2.push_back((int32_t)c);
 						ro.aoff.push_back(a_of_col[c]);
@@ -938,13 +1311,17 @@ static void schur_plan_host(const Structure &st, int shard_rank, int shard_world
 		SaccItem &r = h.recs[q];
 		r.beg = item_beg[q];
 		r.end = item_end[q];
-		r.pad = 0;
+		r.a_tr = 0;
 		r.aoff = -1;
 		if(item_slot[q] >= 0) { // split block: s_multi_kernel sums the slots and adds A
 			r.kind = 2;
 			r.dst = (int64_t)item_slot[q] * dp * dp;
 		} else {
 			r.aoff = add_A ? sblk_aoff[b] : -1;
+			if(r.aoff < -1) { // stored transposed
+				r.aoff = -2 - r.aoff;
+				r.a_tr = 1;
+			}
 			if(sparse_S) {
 				r.kind = 1;
 				r.dst = h.sblk_voff[b];
@@ -1083,7 +1460,7 @@ double schur_plan_host_probe(const Structure &st, int shard_rank, int shard_worl
 	for(size_t q = 0; q < h.recs.size(); ++ q) {
 		mix(((uint64_t)(uint32_t)h.recs[q].beg << 32) | (uint32_t)h.recs[q].end);
 		mix((uint64_t)h.recs[q].dst);
-		mix((uint64_t)h.recs[q].aoff + (uint64_t)h.recs[q].kind);
+		mix((uint64_t)h.recs[q].aoff + (uint64_t)h.recs[q].kind + ((uint64_t)h.recs[q].a_tr << 8)); // (a_tr = 0 in the natural order)
 	}
 	for(size_t q = 0; q < h.xb.size(); ++ q)
 		mix((uint64_t)h.xb[q]);
@@ -1092,12 +1469,56 @@ double schur_plan_host_probe(const Structure &st, int shard_rank, int shard_worl
 	return sec;
 }
 
-// host-only: the filled tile mask the dense Schur plan of a structure would carry (every shard's is the same)
+// host-only: the filled tile mask the dense Schur plan of a structure carries in the natural camera order (every shard's
+// is the same)
 void schur_tile_mask_host_probe(const Structure &st, int shard_rank, int shard_world, std::vector<uint64_t> &words)
 {
-	SchurPlanHost h;
-	schur_plan_host(st, shard_rank, shard_world, false, false, h);
-	words.swap(h.tile_mask);
+	(void)shard_rank;
+	(void)shard_world;
+	int dp, dl;
+	SPP_REQUIRE(schur_applicable(st, &dp, &dl), SPP_E_UNSUPPORTED,
+		"Schur mode needs exactly two block widths ({6,3} or {3,2}) and a block-diagonal landmark part");
+	std::vector<uint8_t> is_lm(st.nb);
+	std::vector<int32_t> pose_of(st.nb, -1);
+	int64_t nc = 0;
+	for(int64_t j = 0; j < st.nb; ++ j)
+		if(!(is_lm[j] = st.dim[j] == dl))
+			pose_of[j] = (int32_t)nc ++;
+	schur_tile_mask(st, is_lm, pose_of, dp, nc * dp, words);
+}
+
+bool schur_cam_order_host_probe(const Structure &st, int shard_rank, int shard_world, bool sparse_S, bool mis, const int64_t *order_in,
+	std::vector<int32_t> &cam_order, TileDagCost cost[2])
+{
+	if(!order_in) {
+		// the order of the PLAN of this shard, read back from its pose_block[] (not a second evaluation of the rule)
+		SchurPlanHost h;
+		schur_plan_host(st, shard_rank, shard_world, sparse_S || mis, mis, h);
+		std::vector<int32_t> cam_of(st.nb, -1);
+		int32_t nc = 0;
+		for(int64_t j = 0; j < st.nb; ++ j)
+			if(!h.is_lm[j])
+				cam_of[j] = nc ++;
+		cam_order.resize((size_t)nc);
+		bool used = false;
+		for(int32_t q = 0; q < nc; ++ q) {
+			cam_order[q] = cam_of[h.pose_block[q]];
+			used = used || cam_order[q] != q;
+		}
+		cost[0] = h.cam_cost[0];
+		cost[1] = h.cam_cost[1];
+		return used;
+	}
+	int dp, dl;
+	SPP_REQUIRE(!sparse_S && !mis && schur_applicable(st, &dp, &dl), SPP_E_UNSUPPORTED,
+		"the model of a given camera order needs the dense guided Schur mode ({6,3} or {3,2} block widths)");
+	std::vector<uint8_t> is_lm(st.nb, 0);
+	std::vector<int32_t> cam_of(st.nb, -1);
+	int64_t nc = 0;
+	for(int64_t j = 0; j < st.nb; ++ j)
+		if(!(is_lm[j] = st.dim[j] == dl))
+			cam_of[j] = (int32_t)nc ++;
+	return schur_cam_order(st, is_lm, cam_of, nc, dp, false, false, order_in, cam_order, cost);
 }
 
 // --------------------------------------------------------------------------------------------------
