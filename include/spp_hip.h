@@ -132,9 +132,11 @@ int spp_block_ordering(int64_t nb, const int64_t *col_ptr, const int64_t *row_id
  * structurally in every CLinearSolver_Schur::Solve_PosDef_Blocky call (guided ordering LinearSolver_Schur.cpp:771-838,
  * the slices LinearSolver_Schur.h:1699-1709, the symbolic part of MultiplyToWith BlockMatrixFBS.inl:1147-1304) as
  * observation lists, the block pattern of S and its per-block lists of block products. Runs on up to 16 host threads
- * (SPP_PLAN_THREADS); the result does not depend on their number. out[0..7] = poses, landmarks of this shard,
- * observations, block products, blocks of S, work items, split blocks, a 64-bit checksum of the lists; *seconds = wall
- * clock of the plan. sparse_S: bit 0 = sparse reduced system, bit 1 = the MIS cut of SPP_MODE_SCHUR_MIS (one block
+ * (SPP_PLAN_THREADS); the result does not depend on their number. out holds NINE values: out[0..6] = poses, landmarks
+ * of this shard, observations, block products, blocks of S, work items, split blocks; out[7] = a 64-bit checksum of the
+ * pair lists, the block list of S, the item records and the XCD ranges; out[8] = a 64-bit checksum of every list and
+ * scalar of the plan that the device plan uploads or keeps (out[7] and the scalars mixed in). *seconds = wall clock of
+ * the plan. sparse_S: bit 0 = sparse reduced system, bit 1 = the MIS cut of SPP_MODE_SCHUR_MIS (one block
  * width; its reduced system is always sparse). For tests and for timing the analysis phase without a device. */
 int spp_schur_plan_host(int64_t nb, const int32_t *dim, const int64_t *col_ptr, const int64_t *row_idx, int shard_rank,
 	int shard_world, int sparse_S, int64_t *out, double *seconds);

@@ -328,7 +328,7 @@ class RefSolver:
 # --------------------------------------------------------------------------------------------------
 # multi-GPU algebra: partial Schur complement of one landmark shard. Landmarks are dealt
 # round-robin over the ranks in ascending block-column order (the rule of build_schur_plan() in
-# slam_plus_plus_amd/csrc/spp_symbolic.cpp); rank 0 alone carries A and the pose part of eta.
+# slam_plus_plus_amd/csrc/spp_schur_plan.cpp); rank 0 alone carries A and the pose part of eta.
 # --------------------------------------------------------------------------------------------------
 def landmark_shard(lam, rank, world):
     dl = int(lam.dim.min())

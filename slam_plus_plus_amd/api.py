@@ -147,19 +147,20 @@ def block_ordering(lam, method=ORDER_AMD):
 
 def schur_plan_host(lam, shard_rank=0, shard_world=1, sparse_S=False, mis=False):
     """Host-only symbolic Schur plan of a BlockCSC pattern (spp_schur_plan_host): returns a dict with the list sizes,
-    a checksum of the lists and the wall clock of the plan. mis: the cut of MODE_SCHUR_MIS (one block width, sparse S).
+    a checksum of the pair / block / item lists (checksum), one of every list and scalar of the plan (checksum_all) and
+    the wall clock of the plan. mis: the cut of MODE_SCHUR_MIS (one block width, sparse S).
     No GPU needed."""
     lib = load_library()
     col_ptr = np.ascontiguousarray(lam.col_ptr, dtype=np.int64)
     row_idx = np.ascontiguousarray(lam.row_idx, dtype=np.int64)
     dim = np.ascontiguousarray(lam.dim, dtype=np.int32)
-    out = np.zeros(8, dtype=np.int64)
+    out = np.zeros(9, dtype=np.int64)
     sec = ctypes.c_double(0.0)
     code = lib.spp_schur_plan_host(lam.nb, _ptr(dim), _ptr(col_ptr), _ptr(row_idx), shard_rank, shard_world,
                                    (1 if sparse_S else 0) | (2 if mis else 0), _ptr(out), ctypes.byref(sec))
     if code != 0:
         raise SppError("spp_schur_plan_host failed: %d" % code)
-    keys = ("nc", "nl", "no", "n_pairs", "n_sblk", "n_items", "n_multi", "checksum")
+    keys = ("nc", "nl", "no", "n_pairs", "n_sblk", "n_items", "n_multi", "checksum", "checksum_all")
     d = dict(zip(keys, (int(v) for v in out)))
     d["seconds"] = sec.value
     return d

@@ -461,8 +461,12 @@ static bool structure_of_pattern(int64_t nb, const int32_t *dim, const int64_t *
 	return true;
 }
 
-int spp_schur_plan_host(int64_t nb, const int32_t *dim, const int64_t *col_ptr, const int64_t *row_idx, int shard_rank,
-	int shard_world, int sparse_S, int64_t *out, double *seconds)
+// what the host-only Schur entry points share: the argument check, the Structure of the pattern, fn(st) for the entry
+// point's return value, exceptions to error codes (out: the entry point's own output array)
+extern "C++" {
+template <class F>
+static int schur_host_entry(int64_t nb, const int32_t *dim, const int64_t *col_ptr, const int64_t *row_idx, int shard_rank,
+	int shard_world, const void *out, F fn)
 {
 	if(nb <= 0 || !dim || !col_ptr || !row_idx || !out || shard_world < 1 || shard_rank < 0 || shard_rank >= shard_world)
 		return SPP_E_BADARG;
@@ -470,10 +474,7 @@ int spp_schur_plan_host(int64_t nb, const int32_t *dim, const int64_t *col_ptr, 
 		Structure st;
 		if(!structure_of_pattern(nb, dim, col_ptr, row_idx, st))
 			return SPP_E_BADARG;
-		const double sec = schur_plan_host_probe(st, shard_rank, shard_world, (sparse_S & 1) != 0, (sparse_S & 2) != 0, out);
-		if(seconds)
-			*seconds = sec;
-		return SPP_OK;
+		return fn(st);
 	} catch(const Error &e) {
 		return e.code;
 	} catch(const std::bad_alloc &) {
@@ -482,28 +483,30 @@ int spp_schur_plan_host(int64_t nb, const int32_t *dim, const int64_t *col_ptr, 
 		return SPP_E_HIP;
 	}
 }
+}
 
+int spp_schur_plan_host(int64_t nb, const int32_t *dim, const int64_t *col_ptr, const int64_t *row_idx, int shard_rank,
+	int shard_world, int sparse_S, int64_t *out, double *seconds)
+{
+	return schur_host_entry(nb, dim, col_ptr, row_idx, shard_rank, shard_world, out, [&](const Structure &st) {
+		const double sec = schur_plan_host_probe(st, shard_rank, shard_world, (sparse_S & 1) != 0, (sparse_S & 2) != 0, out);
+		if(seconds)
+			*seconds = sec;
+		return (int)SPP_OK;
+	});
+}
+
+// (shard_rank, shard_world: checked and otherwise unused -- the mask is over the landmarks of ALL shards)
 int spp_schur_tile_mask_host(int64_t nb, const int32_t *dim, const int64_t *col_ptr, const int64_t *row_idx, int shard_rank,
 	int shard_world, uint64_t *words)
 {
-	if(nb <= 0 || !dim || !col_ptr || !row_idx || !words || shard_world < 1 || shard_rank < 0 || shard_rank >= shard_world)
-		return SPP_E_BADARG;
-	try {
-		Structure st;
-		if(!structure_of_pattern(nb, dim, col_ptr, row_idx, st))
-			return SPP_E_BADARG;
+	return schur_host_entry(nb, dim, col_ptr, row_idx, shard_rank, shard_world, words, [&](const Structure &st) {
 		std::vector<uint64_t> w;
-		schur_tile_mask_host_probe(st, shard_rank, shard_world, w);
+		schur_tile_mask_host_probe(st, w);
 		for(size_t q = 0; q < w.size(); ++ q)
 			words[q] = w[q];
 		return (int)w.size();
-	} catch(const Error &e) {
-		return e.code;
-	} catch(const std::bad_alloc &) {
-		return SPP_E_NOMEM;
-	} catch(...) {
-		return SPP_E_HIP;
-	}
+	});
 }
 
 // host only: the camera order the Schur plan of a structure and landmark shard uses, read back from that plan (flags: 1 sparse S, 2 MIS -- both keep the natural
@@ -514,12 +517,9 @@ int spp_schur_tile_mask_host(int64_t nb, const int32_t *dim, const int64_t *col_
 int spp_schur_cam_order_host(int64_t nb, const int32_t *dim, const int64_t *col_ptr, const int64_t *row_idx, int shard_rank,
 	int shard_world, int flags, const int64_t *order_in, int64_t *cam_order, double *figures)
 {
-	if(nb <= 0 || !dim || !col_ptr || !row_idx || !cam_order || !figures || shard_world < 1 || shard_rank < 0 || shard_rank >= shard_world)
+	if(!figures)
 		return SPP_E_BADARG;
-	try {
-		Structure st;
-		if(!structure_of_pattern(nb, dim, col_ptr, row_idx, st))
-			return SPP_E_BADARG;
+	return schur_host_entry(nb, dim, col_ptr, row_idx, shard_rank, shard_world, cam_order, [&](const Structure &st) {
 		if(order_in) {
 			int64_t nc = 0;
 			const int dmax = *std::max_element(dim, dim + nb);
@@ -528,7 +528,7 @@ int spp_schur_cam_order_host(int64_t nb, const int32_t *dim, const int64_t *col_
 			std::vector<char> seen((size_t)nc, 0);
 			for(int64_t q = 0; q < nc; ++ q) {
 				if(order_in[q] < 0 || order_in[q] >= nc || seen[order_in[q]])
-					return SPP_E_BADARG;
+					return (int)SPP_E_BADARG;
 				seen[order_in[q]] = 1;
 			}
 		}
@@ -544,13 +544,7 @@ int spp_schur_cam_order_host(int64_t nb, const int32_t *dim, const int64_t *col_
 			figures[4 * side + 3] = cost[side].cost_us;
 		}
 		return used ? 1 : 0;
-	} catch(const Error &e) {
-		return e.code;
-	} catch(const std::bad_alloc &) {
-		return SPP_E_NOMEM;
-	} catch(...) {
-		return SPP_E_HIP;
-	}
+	});
 }
 
 int spp_schur_buffer_size(const spp_ctx *ctx, int64_t *n_doubles)

@@ -1547,7 +1547,7 @@ static bool launch_dense_tail(spp_ctx *ctx, double *d_A, int64_t ld, int64_t row
 	// (beta = 0) the 256 CUs start on the first ~6 rows, far tiles included, and the near-diagonal tiles of the rows
 	// behind them start late; beta > 0 holds the far columns back a little in favour of those.
 	// With a tile mask in force the tiles that every early step updates but that row by row get a CU many steps late (the
-	// trailing triangle of a bordered band) are seated first: tail_order_table() in spp_symbolic.cpp has the rule and the
+	// trailing triangle of a bordered band) are seated first: tail_order_table() in spp_tile_plan.cpp has the rule and the
 	// condition under which progress still holds -- it depends on how many workgroups the device holds at once. Without
 	// a mask the table is the sorted one.
 	const bool early = mask != nullptr && sw.tail_early != 0;

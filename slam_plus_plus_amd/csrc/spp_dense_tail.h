@@ -21,12 +21,12 @@
 // fences. Counters carry the epoch of the factorization in their upper bits (no clearing between factorizations).
 // Workgroups are numbered row by row: whatever a workgroup waits for is produced by a workgroup
 // with a smaller index, which never waits for a larger one -- progress does not depend on residency. With a tile mask a
-// set E of trailing tile rows may be numbered in front of all others (tail_order_table, spp_symbolic.cpp): no tile outside
+// set E of trailing tile rows may be numbered in front of all others (tail_order_table, spp_tile_plan.cpp): no tile outside
 // E waits for one of E, and the host uses E only when E and the live tiles outside it are resident together. Every wait
 // is bounded (abort word).
 // Summation order per tile: steps ascending, row tiles ascending -- fixed, bit-reproducible.
 // Structure: the launch takes one 64-bit word per step (bit j of word k = tile (k, j) of the FILLED pattern is nonzero,
-// spp_symbolic.cpp: tile_mask_close). Only tiles with their bit set have a workgroup; tile (i, j) applies step k only if
+// spp_tile_plan.cpp: tile_mask_close). Only tiles with their bit set have a workgroup; tile (i, j) applies step k only if
 // bits i and j of word k are both set, and neither waits for nor fetches a row tile of a step it skips -- such an update
 // subtracts a product with an all-zero row tile, a tile without a workgroup is zero before and after and is never
 // written. With every bit set the launch is the dense one, workgroup for workgroup.

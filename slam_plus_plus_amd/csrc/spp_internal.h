@@ -211,7 +211,8 @@ struct SaccItem {
 	int64_t aoff;      // offset of the A block in vals that this item adds, or -1
 };
 
-struct SchurPlan {
+// the scalars of a plan: what the host plan (spp_schur_plan.cpp: SchurPlanHost) and the device plan both hold
+struct SchurDims {
 	int dp = 0, dl = 0;            // pose / landmark block width
 	int64_t nc = 0, nl = 0;        // poses, landmarks owned by this shard
 	int64_t nl_total = 0;
@@ -220,9 +221,13 @@ struct SchurPlan {
 	int64_t n_sblk = 0;            // blocks of S that are written (upper, incl. diagonal)
 	int64_t n_pairs = 0;           // sum_p k_p (k_p + 1) / 2
 	int64_t n_items = 0, n_multi = 0; // work items (block chunks) / blocks split over several items
-	bool add_A = true;             // this shard adds A and the pose rhs (rank 0)
+	int32_t xcd_max_items = 0;     // longest of the XCDs' item ranges (xcd_beg)
 	bool u_landmark_major = true;  // layout of the packed U blocks (Up): observation order instead of camera-major
 	bool factored = true;          // S accumulation on ONE packed block per observation, V = U F with C^-1 = F F^T (spp_schur.hip)
+};
+
+struct SchurPlan : SchurDims {
+	bool add_A = true;             // this shard adds A and the pose rhs (rank 0)
 	// reduced camera system kept SPARSE (block-CSC, dp x dp blocks) and solved by the supernodal path:
 	// S buffer = [ s_st.nvals block values | n_red reduced rhs ]
 	bool sparse_S = false;
@@ -251,7 +256,6 @@ struct SchurPlan {
 	// S accumulation work items
 	DevBuf<SaccItem> items;        // [n_items] (ordered by camera tiles, not by block)
 	DevBuf<int32_t> xcd_beg;       // [9] item range of each XCD (equal work, not equal counts)
-	int32_t xcd_max_items = 0;     // longest of those ranges
 	DevBuf<int32_t> sblk_i1, sblk_i2; // [n_sblk]
 	DevBuf<int64_t> sblk_aoff;     // [n_sblk] offset of the A block in vals or -1; -2 - offset: the block is stored transposed
 	DevBuf<int32_t> pair_a, pair_b; // [n_pairs]
@@ -390,10 +394,47 @@ double ba_update(spp_ctx *ctx, int64_t nc, double *d_cams, const int64_t *d_cam_
 // ---- spp_symbolic.cpp ----
 void min_degree_order(int64_t nb, const int64_t *col_ptr, const int64_t *row_idx, std::vector<int64_t> &order);
 void nested_dissection_order(int64_t nb, const int64_t *col_ptr, const int64_t *row_idx, std::vector<int64_t> &order);
+
+// ---- spp_tile_plan.cpp (host-side tile planning of the dense factor) ----
+// Tile masks of an n x n matrix (+ right-hand side column n) in 128 x 128 tiles (host only).
+// tile_mask_mark: the tiles the bs x bs blocks (i1[q], i2[q]) at rows / columns bs * index touch (either triangle given,
+// the upper one marked); words is resized to the tile rows, or left EMPTY (= every tile) with more than 64 tile columns.
+// tile_mask_close: diagonal tiles and the right-hand side's tile column set, nothing below the diagonal, then symbolic
+// elimination (for k ascending every pair of nonzero tiles (k, a), (k, b), k < a <= b, fills (a, b)); returns the
+// number of rank-128 tile updates of the filled pattern.
+void tile_mask_mark(int64_t n, int bs, int64_t nblk, const int32_t *i1, const int32_t *i2, std::vector<uint64_t> &words);
+int64_t tile_mask_close(int64_t n, bool has_rhs, bool fill, std::vector<uint64_t> &words);
+// Cost model of the streamed launch on a filled tile mask (host only: tile_dag_cost). The launch is
+// bound by its chain of diagonal tiles or by its tile updates, whichever is longer:
+//   cost = max(path * TAIL_MODEL_STEP_US, updates * TAIL_MODEL_UPDATE_US / resident) + TAIL_MODEL_START_US.
+// The constants are the measured ones of DESIGN sections 10 - 11 (profiles/r04_dense_tail_trace.txt, r06_dense_tail_trace.txt):
+// a step of the chain = 31 - 34 us of potrf_diag panels + 3 - 5 us of hand-over = 36.5 us; a tile applies a row tile
+// in 2.0 us when it only streams (2.6 us while it catches up, 4.6 us is the rate at which the chain emits them); the
+// launch starts 45 us before its first step ends; 256 resident workgroups (one per CU of an MI355X) -- a constant and
+// not the device's count, so that every rank and every host probe chooses the same camera order.
+constexpr double TAIL_MODEL_STEP_US = 36.5, TAIL_MODEL_UPDATE_US = 2.0, TAIL_MODEL_START_US = 45.0;
+constexpr int TAIL_MODEL_RESIDENT = 256;
+struct TileDagCost {
+	int64_t tiles = 0, updates = 0, path = 0; // listed tiles, rank-128 updates, longest chain of diagonal tiles
+	double cost_us = 0;
+};
+TileDagCost tile_dag_cost(int64_t n, const std::vector<uint64_t> &filled, int resident); // (filled: tile_mask_close(n, true, true))
+// workgroup -> tile (i << 16 | j) of the streamed launch for the step words bits[0 .. Tr] of a region (host only; the rule
+// and the progress condition are stated at its definition)
+void tail_order_table(const std::vector<uint64_t> &bits, int Tr, int Tc, bool have_pre, double beta, int resident, bool early,
+	std::vector<int> &order, int *info);
+
+// ---- spp_schur_plan.cpp ----
 void build_schur_plan(spp_ctx *ctx, bool sparse_S, bool mis = false);
 int64_t schur_buffer_doubles(const spp_ctx *ctx); // S | rhs buffer the Schur entry points work on
 bool schur_applicable(const Structure &st, int *dp, int *dl);
-double schur_plan_host_probe(const Structure &st, int shard_rank, int shard_world, bool sparse_S, bool mis, int64_t *out); // host only: plan + checksum, seconds
+double schur_plan_host_probe(const Structure &st, int shard_rank, int shard_world, bool sparse_S, bool mis, int64_t *out); // host only: plan + its two checksums (out[0..8]), seconds
+void schur_tile_mask_host_probe(const Structure &st, std::vector<uint64_t> &words); // the mask a dense Schur plan carries in the NATURAL camera order
+// host only: the camera order the Schur plan of a structure and shard uses, read back from that plan (cam_order[position] = camera in natural numbering)
+// and the model's figures of the natural order / of that order; order_in given: the figures of THAT order in cost[1],
+// nothing is chosen. Returns whether cam_order differs from the identity.
+bool schur_cam_order_host_probe(const Structure &st, int shard_rank, int shard_world, bool sparse_S, bool mis, const int64_t *order_in,
+	std::vector<int32_t> &cam_order, TileDagCost cost[2]);
 
 // ---- spp_sparse (symbolic on host + numeric on device) ----
 void sparse_analyze(spp_ctx *ctx, const Structure &st); // plan for `st` (Lambda, or the sparse reduced system)
@@ -426,39 +467,6 @@ struct TileMaskGuard { // hands a tile mask to the factorizations enqueued while
 	TileMaskGuard(DenseWork &dw, const std::vector<uint64_t> *m) : d(dw) { d.tile_mask = (m && !m->empty()) ? m : nullptr; }
 	~TileMaskGuard() { d.tile_mask = nullptr; }
 };
-// Tile masks of an n x n matrix (+ right-hand side column n) in 128 x 128 tiles (host only, spp_symbolic.cpp).
-// tile_mask_mark: the tiles the bs x bs blocks (i1[q], i2[q]) at rows / columns bs * index touch (either triangle given,
-// the upper one marked); words is resized to the tile rows, or left EMPTY (= every tile) with more than 64 tile columns.
-// tile_mask_close: diagonal tiles and the right-hand side's tile column set, nothing below the diagonal, then symbolic
-// elimination (for k ascending every pair of nonzero tiles (k, a), (k, b), k < a <= b, fills (a, b)); returns the
-// number of rank-128 tile updates of the filled pattern.
-void tile_mask_mark(int64_t n, int bs, int64_t nblk, const int32_t *i1, const int32_t *i2, std::vector<uint64_t> &words);
-int64_t tile_mask_close(int64_t n, bool has_rhs, bool fill, std::vector<uint64_t> &words);
-void schur_tile_mask_host_probe(const Structure &st, int shard_rank, int shard_world, std::vector<uint64_t> &words); // the mask a dense Schur plan carries in the NATURAL camera order
-// Cost model of the streamed launch on a filled tile mask (host only, spp_symbolic.cpp: tile_dag_cost). The launch is
-// bound by its chain of diagonal tiles or by its tile updates, whichever is longer:
-//   cost = max(path * TAIL_MODEL_STEP_US, updates * TAIL_MODEL_UPDATE_US / resident) + TAIL_MODEL_START_US.
-// The constants are the measured ones of DESIGN sections 10 - 11 (profiles/r04_dense_tail_trace.txt, r06_dense_tail_trace.txt):
-// a step of the chain = 31 - 34 us of potrf_diag panels + 3 - 5 us of hand-over = 36.5 us; a tile applies a row tile
-// in 2.0 us when it only streams (2.6 us while it catches up, 4.6 us is the rate at which the chain emits them); the
-// launch starts 45 us before its first step ends; 256 resident workgroups (one per CU of an MI355X) -- a constant and
-// not the device's count, so that every rank and every host probe chooses the same camera order.
-constexpr double TAIL_MODEL_STEP_US = 36.5, TAIL_MODEL_UPDATE_US = 2.0, TAIL_MODEL_START_US = 45.0;
-constexpr int TAIL_MODEL_RESIDENT = 256;
-struct TileDagCost {
-	int64_t tiles = 0, updates = 0, path = 0; // listed tiles, rank-128 updates, longest chain of diagonal tiles
-	double cost_us = 0;
-};
-TileDagCost tile_dag_cost(int64_t n, const std::vector<uint64_t> &filled, int resident); // (filled: tile_mask_close(n, true, true))
-// host only: the camera order the Schur plan of a structure and shard uses, read back from that plan (cam_order[position] = camera in natural numbering)
-// and the model's figures of the natural order / of that order; order_in given: the figures of THAT order in cost[1],
-// nothing is chosen. Returns whether cam_order differs from the identity.
-bool schur_cam_order_host_probe(const Structure &st, int shard_rank, int shard_world, bool sparse_S, bool mis, const int64_t *order_in,
-	std::vector<int32_t> &cam_order, TileDagCost cost[2]);
-// workgroup -> tile (i << 16 | j) of the streamed launch for the step words bits[0 .. Tr] of a region (host only,
-// spp_symbolic.cpp: the rule and the progress condition are stated there)
-void tail_order_table(const std::vector<uint64_t> &bits, int Tr, int Tc, bool have_pre, double beta, int resident, bool early,
-	std::vector<int> &order, int *info);
 // unit tests: the partial factorization of a big sparse front, laid out (identity padding after the w pivots) and
 // factored as the sparse path does; d_F (h x h, ld) <- the result in the unpadded layout, d_image (optional, ldp x hp with
 // ldp = (hp + 1) & ~1, hp = h + pad) <- the padded image
@@ -488,7 +496,7 @@ void phases_collect(spp_ctx *ctx);
 void dom_begin(spp_ctx *ctx);
 void dom_end(spp_ctx *ctx, double flops);
 
-// ---- host threads of the symbolic phases (spp_symbolic.cpp, spp_assemble.hip)
+// ---- host threads of the symbolic phases (spp_schur_plan.cpp, spp_assemble.hip)
 // Runs fn(t) for t = 0 .. nt-1 on nt host threads (fn(0) on the caller's). The symbolic phase is integer work over
 // tens of millions of block products; its passes are cut into independent pieces with precomputed output offsets, so
 // the result does not depend on the number of threads.

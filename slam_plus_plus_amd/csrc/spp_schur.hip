@@ -12,7 +12,7 @@
 //   backsubst_obs/lm l = -l + U^T dx ; dl = (-C^-1) l     :1867-1881 (PostMultiply_Add_FBS_Parallel, PreMultiply_Add)
 // The reference's Permute_UpperTriangular_To / SliceTo / TransposeTo (:1688-1709) move no data here:
 // the kernels address the blocks of the ORIGINAL Lambda through the index lists built once by
-// build_schur_plan() (spp_symbolic.cpp).
+// build_schur_plan() (spp_schur_plan.cpp).
 //
 // Accumulation order of S: the pair list of every S block is sorted by landmark, which is the
 // order in which the reference's product walks the columns of V; sums are sequential per output

@@ -50,7 +50,7 @@ struct Switches {
 	int trsv_chain;           // SPP_TRSV_CHAIN (2): 2: the chain inside one workgroup, 1: a workgroup per hop (round 2), 0: a launch per hop (round 1)
 	int trsv_mform;           // SPP_TRSV_MFORM (1): 0: the chain applies R_{b, b+1} and Tinv_b itself (two tiles per hop)
 
-	// ---- Schur complement (spp_symbolic.cpp, spp_schur.hip)
+	// ---- Schur complement (spp_schur_plan.cpp, spp_schur.hip)
 	bool sacc_ulm;            // SPP_SACC_ULM (1): (unfactored form) packed U landmark-major; 0: camera-major like W
 	bool sacc_factored;       // SPP_SACC_FACTORED (1): 0: two packed blocks per observation (W and U), as in rounds 1-2
 	int64_t sacc_tile;        // SPP_SACC_TILE (4, >= 1): cameras per side of an item tile (1 = plain row-major block order)

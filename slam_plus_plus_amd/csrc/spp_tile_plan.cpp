@@ -1,0 +1,169 @@
+// spp_tile_plan.cpp -- host-side tile planning of the dense factor (integer work on 128 x 128 tile masks): which tiles
+// of a reduced system are structurally nonzero (tile_mask_mark, tile_mask_close), which workgroup of the streamed launch
+// takes which tile (tail_order_table), and the cost model of that launch on a filled mask (tile_dag_cost).
+
+#include "spp_internal.h"
+#include <algorithm>
+
+namespace spp {
+
+// --------------------------------------------------------------------------------------------------
+// Tile structure of a dense reduced system (the streamed dense factor, spp_dense_tail.h, skips structurally zero tiles).
+// A word per tile row of DENSE_NB rows, bit j = tile (i, j); the layout is the factor's: n pivots, the right-hand side
+// in column n, identity padding behind it (diagonal tiles only).
+// --------------------------------------------------------------------------------------------------
+void tile_mask_mark(int64_t n, int bs, int64_t nblk, const int32_t *i1, const int32_t *i2, std::vector<uint64_t> &words)
+{
+	words.clear();
+	const int64_t Tr = (n + DENSE_NB - 1) / DENSE_NB, Tc = n / DENSE_NB + 1;
+	if(Tr < 1 || Tc > 64)
+		return; // (empty: every tile)
+	words.assign((size_t)Tr, 0);
+	for(int64_t q = 0; q < nblk; ++ q) {
+		const int64_t a = std::min(i1[q], i2[q]), b = std::max(i1[q], i2[q]);
+		// a bs x bs block may straddle two tiles in either direction
+		const int64_t r0 = a * bs / DENSE_NB, r1 = std::min<int64_t>(a * bs + bs - 1, n - 1) / DENSE_NB;
+		const int64_t c0 = b * bs / DENSE_NB, c1 = std::min<int64_t>(b * bs + bs - 1, n - 1) / DENSE_NB;
+		if(a < 0 || r0 >= Tr || c0 >= Tr)
+			continue;
+		words[r0] |= (1ull << c0) | (1ull << c1);
+		words[r1] |= (1ull << c0) | (1ull << c1);
+	}
+}
+
+int64_t tile_mask_close(int64_t n, bool has_rhs, bool fill, std::vector<uint64_t> &words)
+{
+	const int64_t Tr = (n + DENSE_NB - 1) / DENSE_NB, Tc = has_rhs ? n / DENSE_NB + 1 : Tr;
+	if(Tr < 1 || Tc > 64 || (int64_t)words.size() != Tr) {
+		words.clear();
+		return -1;
+	}
+	const uint64_t cols = Tc == 64 ? ~0ull : (1ull << Tc) - 1;
+	for(int64_t i = 0; i < Tr; ++ i) {
+		words[i] |= 1ull << i;
+		if(has_rhs)
+			words[i] |= 1ull << (n / DENSE_NB); // the tile column of the right-hand side is nonzero in every row
+		words[i] &= cols & ~((1ull << i) - 1);
+	}
+	int64_t updates = 0;
+	for(int64_t k = 0; k < Tr; ++ k) {
+		const uint64_t r = words[k] & ~((2ull << k) - 1); // nonzero tiles right of the diagonal
+		for(uint64_t m = r; m; m &= m - 1) {
+			const int a = __builtin_ctzll(m);
+			if(a >= Tr)
+				break;
+			const uint64_t f = r & ~((1ull << a) - 1);
+			if(fill)
+				words[a] |= f;
+			updates += __builtin_popcountll(words[a] & f);
+		}
+	}
+	return updates;
+}
+
+// Workgroup -> tile of the streamed launch (spp_dense_tail.h). bits[k + 1], bit j: tile (k, j) of the region is listed,
+// bits[0]: the row panel in front of the region (step -1, applied only with have_pre).
+// Tile (i, j) needs row tiles of (k, i) and (k, j), k < i, so any key alpha i + beta j with alpha > 0, beta >= 0 sorts the
+// tiles topologically: that is the base order (beta = 0: row by row), and with !early the whole table.
+// early: a set E of tiles goes in front of it, those that the base order seats many steps after their first update is
+// out and that then run behind the chain until it has to wait for them.
+//   first(i, j) = the first step tile (i, j) applies (bits i and j of that step's word both set), its own row i if none;
+//   D = resident / (tiles of the widest listed row): whole rows the launch holds resident at its start;
+//   a tile lags if i - first(i, j) > D;
+//   E = the tiles of the longest run of trailing rows r* .. Tr - 1 in which every listed tile lags.
+// Consumers of a tile of row i lie in rows > i, so a trailing run of rows is closed under "consumer of": NO TILE OUTSIDE E
+// WAITS FOR A TILE OF E. The tiles outside E keep the base order among themselves -- topological --, so with E seated
+// they complete one after the other on whatever is left, and then E does (row by row inside E). Progress needs
+// resident > |E| instead of nothing at all; E is used only if
+//   |E| <= resident / 2   and   resident - |E| >= max over r of #{(i, j) outside E : first(i, j) <= r <= i}
+// (the live demand: tiles that have something to do while the chain is at row r), otherwise the table is the base
+// order, entry for entry. info (may be null): {|E|, r*, D, live demand, widest row} -- r* = Tr, |E| = 0 when E is not used.
+void tail_order_table(const std::vector<uint64_t> &bits, int Tr, int Tc, bool have_pre, double beta, int resident, bool early,
+	std::vector<int> &order, int *info)
+{
+	std::vector<std::pair<double, int> > key;
+	for(int i = 0; i < Tr; ++ i)
+		for(int j = i; j < Tc; ++ j)
+			if((bits[(size_t)i + 1] >> j) & 1) // (only nonzero tiles get a workgroup)
+				key.push_back(std::make_pair((double)i + beta * (double)j, (i << 16) | j));
+	std::stable_sort(key.begin(), key.end(), [](const std::pair<double, int> &x, const std::pair<double, int> &y) { return x.first < y.first; });
+	order.resize(key.size());
+	for(size_t q = 0; q < key.size(); ++ q)
+		order[q] = key[q].second;
+	int widest = 1;
+	for(int i = 0; i < Tr; ++ i)
+		widest = std::max(widest, (int)__builtin_popcountll(bits[(size_t)i + 1]));
+	const int D = std::max(resident, 0) / widest;
+	if(info) {
+		info[0] = 0;
+		info[1] = Tr;
+		info[2] = D;
+		info[3] = 0;
+		info[4] = widest;
+	}
+	if(!early || resident <= 0)
+		return;
+	auto first_step = [&](const int i, const int j) -> int {
+		for(int k = have_pre ? -1 : 0; k < i; ++ k) {
+			const uint64_t w = bits[(size_t)k + 1];
+			if((w >> i) & (w >> j) & 1)
+				return k;
+		}
+		return i;
+	};
+	int r_star = Tr;
+	for(int i = Tr - 1; i >= 0; -- i) {
+		bool all_lag = true;
+		for(int j = i; j < Tc && all_lag; ++ j)
+			if((bits[(size_t)i + 1] >> j) & 1)
+				all_lag = i - first_step(i, j) > D;
+		if(!all_lag)
+			break;
+		r_star = i;
+	}
+	int n_early = 0;
+	std::vector<int> live((size_t)Tr + 1, 0); // (as differences first: +1 at first(i, j), -1 behind row i)
+	for(size_t q = 0; q < order.size(); ++ q) {
+		const int i = order[q] >> 16, j = order[q] & 0xffff;
+		if(i >= r_star)
+			++ n_early;
+		else {
+			++ live[(size_t)std::max(first_step(i, j), 0)];
+			-- live[(size_t)i + 1];
+		}
+	}
+	int demand = 0;
+	for(int r = 0, run = 0; r < Tr; ++ r) {
+		run += live[(size_t)r];
+		demand = std::max(demand, run);
+	}
+	if(info)
+		info[3] = demand;
+	if(n_early == 0 || n_early > resident / 2 || resident - n_early < demand)
+		return;
+	std::stable_partition(order.begin(), order.end(), [r_star](const int t) { return (t >> 16) >= r_star; });
+	if(info) {
+		info[0] = n_early;
+		info[1] = r_star;
+	}
+}
+
+TileDagCost tile_dag_cost(int64_t n, const std::vector<uint64_t> &filled, int resident)
+{
+	TileDagCost c;
+	const int64_t Tr = (int64_t)filled.size();
+	std::vector<uint64_t> w(filled);
+	c.updates = tile_mask_close(n, true, true, w); // (closed already: counts the updates)
+	std::vector<int> depth((size_t)Tr, 1);
+	for(int64_t k = 0; k < Tr; ++ k) {
+		c.tiles += __builtin_popcountll(w[k]);
+		for(int64_t j = 0; j < k; ++ j)
+			if((w[j] >> k) & 1)
+				depth[k] = std::max(depth[k], depth[j] + 1);
+		c.path = std::max<int64_t>(c.path, depth[k]);
+	}
+	c.cost_us = std::max(c.path * TAIL_MODEL_STEP_US, c.updates * TAIL_MODEL_UPDATE_US / std::max(1, resident)) + TAIL_MODEL_START_US;
+	return c;
+}
+
+} // namespace spp

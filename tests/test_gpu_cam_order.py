@@ -1,4 +1,4 @@
-"""GPU: the dense Schur path under the camera order of a closed loop (schur_cam_order in spp_symbolic.cpp, DESIGN
+"""GPU: the dense Schur path under the camera order of a closed loop (schur_cam_order in spp_schur_plan.cpp, DESIGN
 section 12) on 300-camera loops (15 tile rows, co-visibility +-36 cameras: a band of 3 tiles, arcs of 3 and 6 tile rows
 exist) -- the smallest shape with two independent arcs at tile granularity.
 

@@ -1,4 +1,4 @@
-"""GPU: the Schur stage itself (spp_schur.hip, plan in spp_symbolic.cpp) against the longdouble reference of
+"""GPU: the Schur stage itself (spp_schur.hip, plan in spp_schur_plan.cpp) against the longdouble reference of
 tests/schur_ref.py, entry by entry -- not only through the final dx.
 
 spp_schur_form writes S | rhs into a caller buffer: every upper entry must lie within 4 (k_ij + 8 dl) eps M_ij of the

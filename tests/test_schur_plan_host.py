@@ -1,7 +1,8 @@
 """Host-only: the symbolic Schur plan (spp_schur_plan_host -- guided ordering, observation lists, block pattern of S and
 its per-block lists of block products; what CLinearSolver_Schur recomputes structurally in every call,
 LinearSolver_Schur.cpp:771-838, LinearSolver_Schur.h:1699-1709, BlockMatrixFBS.inl:1147-1304). No GPU needed: the plan is
-pure integer work on host threads; its result must not depend on their number."""
+pure integer work on host threads; its result must not depend on their number, and it is pinned, list by list, by two
+checksums recorded once (RECORDED below)."""
 import os
 import subprocess
 import sys
@@ -91,3 +92,115 @@ def test_rejects_bad_input():
     lam = orc.lambda_structure(synth.make("se2_small"))[0]  # one block width: no landmark part
     with pytest.raises(api.SppError):
         api.schur_plan_host(lam)
+
+
+# ---- the recorded fingerprint ----------------------------------------------------------------------------------------
+# Per case: nc, nl, no, n_pairs, n_sblk, n_items, n_multi, checksum (pair lists, block list of S, item records, XCD
+# ranges), checksum_all (every list and scalar that the device plan uploads or keeps). Recorded from the plan as it was
+# BEFORE schur_plan_host() was split into phases (spp_schur_plan.cpp); a change of the plan's result has to change this
+# table on purpose. (The synth cases go through numpy's generator: the same values came out of that earlier build on a
+# second machine, so the inputs are portable.) The switches are read once per process, so every environment is a child process that evaluates all
+# of its cases.
+FINGERPRINT_CHILD = r"""
+import sys, json, os
+sys.path[:0] = [%r, os.path.join(%r, "tests")]
+import numpy as np
+from slam_plus_plus_amd import api, synth
+from slam_plus_plus_amd.blockcsc import structure_from_pairs
+from oracle import spp_oracle as orc
+import schur_fixtures as fx
+import test_cam_order_host as co
+
+def lam_of(name):
+    return orc.lambda_structure(synth.make(name))[0]
+
+def ring(camera_blocks):
+    # the smallest closed loop the camera-order rule accepts (tests/test_cam_order_host.py: ring-fifth-6-8); with
+    # camera_blocks also a camera-camera block between neighbours of the loop, which the accepted order stores
+    # transposed wherever it reverses the two (a_tr = 1 item records)
+    nc, dp = 168, 6
+    st = co._graph(nc, dp, co._band_pairs(nc, nc // 10, True))[0]
+    order, used = api.schur_cam_order_host(st)[:2]
+    assert used, "the rule no longer accepts the loop"
+    if not camera_blocks:
+        return st
+    i = np.arange(nc)
+    a, b = np.minimum(i, (i + 1) %% nc), np.maximum(i, (i + 1) %% nc)
+    st = structure_from_pairs(st.dim, np.concatenate([st.row_idx, a]), np.concatenate([st.col_idx, b]))[0]
+    o2, used2 = api.schur_cam_order_host(st)[:2]
+    pos = np.empty(nc, np.int64)
+    pos[o2] = np.arange(nc)
+    assert used2 and np.array_equal(o2, order) and (pos[a] > pos[b]).any(), "no camera-camera block is reversed"
+    return st
+
+out = {}
+def put(tag, lam, *a, **k):
+    d = api.schur_plan_host(lam, *a, **k)
+    out[tag] = [d[key] for key in ("nc", "nl", "no", "n_pairs", "n_sblk", "n_items", "n_multi", "checksum", "checksum_all")]
+
+put("ba_small", lam_of("ba_small"))
+if sys.argv[1] == "all":
+    put("ba_interleaved", lam_of("ba_interleaved"))
+    put("lm2d_small", lam_of("lm2d_small"))
+    put("ba_medium 1/2", lam_of("ba_medium"), 1, 2)
+    banded = lam_of("ba_banded")
+    put("ba_banded sparse 1/2", banded, 1, 2, True)
+    put("ba_banded sparse", banded, 0, 1, True)
+    put("mis66", fx.make("mis66")[0], mis=True)
+    put("ring-fifth-6-8", ring(False))
+    put("ring-fifth-6-8 + camera blocks", ring(True))
+print(json.dumps(out))
+"""
+
+RECORDED = {
+    '': {   # every switch at its default
+        'ba_small': (30, 1500, 7000, 27363, 465, 465, 0, -3483711703387120103, 3715577702227944784),
+        'ba_interleaved': (25, 900, 4000, 14635, 325, 325, 0, 2044530526373732354, 4307527839191075599),
+        'lm2d_small': (80, 200, 802, 2010, 407, 407, 0, -3576261367263093488, 1432125091731537988),
+        'ba_medium 1/2': (150, 10000, 50305, 214529, 5517, 5517, 0, 6976821493733558884, 6692288831176822083),
+        'ba_banded sparse 1/2': (600, 15000, 75000, 225000, 7799, 7799, 0, 7833681322732303198, -645211028342656411),
+        'ba_banded sparse': (600, 30000, 150000, 450000, 7799, 7799, 0, 4482660595254495377, -5375373520449042219),
+        'mis66': (22, 2120, 4239, 6358, 43, 46, 3, 6792182602900669238, -5361852305462679958),
+        'ring-fifth-6-8': (168, 2688, 5376, 8064, 2856, 2856, 0, -1715555521255416321, 6413900661363926547),
+        'ring-fifth-6-8 + camera blocks': (168, 2688, 5376, 8064, 2856, 2856, 0, -5765239483729953131, 5333027880825863054),
+    },
+    'SPP_SACC_FACTORED=0': {
+        'ba_small': (30, 1500, 7000, 27363, 465, 465, 0, 8463305894241590809, -5616273855013661741),
+    },
+    'SPP_SACC_ULM=0': {
+        'ba_small': (30, 1500, 7000, 27363, 465, 465, 0, -3483711703387120103, 3544198973525928305),
+    },
+    'SPP_SACC_XCD=0': {
+        'ba_small': (30, 1500, 7000, 27363, 465, 465, 0, -4663871102261509533, 3526029727418344230),
+    },
+    'SPP_SACC_TILE_COLS=0': {
+        'ba_small': (30, 1500, 7000, 27363, 465, 465, 0, 4922458397623882126, -2765313924536022111),
+    },
+    'SPP_SACC_TILE=1': {
+        'ba_small': (30, 1500, 7000, 27363, 465, 465, 0, 5544147457629794398, -6958558442293214161),
+    },
+}
+
+THREADS = {"one thread": {"SPP_PLAN_THREADS": "1"}, "five threads, every pass cut": {"SPP_PLAN_THREADS": "5", "SPP_PLAN_MIN_WORK": "1"}}
+
+
+def _fingerprints(switch, threads):
+    import json
+    env = {k: v for k, v in os.environ.items() if not k.startswith("SPP_") or k == "SPP_LIB"}
+    env.update(THREADS[threads])
+    if switch:
+        env.update([switch.split("=")])
+    r = subprocess.run([sys.executable, "-c", FINGERPRINT_CHILD % (ROOT, ROOT), "one" if switch else "all"], env=env,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    return {k: tuple(v) for k, v in json.loads(r.stdout.strip().split("\n")[-1]).items()}
+
+
+@pytest.mark.parametrize("threads", list(THREADS))
+@pytest.mark.parametrize("switch", list(RECORDED))
+def test_plan_matches_the_recorded_fingerprint(switch, threads):
+    got = _fingerprints(switch, threads)
+    print(switch or "defaults", threads, got)
+    assert set(got) == set(RECORDED[switch])
+    for case, want in RECORDED[switch].items():
+        assert got[case] == want, (switch, threads, case, got[case], want)

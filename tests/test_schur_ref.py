@@ -10,8 +10,8 @@ import schur_ref
 from slam_plus_plus_amd import api, synth
 from oracle import spp_oracle as orc
 
-PAIR_CHUNK = 2048   # spp_symbolic.cpp: block products per work item of the S accumulation
-BS_OBS = 256        # spp_symbolic.cpp: observations (and landmarks) per group of the fused back-substitution
+PAIR_CHUNK = 2048   # spp_schur_plan.cpp: block products per work item of the S accumulation
+BS_OBS = 256        # spp_schur_plan.cpp: observations (and landmarks) per group of the fused back-substitution
 
 _CACHE = {}
 
@@ -114,7 +114,7 @@ def test_guided_fixture_reaches_its_edges(name):
         run = run + 1 if t == 1 else 0
         best = max(best, run)
     assert best >= BS_OBS, "consecutive single-observation landmarks"
-    # the groups of the fused back-substitution (spp_symbolic.cpp): some group must be cut by its landmark count alone
+    # the groups of the fused back-substitution (spp_schur_plan.cpp): some group must be cut by its landmark count alone
     first, by_count = 0, 0
     for l in range(track.size):
         if R.lm_ptr[l + 1] - R.lm_ptr[first] > BS_OBS or l - first >= BS_OBS:
