@@ -395,6 +395,8 @@ int spp_get_info(const spp_ctx *ctx, int what, int64_t *out)
 	case SPP_INFO_S_LD: *out = (ctx->mode == SPP_MODE_SCHUR && !ctx->schur.sparse_S) ? ctx->schur.ld : 0; break;
 	case SPP_INFO_S_NNZB: *out = (ctx->mode == SPP_MODE_SCHUR) ? ctx->schur.n_sblk : 0; break;
 	case SPP_INFO_DENSE_STREAMED: *out = ctx->dense.tail_rows_last; break;
+	case SPP_INFO_LM_STREAM: *out = (ctx->mode == SPP_MODE_SCHUR) ? ctx->schur.lm_stream_last : 0; break;
+	case SPP_INFO_BS_GROUPS: *out = (ctx->mode == SPP_MODE_SCHUR) ? ctx->schur.n_bs : 0; break;
 	default: return SPP_E_BADARG;
 	}
 	return SPP_OK;

@@ -243,6 +243,7 @@ struct SchurPlan : SchurDims {
 	DevBuf<int32_t> lm_ptr;        // [nl+1] first obs of landmark
 	DevBuf<int32_t> bs_ptr;        // [n_bs+1] landmark ranges of the fused back-substitution (at most 256 observations each); n_bs = 0: two launches
 	int64_t n_bs = 0;
+	int lm_stream_last = 0;        // which landmark-side kernels the last schur_form launched: 0 one lane per block, 1 / 2 the streamed forms (diagnostics: SPP_INFO_LM_STREAM)
 	DevBuf<int64_t> lm_coff;       // [nl] offset of C block in vals
 	DevBuf<int64_t> lm_rbase;      // [nl] scalar offset of the landmark in rhs
 	DevBuf<int32_t> obs_pose;      // [no] reduced pose index

@@ -357,6 +357,158 @@ void obs_fact_kernel(int64_t no, const int32_t *__restrict__ obs_lm, const int64
 	}
 }
 
+// ---- the same, streamed (SPP_LM_STREAM, even block sizes: DP x DL = 6 x 3) ---------------------------------------------
+// The U blocks of a wave's 64 consecutive observations are consecutive 144-byte blocks of the landmark columns of Lambda
+// (only the landmarks' own C blocks lie between them). With one lane per block (load_U) every load instruction of a wave
+// touches 64 lines; here consecutive lanes fetch consecutive 16-byte pieces (8 lines per instruction) into the wave's LDS
+// image, from which every lane takes its own block at the odd stride. (A block may start on an 8-byte boundary -- a
+// column's C block is 72 bytes -- hence the under-aligned vector type.) Every LDS image belongs to one wave: wave barriers
+// only, and a wave past the last observation leaves at once. Per observation the arithmetic is that of obs_fact_kernel.
+// xw: XW_OBS = true writes it in observation order (one contiguous range per wave; rhs_kernel<DP, true> gathers it
+// through cam_obs), false keeps the camera-major slots but stores whole 16-byte pieces, DP / 2 lanes per slot.
+typedef double dbl2_a8 __attribute__((ext_vector_type(2), aligned(8)));
+typedef double dbl2_a16 __attribute__((ext_vector_type(2), aligned(16)));
+
+__device__ __forceinline__ void wave_lds_sync()
+{
+	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+	__builtin_amdgcn_wave_barrier();
+}
+
+// the wave's cooperative fetch: piece p = lane + 64 k of the nact >= 1 blocks whose (offset << 1 | transposed) words are off[0 .. nact)
+template <int BLK>
+__device__ __forceinline__ void fetch_U_pieces(const double *__restrict__ vals, const int64_t *off, int nact, int lane, dbl2_a8 *pc)
+{
+	constexpr int NP = BLK / 2;
+#pragma unroll
+	for(int k = 0; k < NP; ++ k) {
+		const int p = lane + 64 * k, j = p / NP, e = p - j * NP; // (j <= 63)
+		pc[k] = *(const dbl2_a8*)(vals + (off[(j < nact) ? j : nact - 1] >> 1) + 2 * e); // (no branch per load: the rows past the last block repeat it)
+	}
+}
+
+template <int BLK>
+__device__ __forceinline__ void store_U_pieces(double *img, int lane, const dbl2_a8 *pc)
+{
+	constexpr int NP = BLK / 2, ST = BLK | 1;
+#pragma unroll
+	for(int k = 0; k < NP; ++ k) {
+		const int p = lane + 64 * k, j = p / NP, e = p - j * NP;
+		img[j * ST + 2 * e] = pc[k].x;
+		img[j * ST + 2 * e + 1] = pc[k].y;
+	}
+}
+
+// a lane's own block out of the image, as DP x DL column-major (what load_U returns)
+template <int DP, int DL>
+__device__ __forceinline__ void take_U(const double *row, bool transposed, double *U)
+{
+	if(transposed) {
+#pragma unroll
+		for(int r = 0; r < DP; ++ r)
+#pragma unroll
+			for(int q = 0; q < DL; ++ q)
+				U[r + DP * q] = row[q + DL * r];
+	} else {
+#pragma unroll
+		for(int e = 0; e < DP * DL; ++ e)
+			U[e] = row[e];
+	}
+}
+
+template <int DP, int DL, bool XW_OBS>
+__global__ __launch_bounds__(256)
+void obs_fact_stream_kernel(int64_t no, const int32_t *__restrict__ obs_lm, const int64_t *__restrict__ obs_off,
+	const int64_t *__restrict__ lm_rbase, const double *__restrict__ vals, const double *__restrict__ rhs,
+	const double *__restrict__ lfac, const int64_t *__restrict__ lm_coff, const int32_t *__restrict__ obs_wpos, double *__restrict__ Vm, double *__restrict__ Vs,
+	double *__restrict__ xw)
+{
+	constexpr int BLK = DP * DL, ST = BLK | 1, IL = VSplit<BLK>::IL, SIDE = VSplit<BLK>::SIDE, XST = DP | 1;
+	static_assert(BLK % 2 == 0 && IL % 2 == 0 && SIDE % 2 == 0 && DP % 2 == 0, "16-byte pieces");
+	__shared__ double img_all[4][64 * ST];
+	__shared__ int64_t off_all[4][64];
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	double *img = img_all[wave];
+	int64_t *off = off_all[wave];
+	const int64_t a0 = ((int64_t)blockIdx.x * 4 + wave) * 64, a = a0 + lane;
+	if(a0 >= no)
+		return; // (no workgroup barrier below)
+	const bool active = a < no;
+	const int nact = (no - a0 < 64) ? (int)(no - a0) : 64;
+	const int64_t oo = active ? obs_off[a] : 0;
+	const int32_t l = active ? obs_lm[a] : 0; // (an idle lane works on landmark 0 and stores nothing)
+	const int64_t rb = lm_rbase[l], coff = lm_coff[l];
+	off[lane] = oo;
+	wave_lds_sync();
+	dbl2_a8 pc[BLK / 2];
+	fetch_U_pieces<BLK>(vals, off, nact, lane, pc);
+	double F[DL * DL], lv[DL], tv[DL];
+	if(lfac) {
+#pragma unroll
+		for(int e = 0; e < DL * DL; ++ e)
+			F[e] = lfac[(int64_t)l * DL * DL + e];
+	} else
+		lfac_block<DL>(vals + coff, F);
+#pragma unroll
+	for(int q = 0; q < DL; ++ q)
+		lv[q] = rhs[rb + q];
+#pragma unroll
+	for(int q = 0; q < DL; ++ q) { // t = F^T l
+		double sum = 0;
+#pragma unroll
+		for(int u = 0; u < DL; ++ u)
+			if(u <= q)
+				sum += F[u + DL * q] * lv[u];
+		tv[q] = sum;
+	}
+	store_U_pieces<BLK>(img, lane, pc);
+	wave_lds_sync();
+	double U[BLK];
+	take_U<DP, DL>(img + lane * ST, (oo & 1) != 0, U); // (an idle lane computes on a copy of the last block and stores nothing)
+	double V[BLK], Wl[DP];
+#pragma unroll
+	for(int r = 0; r < DP; ++ r)
+		Wl[r] = 0;
+#pragma unroll
+	for(int q = 0; q < DL; ++ q)
+#pragma unroll
+		for(int r = 0; r < DP; ++ r) {
+			double sum = 0;
+#pragma unroll
+			for(int t = 0; t < DL; ++ t)
+				if(t <= q)
+					sum += U[r + DP * t] * F[t + DL * q];
+			V[r + DP * q] = sum;
+			Wl[r] -= sum * tv[q];
+		}
+#pragma unroll
+	for(int e = 0; e < BLK; ++ e)
+		img[lane * ST + e] = V[e]; // (over the lane's own U row, which only this lane read)
+	wave_lds_sync();
+	for(int p = lane; p < nact * (IL / 2); p += 64) { // the in-line parts of the wave's blocks are one contiguous range
+		const int j = p / (IL / 2), e = p - j * (IL / 2);
+		const dbl2_a16 v = {img[j * ST + 2 * e], img[j * ST + 2 * e + 1]};
+		*(dbl2_a16*)(Vm + a0 * IL + 2 * p) = v;
+	}
+	if(SIDE)
+		for(int p = lane; p < nact * (SIDE / 2); p += 64) {
+			const int j = p / (SIDE ? SIDE / 2 : 1), e = p - j * (SIDE / 2);
+			const dbl2_a16 v = {img[j * ST + IL + 2 * e], img[j * ST + IL + 2 * e + 1]};
+			*(dbl2_a16*)(Vs + a0 * SIDE + 2 * p) = v;
+		}
+	wave_lds_sync();
+#pragma unroll
+	for(int r = 0; r < DP; ++ r)
+		img[lane * XST + r] = Wl[r];
+	wave_lds_sync();
+	for(int p = lane; p < nact * (DP / 2); p += 64) {
+		const int j = p / (DP / 2), e = p - j * (DP / 2);
+		const dbl2_a16 v = {img[j * XST + 2 * e], img[j * XST + 2 * e + 1]};
+		const int64_t row = XW_OBS ? a0 + j : (int64_t)obs_wpos[a0 + j];
+		*(dbl2_a16*)(xw + row * DP + 2 * e) = v;
+	}
+}
+
 // ---- S block accumulation: a wave works through a short run of work items ------------------------------
 // Each LANE takes whole pairs (a, b) of the item's list (lane, lane + 64, ...) and forms the DP x DP
 // outer product sum W_a U_b^T in registers (108 FMAs per pair). The blocks are NOT fetched by the lane
@@ -720,7 +872,8 @@ void s_multi_kernel(int64_t n_multi, const int32_t *__restrict__ multi_blk, cons
 }
 
 // ---- reduced right-hand side: one wave per pose; written into padding column n_red of S -----------
-template <int DP>
+// XW_OBS: xw is in observation order (obs_fact_stream_kernel) and is gathered through the pose's list; the sums are the same
+template <int DP, bool XW_OBS>
 __global__ __launch_bounds__(256)
 void rhs_kernel(int64_t nc, const int32_t *__restrict__ cam_ptr, const int32_t *__restrict__ cam_obs,
 	const int64_t *__restrict__ pose_rbase, const double *__restrict__ xw, const double *__restrict__ rhs,
@@ -734,8 +887,9 @@ void rhs_kernel(int64_t nc, const int32_t *__restrict__ cam_ptr, const int32_t *
 #pragma unroll
 	for(int r = 0; r < DP; ++ r)
 		s[r] = 0;
-	for(int32_t q = cam_ptr[i] + lane; q < cam_ptr[i + 1]; q += 64) {
-		const double *x = xw + (int64_t)q * DP; // xw is camera-major: the pose's list is contiguous
+#pragma unroll 4
+	for(int32_t q = cam_ptr[i] + lane; q < cam_ptr[i + 1]; q += 64) { // (unrolled: the gathers of four entries in flight, added in list order)
+		const double *x = xw + (int64_t)(XW_OBS ? cam_obs[q] : q) * DP; // (else xw is camera-major: the pose's list is contiguous)
 #pragma unroll
 		for(int r = 0; r < DP; ++ r)
 			s[r] += x[r];
@@ -887,6 +1041,120 @@ void backsubst_fused_kernel(const int32_t *__restrict__ bs_ptr, const int32_t *_
 	}
 }
 
+// The fused kernel, streamed (SPP_LM_STREAM, even block sizes): a workgroup works through `per` consecutive groups. The
+// U blocks of a group are fetched like those of obs_fact_stream_kernel (each wave the 64 observations its lanes own), and
+// the pieces and dx of group g + 1 are requested BEFORE the landmark step of group g -- whose own operands were requested
+// before that, so that waiting for them does not wait for the fetch -- and land in registers under the serial per-landmark
+// sums. Two product buffers, so one workgroup barrier per group. Per observation and per landmark the operations and their
+// order are those of backsubst_fused_kernel.
+template <int DP, int DL>
+__global__ __launch_bounds__(256)
+void backsubst_stream_kernel(int32_t n_bs, int32_t per, const int32_t *__restrict__ bs_ptr, const int32_t *__restrict__ lm_ptr, const int32_t *__restrict__ obs_pose,
+	const int64_t *__restrict__ obs_off, const int64_t *__restrict__ lm_rbase, const double *__restrict__ cinv,
+	const int64_t *__restrict__ lm_coff, const double *__restrict__ vals, const double *__restrict__ dx, double *__restrict__ rhs)
+{
+	constexpr int BLK = DP * DL, ST = BLK | 1;
+	static_assert(BLK % 2 == 0, "16-byte pieces");
+	__shared__ double img_all[4][64 * ST];
+	__shared__ int64_t off_all[4][64];
+	__shared__ double tq_all[2][256 * DL];
+	const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+	double *img = img_all[wave];
+	int64_t *off = off_all[wave];
+	const int32_t g0 = blockIdx.x * per, g1 = (g0 + per < n_bs) ? g0 + per : n_bs;
+	// the group in flight
+	dbl2_a8 pc[BLK / 2] = {};
+	double dv[DP];
+	int32_t l0, l1, a0, na;
+	bool transposed;
+	auto request = [&](int32_t g) {
+		l0 = bs_ptr[g], l1 = bs_ptr[g + 1];
+		a0 = lm_ptr[l0], na = lm_ptr[l1] - a0;
+		const int64_t oo = (t < na) ? obs_off[(int64_t)a0 + t] : 0;
+		const double *d = dx + (int64_t)((t < na) ? obs_pose[(int64_t)a0 + t] : 0) * DP; // (an idle lane reads pose 0 and uses nothing)
+		transposed = (oo & 1) != 0;
+		off[lane] = oo;
+		wave_lds_sync();
+#pragma unroll
+		for(int r = 0; r < DP; ++ r)
+			dv[r] = d[r];
+		const int rest = na - 64 * wave;
+		if(rest > 0) // (wave-uniform)
+			fetch_U_pieces<BLK>(vals, off, (rest < 64) ? rest : 64, lane, pc);
+	};
+	if(g0 < g1)
+		request(g0);
+	for(int32_t g = g0; g < g1; ++ g) {
+		double *tq = tq_all[(g - g0) & 1];
+		store_U_pieces<BLK>(img, lane, pc);
+		wave_lds_sync();
+		if(t < na) {
+			double u[BLK];
+			take_U<DP, DL>(img + lane * ST, transposed, u);
+#pragma unroll
+			for(int q = 0; q < DL; ++ q) {
+				double sum = 0;
+#pragma unroll
+				for(int r = 0; r < DP; ++ r)
+					sum += dv[r] * u[r + DP * q];
+				tq[t * DL + q] = sum;
+			}
+		}
+		// the landmark step's operands, requested ahead of the next group's fetch
+		const int32_t nlg = l1 - l0, ga0 = a0;
+		const bool lm_lane = t < nlg;
+		const int64_t l = (int64_t)l0 + (lm_lane ? t : 0);
+		const int64_t rb = lm_rbase[l];
+		const int32_t pa = lm_ptr[l] - ga0, pe = lm_ptr[l + 1] - ga0;
+		double tv[DL], m[DL * DL];
+#pragma unroll
+		for(int q = 0; q < DL; ++ q)
+			tv[q] = -rhs[rb + q]; // v_l = -v_l, LinearSolver_Schur.h:1867
+		{
+			const double *src = cinv ? cinv + l * DL * DL : vals + lm_coff[l];
+#pragma unroll
+			for(int e = 0; e < DL * DL; ++ e)
+				m[e] = src[e];
+		}
+		if(g + 1 < g1)
+			request(g + 1);
+		else { // (the last group: have the operands land here too, or the wait for them behind the barrier would also cut into a fetch.
+		       // These pins and the hand-written barrier only steer where the compiler places its waits: the result does not
+		       // depend on them, the overlap does, and nothing but reading the generated code checks that it is still there)
+#pragma unroll
+			for(int q = 0; q < DL; ++ q)
+				asm volatile("" : "+v"(tv[q]));
+#pragma unroll
+			for(int e = 0; e < DL * DL; ++ e)
+				asm volatile("" : "+v"(m[e]));
+			asm volatile("" :: "v"(pa), "v"(pe));
+		}
+		asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); // the products of group g are in LDS (the fetch stays in flight)
+		if(lm_lane) {
+			for(int32_t p = pa; p < pe; ++ p) {
+#pragma unroll
+				for(int q = 0; q < DL; ++ q)
+					tv[q] += tq[p * DL + q];
+			}
+			double Ci[DL * DL];
+			if(cinv) {
+#pragma unroll
+				for(int e = 0; e < DL * DL; ++ e)
+					Ci[e] = m[e];
+			} else
+				cinv_block<DL>(m, Ci);
+#pragma unroll
+			for(int q = 0; q < DL; ++ q) {
+				double sum = 0;
+#pragma unroll
+				for(int u = 0; u < DL; ++ u)
+					sum += Ci[q + DL * u] * tv[u];
+				rhs[rb + q] = sum;
+			}
+		}
+	}
+}
+
 template <int DP>
 __global__ __launch_bounds__(256)
 void scatter_dx_kernel(int64_t nc, const int64_t *__restrict__ pose_rbase, const double *__restrict__ dx,
@@ -899,6 +1167,34 @@ void scatter_dx_kernel(int64_t nc, const int64_t *__restrict__ pose_rbase, const
 }
 
 // --------------------------------------------------------------------------------------------------
+// which streamed form a plan takes: 0 none, 1 xw in observation order, 2 xw camera-major
+template <int DP, int DL>
+static int lm_stream_form(const SchurPlan &sp)
+{
+	if(!(DP == 6 && DL == 3) || !sp.factored)
+		return 0;
+	const int v = switches().lm_stream;
+	return (v == 1 || v == 2) ? v : 0;
+}
+
+template <int DP, int DL, typename... Args>
+static void launch_obs_fact_stream(bool xw_obs, dim3 grid, hipStream_t s, Args... args)
+{
+	if constexpr(DP == 6 && DL == 3) {
+		if(xw_obs)
+			hipLaunchKernelGGL((obs_fact_stream_kernel<DP, DL, true>), grid, dim3(256), 0, s, args...);
+		else
+			hipLaunchKernelGGL((obs_fact_stream_kernel<DP, DL, false>), grid, dim3(256), 0, s, args...);
+	}
+}
+
+template <int DP, int DL, typename... Args>
+static void launch_backsubst_stream(dim3 grid, hipStream_t s, Args... args)
+{
+	if constexpr(DP == 6 && DL == 3)
+		hipLaunchKernelGGL((backsubst_stream_kernel<DP, DL>), grid, dim3(256), 0, s, args...);
+}
+
 template <int DP, int DL>
 static void schur_form_t(spp_ctx *ctx, const double *d_vals, const double *d_rhs, double *S)
 {
@@ -921,12 +1217,20 @@ static void schur_form_t(spp_ctx *ctx, const double *d_vals, const double *d_rhs
 	if(sp.nl && !onfly)
 		hipLaunchKernelGGL((cinv_kernel<DL>), dim3((unsigned)((sp.nl + 255) / 256)), dim3(256), 0, s,
 			sp.nl, sp.lm_coff.p, d_vals, sp.cinv.p, sp.factored ? sp.lfac.p : nullptr);
-	if(sp.no && sp.factored)
-		hipLaunchKernelGGL((obs_fact_kernel<DP, DL>), dim3((unsigned)((sp.no + 255) / 256)), dim3(256), 0, s,
-			sp.no, sp.obs_lm.p, sp.obs_off.p, sp.lm_rbase.p, d_vals, d_rhs, onfly ? (const double*)nullptr : (const double*)sp.lfac.p, sp.lm_coff.p,
+	// the streamed landmark-side kernels (SPP_LM_STREAM): built, measured and tested for the factored form with 6 x 3 blocks only
+	const int lm_stream = lm_stream_form<DP, DL>(sp);
+	sp.lm_stream_last = lm_stream;
+	const double *lfac_arg = onfly ? (const double*)nullptr : (const double*)sp.lfac.p;
+	const dim3 obs_grid((unsigned)((sp.no + 255) / 256));
+	if(sp.no && lm_stream)
+		launch_obs_fact_stream<DP, DL>(lm_stream == 1, obs_grid, s, sp.no, sp.obs_lm.p, sp.obs_off.p, sp.lm_rbase.p, d_vals, d_rhs, lfac_arg,
+			sp.lm_coff.p, sp.obs_wpos.p, Vm, Vs, sp.xw.p);
+	else if(sp.no && sp.factored)
+		hipLaunchKernelGGL((obs_fact_kernel<DP, DL>), obs_grid, dim3(256), 0, s,
+			sp.no, sp.obs_lm.p, sp.obs_off.p, sp.lm_rbase.p, d_vals, d_rhs, lfac_arg, sp.lm_coff.p,
 			sp.obs_wpos.p, Vm, Vs, sp.xw.p);
 	else if(sp.no)
-		hipLaunchKernelGGL((obs_kernel<DP, DL>), dim3((unsigned)((sp.no + 255) / 256)), dim3(256), 0, s,
+		hipLaunchKernelGGL((obs_kernel<DP, DL>), obs_grid, dim3(256), 0, s,
 			sp.no, sp.obs_lm.p, sp.obs_off.p, sp.lm_rbase.p, d_vals, d_rhs, sp.cinv.p, sp.obs_wpos.p, sp.W.p, sp.Up.p, sp.xw.p, sp.u_landmark_major ? 1 : 0);
 	phase_end(ctx, SPP_PHASE_SCHUR_INV);
 	phase_begin(ctx, SPP_PHASE_SCHUR_GEMM);
@@ -948,8 +1252,11 @@ static void schur_form_t(spp_ctx *ctx, const double *d_vals, const double *d_rhs
 			sp.partial.p, d_vals, sp.add_A ? 1 : 0, S, ld, voff);
 	phase_end(ctx, SPP_PHASE_SCHUR_GEMM);
 	phase_begin(ctx, SPP_PHASE_SCHUR_RHS);
-	if(sp.nc)
-		hipLaunchKernelGGL((rhs_kernel<DP>), dim3((unsigned)((sp.nc + 3) / 4)), dim3(256), 0, s,
+	if(sp.nc && lm_stream == 1)
+		hipLaunchKernelGGL((rhs_kernel<DP, true>), dim3((unsigned)((sp.nc + 3) / 4)), dim3(256), 0, s,
+			sp.nc, sp.cam_ptr.p, sp.cam_obs.p, sp.pose_rbase.p, sp.xw.p, d_rhs, sp.add_A ? 1 : 0, xcol);
+	else if(sp.nc)
+		hipLaunchKernelGGL((rhs_kernel<DP, false>), dim3((unsigned)((sp.nc + 3) / 4)), dim3(256), 0, s,
 			sp.nc, sp.cam_ptr.p, sp.cam_obs.p, sp.pose_rbase.p, sp.xw.p, d_rhs, sp.add_A ? 1 : 0, xcol);
 	phase_end(ctx, SPP_PHASE_SCHUR_RHS);
 	SPP_HIP_CHECK(hipGetLastError());
@@ -990,7 +1297,14 @@ static int schur_finish_t(spp_ctx *ctx, const double *d_vals, double *S, double 
 	static_assert(DL <= DP, "the products U^T dx reuse the W l buffer (DP doubles per observation)");
 	const int bs_fused = switches().backsubst_fused;
 	const double *cinv_arg = (sp.factored && DL <= 3) ? (const double*)nullptr : (const double*)sp.cinv.p;
-	if(bs_fused && sp.n_bs > 0)
+	// consecutive groups per workgroup of the streamed kernel: 4 where that still leaves every CU a workgroup, else 1 (a
+	// small problem wants all of its groups side by side, not a pipeline: Ladybug-49 has 130 groups)
+	const int32_t bs_per = (sp.n_bs >= 1024) ? 4 : 1;
+	if(bs_fused && sp.n_bs > 0 && lm_stream_form<DP, DL>(sp))
+		launch_backsubst_stream<DP, DL>(dim3((unsigned)((sp.n_bs + bs_per - 1) / bs_per)), s,
+			(int32_t)sp.n_bs, bs_per, (const int32_t*)sp.bs_ptr.p, (const int32_t*)sp.lm_ptr.p, (const int32_t*)sp.obs_pose.p, (const int64_t*)sp.obs_off.p,
+			(const int64_t*)sp.lm_rbase.p, cinv_arg, (const int64_t*)sp.lm_coff.p, d_vals, (const double*)xcol, d_rhs);
+	else if(bs_fused && sp.n_bs > 0)
 		hipLaunchKernelGGL((backsubst_fused_kernel<DP, DL>), dim3((unsigned)sp.n_bs), dim3(256), 0, s,
 			sp.bs_ptr.p, sp.lm_ptr.p, sp.obs_pose.p, sp.obs_off.p, sp.lm_rbase.p, cinv_arg, sp.lm_coff.p, d_vals, xcol, d_rhs);
 	else {
