@@ -173,7 +173,7 @@ int spp_schur_unpack(spp_ctx *ctx, const double *d_packed, double *d_S_rhs);
  * NonlinearSolver_Lambda_Base.h:1852-1931, BaseTypes_Binary.h:525-660) and Refresh_Lambda =
  * Calculate_Hessians_v2 over all edges + ReduceAll (numeric; _Lambda_Base.h:1658-1688,
  * BaseTypes_Binary.h:759-848, _Lambda_Base.h:563-607,152-197).
- * One homogeneous binary-edge group: residual dimension rd, vertex 0 width d0, vertex 1 width d1.
+ * One homogeneous binary-edge group (several: spp_assemble_analyze_groups below): residual dimension rd, vertex 0 width d0, vertex 1 width d1.
  * J0: ne x (rd x d0) col-major, J1: ne x (rd x d1), Omega: ne x (rd x rd), r: ne x rd.
  * The unary factor (identity, FlatSystem.h:441,467) is added to the diagonal block of vertex
  * `unary_vertex` (pass -1 for none). The reference's default build puts it on vertex 0 whatever its type
@@ -195,6 +195,30 @@ int spp_assemble_device(spp_ctx *ctx, const double *d_J0, const double *d_J1,
  * H11 and the second vertex's right-hand side once. The array is NOT copied (it must stay valid); NULL restores plain
  * edges; spp_assemble_analyze resets it. */
 int spp_assemble_set_edge_weights(spp_ctx *ctx, const double *d_w);
+/* Several edge groups in one Lambda: odometry (3,3,3) beside landmark observations (3,2,2), camera-camera constraints
+ * (6,6,6) beside projections (6,3,2) -- the reference's AddEntriesInSparseSystem / Refresh_Lambda run over an edge pool of
+ * several types alike (NonlinearSolver_Lambda_Base.h:1852-1931, 1658-1688; the reduction plan sums a destination's sources
+ * in the order the edges were added, whatever their types: :563-607, 152-197; BaseTypes_Binary.h:759-848 per edge).
+ * Group g: h_ne[g] edges h_v0[g] -> h_v1[g] of shape (h_d0[g], h_d1[g], h_rd[g]), one of the four above; two groups may
+ * share a shape. h_seq[g][e]: position of that edge in the graph's global edge order (all of them a permutation of
+ * 0 .. sum(ne) - 1; h_seq, or h_seq[g], NULL: the position in the concatenation of the groups). Every destination -- diagonal
+ * block, eta segment, off-diagonal block, also one fed by several groups -- sums its contributions in ascending position,
+ * first assigned, rest added (vertices of degree > 24: the fixed butterfly of the wave kernel over that order). The
+ * structure (spp_assemble_get_structure, NNZB / NVALS) is the union: every diagonal block and one upper block per
+ * connected pair. With one group and no h_seq this IS spp_assemble_analyze, and spp_assemble_device accepts the plan;
+ * spp_assemble_groups_device (host arrays of n_groups device pointers) accepts any plan and gives the same bits on a
+ * one-group plan.
+ * Unary factor and damping as above; robust weights per group (NULL: plain), reset by either analyze call.
+ * SPP_E_UNSUPPORTED: a shape not instantiated, more than SPP_MAX_EDGE_GROUPS groups. SPP_E_BADARG: a vertex width that does
+ * not match its group, a bad index, a self edge, h_seq not a permutation; the ctx then holds no assembly plan.
+ * SPP_E_STATE: spp_assemble_device on a plan of several groups, spp_assemble_groups_device without a plan. */
+#define SPP_MAX_EDGE_GROUPS 4
+int spp_assemble_analyze_groups(spp_ctx *ctx, int64_t nv, const int32_t *h_dim, int n_groups,
+	const int64_t *h_ne, const int64_t *const *h_v0, const int64_t *const *h_v1, const int64_t *const *h_seq,
+	const int32_t *h_d0, const int32_t *h_d1, const int32_t *h_rd, int64_t unary_vertex);
+int spp_assemble_groups_device(spp_ctx *ctx, const double *const *d_J0, const double *const *d_J1,
+	const double *const *d_Omega, const double *const *d_r, double damping, double *d_vals_out, double *d_eta_out);
+int spp_assemble_set_group_edge_weights(spp_ctx *ctx, int group, const double *d_w);
 /* the weights themselves, on the device: w_e = kernel(||r_e|| / scale) -- CRobustify_ErrorNorm_Default::f_RobustWeight
  * (include/slam/RobustUtils.h:396-400) with kind 0 = Huber, w = 1 for x <= param, param / x beyond (CHuberLoss::operator (),
  * include/geometry/RobustLoss.h:100-104; the reference's default param is 1.345). Asynchronous on the ctx stream. */
@@ -216,6 +240,25 @@ int spp_se2_linearize_device(spp_ctx *ctx, int64_t n_edges, const int32_t *d_v0,
 	const double *d_poses, const double *d_measurements, double *d_J0, double *d_J1, double *d_r);
 int spp_se2_update_device(spp_ctx *ctx, int64_t n_vertices, double *d_poses, const double *d_dx, int apply,
 	double *h_dx_norm2);
+
+/* ---- on-device geometry of 2D landmark SLAM (CEdgePose2D + CEdgePoseLandmark2D) ----------------------
+ * Poses (x y theta) and landmarks (x y) live in ONE flat state laid out like eta (in 2D the increment has the state's
+ * layout); vertices are addressed by scalar offset (int64), so 2-wide vertices may sit between the poses.
+ * spp_se2_linearize_at_device: spp_se2_linearize_device with the two pose offsets given per edge (3 * id reproduces it).
+ * spp_se2_rb_linearize_device: per observation the expectation (||l - p||, clamp(atan2(dn, de) - theta)) and the 2x3 / 2x2
+ * Jacobians of C2DJacobians::Observation2D_RangeBearing (include/slam/2DSolverBase.h:443-496; the range is floored at 1e-5
+ * before the Jacobians are formed), r = z - h with the bearing error wrapped (CEdgePoseLandmark2D::
+ * Calculate_Jacobians_Expectation_Error, include/slam/SE2_Types.h:562-573); layout of the (3,2,2) group: J0 ne x (2x3)
+ * column-major, J1 ne x (2x2), r ne x 2.
+ * spp_slam2d_update_device: ||dx||^2 over the n state entries (two-stage sum) and, if `apply`, x += dx, the n_pose_angles
+ * entries at d_angle_off clamped afterwards (CVertexPose2D::Operator_Plus, SE2_Types.h:70-74); landmarks are plain sums
+ * (CVertexLandmark2D::Operator_Plus, :89). Synchronizes the stream. */
+int spp_se2_linearize_at_device(spp_ctx *ctx, int64_t n_edges, const int64_t *d_off0, const int64_t *d_off1,
+	const double *d_state, const double *d_measurements, double *d_J0, double *d_J1, double *d_r);
+int spp_se2_rb_linearize_device(spp_ctx *ctx, int64_t n_edges, const int64_t *d_pose_off, const int64_t *d_lm_off,
+	const double *d_state, const double *d_measurements, double *d_J0, double *d_J1, double *d_r);
+int spp_slam2d_update_device(spp_ctx *ctx, int64_t n, double *d_state, const double *d_dx, int64_t n_pose_angles,
+	const int64_t *d_angle_off, int apply, double *h_dx_norm2);
 
 /* ---- on-device geometry of 3D pose graphs (CEdgePose3D) ---------------------------
  * Poses: 6 doubles [t | axis-angle]. Expectation = C3DJacobians::Absolute_to_Relative(v0, v1), error

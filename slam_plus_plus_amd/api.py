@@ -31,7 +31,9 @@ EXPORTS = [
     "spp_analyze", "spp_set_shard", "spp_get_info", "spp_get_ordering", "spp_factor_solve",
     "spp_factor_solve_device", "spp_schur_buffer_size", "spp_schur_form", "spp_schur_finish",
     "spp_schur_packed_size", "spp_schur_pack", "spp_schur_unpack",
-    "spp_assemble_analyze", "spp_assemble_get_structure", "spp_assemble_device", "spp_assemble_set_edge_weights", "spp_device_malloc",
+    "spp_assemble_analyze", "spp_assemble_get_structure", "spp_assemble_device", "spp_assemble_set_edge_weights",
+    "spp_assemble_analyze_groups", "spp_assemble_groups_device", "spp_assemble_set_group_edge_weights",
+    "spp_se2_linearize_at_device", "spp_se2_rb_linearize_device", "spp_slam2d_update_device", "spp_device_malloc",
     "spp_device_free", "spp_memcpy_h2d", "spp_memcpy_d2h", "spp_memcpy_d2d", "spp_get_phase_ms", "spp_get_dominant_kernel",
     "spp_microbench_copy", "spp_microbench_mfma_f64", "spp_microbench_ctile", "spp_microbench_update", "spp_block_ordering", "spp_schur_plan_host", "spp_set_profiling", "spp_se2_linearize_device", "spp_se2_update_device", "spp_ba_linearize_device", "spp_ba_update_device", "spp_se3_linearize_device", "spp_se3_update_device", "spp_edge_chi2_device", "spp_edge_robust_weights_device", "spp_edge_hessian_maxdiag_device",
     "spp_lm_gain_denominator_device", "spp_dense_potrf_upper", "spp_dense_posv",
@@ -82,6 +84,12 @@ def load_library():
         "spp_assemble_get_structure": (cint, [vp, vp, vp, vp]),
         "spp_assemble_device": (cint, [vp, vp, vp, vp, vp, dbl, vp, vp]),
         "spp_assemble_set_edge_weights": (cint, [vp, vp]),
+        "spp_assemble_analyze_groups": (cint, [vp, i64, vp, cint, vp, vp, vp, vp, vp, vp, vp, i64]),
+        "spp_assemble_groups_device": (cint, [vp, vp, vp, vp, vp, dbl, vp, vp]),
+        "spp_assemble_set_group_edge_weights": (cint, [vp, cint, vp]),
+        "spp_se2_linearize_at_device": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+        "spp_se2_rb_linearize_device": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+        "spp_slam2d_update_device": (cint, [vp, i64, vp, vp, i64, vp, cint, _c_f64p]),
         "spp_device_malloc": (cint, [vp, ctypes.c_size_t, ctypes.POINTER(vp)]),
         "spp_device_free": (cint, [vp, vp]),
         "spp_memcpy_h2d": (cint, [vp, vp, vp, ctypes.c_size_t]),
@@ -340,6 +348,21 @@ class Context:
         self._check(self.lib.spp_se2_update_device(self.h, n_vertices, d_poses, d_dx, 1 if apply else 0, ctypes.byref(out)))
         return out.value ** 0.5
 
+    def se2_linearize_at_device(self, n_edges, d_off0, d_off1, d_state, d_meas, d_J0, d_J1, d_r):
+        """se2_linearize_device with the poses at scalar offsets (int64) into one flat state"""
+        return self._check(self.lib.spp_se2_linearize_at_device(self.h, n_edges, d_off0, d_off1, d_state, d_meas, d_J0, d_J1, d_r))
+
+    def se2_rb_linearize_device(self, n_edges, d_pose_off, d_lm_off, d_state, d_meas, d_J0, d_J1, d_r):
+        """range-bearing observations (CEdgePoseLandmark2D): the (3, 2, 2) group's J0, J1, r"""
+        return self._check(self.lib.spp_se2_rb_linearize_device(self.h, n_edges, d_pose_off, d_lm_off, d_state, d_meas, d_J0, d_J1, d_r))
+
+    def slam2d_update_device(self, n, d_state, d_dx, n_pose_angles, d_angle_off, apply=True):
+        """returns ||dx|| (host); when `apply`, state += dx with the pose angles at d_angle_off clamped"""
+        out = ctypes.c_double()
+        self._check(self.lib.spp_slam2d_update_device(self.h, n, d_state, d_dx, n_pose_angles, d_angle_off, 1 if apply else 0,
+                                                      ctypes.byref(out)))
+        return out.value ** 0.5
+
     def se3_linearize_device(self, n_edges, d_v0, d_v1, d_poses, d_meas, d_J0, d_J1, d_r):
         return self._check(self.lib.spp_se3_linearize_device(self.h, n_edges, d_v0, d_v1, d_poses, d_meas, d_J0, d_J1, d_r))
 
@@ -433,6 +456,9 @@ class Context:
         v1 = np.ascontiguousarray(v1, dtype=np.int64)
         self._check(self.lib.spp_assemble_analyze(self.h, dim.size, _ptr(dim), v0.size, _ptr(v0), _ptr(v1),
                                                    d0, d1, rd, int(unary_vertex)))
+        return self._assemble_structure(dim)
+
+    def _assemble_structure(self, dim):
         nb, nnzb = dim.size, self.info("NNZB")
         col_ptr = np.empty(nb + 1, dtype=np.int64)
         row_idx = np.empty(nnzb, dtype=np.int64)
@@ -440,6 +466,32 @@ class Context:
         self._check(self.lib.spp_assemble_get_structure(self.h, _ptr(col_ptr), _ptr(row_idx), _ptr(blk_off)))
         from .blockcsc import BlockCSC
         return BlockCSC(dim, col_ptr, row_idx, blk_off, None, nvals=self.info("NVALS"))
+
+    def assemble_analyze_groups(self, dim, groups, seq=None, unary_vertex=-1):
+        """several edge groups in one Lambda. groups: a list of (v0, v1, d0, d1, rd); seq: None, or per group the global
+        position of each edge (or None). Returns the union structure, as assemble_analyze does."""
+        dim = np.ascontiguousarray(dim, dtype=np.int32)
+        ng = len(groups)
+        v0 = [np.ascontiguousarray(g[0], dtype=np.int64) for g in groups]
+        v1 = [np.ascontiguousarray(g[1], dtype=np.int64) for g in groups]
+        sq = [None if (seq is None or q is None) else np.ascontiguousarray(q, dtype=np.int64) for q in (seq or [None] * ng)]
+        parr = lambda arrs: (ctypes.c_void_p * ng)(*[None if a is None else a.ctypes.data for a in arrs])
+        ne = np.array([a.size for a in v0], dtype=np.int64)
+        d0, d1, rd = (np.array([g[k] for g in groups], dtype=np.int32) for k in (2, 3, 4))
+        self._check(self.lib.spp_assemble_analyze_groups(self.h, dim.size, _ptr(dim), ng, _ptr(ne), parr(v0), parr(v1),
+                                                          None if seq is None else parr(sq), _ptr(d0), _ptr(d1), _ptr(rd),
+                                                          int(unary_vertex)))
+        return self._assemble_structure(dim)
+
+    def assemble_groups_device(self, d_J0, d_J1, d_Om, d_r, damping, d_vals, d_eta):
+        """d_J0 ... d_r: one device pointer per group"""
+        parr = lambda ptrs: (ctypes.c_void_p * len(ptrs))(*ptrs)
+        return self._check(self.lib.spp_assemble_groups_device(self.h, parr(d_J0), parr(d_J1), parr(d_Om), parr(d_r),
+                                                               float(damping), d_vals, d_eta))
+
+    def assemble_set_group_edge_weights(self, group, d_w):
+        """robust edges of one group: device array of one weight per edge of that group (None: plain edges)"""
+        return self._check(self.lib.spp_assemble_set_group_edge_weights(self.h, int(group), d_w))
 
     def assemble_set_edge_weights(self, d_w):
         """robust edges: device array of one weight per edge for the following assemble_device calls (None: plain edges)"""

@@ -684,11 +684,37 @@ int spp_factor_solve(spp_ctx *ctx, const double *h_vals, double *h_rhs)
 int spp_assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *h_dim, int64_t ne, const int64_t *h_v0,
 	const int64_t *h_v1, int d0, int d1, int rd, int64_t unary_vertex)
 {
-	if(!ctx || !h_dim || !h_v0 || !h_v1 || nv <= 0 || ne <= 0)
+	if(!ctx)
+		return SPP_E_BADARG;
+	assemble_release(ctx); // whatever happens below: after a rejected call the ctx holds no assembly plan
+	if(!h_dim || !h_v0 || !h_v1 || nv <= 0 || ne <= 0)
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
-	assemble_analyze(ctx, nv, h_dim, ne, h_v0, h_v1, d0, d1, rd, unary_vertex);
+	assemble_analyze(ctx, nv, h_dim, 1, &ne, &h_v0, &h_v1, nullptr, &d0, &d1, &rd, unary_vertex);
+	return SPP_OK;
+	SPP_CATCH(ctx)
+}
+
+int spp_assemble_analyze_groups(spp_ctx *ctx, int64_t nv, const int32_t *h_dim, int n_groups, const int64_t *h_ne,
+	const int64_t *const *h_v0, const int64_t *const *h_v1, const int64_t *const *h_seq, const int32_t *h_d0,
+	const int32_t *h_d1, const int32_t *h_rd, int64_t unary_vertex)
+{
+	if(!ctx)
+		return SPP_E_BADARG;
+	assemble_release(ctx); // whatever happens below: after a rejected call the ctx holds no assembly plan
+	if(!h_dim || nv <= 0 || n_groups <= 0 || !h_ne || !h_v0 || !h_v1 || !h_d0 || !h_d1 || !h_rd)
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	SPP_REQUIRE(n_groups <= SPP_MAX_EDGE_GROUPS, SPP_E_UNSUPPORTED, "more than SPP_MAX_EDGE_GROUPS edge groups");
+	int64_t total = 0;
+	for(int g = 0; g < n_groups; ++ g) {
+		SPP_REQUIRE(h_ne[g] >= 0 && (!h_ne[g] || (h_v0[g] && h_v1[g])), SPP_E_BADARG, "edge group without vertex arrays");
+		total += h_ne[g];
+	}
+	SPP_REQUIRE(total > 0, SPP_E_BADARG, "no edges");
+	assemble_analyze(ctx, nv, h_dim, n_groups, h_ne, h_v0, h_v1, h_seq, h_d0, h_d1, h_rd, unary_vertex);
 	return SPP_OK;
 	SPP_CATCH(ctx)
 }
@@ -708,10 +734,31 @@ int spp_assemble_device(spp_ctx *ctx, const double *d_J0, const double *d_J1, co
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
 	SPP_REQUIRE(ctx->assemble, SPP_E_STATE, "spp_assemble_device: call spp_assemble_analyze first");
+	SPP_REQUIRE(assemble_n_groups(ctx) == 1, SPP_E_STATE, "spp_assemble_device: the plan has several edge groups (spp_assemble_groups_device)");
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	phases_reset(ctx);
 	phase_begin(ctx, SPP_PHASE_ASSEMBLE);
 	assemble_run(ctx, d_J0, d_J1, d_Omega, d_r, damping, d_vals_out, d_eta_out);
+	phase_end(ctx, SPP_PHASE_ASSEMBLE);
+	phases_collect(ctx);
+	return SPP_OK;
+	SPP_CATCH(ctx)
+}
+
+int spp_assemble_groups_device(spp_ctx *ctx, const double *const *d_J0, const double *const *d_J1,
+	const double *const *d_Omega, const double *const *d_r, double damping, double *d_vals_out, double *d_eta_out)
+{
+	if(!ctx || !d_J0 || !d_J1 || !d_Omega || !d_r || !d_vals_out || !d_eta_out)
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	SPP_REQUIRE(ctx->assemble, SPP_E_STATE, "spp_assemble_groups_device: call spp_assemble_analyze_groups first");
+	for(int g = 0; g < assemble_n_groups(ctx); ++ g) // (a group without edges needs no arrays)
+		SPP_REQUIRE(!assemble_group_edges(ctx, g) || (d_J0[g] && d_J1[g] && d_Omega[g] && d_r[g]), SPP_E_BADARG,
+			"spp_assemble_groups_device: null array of an edge group");
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	phases_reset(ctx);
+	phase_begin(ctx, SPP_PHASE_ASSEMBLE);
+	assemble_groups_run(ctx, d_J0, d_J1, d_Omega, d_r, damping, d_vals_out, d_eta_out);
 	phase_end(ctx, SPP_PHASE_ASSEMBLE);
 	phases_collect(ctx);
 	return SPP_OK;
@@ -724,7 +771,19 @@ int spp_assemble_set_edge_weights(spp_ctx *ctx, const double *d_w)
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
 	SPP_REQUIRE(ctx->assemble, SPP_E_STATE, "spp_assemble_set_edge_weights: call spp_assemble_analyze first");
-	assemble_set_edge_weights(ctx, d_w);
+	assemble_set_edge_weights(ctx, 0, d_w);
+	return SPP_OK;
+	SPP_CATCH(ctx)
+}
+
+int spp_assemble_set_group_edge_weights(spp_ctx *ctx, int group, const double *d_w)
+{
+	if(!ctx)
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	SPP_REQUIRE(ctx->assemble, SPP_E_STATE, "spp_assemble_set_group_edge_weights: call spp_assemble_analyze_groups first");
+	SPP_REQUIRE(group >= 0 && group < assemble_n_groups(ctx), SPP_E_BADARG, "spp_assemble_set_group_edge_weights: no such edge group");
+	assemble_set_edge_weights(ctx, group, d_w);
 	return SPP_OK;
 	SPP_CATCH(ctx)
 }
@@ -749,6 +808,44 @@ int spp_se2_update_device(spp_ctx *ctx, int64_t n_vertices, double *d_poses, con
 	SPP_TRY(ctx)
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	const double n2 = se2_update(ctx, n_vertices, d_poses, d_dx, apply != 0);
+	if(h_dx_norm2)
+		*h_dx_norm2 = n2;
+	return SPP_OK;
+	SPP_CATCH(ctx)
+}
+
+int spp_se2_linearize_at_device(spp_ctx *ctx, int64_t n_edges, const int64_t *d_off0, const int64_t *d_off1,
+	const double *d_state, const double *d_measurements, double *d_J0, double *d_J1, double *d_r)
+{
+	if(!ctx || n_edges < 0 || !d_off0 || !d_off1 || !d_state || !d_measurements || !d_J0 || !d_J1 || !d_r)
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	se2_linearize_at(ctx, n_edges, d_off0, d_off1, d_state, d_measurements, d_J0, d_J1, d_r);
+	return SPP_OK;
+	SPP_CATCH(ctx)
+}
+
+int spp_se2_rb_linearize_device(spp_ctx *ctx, int64_t n_edges, const int64_t *d_pose_off, const int64_t *d_lm_off,
+	const double *d_state, const double *d_measurements, double *d_J0, double *d_J1, double *d_r)
+{
+	if(!ctx || n_edges < 0 || !d_pose_off || !d_lm_off || !d_state || !d_measurements || !d_J0 || !d_J1 || !d_r)
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	se2_rb_linearize(ctx, n_edges, d_pose_off, d_lm_off, d_state, d_measurements, d_J0, d_J1, d_r);
+	return SPP_OK;
+	SPP_CATCH(ctx)
+}
+
+int spp_slam2d_update_device(spp_ctx *ctx, int64_t n, double *d_state, const double *d_dx, int64_t n_pose_angles,
+	const int64_t *d_angle_off, int apply, double *h_dx_norm2)
+{
+	if(!ctx || n < 0 || n_pose_angles < 0 || !d_state || !d_dx || (n_pose_angles && !d_angle_off))
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	const double n2 = slam2d_update(ctx, n, d_state, d_dx, n_pose_angles, d_angle_off, apply != 0);
 	if(h_dx_norm2)
 		*h_dx_norm2 = n2;
 	return SPP_OK;

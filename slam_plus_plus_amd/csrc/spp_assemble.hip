@@ -24,15 +24,25 @@
 
 #include "spp_internal.h"
 #include <algorithm>
+#include <cstdint>
 
 namespace spp {
 
+// One plan type for one edge group and for several: edges are numbered through the concatenation of the groups
+// (group g holds the indices gstart[g] .. gstart[g + 1)), every list below holds such indices in ascending GLOBAL position
+// (h_seq of spp_assemble_analyze_groups; the concatenation itself without it). With one group and no h_seq that is the
+// edge index itself: the lists are then those the one-group kernels have always read.
+static const int MAX_WIDTH_CLASSES = 3; // distinct vertex widths of the instantiated shapes: 6, 3, 2
+
 struct AssemblePlan {
-	int d0 = 0, d1 = 0, rd = 0;
+	int n_groups = 1;
+	int d0[SPP_MAX_EDGE_GROUPS] = {0}, d1[SPP_MAX_EDGE_GROUPS] = {0}, rd[SPP_MAX_EDGE_GROUPS] = {0};
+	int64_t gstart[SPP_MAX_EDGE_GROUPS + 1] = {0};
+	int n_cls = 0, cls_dim[MAX_WIDTH_CLASSES] = {0}; // vertex width classes, in order of first appearance (d0, d1 of group 0, ...)
+	int n_shapes = 0, shape_group[SPP_MAX_EDGE_GROUPS] = {0}; // distinct (d0, d1, rd): the first group of each
 	int64_t nv = 0, ne = 0, unary_vertex = -1;
 	Structure st;
 	int64_t n_ob = 0;
-	std::vector<int64_t> h_vlist_seq[2], h_vlist_wave[2]; // per vertex-dimension class (d0 / d1)
 	DevBuf<unsigned char> index_store; // the one allocation behind the index arrays below (UploadArena)
 	DevBuf<int32_t> ob_ptr;     // [n_ob+1]
 	DevBuf<int32_t> ob_edge;    // edge | reversed << 31
@@ -41,9 +51,12 @@ struct AssemblePlan {
 	DevBuf<int32_t> vl_entry;   // edge << 1 | side
 	DevBuf<int64_t> v_doff;     // [nv] offset of the diagonal block
 	DevBuf<int64_t> v_base;     // [nv] scalar offset in eta
-	DevBuf<int32_t> vlist_seq[2], vlist_wave[2];
-	int64_t n_seq[2] = {0, 0}, n_wave[2] = {0, 0};
-	const double *edge_weights = nullptr; // device, one robust weight per edge, or null (assemble_set_edge_weights; not owned)
+	DevBuf<int32_t> vlist_seq[MAX_WIDTH_CLASSES], vlist_wave[MAX_WIDTH_CLASSES];
+	int64_t n_seq[MAX_WIDTH_CLASSES] = {0}, n_wave[MAX_WIDTH_CLASSES] = {0};
+	DevBuf<int32_t> oblist[SPP_MAX_EDGE_GROUPS]; // off-diagonal blocks of each shape (more than one shape only; else all of them)
+	int64_t n_oblist[SPP_MAX_EDGE_GROUPS] = {0};
+	// device, one robust weight per edge of the group, or null (assemble_set_edge_weights; not owned)
+	const double *edge_weights[SPP_MAX_EDGE_GROUPS] = {nullptr};
 };
 
 void assemble_release(spp_ctx *ctx)
@@ -60,34 +73,97 @@ void assemble_get_structure(const spp_ctx *ctx, int64_t *col_ptr, int64_t *row_i
 	std::copy(st.blk_off.begin(), st.blk_off.end(), blk_off);
 }
 
-void assemble_set_edge_weights(spp_ctx *ctx, const double *d_w)
+void assemble_set_edge_weights(spp_ctx *ctx, int group, const double *d_w)
 {
-	ctx->assemble->edge_weights = d_w;
+	ctx->assemble->edge_weights[group] = d_w;
+}
+
+int assemble_n_groups(const spp_ctx *ctx)
+{
+	return ctx->assemble->n_groups;
+}
+
+int64_t assemble_group_edges(const spp_ctx *ctx, int group)
+{
+	return ctx->assemble->gstart[group + 1] - ctx->assemble->gstart[group];
 }
 
 static const int SEQ_MAX_DEGREE = 24;
 
-void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int64_t ne, const int64_t *v0,
-	const int64_t *v1, int d0, int d1, int rd, int64_t unary_vertex)
+static bool shape_instantiated(int d0, int d1, int rd)
 {
-	SPP_REQUIRE((d0 == 6 && d1 == 3 && rd == 2) || (d0 == 3 && d1 == 3 && rd == 3) ||
-		(d0 == 6 && d1 == 6 && rd == 6) || (d0 == 3 && d1 == 2 && rd == 2), SPP_E_UNSUPPORTED,
-		"edge group (d0, d1, rd) not instantiated: (6,3,2) (3,3,3) (6,6,6) (3,2,2)");
-	SPP_REQUIRE(ne < (int64_t(1) << 30), SPP_E_UNSUPPORTED, "too many edges for 31-bit edge indices");
+	return (d0 == 6 && d1 == 3 && rd == 2) || (d0 == 3 && d1 == 3 && rd == 3) || (d0 == 6 && d1 == 6 && rd == 6) ||
+		(d0 == 3 && d1 == 2 && rd == 2);
+}
+
+void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int n_groups, const int64_t *g_ne,
+	const int64_t *const *g_v0, const int64_t *const *g_v1, const int64_t *const *g_seq, const int *g_d0, const int *g_d1,
+	const int *g_rd, int64_t unary_vertex)
+{
 	assemble_release(ctx); // after a rejected call the ctx has NO assembly plan (spp_assemble_device then fails its state check)
+	SPP_REQUIRE(n_groups >= 1 && n_groups <= SPP_MAX_EDGE_GROUPS, SPP_E_UNSUPPORTED, "more than SPP_MAX_EDGE_GROUPS edge groups");
+	int64_t ne = 0;
+	for(int g = 0; g < n_groups; ++ g) {
+		SPP_REQUIRE(shape_instantiated(g_d0[g], g_d1[g], g_rd[g]), SPP_E_UNSUPPORTED,
+			"edge group (d0, d1, rd) not instantiated: (6,3,2) (3,3,3) (6,6,6) (3,2,2)");
+		ne += g_ne[g];
+	}
+	SPP_REQUIRE(ne < (int64_t(1) << 30), SPP_E_UNSUPPORTED, "too many edges for 31-bit edge indices");
 	VClock clk("assemble_analyze");
 	const int nt = plan_threads(ne);
-	run_threads(nt, [&](int t) {
-		for(int64_t e = ne * t / nt, e1 = ne * (t + 1) / nt; e < e1; ++ e) {
-			SPP_REQUIRE(v0[e] >= 0 && v0[e] < nv && v1[e] >= 0 && v1[e] < nv && v0[e] != v1[e], SPP_E_BADARG, "bad edge");
-			SPP_REQUIRE(dim[v0[e]] == d0 && dim[v1[e]] == d1, SPP_E_BADARG, "vertex width does not match the edge group");
-		}
-	});
+	for(int g = 0; g < n_groups; ++ g) {
+		const int64_t *v0 = g_v0[g], *v1 = g_v1[g], gne = g_ne[g];
+		const int d0 = g_d0[g], d1 = g_d1[g];
+		run_threads(nt, [&](int t) {
+			for(int64_t e = gne * t / nt, e1 = gne * (t + 1) / nt; e < e1; ++ e) {
+				SPP_REQUIRE(v0[e] >= 0 && v0[e] < nv && v1[e] >= 0 && v1[e] < nv && v0[e] != v1[e], SPP_E_BADARG, "bad edge");
+				SPP_REQUIRE(dim[v0[e]] == d0 && dim[v1[e]] == d1, SPP_E_BADARG, "vertex width does not match the edge group");
+			}
+		});
+	}
 	SPP_REQUIRE(unary_vertex < nv, SPP_E_BADARG, "unary_vertex out of range");
 	// built in a local object, installed in the ctx only when complete
 	struct PlanGuard { AssemblePlan *p; ~PlanGuard() { delete p; } } guard = {new AssemblePlan};
 	AssemblePlan *ap = guard.p;
-	ap->d0 = d0; ap->d1 = d1; ap->rd = rd; ap->nv = nv; ap->ne = ne; ap->unary_vertex = unary_vertex;
+	ap->n_groups = n_groups; ap->nv = nv; ap->ne = ne; ap->unary_vertex = unary_vertex;
+	for(int g = 0; g < n_groups; ++ g) {
+		ap->d0[g] = g_d0[g]; ap->d1[g] = g_d1[g]; ap->rd[g] = g_rd[g];
+		ap->gstart[g + 1] = ap->gstart[g] + g_ne[g];
+		for(int w : {g_d0[g], g_d1[g]}) {
+			if(std::find(ap->cls_dim, ap->cls_dim + ap->n_cls, w) == ap->cls_dim + ap->n_cls)
+				ap->cls_dim[ap->n_cls ++] = w;
+		}
+		int s = 0; // (the four shapes differ in (d0, d1) already)
+		while(s < ap->n_shapes && (ap->d0[ap->shape_group[s]] != g_d0[g] || ap->d1[ap->shape_group[s]] != g_d1[g]))
+			++ s;
+		if(s == ap->n_shapes)
+			ap->shape_group[ap->n_shapes ++] = g;
+	}
+	// ---- the edges in the order of their global positions: everything below walks positions, v0[q] / v1[q] are the vertices
+	// of the edge at position q and edge_at(q) its index in the concatenation of the groups. One group without h_seq: the
+	// caller's arrays as they stand
+	const int64_t *v0 = g_v0[0], *v1 = g_v1[0];
+	HVec<int64_t> pv0, pv1;
+	HVec<int32_t> pedge;
+	const bool identity = n_groups == 1 && !(g_seq && g_seq[0]);
+	if(!identity) {
+		pv0.resize(ne);
+		pv1.resize(ne);
+		pedge.assign(ne, -1);
+		for(int g = 0; g < n_groups; ++ g) {
+			const int64_t *seq = g_seq ? g_seq[g] : nullptr;
+			for(int64_t e = 0; e < g_ne[g]; ++ e) {
+				const int64_t q = seq ? seq[e] : ap->gstart[g] + e;
+				SPP_REQUIRE(q >= 0 && q < ne && pedge[q] < 0, SPP_E_BADARG, "h_seq is not a permutation of the edge positions");
+				pedge[q] = (int32_t)(ap->gstart[g] + e);
+				pv0[q] = g_v0[g][e];
+				pv1[q] = g_v1[g][e];
+			}
+		}
+		v0 = pv0.data();
+		v1 = pv1.data();
+	}
+	auto edge_at = [&](int64_t q) { return identity ? (int32_t)q : pedge[q]; };
 	// ---- Lambda structure: diagonal of every vertex + upper block of every edge
 	// (_Lambda_Base.h:1863-1881 builds all block rows/cols first, then :1897 allocates edge blocks)
 	HVec<std::pair<int64_t, int64_t> > key(ne); // (col, row)
@@ -198,8 +274,8 @@ void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int64_t ne, 
 				ob_off[k] = off;
 				off += (int64_t)dim[r] * dim[c];
 				for(; q < qe && key[eorder[q]].second == r; ++ q) {
-					const int64_t e = eorder[q]; // stable sort: edges of one block stay in edge order
-					ob_edge[q] = (int32_t)e | (v0[e] > v1[e] ? (int32_t)0x80000000 : 0);
+					const int64_t e = eorder[q]; // stable sort: edges of one block stay in the order of their positions
+					ob_edge[q] = edge_at(e) | (v0[e] > v1[e] ? (int32_t)0x80000000 : 0);
 				}
 				ob_ptr[++ k] = (int32_t)q;
 			}
@@ -223,22 +299,32 @@ void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int64_t ne, 
 	{
 		HVec<int32_t> fill(vl_ptr.begin(), vl_ptr.end() - 1);
 		for(int64_t e = 0; e < ne; ++ e) { // within an edge vertex 0 registers before vertex 1
-			vl_entry[fill[v0[e]] ++] = (int32_t)(e << 1);
-			vl_entry[fill[v1[e]] ++] = (int32_t)(e << 1) | 1;
+			vl_entry[fill[v0[e]] ++] = edge_at(e) << 1;
+			vl_entry[fill[v1[e]] ++] = (edge_at(e) << 1) | 1;
 		}
 	}
-	for(int cls = 0; cls < 2; ++ cls) {
-		ap->h_vlist_seq[cls].clear();
-		ap->h_vlist_wave[cls].clear();
-	}
-	std::vector<int32_t> lseq[2], lwave[2];
+	std::vector<int32_t> lseq[MAX_WIDTH_CLASSES], lwave[MAX_WIDTH_CLASSES];
 	for(int64_t v = 0; v < nv; ++ v) {
-		const int cls = (dim[v] == d0) ? 0 : 1;
-		SPP_REQUIRE(dim[v] == d0 || dim[v] == d1, SPP_E_BADARG, "vertex width outside of the edge group");
+		const int cls = (int)(std::find(ap->cls_dim, ap->cls_dim + ap->n_cls, dim[v]) - ap->cls_dim);
+		SPP_REQUIRE(cls < ap->n_cls, SPP_E_BADARG, "vertex width outside of the edge group");
 		if(vl_ptr[v + 1] - vl_ptr[v] <= SEQ_MAX_DEGREE)
 			lseq[cls].push_back((int32_t)v);
 		else
 			lwave[cls].push_back((int32_t)v);
+	}
+	// several shapes: the off-diagonal blocks of each (a block's edges share its two widths, hence its shape); one launch each
+	std::vector<int32_t> loblist[SPP_MAX_EDGE_GROUPS];
+	if(ap->n_shapes > 1) {
+		for(int64_t b = 0; b < n_ob; ++ b) {
+			const int32_t e = ob_edge[ob_ptr[b]] & 0x7fffffff;
+			int g = 0;
+			while(e >= ap->gstart[g + 1])
+				++ g;
+			int sh = 0;
+			while(ap->d0[ap->shape_group[sh]] != ap->d0[g] || ap->d1[ap->shape_group[sh]] != ap->d1[g])
+				++ sh;
+			loblist[sh].push_back((int32_t)b);
+		}
 	}
 	clk.lap("vertex lists");
 	hipStream_t s = ctx->stream;
@@ -253,7 +339,11 @@ void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int64_t ne, 
 		std::vector<int64_t> vb(st.base.begin(), st.base.end() - 1);
 		arena.add(ap->v_base, vb);
 	}
-	for(int cls = 0; cls < 2; ++ cls) {
+	for(int sh = 0; sh < ap->n_shapes && ap->n_shapes > 1; ++ sh) {
+		ap->n_oblist[sh] = (int64_t)loblist[sh].size();
+		arena.add(ap->oblist[sh], loblist[sh]);
+	}
+	for(int cls = 0; cls < ap->n_cls; ++ cls) {
 		ap->n_seq[cls] = (int64_t)lseq[cls].size();
 		ap->n_wave[cls] = (int64_t)lwave[cls].size();
 		arena.add(ap->vlist_seq[cls], lseq[cls]);
@@ -535,6 +625,279 @@ void vertex_wave_kernel(int64_t nlist, const int32_t *__restrict__ vlist, const 
 		store_vertex<D>(H, g, v == unary_vertex, damping, vals + v_doff[v], eta + v_base[v]);
 }
 
+// --------------------------------------------------------------------------------------------------
+// several edge groups (spp_assemble_groups_device): the same three kernels, with the pointer set of every group passed by
+// value. A list entry is an index into the concatenation of the groups; comparing it with the (at most four) group starts
+// gives the group, the group gives the pointers and the shape, and the shape selects the body instantiated for it. Every
+// body is the one the one-group kernels run (jt_omega / vertex_contrib / load_contrib above), applied in the order of the
+// lists: plain edges give the one-group kernels' bits (one shape split into two groups is bit-identical to the one group).
+// With robust weights the compiler contracts w * s + sum into an FMA in some of the kernels and not in others, so weighted
+// sums may differ from the one-group kernels' in the last bit; a plan of ONE group therefore runs the one-group kernels
+// (assemble_groups_run), and the two entry points agree bit for bit on it whatever the weights. Traffic is unchanged: each edge's J / Omega / r is read by
+// the three destinations it feeds; what the groups share is the launches.
+// --------------------------------------------------------------------------------------------------
+enum { SHAPE_632 = 0, SHAPE_333 = 1, SHAPE_666 = 2, SHAPE_322 = 3 };
+
+struct GroupPtrs {
+	const double *J0, *J1, *Om, *r, *w;
+	int32_t start; // first index of the group in the concatenation; INT32_MAX past the last group
+	int32_t shape;
+};
+
+struct GroupArgs { // (four members, not an array: every access is then a kernel argument in scalar registers, never scratch)
+	GroupPtrs g0, g1, g2, g3;
+};
+
+// the operands of one edge: its group's arrays and its index inside them
+struct EdgeRef {
+	const double *J0, *J1, *Om, *r, *w;
+	int32_t e, shape;
+};
+
+// (by value: `g == 0 ? ga.g0.m : ...` on the members themselves is a choice between ADDRESSES, which sends the argument
+// struct to scratch)
+template <class T>
+__device__ __forceinline__ T pick4(int g, T a, T b, T c, T d)
+{
+	return g == 0 ? a : g == 1 ? b : g == 2 ? c : d;
+}
+
+__device__ __forceinline__ EdgeRef edge_ref(const GroupArgs &ga, int32_t ce)
+{
+	static_assert(SPP_MAX_EDGE_GROUPS == 4, "GroupArgs holds four groups");
+	const int g = (ce >= ga.g1.start) + (ce >= ga.g2.start) + (ce >= ga.g3.start);
+#define SPP_PICK(m) pick4(g, ga.g0.m, ga.g1.m, ga.g2.m, ga.g3.m)
+	EdgeRef x;
+	x.J0 = SPP_PICK(J0); x.J1 = SPP_PICK(J1); x.Om = SPP_PICK(Om); x.r = SPP_PICK(r); x.w = SPP_PICK(w);
+	x.e = ce - SPP_PICK(start);
+	x.shape = SPP_PICK(shape);
+#undef SPP_PICK
+	return x;
+}
+
+// the blocks oblist[0 .. n) (all blocks 0 .. n when null) have the shape (D0, D1, RD); their edges may come from any group of it
+template <int D0, int D1, int RD>
+__global__ __launch_bounds__(256)
+void offdiag_groups_kernel(int64_t n, const int32_t *__restrict__ oblist, const int32_t *__restrict__ ob_ptr,
+	const int32_t *__restrict__ ob_edge, const int64_t *__restrict__ ob_off, const GroupArgs ga, double *__restrict__ vals)
+{
+	const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if(t >= n)
+		return;
+	const int64_t b = oblist ? oblist[t] : t;
+	double acc[D0 * D1];
+	bool first = true;
+	for(int32_t q = ob_ptr[b]; q < ob_ptr[b + 1]; ++ q) {
+		const int32_t ee = ob_edge[q];
+		const EdgeRef x = edge_ref(ga, ee & 0x7fffffff);
+		const int64_t e = x.e;
+		const bool rev = ee < 0;
+		double j0[RD * D0], j1[RD * D1], om[RD * RD], T[D0 * RD];
+#pragma unroll
+		for(int i = 0; i < RD * D0; ++ i) j0[i] = x.J0[e * RD * D0 + i];
+#pragma unroll
+		for(int i = 0; i < RD * D1; ++ i) j1[i] = x.J1[e * RD * D1 + i];
+#pragma unroll
+		for(int i = 0; i < RD * RD; ++ i) om[i] = x.Om[e * RD * RD + i];
+		jt_omega<D0, RD>(j0, om, T);
+		if(x.w) { // robust edge, as in offdiag_kernel
+			const double wgt = x.w[e];
+#pragma unroll
+			for(int i = 0; i < D0 * RD; ++ i)
+				T[i] *= wgt;
+		}
+#pragma unroll
+		for(int c = 0; c < D1; ++ c)
+#pragma unroll
+			for(int i = 0; i < D0; ++ i) {
+				double s = 0;
+#pragma unroll
+				for(int l = 0; l < RD; ++ l)
+					s += T[i + l * D0] * j1[l + c * RD];
+				const int idx = rev ? (c + i * D1) : (i + c * D0);
+				acc[idx] = first ? s : acc[idx] + s;
+			}
+		first = false;
+	}
+	double *o = vals + ob_off[b];
+#pragma unroll
+	for(int i = 0; i < D0 * D1; ++ i)
+		o[i] = acc[i];
+}
+
+// contribution of one list entry to a vertex of width D: the body of the entry's shape (a shape without a D-wide side
+// cannot occur in the list of such a vertex)
+template <int D>
+__device__ __forceinline__ void load_contrib_groups(int32_t entry, const GroupArgs &ga, double *H, double *g)
+{
+	const EdgeRef x = edge_ref(ga, entry >> 1);
+	const int32_t le = (x.e << 1) | (entry & 1);
+	switch(x.shape) {
+	case SHAPE_632:
+		if(D == 6 || D == 3)
+			load_contrib<D, 6, 3, 2>(le, x.J0, x.J1, x.Om, x.r, x.w, H, g);
+		break;
+	case SHAPE_333:
+		if(D == 3)
+			load_contrib<D, 3, 3, 3>(le, x.J0, x.J1, x.Om, x.r, x.w, H, g);
+		break;
+	case SHAPE_666:
+		if(D == 6)
+			load_contrib<D, 6, 6, 6>(le, x.J0, x.J1, x.Om, x.r, x.w, H, g);
+		break;
+	default:
+		if(D == 3 || D == 2)
+			load_contrib<D, 3, 2, 2>(le, x.J0, x.J1, x.Om, x.r, x.w, H, g);
+		break;
+	}
+}
+
+template <int D>
+__global__ __launch_bounds__(256)
+void vertex_seq_groups_kernel(int64_t nlist, const int32_t *__restrict__ vlist, const int32_t *__restrict__ vl_ptr,
+	const int32_t *__restrict__ vl_entry, const int64_t *__restrict__ v_doff, const int64_t *__restrict__ v_base,
+	const GroupArgs ga, int64_t unary_vertex, double damping, double *__restrict__ vals, double *__restrict__ eta)
+{
+	const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if(t >= nlist)
+		return;
+	const int32_t v = vlist[t];
+	double H[D * D], g[D];
+#pragma unroll
+	for(int i = 0; i < D * D; ++ i) H[i] = 0;
+#pragma unroll
+	for(int i = 0; i < D; ++ i) g[i] = 0;
+	bool first = true;
+	for(int32_t q = vl_ptr[v]; q < vl_ptr[v + 1]; ++ q) {
+		double Hc[D * D], gc[D];
+		load_contrib_groups<D>(vl_entry[q], ga, Hc, gc);
+		if(first) { // the first source is assigned, the others are added (_Lambda_Base.h:598-604)
+#pragma unroll
+			for(int c = 0; c < D; ++ c)
+#pragma unroll
+				for(int i = 0; i <= c; ++ i) H[i + c * D] = Hc[i + c * D];
+#pragma unroll
+			for(int i = 0; i < D; ++ i) g[i] = gc[i];
+			first = false;
+		} else {
+#pragma unroll
+			for(int c = 0; c < D; ++ c)
+#pragma unroll
+				for(int i = 0; i <= c; ++ i) H[i + c * D] += Hc[i + c * D];
+#pragma unroll
+			for(int i = 0; i < D; ++ i) g[i] += gc[i];
+		}
+	}
+	store_vertex<D>(H, g, v == unary_vertex, damping, vals + v_doff[v], eta + v_base[v]);
+}
+
+template <int D>
+__global__ __launch_bounds__(256)
+void vertex_wave_groups_kernel(int64_t nlist, const int32_t *__restrict__ vlist, const int32_t *__restrict__ vl_ptr,
+	const int32_t *__restrict__ vl_entry, const int64_t *__restrict__ v_doff, const int64_t *__restrict__ v_base,
+	const GroupArgs ga, int64_t unary_vertex, double damping, double *__restrict__ vals, double *__restrict__ eta)
+{
+	const int64_t t = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+	const int lane = threadIdx.x & 63;
+	if(t >= nlist)
+		return;
+	const int32_t v = vlist[t];
+	double H[D * D], g[D];
+#pragma unroll
+	for(int i = 0; i < D * D; ++ i) H[i] = 0;
+#pragma unroll
+	for(int i = 0; i < D; ++ i) g[i] = 0;
+	for(int32_t q = vl_ptr[v] + lane; q < vl_ptr[v + 1]; q += 64) {
+		double Hc[D * D], gc[D];
+		load_contrib_groups<D>(vl_entry[q], ga, Hc, gc);
+#pragma unroll
+		for(int c = 0; c < D; ++ c)
+#pragma unroll
+			for(int i = 0; i <= c; ++ i) H[i + c * D] += Hc[i + c * D];
+#pragma unroll
+		for(int i = 0; i < D; ++ i) g[i] += gc[i];
+	}
+#pragma unroll
+	for(int c = 0; c < D; ++ c)
+#pragma unroll
+		for(int i = 0; i <= c; ++ i) {
+			double x = H[i + c * D];
+#pragma unroll
+			for(int off = 32; off > 0; off >>= 1)
+				x += __shfl_xor(x, off);
+			H[i + c * D] = x;
+		}
+#pragma unroll
+	for(int i = 0; i < D; ++ i) {
+		double x = g[i];
+#pragma unroll
+		for(int off = 32; off > 0; off >>= 1)
+			x += __shfl_xor(x, off);
+		g[i] = x;
+	}
+	if(lane == 0)
+		store_vertex<D>(H, g, v == unary_vertex, damping, vals + v_doff[v], eta + v_base[v]);
+}
+
+static int shape_id(int d0, int d1)
+{
+	return d0 == 6 ? (d1 == 3 ? SHAPE_632 : SHAPE_666) : (d1 == 3 ? SHAPE_333 : SHAPE_322);
+}
+
+// launches: one per distinct shape (off-diagonal blocks) + at most two per vertex width class -- whatever the graph's size
+void assemble_groups_run(spp_ctx *ctx, const double *const *J0, const double *const *J1, const double *const *Om,
+	const double *const *r, double damping, double *vals, double *eta)
+{
+	AssemblePlan *ap = ctx->assemble;
+	if(ap->n_groups == 1) { // the one-group case IS spp_assemble_device: same kernels, same bits
+		assemble_run(ctx, J0[0], J1[0], Om[0], r[0], damping, vals, eta);
+		return;
+	}
+	hipStream_t s = ctx->stream;
+	GroupArgs ga;
+	GroupPtrs *gp[SPP_MAX_EDGE_GROUPS] = {&ga.g0, &ga.g1, &ga.g2, &ga.g3};
+	for(int g = 0; g < SPP_MAX_EDGE_GROUPS; ++ g) {
+		if(g < ap->n_groups)
+			*gp[g] = GroupPtrs{J0[g], J1[g], Om[g], r[g], ap->edge_weights[g], (int32_t)ap->gstart[g], shape_id(ap->d0[g], ap->d1[g])};
+		else
+			*gp[g] = GroupPtrs{nullptr, nullptr, nullptr, nullptr, nullptr, INT32_MAX, 0};
+	}
+	for(int sh = 0; sh < ap->n_shapes; ++ sh) {
+		const int64_t n = ap->n_shapes > 1 ? ap->n_oblist[sh] : ap->n_ob;
+		const int32_t *list = ap->n_shapes > 1 ? ap->oblist[sh].p : nullptr;
+		if(!n)
+			continue;
+#define SPP_OFFDIAG_LAUNCH(D0, D1, RD) \
+		hipLaunchKernelGGL((offdiag_groups_kernel<D0, D1, RD>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, \
+			n, list, ap->ob_ptr.p, ap->ob_edge.p, ap->ob_off.p, ga, vals)
+		switch(gp[ap->shape_group[sh]]->shape) {
+		case SHAPE_632: SPP_OFFDIAG_LAUNCH(6, 3, 2); break;
+		case SHAPE_333: SPP_OFFDIAG_LAUNCH(3, 3, 3); break;
+		case SHAPE_666: SPP_OFFDIAG_LAUNCH(6, 6, 6); break;
+		default: SPP_OFFDIAG_LAUNCH(3, 2, 2); break;
+		}
+#undef SPP_OFFDIAG_LAUNCH
+	}
+	for(int cls = 0; cls < ap->n_cls; ++ cls) {
+#define SPP_VERTEX_LAUNCH(D) \
+		if(ap->n_seq[cls]) \
+			hipLaunchKernelGGL((vertex_seq_groups_kernel<D>), dim3((unsigned)((ap->n_seq[cls] + 255) / 256)), dim3(256), 0, s, \
+				ap->n_seq[cls], ap->vlist_seq[cls].p, ap->vl_ptr.p, ap->vl_entry.p, ap->v_doff.p, ap->v_base.p, ga, \
+				ap->unary_vertex, damping, vals, eta); \
+		if(ap->n_wave[cls]) \
+			hipLaunchKernelGGL((vertex_wave_groups_kernel<D>), dim3((unsigned)((ap->n_wave[cls] + 3) / 4)), dim3(256), 0, s, \
+				ap->n_wave[cls], ap->vlist_wave[cls].p, ap->vl_ptr.p, ap->vl_entry.p, ap->v_doff.p, ap->v_base.p, ga, \
+				ap->unary_vertex, damping, vals, eta);
+		switch(ap->cls_dim[cls]) {
+		case 6: SPP_VERTEX_LAUNCH(6) break;
+		case 3: SPP_VERTEX_LAUNCH(3) break;
+		default: SPP_VERTEX_LAUNCH(2) break;
+		}
+#undef SPP_VERTEX_LAUNCH
+	}
+	SPP_HIP_CHECK(hipGetLastError());
+}
+
 template <int D0, int D1, int RD>
 static void assemble_t(spp_ctx *ctx, const double *J0, const double *J1, const double *Om, const double *r,
 	double damping, double *vals, double *eta)
@@ -543,16 +906,16 @@ static void assemble_t(spp_ctx *ctx, const double *J0, const double *J1, const d
 	hipStream_t s = ctx->stream;
 	if(ap->n_ob)
 		hipLaunchKernelGGL((offdiag_kernel<D0, D1, RD>), dim3((unsigned)((ap->n_ob + 255) / 256)), dim3(256), 0, s,
-			ap->n_ob, ap->ob_ptr.p, ap->ob_edge.p, ap->ob_off.p, J0, J1, Om, ap->edge_weights, vals);
+			ap->n_ob, ap->ob_ptr.p, ap->ob_edge.p, ap->ob_off.p, J0, J1, Om, ap->edge_weights[0], vals);
 #define SPP_VERTEX_LAUNCH(D, cls) \
 	if(ap->n_seq[cls]) \
 		hipLaunchKernelGGL((vertex_seq_kernel<D, D0, D1, RD>), dim3((unsigned)((ap->n_seq[cls] + 255) / 256)), dim3(256), 0, s, \
 			ap->n_seq[cls], ap->vlist_seq[cls].p, ap->vl_ptr.p, ap->vl_entry.p, ap->v_doff.p, ap->v_base.p, \
-			J0, J1, Om, r, ap->edge_weights, ap->unary_vertex, damping, vals, eta); \
+			J0, J1, Om, r, ap->edge_weights[0], ap->unary_vertex, damping, vals, eta); \
 	if(ap->n_wave[cls]) \
 		hipLaunchKernelGGL((vertex_wave_kernel<D, D0, D1, RD>), dim3((unsigned)((ap->n_wave[cls] + 3) / 4)), dim3(256), 0, s, \
 			ap->n_wave[cls], ap->vlist_wave[cls].p, ap->vl_ptr.p, ap->vl_entry.p, ap->v_doff.p, ap->v_base.p, \
-			J0, J1, Om, r, ap->edge_weights, ap->unary_vertex, damping, vals, eta);
+			J0, J1, Om, r, ap->edge_weights[0], ap->unary_vertex, damping, vals, eta);
 	SPP_VERTEX_LAUNCH(D0, 0)
 	if(D0 != D1) {
 		SPP_VERTEX_LAUNCH(D1, 1)
@@ -565,9 +928,9 @@ void assemble_run(spp_ctx *ctx, const double *J0, const double *J1, const double
 	double damping, double *vals, double *eta)
 {
 	AssemblePlan *ap = ctx->assemble;
-	if(ap->d0 == 6 && ap->d1 == 3) assemble_t<6, 3, 2>(ctx, J0, J1, Om, r, damping, vals, eta);
-	else if(ap->d0 == 3 && ap->d1 == 3) assemble_t<3, 3, 3>(ctx, J0, J1, Om, r, damping, vals, eta);
-	else if(ap->d0 == 6 && ap->d1 == 6) assemble_t<6, 6, 6>(ctx, J0, J1, Om, r, damping, vals, eta);
+	if(ap->d0[0] == 6 && ap->d1[0] == 3) assemble_t<6, 3, 2>(ctx, J0, J1, Om, r, damping, vals, eta);
+	else if(ap->d0[0] == 3 && ap->d1[0] == 3) assemble_t<3, 3, 3>(ctx, J0, J1, Om, r, damping, vals, eta);
+	else if(ap->d0[0] == 6 && ap->d1[0] == 6) assemble_t<6, 6, 6>(ctx, J0, J1, Om, r, damping, vals, eta);
 	else assemble_t<3, 2, 2>(ctx, J0, J1, Om, r, damping, vals, eta);
 }
 

@@ -678,4 +678,130 @@ double se2_update(spp_ctx *ctx, int64_t nv, double *d_poses, const double *d_dx,
 	return h;
 }
 
+// --------------------------------------------------------------------------------------------------
+// 2D landmark SLAM: 3-wide poses and 2-wide landmarks in ONE flat state laid out like eta (state and increment have
+// the same layout in 2D), vertices addressed by their scalar offset. Reference (functional spec):
+//   C2DJacobians::Observation2D_RangeBearing                  include/slam/2DSolverBase.h:443-496
+//   CEdgePoseLandmark2D::Calculate_Jacobians_Expectation_Error include/slam/SE2_Types.h:562-573
+//   CVertexPose2D::Operator_Plus (angle clamped) / CVertexLandmark2D::Operator_Plus (plain sum)  SE2_Types.h:70-74, :89
+// One thread per edge; the odometry edge moves what se2_linearize_kernel moves (+ 2 x 8 B of offsets instead of 2 x 4 B
+// of ids), the observation 24 + 16 B of gathered state, 16 B measurement and 16 B offsets in, 96 B out.
+// --------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256)
+void se2_linearize_at_kernel(int64_t ne, const int64_t *__restrict__ off0, const int64_t *__restrict__ off1,
+	const double *__restrict__ state, const double *__restrict__ meas, double *__restrict__ J0,
+	double *__restrict__ J1, double *__restrict__ r)
+{
+	const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if(e >= ne)
+		return;
+	// the body of se2_linearize_kernel, the two poses at their given offsets
+	const double *p1 = state + off0[e], *p2 = state + off1[e];
+	const double p1e = p1[0], p1n = p1[1], p1a = p1[2];
+	const double de = p2[0] - p1e, dn = p2[1] - p1n;
+	double s, c;
+	sincos(p1a, &s, &c);
+	const double hf = c * de + s * dn, hl = -s * de + c * dn, ha = clamp_angle_2pi(p2[2] - p1a);
+	const double *z = meas + 3 * e;
+	r[3 * e + 0] = z[0] - hf;
+	r[3 * e + 1] = z[1] - hl;
+	r[3 * e + 2] = clamp_angular_error_2pi(z[2] - ha);
+	double *a = J0 + 9 * e;
+	a[0] = -c;  a[1] = s;   a[2] = 0;
+	a[3] = -s;  a[4] = -c;  a[5] = 0;
+	a[6] = -s * de + c * dn;
+	a[7] = -c * de - s * dn;
+	a[8] = -1;
+	double *b = J1 + 9 * e;
+	b[0] = c;   b[1] = -s;  b[2] = 0;
+	b[3] = s;   b[4] = c;   b[5] = 0;
+	b[6] = 0;   b[7] = 0;   b[8] = 1;
+}
+
+__global__ __launch_bounds__(256)
+void se2_rb_linearize_kernel(int64_t ne, const int64_t *__restrict__ pose_off, const int64_t *__restrict__ lm_off,
+	const double *__restrict__ state, const double *__restrict__ meas, double *__restrict__ J0,
+	double *__restrict__ J1, double *__restrict__ r)
+{
+	const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if(e >= ne)
+		return;
+	const double *p = state + pose_off[e], *l = state + lm_off[e];
+	const double de = l[0] - p[0], dn = l[1] - p[1], pa = p[2];
+	double d = sqrt(de * de + dn * dn);
+	const double hb = clamp_angle_2pi(atan2(dn, de) - pa);
+	if(fabs(d) < 1e-5)
+		d = 1e-5; // the floor comes BEFORE the Jacobians (2DSolverBase.h:475-476)
+	const double d2 = d * d;
+	r[2 * e] = meas[2 * e] - d;
+	r[2 * e + 1] = clamp_angular_error_2pi(meas[2 * e + 1] - hb);
+	double *a = J0 + 6 * e; // 2 x 3 column-major
+	a[0] = -de / d;  a[1] = dn / d2;
+	a[2] = -dn / d;  a[3] = -de / d2;
+	a[4] = 0;        a[5] = -1;
+	double *b = J1 + 4 * e; // 2 x 2 column-major
+	b[0] = de / d;   b[1] = -dn / d2;
+	b[2] = dn / d;   b[3] = de / d2;
+}
+
+__global__ __launch_bounds__(256)
+void axpy1_kernel(int64_t n, double *__restrict__ x, const double *__restrict__ dx)
+{
+	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if(i < n)
+		x[i] += dx[i];
+}
+
+__global__ __launch_bounds__(256)
+void clamp_angles_kernel(int64_t na, const int64_t *__restrict__ off, double *__restrict__ x)
+{
+	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if(i < na)
+		x[off[i]] = clamp_angle_2pi(x[off[i]]);
+}
+
+void se2_linearize_at(spp_ctx *ctx, int64_t ne, const int64_t *d_off0, const int64_t *d_off1, const double *d_state,
+	const double *d_meas, double *d_J0, double *d_J1, double *d_r)
+{
+	if(!ne)
+		return;
+	hipLaunchKernelGGL(se2_linearize_at_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, ctx->stream,
+		ne, d_off0, d_off1, d_state, d_meas, d_J0, d_J1, d_r);
+	SPP_HIP_CHECK(hipGetLastError());
+}
+
+void se2_rb_linearize(spp_ctx *ctx, int64_t ne, const int64_t *d_pose_off, const int64_t *d_lm_off, const double *d_state,
+	const double *d_meas, double *d_J0, double *d_J1, double *d_r)
+{
+	if(!ne)
+		return;
+	hipLaunchKernelGGL(se2_rb_linearize_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, ctx->stream,
+		ne, d_pose_off, d_lm_off, d_state, d_meas, d_J0, d_J1, d_r);
+	SPP_HIP_CHECK(hipGetLastError());
+}
+
+// ||dx||^2 (two-stage sum, as se3_update) and, if apply, x += dx over the flat state, then the pose angles clamped: the sum
+// is rounded once and then reduced, which is what CVertexPose2D::Operator_Plus does; landmarks keep the plain sum
+double slam2d_update(spp_ctx *ctx, int64_t n, double *d_state, const double *d_dx, int64_t n_angles,
+	const int64_t *d_angle_off, bool apply)
+{
+	if(!n)
+		return 0;
+	const int64_t nwg = (n + 255) / 256;
+	ctx->geom_partial.reserve((size_t)nwg + 1);
+	hipLaunchKernelGGL(norm2_partial_kernel, dim3((unsigned)nwg), dim3(256), 0, ctx->stream, n, d_dx, ctx->geom_partial.p + 1);
+	hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, ctx->stream, nwg, ctx->geom_partial.p + 1, ctx->geom_partial.p);
+	if(apply) {
+		hipLaunchKernelGGL(axpy1_kernel, dim3((unsigned)nwg), dim3(256), 0, ctx->stream, n, d_state, d_dx);
+		if(n_angles)
+			hipLaunchKernelGGL(clamp_angles_kernel, dim3((unsigned)((n_angles + 255) / 256)), dim3(256), 0, ctx->stream,
+				n_angles, d_angle_off, d_state);
+	}
+	SPP_HIP_CHECK(hipGetLastError());
+	double h = 0;
+	SPP_HIP_CHECK(hipMemcpyAsync(&h, ctx->geom_partial.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	SPP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+	return h;
+}
+
 } // namespace spp

@@ -379,6 +379,12 @@ namespace spp {
 void se2_linearize(spp_ctx *ctx, int64_t ne, const int32_t *d_v0, const int32_t *d_v1, const double *d_poses,
 	const double *d_meas, double *d_J0, double *d_J1, double *d_r);
 double se2_update(spp_ctx *ctx, int64_t nv, double *d_poses, const double *d_dx, bool apply);
+void se2_linearize_at(spp_ctx *ctx, int64_t ne, const int64_t *d_off0, const int64_t *d_off1, const double *d_state,
+	const double *d_meas, double *d_J0, double *d_J1, double *d_r);
+void se2_rb_linearize(spp_ctx *ctx, int64_t ne, const int64_t *d_off0, const int64_t *d_off1, const double *d_state,
+	const double *d_meas, double *d_J0, double *d_J1, double *d_r);
+double slam2d_update(spp_ctx *ctx, int64_t n, double *d_state, const double *d_dx, int64_t n_angles,
+	const int64_t *d_angle_off, bool apply);
 double edge_chi2(spp_ctx *ctx, int64_t ne, int rd, const double *d_r, const double *d_Om);
 void edge_robust_weights(spp_ctx *ctx, int64_t ne, int rd, int kind, double scale, double param, const double *d_r, double *d_w);
 double edge_hessian_maxdiag(spp_ctx *ctx, int64_t ne, int rd, int d0, int d1, const double *d_J0, const double *d_J1,
@@ -480,11 +486,17 @@ double microbench_ctile(spp_ctx *ctx, int n, int iters);
 double microbench_update(spp_ctx *ctx, int64_t m, int iters);
 
 // ---- spp_assemble.hip ----
-void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int64_t ne, const int64_t *v0,
-	const int64_t *v1, int d0, int d1, int rd, int64_t unary_vertex);
+// one plan type: spp_assemble_analyze is the one-group case (g_seq null: the groups concatenated in group order)
+void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int n_groups, const int64_t *g_ne,
+	const int64_t *const *g_v0, const int64_t *const *g_v1, const int64_t *const *g_seq, const int *g_d0, const int *g_d1,
+	const int *g_rd, int64_t unary_vertex);
+int assemble_n_groups(const spp_ctx *ctx);
+int64_t assemble_group_edges(const spp_ctx *ctx, int group);
 void assemble_run(spp_ctx *ctx, const double *J0, const double *J1, const double *Om, const double *r,
-	double damping, double *vals, double *eta);
-void assemble_set_edge_weights(spp_ctx *ctx, const double *d_w); // null: plain edges
+	double damping, double *vals, double *eta); // plans of one group
+void assemble_groups_run(spp_ctx *ctx, const double *const *J0, const double *const *J1, const double *const *Om,
+	const double *const *r, double damping, double *vals, double *eta); // host arrays of n_groups device pointers
+void assemble_set_edge_weights(spp_ctx *ctx, int group, const double *d_w); // null: plain edges
 void assemble_release(spp_ctx *ctx);
 void assemble_get_structure(const spp_ctx *ctx, int64_t *col_ptr, int64_t *row_idx, int64_t *blk_off);
 

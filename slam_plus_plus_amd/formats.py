@@ -443,3 +443,190 @@ def problem_from_graph(path):
             raise ValueError("2D pose graph: %d poses are not reachable through forward edges" % int((~seen).sum()))
         return se2_linearize(poses, e, g["se2_info"]), "2D pose graph file (%d poses, %d edges)" % (n, e.shape[0])
     raise ValueError("no edges of a known type in %s" % path)
+
+
+# --------------------------------------------------------------------------------------------------
+# 2D landmark SLAM: poses (3) + point landmarks (2), odometry + range-bearing observations
+# --------------------------------------------------------------------------------------------------
+_LM2_XY_EDGE = {"LANDMARK2:XY", "EDGE_SE2_XY", "EDGE_BEARING_SE2_XY", "LANDMARK"}   # ParsePrimitives.h:270-273
+_LM2_RB_EDGE = {"LANDMARK2:RB", "EDGE_SE2_RB", "EDGE_BEARING_SE2_RB"}                # :363-365
+_TWO_PI = 2 * np.pi
+
+
+def _clamp_angle_2pi(a):
+    """C2DJacobians::f_ClampAngle_2Pi (2DSolverBase.h:44-67)"""
+    return np.fmod(a, _TWO_PI)
+
+
+def _clamp_angular_error_2pi(e):
+    """C2DJacobians::f_ClampAngularError_2Pi (2DSolverBase.h:79-94): the smallest in magnitude of e, e - 2 pi, e + 2 pi"""
+    e = np.fmod(e, _TWO_PI)
+    a, b = e - _TWO_PI, e + _TWO_PI
+    m = np.where(np.abs(e) < np.abs(a), e, a)
+    return np.where(np.abs(m) < np.abs(b), m, b)
+
+
+def _se2_compose(p, d):
+    """C2DJacobians::Relative_to_Absolute (2DSolverBase.h:96-130): p (+) d, angle clamped"""
+    c, s = np.cos(p[2]), np.sin(p[2])
+    return np.array([p[0] + c * d[0] - s * d[1], p[1] + s * d[0] + c * d[1], _clamp_angle_2pi(p[2] + d[2])])
+
+
+def slam2d_offsets(dim):
+    base = np.zeros(len(dim) + 1, dtype=np.int64)
+    np.cumsum(dim, out=base[1:])
+    return base
+
+
+def load_slam2d_graph(path):
+    """A 2D landmark SLAM graph as the reference's parser and edge constructors would build it, line by line. Returns
+      dim (nv,) 3 for a pose / 2 for a landmark, state (flat, laid out by dim), vertex ids 0 .. nv - 1,
+      odo (m, 5) i j dx dy dtheta + odo_info (m, 3, 3) + odo_seq (m,) position among all edges of the file,
+      obs (k, 4) pose landmark range bearing + obs_info (k, 2, 2) + obs_seq (k,).
+    Tokens: VERTEX_SE2 / VERTEX2 / VERTEX (ParsePrimitives.h:420-422; the parser has NO token for a 2D landmark vertex),
+    the odometry tokens of load_graph, the XY landmark tokens (:270-273) and the RB ones (:363-365).
+    * an XY measurement is converted to polar and its information REPLACED BY THE IDENTITY (CEdgePoseLandmark2D::v_ToPolar /
+      t_ToPolar, SE2_Types.h:602-616; the parser itself warns that chi2 is then incorrect); RB tokens keep both;
+    * an edge that names the landmark first is swapped (SE2_Types.h:437-442: a known first vertex of width 2, or a known
+      second one of width 3), so obs[:, 0] is always the pose;
+    * a vertex an edge meets first is initialised from it: a pose by composing the odometry (the null vertex for the
+      very first), a landmark by CRelative_to_Absolute_XY_Initializer (pose (+) (dx, dy), SE2_Types.h:381-409) or by
+      CRelative_to_Absolute_RangeBearing_Initializer (:347-375). The latter is mirrored as written: it composes the pose
+      with (range, 0, bearing) and stores (the NORM of the resulting position, the resulting angle) as the landmark."""
+    state, dimof = {}, {}
+    odo, odo_info, odo_seq, obs, obs_info, obs_seq = [], [], [], [], [], []
+    n_edges = 0
+
+    def known(v, d):
+        return v in state and dimof[v] == d
+
+    with open(path) as f:
+        for ln in f:
+            t = ln.split()
+            if not t or t[0].startswith("#") or t[0].startswith("%"):
+                continue
+            tok, a = t[0].upper(), t[1:]
+            if tok in _SE2_VERTEX and len(a) >= 4:
+                v = int(a[0])
+                state[v], dimof[v] = np.array([float(x) for x in a[1:4]]), 3
+            elif tok in _SE2_EDGE and len(a) >= 11:
+                i, j = int(a[0]), int(a[1])
+                z = np.array([float(x) for x in a[2:5]])
+                if i not in state:
+                    state[i], dimof[i] = np.zeros(3), 3           # CInitializeNullVertex
+                if j not in state:
+                    state[j], dimof[j] = _se2_compose(state[i], z), 3
+                odo.append([i, j, *z])
+                odo_info.append(_upper_to_full([float(x) for x in a[5:11]], 3))
+                odo_seq.append(n_edges)
+                n_edges += 1
+            elif (tok in _LM2_XY_EDGE or tok in _LM2_RB_EDGE) and len(a) >= 7:
+                i, j = int(a[0]), int(a[1])
+                z = np.array([float(a[2]), float(a[3])])
+                info = _upper_to_full([float(x) for x in a[4:7]], 2)
+                if known(i, 2) or known(j, 3):
+                    i, j = j, i
+                if i not in state:
+                    state[i], dimof[i] = np.zeros(3), 3
+                if tok in _LM2_XY_EDGE:
+                    if j not in state:
+                        state[j], dimof[j] = _se2_compose(state[i], [z[0], z[1], 0.0])[:2], 2
+                    z = np.array([np.hypot(z[0], z[1]), _clamp_angle_2pi(np.arctan2(z[1], z[0]))])
+                    info = np.eye(2)
+                elif j not in state:
+                    q = _se2_compose(state[i], [z[0], 0.0, z[1]])
+                    state[j], dimof[j] = np.array([np.hypot(q[0], q[1]), q[2]]), 2
+                obs.append([i, j, *z])
+                obs_info.append(info)
+                obs_seq.append(n_edges)
+                n_edges += 1
+    nv = max(state) + 1 if state else 0
+    if sorted(state) != list(range(nv)):
+        raise ValueError("vertex ids are not 0 .. n-1: %s" % path)
+    dim = np.array([dimof[v] for v in range(nv)], dtype=np.int32)
+    return dict(dim=dim, state=np.concatenate([state[v] for v in range(nv)]) if nv else np.zeros(0),
+                odo=np.array(odo).reshape(-1, 5), odo_info=np.array(odo_info).reshape(-1, 3, 3),
+                odo_seq=np.array(odo_seq, dtype=np.int64), obs=np.array(obs).reshape(-1, 4),
+                obs_info=np.array(obs_info).reshape(-1, 2, 2), obs_seq=np.array(obs_seq, dtype=np.int64))
+
+
+def save_slam2d_graph(path, dim, state, odo, odo_info, obs, obs_info, odo_seq=None, obs_seq=None):
+    """VERTEX_SE2 for every pose (landmarks have no vertex token: the reader initialises them from their first
+    observation), EDGE_SE2 and EDGE_SE2_RB (range bearing + the 3 upper values of the information) in the global edge
+    order, everything with %.17g."""
+    dim = np.asarray(dim)
+    base = slam2d_offsets(dim)
+    m, k = len(odo), len(obs)
+    odo_seq = np.arange(m) if odo_seq is None else np.asarray(odo_seq)
+    obs_seq = m + np.arange(k) if obs_seq is None else np.asarray(obs_seq)
+    lines = [None] * (m + k)
+    iu = np.triu_indices(3)
+    for e, mat, q in zip(odo, odo_info, odo_seq):
+        lines[q] = "EDGE_SE2 %d %d %.17g %.17g %.17g " % (int(e[0]), int(e[1]), e[2], e[3], e[4]) + \
+            " ".join("%.17g" % x for x in np.asarray(mat)[iu])
+    for e, mat, q in zip(obs, obs_info, obs_seq):
+        mat = np.asarray(mat)
+        lines[q] = "EDGE_SE2_RB %d %d %.17g %.17g %.17g %.17g %.17g" % (int(e[0]), int(e[1]), e[2], e[3],
+                                                                        mat[0, 0], mat[0, 1], mat[1, 1])
+    with open(path, "w") as f:
+        for v in np.flatnonzero(dim == 3):
+            f.write("VERTEX_SE2 %d %.17g %.17g %.17g\n" % (v, *state[base[v]:base[v] + 3]))
+        f.write("\n".join(lines) + "\n")
+
+
+def slam2d_linearize(dim, state, odo, odo_info, obs, obs_info, unary_vertex=0):
+    """The two edge groups of a 2D landmark SLAM graph at `state` (flat, laid out by dim), as synth.Problems over the
+    SAME vertices: odometry (3, 3, 3) -- C2DJacobians::Absolute_to_Relative, 2DSolverBase.h:373-418, error of CEdgePose2D --
+    and observations (3, 2, 2) -- Observation2D_RangeBearing, :443-496 (range floored at 1e-5 before the Jacobians),
+    error of CEdgePoseLandmark2D with the bearing wrapped, SE2_Types.h:562-573. Angles are clamped exactly as there."""
+    from .synth import Problem
+    dim = np.asarray(dim, dtype=np.int32)
+    x = np.asarray(state, dtype=np.float64)
+    base = slam2d_offsets(dim)
+    odo = np.asarray(odo, dtype=np.float64).reshape(-1, 5)
+    obs = np.asarray(obs, dtype=np.float64).reshape(-1, 4)
+    # odometry
+    v0, v1 = odo[:, 0].astype(np.int64), odo[:, 1].astype(np.int64)
+    m = v0.size
+    p1 = x[base[v0][:, None] + np.arange(3)]
+    p2 = x[base[v1][:, None] + np.arange(3)]
+    c, s = np.cos(p1[:, 2]), np.sin(p1[:, 2])
+    d = p2[:, :2] - p1[:, :2]
+    J0, J1 = np.zeros((m, 3, 3)), np.zeros((m, 3, 3))
+    J0[:, 0, 0], J0[:, 0, 1], J0[:, 0, 2] = -c, -s, -s * d[:, 0] + c * d[:, 1]
+    J0[:, 1, 0], J0[:, 1, 1], J0[:, 1, 2] = s, -c, -c * d[:, 0] - s * d[:, 1]
+    J0[:, 2, 2] = -1
+    J1[:, 0, 0], J1[:, 0, 1] = c, s
+    J1[:, 1, 0], J1[:, 1, 1] = -s, c
+    J1[:, 2, 2] = 1
+    r = np.empty((m, 3))
+    r[:, 0] = odo[:, 2] - (c * d[:, 0] + s * d[:, 1])
+    r[:, 1] = odo[:, 3] - (-s * d[:, 0] + c * d[:, 1])
+    r[:, 2] = _clamp_angular_error_2pi(odo[:, 4] - _clamp_angle_2pi(p2[:, 2] - p1[:, 2]))
+    g_odo = Problem(name="slam2d_odometry", dim=dim, v0=v0, v1=v1, d0=3, d1=3, rd=3,
+                    J0=np.ascontiguousarray(J0.transpose(0, 2, 1)).reshape(m, 9),
+                    J1=np.ascontiguousarray(J1.transpose(0, 2, 1)).reshape(m, 9),
+                    Om=np.asarray(odo_info, dtype=np.float64).reshape(m, 9), r=r, unary_vertex=unary_vertex, damping=0.0)
+    # observations
+    vp, vl = obs[:, 0].astype(np.int64), obs[:, 1].astype(np.int64)
+    k = vp.size
+    p = x[base[vp][:, None] + np.arange(3)]
+    l = x[base[vl][:, None] + np.arange(2)]
+    de, dn = l[:, 0] - p[:, 0], l[:, 1] - p[:, 1]
+    rng = np.sqrt(de * de + dn * dn)
+    hb = _clamp_angle_2pi(np.arctan2(dn, de) - p[:, 2])
+    rng = np.where(np.abs(rng) < 1e-5, 1e-5, rng)
+    d2 = rng * rng
+    H0, H1 = np.zeros((k, 2, 3)), np.zeros((k, 2, 2))
+    H0[:, 0, 0], H0[:, 0, 1] = -de / rng, -dn / rng
+    H0[:, 1, 0], H0[:, 1, 1], H0[:, 1, 2] = dn / d2, -de / d2, -1
+    H1[:, 0, 0], H1[:, 0, 1] = de / rng, dn / rng
+    H1[:, 1, 0], H1[:, 1, 1] = -dn / d2, de / d2
+    ro = np.empty((k, 2))
+    ro[:, 0] = obs[:, 2] - rng
+    ro[:, 1] = _clamp_angular_error_2pi(obs[:, 3] - hb)
+    g_obs = Problem(name="slam2d_observations", dim=dim, v0=vp, v1=vl, d0=3, d1=2, rd=2,
+                    J0=np.ascontiguousarray(H0.transpose(0, 2, 1)).reshape(k, 6),
+                    J1=np.ascontiguousarray(H1.transpose(0, 2, 1)).reshape(k, 4),
+                    Om=np.asarray(obs_info, dtype=np.float64).reshape(k, 4), r=ro, unary_vertex=unary_vertex, damping=0.0)
+    return g_odo, g_obs

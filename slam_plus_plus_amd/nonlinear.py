@@ -17,7 +17,7 @@ import math
 import numpy as np
 
 from . import api
-from .formats import se2_linearize, se3_linearize, se3_plus, ba_linearize
+from .formats import se2_linearize, se3_linearize, se3_plus, ba_linearize, slam2d_linearize, slam2d_offsets
 
 
 class CPoseGraph2D:
@@ -62,6 +62,136 @@ class CPoseGraph3D:
     def chi2(self):
         prob = self.linearize()
         return float(np.einsum("ei,eij,ej->", prob.r, prob.Om.reshape(-1, 6, 6), prob.r))
+
+
+class CSlam2D:
+    """2D landmark SLAM 'system': 3-wide poses and 2-wide landmarks in one flat state laid out by `dim` (the layout of
+    eta: in 2D state and increment coincide), odometry edges odo (m, 5) i j dx dy dtheta + odo_info (m, 3, 3)
+    (CEdgePose2D) and observations obs (k, 4) pose landmark range bearing + obs_info (k, 2, 2) (CEdgePoseLandmark2D).
+    odo_seq / obs_seq: position of every edge in the graph's edge order (default: odometry, then observations)."""
+
+    def __init__(self, dim, state, odo, odo_info, obs, obs_info, odo_seq=None, obs_seq=None, unary_vertex=0):
+        self.dim = np.asarray(dim, dtype=np.int32)
+        self.state = np.array(state, dtype=np.float64)
+        self.odo, self.odo_info = np.asarray(odo, dtype=np.float64), np.asarray(odo_info, dtype=np.float64)
+        self.obs, self.obs_info = np.asarray(obs, dtype=np.float64), np.asarray(obs_info, dtype=np.float64)
+        m, k = self.odo.shape[0], self.obs.shape[0]
+        self.odo_seq = np.arange(m, dtype=np.int64) if odo_seq is None else np.asarray(odo_seq, dtype=np.int64)
+        self.obs_seq = m + np.arange(k, dtype=np.int64) if obs_seq is None else np.asarray(obs_seq, dtype=np.int64)
+        self.unary_vertex = unary_vertex
+        self.base = slam2d_offsets(self.dim)
+        self.angle_off = self.base[:-1][self.dim == 3] + 2
+
+    @classmethod
+    def from_problem(cls, p):
+        """from synth.slam2d_problem or formats.load_slam2d_graph"""
+        return cls(p["dim"], p["state"], p["odo"], p["odo_info"], p["obs"], p["obs_info"], p.get("odo_seq"), p.get("obs_seq"),
+                   p.get("unary_vertex", 0))
+
+    def linearize(self):
+        """the two edge groups (odometry, observations) as synth.Problems over the same vertices"""
+        return slam2d_linearize(self.dim, self.state, self.odo, self.odo_info, self.obs, self.obs_info, self.unary_vertex)
+
+    def groups(self):
+        return [(self.odo[:, 0], self.odo[:, 1], 3, 3, 3), (self.obs[:, 0], self.obs[:, 1], 3, 2, 2)]
+
+    def plus(self, dx):
+        self.state += dx
+        self.state[self.angle_off] = np.fmod(self.state[self.angle_off], 2 * math.pi)  # poses only (SE2_Types.h:70-74, :89)
+
+    def chi2(self):
+        return float(sum(np.einsum("ei,eij,ej->", g.r, g.Om.reshape(-1, g.rd, g.rd), g.r) for g in self.linearize()))
+
+
+class _DeviceGroupsPath:
+    """Jacobians on the host, multi-group device assembly + device solve (host_jacobians=True for CSlam2D)"""
+
+    def __init__(self, device=0, seq=None):
+        self.ctx = api.Context(device)
+        self.seq = seq   # per group: the position of every edge in the graph's edge order (None: groups concatenated)
+
+    def solve(self, groups, first):
+        ctx = self.ctx
+        if first:
+            self.st = ctx.assemble_analyze_groups(groups[0].dim, [(g.v0, g.v1, g.d0, g.d1, g.rd) for g in groups],
+                                                  self.seq, groups[0].unary_vertex)
+            self.d_vals, self.d_eta = api.DeviceArray(ctx, self.st.nvals), api.DeviceArray(ctx, self.st.n)
+            self.d_in = [[api.DeviceArray(ctx, a.size) for a in (g.J0, g.J1, g.Om, g.r)] for g in groups]
+        for d4, g in zip(self.d_in, groups):
+            for d, a in zip(d4, (g.J0, g.J1, g.Om, g.r)):
+                d.upload(np.ascontiguousarray(a).ravel())
+        ctx.assemble_groups_device(*[[d4[k].ptr for d4 in self.d_in] for k in range(4)], 0.0, self.d_vals.ptr, self.d_eta.ptr)
+        if first:
+            ctx.analyze(self.st, api.MODE_AUTO)
+        if ctx.factor_solve_device(self.d_vals.ptr, self.d_eta.ptr) != 0:
+            return False, None
+        return True, self.d_eta.download()
+
+    def close(self):
+        self.ctx.close()
+
+
+class _ResidentSlam2DPath:
+    """the whole Gauss-Newton iteration of a CSlam2D in HBM: both linearize kernels (spp_se2_linearize_at_device,
+    spp_se2_rb_linearize_device), spp_assemble_groups_device, analyze once, spp_factor_solve_device,
+    spp_slam2d_update_device. Host traffic: the 8-byte norm per spp_slam2d_update_device call -- one in step() (the
+    stopping test), one in apply() (the kernel's sibling entry points return it whenever they run), so 16 bytes and two
+    stream synchronisations per applied iteration, as in _ResidentPath."""
+
+    def __init__(self, device=0):
+        self.ctx = api.Context(device)
+
+    def begin(self, system):
+        ctx, s = self.ctx, system
+        up = lambda a: api.DeviceArray.from_host(ctx, np.ascontiguousarray(a).ravel())
+        self.m, self.k, self.n = s.odo.shape[0], s.obs.shape[0], s.state.size
+        self.st = ctx.assemble_analyze_groups(s.dim, s.groups(), [s.odo_seq, s.obs_seq], s.unary_vertex)
+        off = lambda col: up(s.base[col.astype(np.int64)])
+        self.d_off = [off(s.odo[:, 0]), off(s.odo[:, 1]), off(s.obs[:, 0]), off(s.obs[:, 1])]
+        self.d_meas = [up(s.odo[:, 2:5]), up(s.obs[:, 2:4])]
+        self.d_Om = [up(s.odo_info), up(s.obs_info)]
+        self.d_state, self.d_angle = up(s.state), up(s.angle_off.astype(np.int64))
+        self.n_angle = s.angle_off.size
+        self.d_J0 = [api.DeviceArray(ctx, 9 * self.m), api.DeviceArray(ctx, 6 * self.k)]
+        self.d_J1 = [api.DeviceArray(ctx, 9 * self.m), api.DeviceArray(ctx, 4 * self.k)]
+        self.d_r = [api.DeviceArray(ctx, 3 * self.m), api.DeviceArray(ctx, 2 * self.k)]
+        self.d_vals, self.d_eta = api.DeviceArray(ctx, self.st.nvals), api.DeviceArray(ctx, self.st.n)
+        self.analyzed = False
+
+    def linearize(self):
+        ctx = self.ctx
+        ctx.se2_linearize_at_device(self.m, self.d_off[0].ptr, self.d_off[1].ptr, self.d_state.ptr, self.d_meas[0].ptr,
+                                    self.d_J0[0].ptr, self.d_J1[0].ptr, self.d_r[0].ptr)
+        ctx.se2_rb_linearize_device(self.k, self.d_off[2].ptr, self.d_off[3].ptr, self.d_state.ptr, self.d_meas[1].ptr,
+                                    self.d_J0[1].ptr, self.d_J1[1].ptr, self.d_r[1].ptr)
+
+    def chi2(self):
+        """error at the current state: the sum over the groups (re-linearizes)"""
+        self.linearize()
+        return (self.ctx.edge_chi2_device(self.m, 3, self.d_r[0].ptr, self.d_Om[0].ptr) +
+                self.ctx.edge_chi2_device(self.k, 2, self.d_r[1].ptr, self.d_Om[1].ptr))
+
+    def step(self):
+        ctx = self.ctx
+        self.linearize()
+        ptrs = lambda arrs: [a.ptr for a in arrs]
+        ctx.assemble_groups_device(ptrs(self.d_J0), ptrs(self.d_J1), ptrs(self.d_Om), ptrs(self.d_r), 0.0,
+                                   self.d_vals.ptr, self.d_eta.ptr)
+        if not self.analyzed:
+            ctx.analyze(self.st, api.MODE_AUTO)
+            self.analyzed = True
+        if ctx.factor_solve_device(self.d_vals.ptr, self.d_eta.ptr) != 0:
+            return False, 0.0
+        return True, ctx.slam2d_update_device(self.n, self.d_state.ptr, self.d_eta.ptr, self.n_angle, self.d_angle.ptr, apply=False)
+
+    def apply(self):
+        self.ctx.slam2d_update_device(self.n, self.d_state.ptr, self.d_eta.ptr, self.n_angle, self.d_angle.ptr, apply=True)
+
+    def finish(self, system):
+        system.state[:] = self.d_state.download()
+
+    def close(self):
+        self.ctx.close()
 
 
 class _DevicePath:
@@ -148,7 +278,11 @@ class CNonlinearSolver_Lambda:
     def __init__(self, system, path=None, device=0, verbose=False, host_jacobians=False):
         self.system = system
         if path is None:  # the product paths need the GPU; host_jacobians keeps the linearization in numpy
-            path = _DevicePath(device) if host_jacobians else _ResidentPath(device)
+            if isinstance(system, CSlam2D):
+                path = (_DeviceGroupsPath(device, [system.odo_seq, system.obs_seq]) if host_jacobians
+                        else _ResidentSlam2DPath(device))
+            else:
+                path = _DevicePath(device) if host_jacobians else _ResidentPath(device)
         self.path = path
         self.verbose = verbose
         self.n_iterations = 0

@@ -291,6 +291,95 @@ def landmark2d_problem(n_poses=80, n_lm=200, seed=32, interleave=False, name="lm
                    Om=Om, r=r, unary_vertex=0, damping=1e-2)
 
 
+def slam2d_problem(n_poses=60, n_lm=90, seed=68, interleave=False, name="slam2d", views=(2, 5), window=6):
+    """2D landmark SLAM as a real dataset has it (victoria-park style): a planar trajectory with noisy odometry
+    (CEdgePose2D) and n_poses // 5 loop closures, landmarks each seen from 2..5 nearby poses by noisy range-bearing
+    (CEdgePoseLandmark2D) -- two edge groups, (3, 3, 3) and (3, 2, 2), over the same vertices. Geometrically consistent:
+    the measurements come from a ground truth, the initial estimate is dead reckoning along the odometry, every landmark
+    starts where its first observation puts it. interleave=True shuffles the vertex ids (vertex 0 stays the first pose,
+    which carries the unary factor), so that landmarks sit between the poses and about half of the pose-landmark
+    blocks are stored transposed. The edges are in the order of an incremental run: each when its later pose arrives.
+    views / window: every landmark is seen from views[0] .. views[1] poses at most `window` steps from its centre pose
+    (victoria-park has few landmarks seen many times: 6969 poses, 151 landmarks, about 3600 observations).
+    Returns Problem(dim, state (flat, laid out by dim), odo (m, 5), odo_info, odo_seq, obs (k, 4) pose landmark range
+    bearing, obs_info, obs_seq, pose_id, lm_id, truth, unary_vertex)."""
+    rng = np.random.default_rng(seed)
+    nv = n_poses + n_lm
+    if interleave:
+        ids = 1 + rng.permutation(nv - 1)
+        pose_id, lm_id = np.concatenate([[0], ids[:n_poses - 1]]), ids[n_poses - 1:]
+    else:
+        pose_id, lm_id = np.arange(n_poses), n_poses + np.arange(n_lm)
+    # ground truth: unit steps, slowly turning
+    th = np.cumsum(np.concatenate([[0.0], rng.normal(0.05, 0.25, size=n_poses - 1)]))
+    xy = np.zeros((n_poses, 2))
+    xy[1:] = np.cumsum(np.stack([np.cos(th[:-1]), np.sin(th[:-1])], axis=1), axis=0)
+    P = np.concatenate([xy, th[:, None]], axis=1)
+
+    def rel(i, j):  # pose j in the frame of pose i
+        c, s = np.cos(P[i, 2]), np.sin(P[i, 2])
+        d = P[j, :2] - P[i, :2]
+        return np.stack([c * d[:, 0] + s * d[:, 1], -s * d[:, 0] + c * d[:, 1], P[j, 2] - P[i, 2]], axis=1)
+
+    oi = np.arange(n_poses - 1)
+    oj = oi + 1
+    lc = np.sort(np.stack([rng.choice(n_poses, size=2, replace=False) for _ in range(n_poses // 5)]), axis=1)
+    oi, oj = np.concatenate([oi, lc[:, 0]]), np.concatenate([oj, lc[:, 1]])
+    # wheel odometry along the chain, loop closures from a four times finer sensor (scan matching): the dead-reckoned
+    # estimate then misses the closures by tens of their sigmas while staying inside Gauss-Newton's basin
+    sig = np.where((np.arange(oi.size) < n_poses - 1)[:, None], np.array([0.02, 0.02, 0.004]), np.array([0.005, 0.005, 0.001]))
+    z_odo = rel(oi, oj) + rng.normal(0, 1, size=(oi.size, 3)) * sig
+    odo_info = np.zeros((oi.size, 3, 3))
+    odo_info[:, [0, 1, 2], [0, 1, 2]] = 1.0 / sig ** 2
+    # landmarks: 3 .. 6 m off a centre pose, seen from 2 .. 5 poses around it
+    centre = rng.integers(0, n_poses, size=n_lm)
+    ang, dist = rng.uniform(-np.pi, np.pi, size=n_lm), rng.uniform(3.0, 6.0, size=n_lm)
+    Lm = xy[centre] + dist[:, None] * np.stack([np.cos(ang), np.sin(ang)], axis=1)
+    po, lo = [], []
+    for l in range(n_lm):
+        seen = np.unique(np.clip(centre[l] + rng.integers(-window, window + 1, size=rng.integers(views[0], views[1] + 1)), 0, n_poses - 1))
+        if seen.size < 2:
+            seen = np.unique(np.clip([centre[l] - 1, centre[l], centre[l] + 1], 0, n_poses - 1))[:2]
+        po.append(seen)
+        lo.append(np.full(seen.size, l))
+    po, lo = np.concatenate(po), np.concatenate(lo)
+    d = Lm[lo] - xy[po]
+    z_obs = np.stack([np.hypot(d[:, 0], d[:, 1]), np.arctan2(d[:, 1], d[:, 0]) - th[po]], axis=1)
+    z_obs += rng.normal(0, 1, size=z_obs.shape) * np.array([0.05, 0.01])
+    z_obs[:, 1] = np.fmod(z_obs[:, 1], 2 * np.pi)
+    obs_info = np.tile(np.diag([400.0, 10000.0]), (po.size, 1, 1))
+    # global edge order: by the later pose of the edge, odometry before the observations made there
+    t_all = np.concatenate([np.maximum(oi, oj), po])
+    order = np.argsort(t_all, kind="stable")
+    seq = np.empty(order.size, dtype=np.int64)
+    seq[order] = np.arange(order.size)
+    # initial estimate: dead reckoning, landmarks from their first observation (in the global order)
+    est = np.zeros((n_poses, 3))
+    for i in range(n_poses - 1):
+        c, s_ = np.cos(est[i, 2]), np.sin(est[i, 2])
+        est[i + 1] = [est[i, 0] + c * z_odo[i, 0] - s_ * z_odo[i, 1], est[i, 1] + s_ * z_odo[i, 0] + c * z_odo[i, 1],
+                      np.fmod(est[i, 2] + z_odo[i, 2], 2 * np.pi)]
+    first = np.full(n_lm, -1)
+    for k in np.argsort(seq[oi.size:], kind="stable"):
+        if first[lo[k]] < 0:
+            first[lo[k]] = k
+    b = est[po[first], 2] + z_obs[first, 1]
+    lm_est = est[po[first], :2] + z_obs[first, :1] * np.stack([np.cos(b), np.sin(b)], axis=1)
+    dim = np.empty(nv, dtype=np.int32)
+    dim[pose_id], dim[lm_id] = 3, 2
+    base = np.zeros(nv + 1, dtype=np.int64)
+    np.cumsum(dim, out=base[1:])
+    state = np.empty(base[-1])
+    state[base[pose_id][:, None] + np.arange(3)] = est
+    state[base[lm_id][:, None] + np.arange(2)] = lm_est
+    f = lambda a: a.astype(np.float64)
+    return Problem(name=name, dim=dim, state=state, unary_vertex=0, pose_id=pose_id, lm_id=lm_id,
+                   odo=np.concatenate([f(pose_id[oi])[:, None], f(pose_id[oj])[:, None], z_odo], axis=1), odo_info=odo_info,
+                   odo_seq=seq[:oi.size].copy(),
+                   obs=np.concatenate([f(pose_id[po])[:, None], f(lm_id[lo])[:, None], z_obs], axis=1), obs_info=obs_info,
+                   obs_seq=seq[oi.size:].copy(), truth=dict(poses=P, landmarks=Lm))
+
+
 def pose_graph_states(prob):
     """The same pose graph as states + measurements in the REFERENCE's parameterization, as input of
     spp_se2_/se3_linearize_device: poses (n, 3) x y theta or (n, 6) [t | axis-angle] at the noisy estimate,
@@ -327,6 +416,8 @@ CONFIGS = {
     "ba_banded": lambda: ba_problem(600, 30000, 150000, 600, heavy_tail=False, spread=0.01, name="ba_banded"),
     "lm2d_small": lambda: landmark2d_problem(80, 200, 32),
     "lm2d_interleaved": lambda: landmark2d_problem(60, 150, 33, interleave=True, name="lm2d_interleaved"),
+    "slam2d_small": lambda: slam2d_problem(60, 90, 68, name="slam2d_small"),
+    "slam2d_interleaved": lambda: slam2d_problem(150, 300, 62, interleave=True, name="slam2d_interleaved"),
     "se2_small": lambda: se2_problem(300, 150, 12, name="se2_small"),
     "se3_small": lambda: se3_problem(8, 12, 13, name="se3_small"),
 }
