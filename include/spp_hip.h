@@ -175,6 +175,8 @@ int spp_schur_unpack(spp_ctx *ctx, const double *d_packed, double *d_S_rhs);
  * BaseTypes_Binary.h:759-848, _Lambda_Base.h:563-607,152-197).
  * One homogeneous binary-edge group (several: spp_assemble_analyze_groups below): residual dimension rd, vertex 0 width d0, vertex 1 width d1.
  * J0: ne x (rd x d0) col-major, J1: ne x (rd x d1), Omega: ne x (rd x rd), r: ne x rd.
+ * Instantiated shapes (d0, d1, rd): (6,3,2) projections, (3,3,3) 2D odometry, (6,6,6) 3D odometry, (3,2,2) 2D landmark
+ * observations, (6,3,3) 3D landmark (XYZ) observations; any other is SPP_E_UNSUPPORTED.
  * The unary factor (identity, FlatSystem.h:441,467) is added to the diagonal block of vertex
  * `unary_vertex` (pass -1 for none). The reference's default build puts it on vertex 0 whatever its type
  * (__AUTO_UNARY_FACTOR_ON_VERTEX_ZERO, FlatSystem.h:331-337, _Lambda_Base.h:1903-1924; without that macro: on the
@@ -199,8 +201,9 @@ int spp_assemble_set_edge_weights(spp_ctx *ctx, const double *d_w);
  * (6,6,6) beside projections (6,3,2) -- the reference's AddEntriesInSparseSystem / Refresh_Lambda run over an edge pool of
  * several types alike (NonlinearSolver_Lambda_Base.h:1852-1931, 1658-1688; the reduction plan sums a destination's sources
  * in the order the edges were added, whatever their types: :563-607, 152-197; BaseTypes_Binary.h:759-848 per edge).
- * Group g: h_ne[g] edges h_v0[g] -> h_v1[g] of shape (h_d0[g], h_d1[g], h_rd[g]), one of the four above; two groups may
- * share a shape. h_seq[g][e]: position of that edge in the graph's global edge order (all of them a permutation of
+ * Group g: h_ne[g] edges h_v0[g] -> h_v1[g] of shape (h_d0[g], h_d1[g], h_rd[g]), one of the five above; two groups may
+ * share a shape, but (6,3,2) and (6,3,3) may not appear in one plan: they share their widths, so one off-diagonal block
+ * could be fed by both, and a block is summed by the kernel of ONE shape (SPP_E_UNSUPPORTED). h_seq[g][e]: position of that edge in the graph's global edge order (all of them a permutation of
  * 0 .. sum(ne) - 1; h_seq, or h_seq[g], NULL: the position in the concatenation of the groups). Every destination -- diagonal
  * block, eta segment, off-diagonal block, also one fed by several groups -- sums its contributions in ascending position,
  * first assigned, rest added (vertices of degree > 24: the fixed butterfly of the wave kernel over that order). The
@@ -209,7 +212,7 @@ int spp_assemble_set_edge_weights(spp_ctx *ctx, const double *d_w);
  * spp_assemble_groups_device (host arrays of n_groups device pointers) accepts any plan and gives the same bits on a
  * one-group plan.
  * Unary factor and damping as above; robust weights per group (NULL: plain), reset by either analyze call.
- * SPP_E_UNSUPPORTED: a shape not instantiated, more than SPP_MAX_EDGE_GROUPS groups. SPP_E_BADARG: a vertex width that does
+ * SPP_E_UNSUPPORTED: a shape not instantiated, (6,3,2) beside (6,3,3), more than SPP_MAX_EDGE_GROUPS groups. SPP_E_BADARG: a vertex width that does
  * not match its group, a bad index, a self edge, h_seq not a permutation; the ctx then holds no assembly plan.
  * SPP_E_STATE: spp_assemble_device on a plan of several groups, spp_assemble_groups_device without a plan. */
 #define SPP_MAX_EDGE_GROUPS 4
@@ -271,6 +274,28 @@ int spp_se3_linearize_device(spp_ctx *ctx, int64_t n_edges, const int32_t *d_v0,
 int spp_se3_update_device(spp_ctx *ctx, int64_t n_vertices, double *d_poses, const double *d_dx, int apply,
 	double *h_dx_norm2);
 
+/* ---- on-device geometry of 3D landmark SLAM (CEdgePose3D + CEdgePoseLandmark3D) ----------------------
+ * Poses [t | axis-angle] (6) and landmarks XYZ (3) live in ONE flat state laid out like eta (in 3D, too, the increment
+ * has the state's layout); vertices are addressed by scalar offset (int64), so landmarks may sit between the poses.
+ * spp_se3_linearize_at_device: spp_se3_linearize_device with the two pose offsets given per edge (6 * id reproduces it,
+ * bit for bit).
+ * spp_se3_xyz_linearize_device: per observation the expectation e = R(a)^T (l - t) of C3DJacobians::
+ * Absolute_to_Relative_Landmark (include/slam/3DSolverBase.h:1528-1539), r = z - e, nothing wrapped (CEdgePoseLandmark3D::
+ * Calculate_Jacobians_Expectation_Error, include/slam/SE3_Types.h:568-586), and the Jacobians w.r.t. the pose increment of
+ * Relative_to_Absolute (t' = t + R dt, R' = R exp(dr), 3DSolverBase.h:807-850) and w.r.t. the landmark -- analytic here,
+ * d e / d pose = [-I | [e]x], d e / d l = R^T, forward differences with delta = 1e-9 in the reference (:1602-1637). Layout
+ * of the (6,3,3) group: J0 ne x (3x6) column-major, J1 ne x (3x3), r ne x 3.
+ * spp_slam3d_update_device: ||dx||^2 over the n state entries (two-stage sum) and, if `apply`, the 6 entries at each of
+ * the n_poses offsets d_pose_off <- pose (+) dx (CVertexPose3D::Operator_Plus, the composition spp_se3_update_device
+ * applies, same bits), every other entry a plain sum (CVertexLandmark3D::Operator_Plus, SE3_Types.h:110-113).
+ * Synchronizes the stream. */
+int spp_se3_linearize_at_device(spp_ctx *ctx, int64_t n_edges, const int64_t *d_off0, const int64_t *d_off1,
+	const double *d_state, const double *d_measurements, double *d_J0, double *d_J1, double *d_r);
+int spp_se3_xyz_linearize_device(spp_ctx *ctx, int64_t n_edges, const int64_t *d_pose_off, const int64_t *d_lm_off,
+	const double *d_state, const double *d_measurements, double *d_J0, double *d_J1, double *d_r);
+int spp_slam3d_update_device(spp_ctx *ctx, int64_t n, double *d_state, const double *d_dx, int64_t n_poses,
+	const int64_t *d_pose_off, int apply, double *h_dx_norm2);
+
 /* ---- on-device geometry of bundle adjustment (CEdgeP2C3D) -------------------------
  * Cameras: 6 doubles each [t | axis-angle], world -> camera, and 5 constant intrinsics each (fx fy cx cy k:
  * CVertexCam, include/slam/BA_Types.h); points: XYZ. spp_ba_linearize_device evaluates per observation the
@@ -295,7 +320,8 @@ int spp_ba_update_device(spp_ctx *ctx, int64_t n_cams, double *d_cams, const int
  * chi2 = sum_e r_e^T Omega_e r_e (f_Error, :1078-1095); the largest diagonal entry of any vertex Hessian
  * J_i^T Omega J_i over all edges (f_InitialDamping multiplies it by tau = 1e-3, :151-199); the denominator
  * dx . (alpha dx + eta) of the gain ratio (Aftermath, :204-222). Device inputs, host outputs, deterministic
- * reductions; each call synchronizes the stream. rd / (d0, d1): the edge group of spp_assemble_analyze. */
+ * reductions; each call synchronizes the stream. rd / (d0, d1): the edge group of spp_assemble_analyze (chi2: rd 2, 3
+ * or 6; max diagonal: (rd, d0, d1) = (2,6,3), (3,3,3), (6,6,6) or (3,6,3), the XYZ observations). */
 int spp_edge_chi2_device(spp_ctx *ctx, int64_t n_edges, int rd, const double *d_r, const double *d_Omega, double *h_chi2);
 int spp_edge_hessian_maxdiag_device(spp_ctx *ctx, int64_t n_edges, int rd, int d0, int d1, const double *d_J0,
 	const double *d_J1, const double *d_Omega, double *h_max);

@@ -33,7 +33,8 @@ EXPORTS = [
     "spp_schur_packed_size", "spp_schur_pack", "spp_schur_unpack",
     "spp_assemble_analyze", "spp_assemble_get_structure", "spp_assemble_device", "spp_assemble_set_edge_weights",
     "spp_assemble_analyze_groups", "spp_assemble_groups_device", "spp_assemble_set_group_edge_weights",
-    "spp_se2_linearize_at_device", "spp_se2_rb_linearize_device", "spp_slam2d_update_device", "spp_device_malloc",
+    "spp_se2_linearize_at_device", "spp_se2_rb_linearize_device", "spp_slam2d_update_device",
+    "spp_se3_linearize_at_device", "spp_se3_xyz_linearize_device", "spp_slam3d_update_device", "spp_device_malloc",
     "spp_device_free", "spp_memcpy_h2d", "spp_memcpy_d2h", "spp_memcpy_d2d", "spp_get_phase_ms", "spp_get_dominant_kernel",
     "spp_microbench_copy", "spp_microbench_mfma_f64", "spp_microbench_ctile", "spp_microbench_update", "spp_block_ordering", "spp_schur_plan_host", "spp_set_profiling", "spp_se2_linearize_device", "spp_se2_update_device", "spp_ba_linearize_device", "spp_ba_update_device", "spp_se3_linearize_device", "spp_se3_update_device", "spp_edge_chi2_device", "spp_edge_robust_weights_device", "spp_edge_hessian_maxdiag_device",
     "spp_lm_gain_denominator_device", "spp_dense_potrf_upper", "spp_dense_posv",
@@ -90,6 +91,9 @@ def load_library():
         "spp_se2_linearize_at_device": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
         "spp_se2_rb_linearize_device": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
         "spp_slam2d_update_device": (cint, [vp, i64, vp, vp, i64, vp, cint, _c_f64p]),
+        "spp_se3_linearize_at_device": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+        "spp_se3_xyz_linearize_device": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+        "spp_slam3d_update_device": (cint, [vp, i64, vp, vp, i64, vp, cint, _c_f64p]),
         "spp_device_malloc": (cint, [vp, ctypes.c_size_t, ctypes.POINTER(vp)]),
         "spp_device_free": (cint, [vp, vp]),
         "spp_memcpy_h2d": (cint, [vp, vp, vp, ctypes.c_size_t]),
@@ -360,6 +364,21 @@ class Context:
         """returns ||dx|| (host); when `apply`, state += dx with the pose angles at d_angle_off clamped"""
         out = ctypes.c_double()
         self._check(self.lib.spp_slam2d_update_device(self.h, n, d_state, d_dx, n_pose_angles, d_angle_off, 1 if apply else 0,
+                                                      ctypes.byref(out)))
+        return out.value ** 0.5
+
+    def se3_linearize_at_device(self, n_edges, d_off0, d_off1, d_state, d_meas, d_J0, d_J1, d_r):
+        """se3_linearize_device with the poses at scalar offsets (int64) into one flat state"""
+        return self._check(self.lib.spp_se3_linearize_at_device(self.h, n_edges, d_off0, d_off1, d_state, d_meas, d_J0, d_J1, d_r))
+
+    def se3_xyz_linearize_device(self, n_edges, d_pose_off, d_lm_off, d_state, d_meas, d_J0, d_J1, d_r):
+        """XYZ observations of a landmark from a 6D pose (CEdgePoseLandmark3D): the (6, 3, 3) group's J0, J1, r"""
+        return self._check(self.lib.spp_se3_xyz_linearize_device(self.h, n_edges, d_pose_off, d_lm_off, d_state, d_meas, d_J0, d_J1, d_r))
+
+    def slam3d_update_device(self, n, d_state, d_dx, n_poses, d_pose_off, apply=True):
+        """returns ||dx|| (host); when `apply`, the poses at d_pose_off are composed with their increment, the rest added"""
+        out = ctypes.c_double()
+        self._check(self.lib.spp_slam3d_update_device(self.h, n, d_state, d_dx, n_poses, d_pose_off, 1 if apply else 0,
                                                       ctypes.byref(out)))
         return out.value ** 0.5
 

@@ -920,6 +920,44 @@ int spp_edge_robust_weights_device(spp_ctx *ctx, int64_t n_edges, int rd, int ki
 	SPP_CATCH(ctx)
 }
 
+int spp_se3_linearize_at_device(spp_ctx *ctx, int64_t n_edges, const int64_t *d_off0, const int64_t *d_off1,
+	const double *d_state, const double *d_measurements, double *d_J0, double *d_J1, double *d_r)
+{
+	if(!ctx || n_edges < 0 || !d_off0 || !d_off1 || !d_state || !d_measurements || !d_J0 || !d_J1 || !d_r)
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	se3_linearize_at(ctx, n_edges, d_off0, d_off1, d_state, d_measurements, d_J0, d_J1, d_r);
+	return SPP_OK;
+	SPP_CATCH(ctx)
+}
+
+int spp_se3_xyz_linearize_device(spp_ctx *ctx, int64_t n_edges, const int64_t *d_pose_off, const int64_t *d_lm_off,
+	const double *d_state, const double *d_measurements, double *d_J0, double *d_J1, double *d_r)
+{
+	if(!ctx || n_edges < 0 || !d_pose_off || !d_lm_off || !d_state || !d_measurements || !d_J0 || !d_J1 || !d_r)
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	se3_xyz_linearize(ctx, n_edges, d_pose_off, d_lm_off, d_state, d_measurements, d_J0, d_J1, d_r);
+	return SPP_OK;
+	SPP_CATCH(ctx)
+}
+
+int spp_slam3d_update_device(spp_ctx *ctx, int64_t n, double *d_state, const double *d_dx, int64_t n_poses,
+	const int64_t *d_pose_off, int apply, double *h_dx_norm2)
+{
+	if(!ctx || n < 0 || n_poses < 0 || !d_state || !d_dx || (n_poses && !d_pose_off))
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	const double n2 = slam3d_update(ctx, n, d_state, d_dx, n_poses, d_pose_off, apply != 0);
+	if(h_dx_norm2)
+		*h_dx_norm2 = n2;
+	return SPP_OK;
+	SPP_CATCH(ctx)
+}
+
 int spp_edge_chi2_device(spp_ctx *ctx, int64_t n_edges, int rd, const double *d_r, const double *d_Omega, double *h_chi2)
 {
 	if(!ctx || n_edges < 0 || !d_r || !d_Omega || !h_chi2)

@@ -90,10 +90,15 @@ int64_t assemble_group_edges(const spp_ctx *ctx, int group)
 
 static const int SEQ_MAX_DEGREE = 24;
 
+static bool same_shape(const AssemblePlan *ap, int ga, int gb)
+{
+	return ap->d0[ga] == ap->d0[gb] && ap->d1[ga] == ap->d1[gb] && ap->rd[ga] == ap->rd[gb];
+}
+
 static bool shape_instantiated(int d0, int d1, int rd)
 {
 	return (d0 == 6 && d1 == 3 && rd == 2) || (d0 == 3 && d1 == 3 && rd == 3) || (d0 == 6 && d1 == 6 && rd == 6) ||
-		(d0 == 3 && d1 == 2 && rd == 2);
+		(d0 == 3 && d1 == 2 && rd == 2) || (d0 == 6 && d1 == 3 && rd == 3);
 }
 
 void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int n_groups, const int64_t *g_ne,
@@ -105,7 +110,7 @@ void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int n_groups
 	int64_t ne = 0;
 	for(int g = 0; g < n_groups; ++ g) {
 		SPP_REQUIRE(shape_instantiated(g_d0[g], g_d1[g], g_rd[g]), SPP_E_UNSUPPORTED,
-			"edge group (d0, d1, rd) not instantiated: (6,3,2) (3,3,3) (6,6,6) (3,2,2)");
+			"edge group (d0, d1, rd) not instantiated: (6,3,2) (3,3,3) (6,6,6) (3,2,2) (6,3,3)");
 		ne += g_ne[g];
 	}
 	SPP_REQUIRE(ne < (int64_t(1) << 30), SPP_E_UNSUPPORTED, "too many edges for 31-bit edge indices");
@@ -133,11 +138,20 @@ void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int n_groups
 			if(std::find(ap->cls_dim, ap->cls_dim + ap->n_cls, w) == ap->cls_dim + ap->n_cls)
 				ap->cls_dim[ap->n_cls ++] = w;
 		}
-		int s = 0; // (the four shapes differ in (d0, d1) already)
-		while(s < ap->n_shapes && (ap->d0[ap->shape_group[s]] != g_d0[g] || ap->d1[ap->shape_group[s]] != g_d1[g]))
+		int s = 0; // a shape is (d0, d1, rd): (6,3,2) and (6,3,3) share their widths
+		while(s < ap->n_shapes && !same_shape(ap, ap->shape_group[s], g))
 			++ s;
 		if(s == ap->n_shapes)
 			ap->shape_group[ap->n_shapes ++] = g;
+	}
+	// two shapes of the same widths could feed ONE off-diagonal block (a pose-landmark pair joined by a (6,3,2) and by a
+	// (6,3,3) edge), which no off-diagonal kernel sums: such a plan is rejected as a whole
+	for(int a = 0; a < ap->n_shapes; ++ a) {
+		for(int b = a + 1; b < ap->n_shapes; ++ b) {
+			const int ga = ap->shape_group[a], gb = ap->shape_group[b];
+			SPP_REQUIRE(ap->d0[ga] != ap->d0[gb] || ap->d1[ga] != ap->d1[gb], SPP_E_UNSUPPORTED,
+				"edge groups (6,3,2) and (6,3,3) in one plan: their off-diagonal blocks could mix two shapes");
+		}
 	}
 	// ---- the edges in the order of their global positions: everything below walks positions, v0[q] / v1[q] are the vertices
 	// of the edge at position q and edge_at(q) its index in the concatenation of the groups. One group without h_seq: the
@@ -312,7 +326,7 @@ void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int n_groups
 		else
 			lwave[cls].push_back((int32_t)v);
 	}
-	// several shapes: the off-diagonal blocks of each (a block's edges share its two widths, hence its shape); one launch each
+	// several shapes: the off-diagonal blocks of each (a block's edges share its two widths, hence its shape: the one pair of shapes with equal widths was rejected above); one launch each
 	std::vector<int32_t> loblist[SPP_MAX_EDGE_GROUPS];
 	if(ap->n_shapes > 1) {
 		for(int64_t b = 0; b < n_ob; ++ b) {
@@ -321,7 +335,7 @@ void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int n_groups
 			while(e >= ap->gstart[g + 1])
 				++ g;
 			int sh = 0;
-			while(ap->d0[ap->shape_group[sh]] != ap->d0[g] || ap->d1[ap->shape_group[sh]] != ap->d1[g])
+			while(!same_shape(ap, ap->shape_group[sh], g))
 				++ sh;
 			loblist[sh].push_back((int32_t)b);
 		}
@@ -636,7 +650,7 @@ void vertex_wave_kernel(int64_t nlist, const int32_t *__restrict__ vlist, const 
 // (assemble_groups_run), and the two entry points agree bit for bit on it whatever the weights. Traffic is unchanged: each edge's J / Omega / r is read by
 // the three destinations it feeds; what the groups share is the launches.
 // --------------------------------------------------------------------------------------------------
-enum { SHAPE_632 = 0, SHAPE_333 = 1, SHAPE_666 = 2, SHAPE_322 = 3 };
+enum { SHAPE_632 = 0, SHAPE_333 = 1, SHAPE_666 = 2, SHAPE_322 = 3, SHAPE_633 = 4 };
 
 struct GroupPtrs {
 	const double *J0, *J1, *Om, *r, *w;
@@ -726,8 +740,10 @@ void offdiag_groups_kernel(int64_t n, const int32_t *__restrict__ oblist, const 
 }
 
 // contribution of one list entry to a vertex of width D: the body of the entry's shape (a shape without a D-wide side
-// cannot occur in the list of such a vertex)
-template <int D>
+// cannot occur in the list of such a vertex). W633: the plan holds a (6,3,3) group; without one the switch is the four-way
+// switch the kernels had before that shape existed, instruction for instruction (measured: with the fifth case compiled
+// in, the 2D odometry + observation assembly of tools/slam2d_time.py took 46.7 us instead of 45.9 us)
+template <int D, bool W633>
 __device__ __forceinline__ void load_contrib_groups(int32_t entry, const GroupArgs &ga, double *H, double *g)
 {
 	const EdgeRef x = edge_ref(ga, entry >> 1);
@@ -746,13 +762,16 @@ __device__ __forceinline__ void load_contrib_groups(int32_t entry, const GroupAr
 			load_contrib<D, 6, 6, 6>(le, x.J0, x.J1, x.Om, x.r, x.w, H, g);
 		break;
 	default:
-		if(D == 3 || D == 2)
+		if(W633 && x.shape == SHAPE_633) {
+			if(D == 6 || D == 3)
+				load_contrib<D, 6, 3, 3>(le, x.J0, x.J1, x.Om, x.r, x.w, H, g);
+		} else if(D == 3 || D == 2)
 			load_contrib<D, 3, 2, 2>(le, x.J0, x.J1, x.Om, x.r, x.w, H, g);
 		break;
 	}
 }
 
-template <int D>
+template <int D, bool W633>
 __global__ __launch_bounds__(256)
 void vertex_seq_groups_kernel(int64_t nlist, const int32_t *__restrict__ vlist, const int32_t *__restrict__ vl_ptr,
 	const int32_t *__restrict__ vl_entry, const int64_t *__restrict__ v_doff, const int64_t *__restrict__ v_base,
@@ -770,7 +789,7 @@ void vertex_seq_groups_kernel(int64_t nlist, const int32_t *__restrict__ vlist, 
 	bool first = true;
 	for(int32_t q = vl_ptr[v]; q < vl_ptr[v + 1]; ++ q) {
 		double Hc[D * D], gc[D];
-		load_contrib_groups<D>(vl_entry[q], ga, Hc, gc);
+		load_contrib_groups<D, W633>(vl_entry[q], ga, Hc, gc);
 		if(first) { // the first source is assigned, the others are added (_Lambda_Base.h:598-604)
 #pragma unroll
 			for(int c = 0; c < D; ++ c)
@@ -791,7 +810,7 @@ void vertex_seq_groups_kernel(int64_t nlist, const int32_t *__restrict__ vlist, 
 	store_vertex<D>(H, g, v == unary_vertex, damping, vals + v_doff[v], eta + v_base[v]);
 }
 
-template <int D>
+template <int D, bool W633>
 __global__ __launch_bounds__(256)
 void vertex_wave_groups_kernel(int64_t nlist, const int32_t *__restrict__ vlist, const int32_t *__restrict__ vl_ptr,
 	const int32_t *__restrict__ vl_entry, const int64_t *__restrict__ v_doff, const int64_t *__restrict__ v_base,
@@ -809,7 +828,7 @@ void vertex_wave_groups_kernel(int64_t nlist, const int32_t *__restrict__ vlist,
 	for(int i = 0; i < D; ++ i) g[i] = 0;
 	for(int32_t q = vl_ptr[v] + lane; q < vl_ptr[v + 1]; q += 64) {
 		double Hc[D * D], gc[D];
-		load_contrib_groups<D>(vl_entry[q], ga, Hc, gc);
+		load_contrib_groups<D, W633>(vl_entry[q], ga, Hc, gc);
 #pragma unroll
 		for(int c = 0; c < D; ++ c)
 #pragma unroll
@@ -839,9 +858,11 @@ void vertex_wave_groups_kernel(int64_t nlist, const int32_t *__restrict__ vlist,
 		store_vertex<D>(H, g, v == unary_vertex, damping, vals + v_doff[v], eta + v_base[v]);
 }
 
-static int shape_id(int d0, int d1)
+static int shape_id(int d0, int d1, int rd)
 {
-	return d0 == 6 ? (d1 == 3 ? SHAPE_632 : SHAPE_666) : (d1 == 3 ? SHAPE_333 : SHAPE_322);
+	if(d0 == 6)
+		return d1 == 6 ? SHAPE_666 : (rd == 3 ? SHAPE_633 : SHAPE_632);
+	return d1 == 3 ? SHAPE_333 : SHAPE_322;
 }
 
 // launches: one per distinct shape (off-diagonal blocks) + at most two per vertex width class -- whatever the graph's size
@@ -858,7 +879,7 @@ void assemble_groups_run(spp_ctx *ctx, const double *const *J0, const double *co
 	GroupPtrs *gp[SPP_MAX_EDGE_GROUPS] = {&ga.g0, &ga.g1, &ga.g2, &ga.g3};
 	for(int g = 0; g < SPP_MAX_EDGE_GROUPS; ++ g) {
 		if(g < ap->n_groups)
-			*gp[g] = GroupPtrs{J0[g], J1[g], Om[g], r[g], ap->edge_weights[g], (int32_t)ap->gstart[g], shape_id(ap->d0[g], ap->d1[g])};
+			*gp[g] = GroupPtrs{J0[g], J1[g], Om[g], r[g], ap->edge_weights[g], (int32_t)ap->gstart[g], shape_id(ap->d0[g], ap->d1[g], ap->rd[g])};
 		else
 			*gp[g] = GroupPtrs{nullptr, nullptr, nullptr, nullptr, nullptr, INT32_MAX, 0};
 	}
@@ -874,24 +895,31 @@ void assemble_groups_run(spp_ctx *ctx, const double *const *J0, const double *co
 		case SHAPE_632: SPP_OFFDIAG_LAUNCH(6, 3, 2); break;
 		case SHAPE_333: SPP_OFFDIAG_LAUNCH(3, 3, 3); break;
 		case SHAPE_666: SPP_OFFDIAG_LAUNCH(6, 6, 6); break;
+		case SHAPE_633: SPP_OFFDIAG_LAUNCH(6, 3, 3); break;
 		default: SPP_OFFDIAG_LAUNCH(3, 2, 2); break;
 		}
 #undef SPP_OFFDIAG_LAUNCH
 	}
+	bool with_633 = false;
+	for(int g = 0; g < ap->n_groups; ++ g)
+		with_633 = with_633 || gp[g]->shape == SHAPE_633;
 	for(int cls = 0; cls < ap->n_cls; ++ cls) {
-#define SPP_VERTEX_LAUNCH(D) \
+#define SPP_VERTEX_LAUNCH(D, W633) \
 		if(ap->n_seq[cls]) \
-			hipLaunchKernelGGL((vertex_seq_groups_kernel<D>), dim3((unsigned)((ap->n_seq[cls] + 255) / 256)), dim3(256), 0, s, \
+			hipLaunchKernelGGL((vertex_seq_groups_kernel<D, W633>), dim3((unsigned)((ap->n_seq[cls] + 255) / 256)), dim3(256), 0, s, \
 				ap->n_seq[cls], ap->vlist_seq[cls].p, ap->vl_ptr.p, ap->vl_entry.p, ap->v_doff.p, ap->v_base.p, ga, \
 				ap->unary_vertex, damping, vals, eta); \
 		if(ap->n_wave[cls]) \
-			hipLaunchKernelGGL((vertex_wave_groups_kernel<D>), dim3((unsigned)((ap->n_wave[cls] + 3) / 4)), dim3(256), 0, s, \
+			hipLaunchKernelGGL((vertex_wave_groups_kernel<D, W633>), dim3((unsigned)((ap->n_wave[cls] + 3) / 4)), dim3(256), 0, s, \
 				ap->n_wave[cls], ap->vlist_wave[cls].p, ap->vl_ptr.p, ap->vl_entry.p, ap->v_doff.p, ap->v_base.p, ga, \
 				ap->unary_vertex, damping, vals, eta);
-		switch(ap->cls_dim[cls]) {
-		case 6: SPP_VERTEX_LAUNCH(6) break;
-		case 3: SPP_VERTEX_LAUNCH(3) break;
-		default: SPP_VERTEX_LAUNCH(2) break;
+		switch(ap->cls_dim[cls] + (with_633 ? 10 : 0)) {
+		case 6: SPP_VERTEX_LAUNCH(6, false) break;
+		case 3: SPP_VERTEX_LAUNCH(3, false) break;
+		case 2: SPP_VERTEX_LAUNCH(2, false) break;
+		case 16: SPP_VERTEX_LAUNCH(6, true) break;
+		case 13: SPP_VERTEX_LAUNCH(3, true) break;
+		default: SPP_VERTEX_LAUNCH(2, true) break;
 		}
 #undef SPP_VERTEX_LAUNCH
 	}
@@ -928,10 +956,13 @@ void assemble_run(spp_ctx *ctx, const double *J0, const double *J1, const double
 	double damping, double *vals, double *eta)
 {
 	AssemblePlan *ap = ctx->assemble;
-	if(ap->d0[0] == 6 && ap->d1[0] == 3) assemble_t<6, 3, 2>(ctx, J0, J1, Om, r, damping, vals, eta);
-	else if(ap->d0[0] == 3 && ap->d1[0] == 3) assemble_t<3, 3, 3>(ctx, J0, J1, Om, r, damping, vals, eta);
-	else if(ap->d0[0] == 6 && ap->d1[0] == 6) assemble_t<6, 6, 6>(ctx, J0, J1, Om, r, damping, vals, eta);
-	else assemble_t<3, 2, 2>(ctx, J0, J1, Om, r, damping, vals, eta);
+	switch(shape_id(ap->d0[0], ap->d1[0], ap->rd[0])) {
+	case SHAPE_632: assemble_t<6, 3, 2>(ctx, J0, J1, Om, r, damping, vals, eta); break;
+	case SHAPE_333: assemble_t<3, 3, 3>(ctx, J0, J1, Om, r, damping, vals, eta); break;
+	case SHAPE_666: assemble_t<6, 6, 6>(ctx, J0, J1, Om, r, damping, vals, eta); break;
+	case SHAPE_633: assemble_t<6, 3, 3>(ctx, J0, J1, Om, r, damping, vals, eta); break;
+	default: assemble_t<3, 2, 2>(ctx, J0, J1, Om, r, damping, vals, eta); break;
+	}
 }
 
 } // namespace spp

@@ -304,15 +304,11 @@ __device__ __forceinline__ void quat_mul(const double *p, const double *q, doubl
 	o[3] = p[0] * q[3] + p[1] * q[2] - p[2] * q[1] + p[3] * q[0];
 }
 
-__global__ __launch_bounds__(256)
-void se3_linearize_kernel(int64_t ne, const int32_t *__restrict__ v0, const int32_t *__restrict__ v1,
-	const double *__restrict__ poses, const double *__restrict__ meas, double *__restrict__ J0,
-	double *__restrict__ J1, double *__restrict__ r)
+// the edge e between the poses at p1 and p2 (se3_linearize_kernel: poses + 6 id; se3_linearize_at_kernel: state + offset)
+__device__ __forceinline__ void se3_linearize_edge(int64_t e, const double *__restrict__ p1, const double *__restrict__ p2,
+	const double *__restrict__ meas, double *__restrict__ J0, double *__restrict__ J1, double *__restrict__ r)
 {
-	const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if(e >= ne)
-		return;
-	const double *p1 = poses + 6 * (int64_t)v0[e], *p2 = poses + 6 * (int64_t)v1[e], *z = meas + 6 * e;
+	const double *z = meas + 6 * e;
 	double R1[9], R2[9], Re[9];
 	axis_angle_to_rot(p1 + 3, R1);
 	axis_angle_to_rot(p2 + 3, R2);
@@ -377,24 +373,39 @@ void se3_linearize_kernel(int64_t ne, const int32_t *__restrict__ v0, const int3
 		}
 }
 
-// 6D pose (+): t' = t + R dt, R' = R exp(dr) (CVertexPose3D::Operator_Plus, SE3_Types.h:44-47)
+__global__ __launch_bounds__(256)
+void se3_linearize_kernel(int64_t ne, const int32_t *__restrict__ v0, const int32_t *__restrict__ v1,
+	const double *__restrict__ poses, const double *__restrict__ meas, double *__restrict__ J0,
+	double *__restrict__ J1, double *__restrict__ r)
+{
+	const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if(e >= ne)
+		return;
+	se3_linearize_edge(e, poses + 6 * (int64_t)v0[e], poses + 6 * (int64_t)v1[e], meas, J0, J1, r);
+}
+
+// 6D pose (+): t' = t + R dt, R' = R exp(dr) (CVertexPose3D::Operator_Plus, SE3_Types.h:44-47); o may be p
+__device__ __forceinline__ void se3_plus(const double *p, const double *d, double *o)
+{
+	double R[9], q1[4], q2[4], q[4];
+	axis_angle_to_rot(p + 3, R);
+	const double t0 = p[0] + (R[0] * d[0] + R[1] * d[1] + R[2] * d[2]);
+	const double t1 = p[1] + (R[3] * d[0] + R[4] * d[1] + R[5] * d[2]);
+	const double t2 = p[2] + (R[6] * d[0] + R[7] * d[1] + R[8] * d[2]);
+	aa_to_quat(p + 3, q1);
+	aa_to_quat(d + 3, q2);
+	quat_mul(q1, q2, q);
+	o[0] = t0; o[1] = t1; o[2] = t2;
+	quat_to_aa(q[0], q[1], q[2], q[3], o + 3);
+}
+
 __global__ __launch_bounds__(256)
 void se3_update_kernel(int64_t nv, double *__restrict__ poses, const double *__restrict__ dx)
 {
 	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if(i >= nv)
 		return;
-	double *p = poses + 6 * i;
-	const double *d = dx + 6 * i;
-	double R[9], q1[4], q2[4], q[4];
-	axis_angle_to_rot(p + 3, R);
-	p[0] += R[0] * d[0] + R[1] * d[1] + R[2] * d[2];
-	p[1] += R[3] * d[0] + R[4] * d[1] + R[5] * d[2];
-	p[2] += R[6] * d[0] + R[7] * d[1] + R[8] * d[2];
-	aa_to_quat(p + 3, q1);
-	aa_to_quat(d + 3, q2);
-	quat_mul(q1, q2, q);
-	quat_to_aa(q[0], q[1], q[2], q[3], p + 3);
+	se3_plus(poses + 6 * i, dx + 6 * i, poses + 6 * i);
 }
 
 // --------------------------------------------------------------------------------------------------
@@ -574,7 +585,8 @@ double edge_hessian_maxdiag(spp_ctx *ctx, int64_t ne, int rd, int d0, int d1, co
 	if(rd == 2 && d0 == 6 && d1 == 3) hipLaunchKernelGGL((edge_maxdiag_kernel<2, 6, 3>), g, b, 0, ctx->stream, ne, d_J0, d_J1, d_Om, part);
 	else if(rd == 3 && d0 == 3 && d1 == 3) hipLaunchKernelGGL((edge_maxdiag_kernel<3, 3, 3>), g, b, 0, ctx->stream, ne, d_J0, d_J1, d_Om, part);
 	else if(rd == 6 && d0 == 6 && d1 == 6) hipLaunchKernelGGL((edge_maxdiag_kernel<6, 6, 6>), g, b, 0, ctx->stream, ne, d_J0, d_J1, d_Om, part);
-	else throw Error(SPP_E_UNSUPPORTED, "max Hessian diagonal: edge group must be (2,6,3), (3,3,3) or (6,6,6)");
+	else if(rd == 3 && d0 == 6 && d1 == 3) hipLaunchKernelGGL((edge_maxdiag_kernel<3, 6, 3>), g, b, 0, ctx->stream, ne, d_J0, d_J1, d_Om, part);
+	else throw Error(SPP_E_UNSUPPORTED, "max Hessian diagonal: edge group must be (2,6,3), (3,3,3), (6,6,6) or (3,6,3)");
 	hipLaunchKernelGGL(max_partials_kernel, dim3(1), dim3(256), 0, ctx->stream, nwg, part, ctx->geom_partial.p);
 	return fetch_scalar(ctx);
 }
@@ -796,6 +808,128 @@ double slam2d_update(spp_ctx *ctx, int64_t n, double *d_state, const double *d_d
 		if(n_angles)
 			hipLaunchKernelGGL(clamp_angles_kernel, dim3((unsigned)((n_angles + 255) / 256)), dim3(256), 0, ctx->stream,
 				n_angles, d_angle_off, d_state);
+	}
+	SPP_HIP_CHECK(hipGetLastError());
+	double h = 0;
+	SPP_HIP_CHECK(hipMemcpyAsync(&h, ctx->geom_partial.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	SPP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+	return h;
+}
+
+// --------------------------------------------------------------------------------------------------
+// 3D landmark SLAM: 6-wide poses [t | axis-angle] and 3-wide landmarks in ONE flat state laid out like eta (in 3D, too,
+// state and increment have the same layout), vertices addressed by their scalar offset. Reference (functional spec):
+//   C3DJacobians::Absolute_to_Relative_Landmark   e = R(a)^T (l - t)       include/slam/3DSolverBase.h:1528-1539
+//   its Jacobians: forward differences (delta = 1e-9) over pose (+) d = Relative_to_Absolute(pose, d) (:807-850: t' = t +
+//   R dt, R' = R exp(dr)) and over an additive landmark increment        :1602-1637
+//   CEdgePoseLandmark3D::Calculate_Jacobians_Expectation_Error  r = z - e, nothing wrapped   include/slam/SE3_Types.h:568-586
+//   CVertexLandmark3D::Operator_Plus (plain sum)                          SE3_Types.h:110-113
+// Here analytic: e(t + R dt, R exp(dr)) = exp(dr)^T (e - dt) = e - dt - dr x e + O(d^2), so
+//   d e / d dt = -I,  d e / d dr = [e]x,  d e / d l = R^T.
+// One thread per observation: 6 + 3 gathered doubles, 24 B measurement, 16 B offsets in; 240 B out (J0 3 x 6, J1 3 x 3
+// column-major, r 3); a wave's stores fill whole cache lines of the three outputs.
+// --------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256)
+void se3_linearize_at_kernel(int64_t ne, const int64_t *__restrict__ off0, const int64_t *__restrict__ off1,
+	const double *__restrict__ state, const double *__restrict__ meas, double *__restrict__ J0,
+	double *__restrict__ J1, double *__restrict__ r)
+{
+	const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if(e >= ne)
+		return;
+	se3_linearize_edge(e, state + off0[e], state + off1[e], meas, J0, J1, r);
+}
+
+__global__ __launch_bounds__(256)
+void se3_xyz_linearize_kernel(int64_t ne, const int64_t *__restrict__ pose_off, const int64_t *__restrict__ lm_off,
+	const double *__restrict__ state, const double *__restrict__ meas, double *__restrict__ J0,
+	double *__restrict__ J1, double *__restrict__ r)
+{
+	const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if(e >= ne)
+		return;
+	const double *p = state + pose_off[e], *l = state + lm_off[e], *z = meas + 3 * e;
+	double R[9];
+	axis_angle_to_rot(p + 3, R);
+	const double d0 = l[0] - p[0], d1 = l[1] - p[1], d2 = l[2] - p[2];
+	const double e0 = R[0] * d0 + R[3] * d1 + R[6] * d2, e1 = R[1] * d0 + R[4] * d1 + R[7] * d2,
+		e2 = R[2] * d0 + R[5] * d1 + R[8] * d2; // R^T (l - t)
+	double *ro = r + 3 * e;
+	ro[0] = z[0] - e0; ro[1] = z[1] - e1; ro[2] = z[2] - e2;
+	double *a = J0 + 18 * e; // [ -I | [e]x ], element (row, col) at row + 3 col
+	a[0] = -1; a[1] = 0;  a[2] = 0;
+	a[3] = 0;  a[4] = -1; a[5] = 0;
+	a[6] = 0;  a[7] = 0;  a[8] = -1;
+	a[9] = 0;    a[10] = e2;  a[11] = -e1;
+	a[12] = -e2; a[13] = 0;   a[14] = e0;
+	a[15] = e1;  a[16] = -e0; a[17] = 0;
+	double *b = J1 + 9 * e; // R^T column-major = R row-major
+#pragma unroll
+	for(int q = 0; q < 9; ++ q)
+		b[q] = R[q];
+}
+
+// the listed poses' new values into tmp (6 each), from the state BEFORE the plain sum below touches it
+__global__ __launch_bounds__(256)
+void slam3d_pose_plus_kernel(int64_t np, const int64_t *__restrict__ pose_off, const double *__restrict__ x,
+	const double *__restrict__ dx, double *__restrict__ tmp)
+{
+	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if(i >= np)
+		return;
+	se3_plus(x + pose_off[i], dx + pose_off[i], tmp + 6 * i);
+}
+
+__global__ __launch_bounds__(256)
+void slam3d_pose_store_kernel(int64_t np, const int64_t *__restrict__ pose_off, const double *__restrict__ tmp,
+	double *__restrict__ x)
+{
+	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; // one thread per pose entry
+	if(i < 6 * np)
+		x[pose_off[i / 6] + i % 6] = tmp[i];
+}
+
+void se3_linearize_at(spp_ctx *ctx, int64_t ne, const int64_t *d_off0, const int64_t *d_off1, const double *d_state,
+	const double *d_meas, double *d_J0, double *d_J1, double *d_r)
+{
+	if(!ne)
+		return;
+	hipLaunchKernelGGL(se3_linearize_at_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, ctx->stream,
+		ne, d_off0, d_off1, d_state, d_meas, d_J0, d_J1, d_r);
+	SPP_HIP_CHECK(hipGetLastError());
+}
+
+void se3_xyz_linearize(spp_ctx *ctx, int64_t ne, const int64_t *d_pose_off, const int64_t *d_lm_off, const double *d_state,
+	const double *d_meas, double *d_J0, double *d_J1, double *d_r)
+{
+	if(!ne)
+		return;
+	hipLaunchKernelGGL(se3_xyz_linearize_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, ctx->stream,
+		ne, d_pose_off, d_lm_off, d_state, d_meas, d_J0, d_J1, d_r);
+	SPP_HIP_CHECK(hipGetLastError());
+}
+
+// ||dx||^2 over the flat increment (two-stage sum, as se3_update) and, if apply: the listed poses composed (se3_plus on the
+// old state, parked behind the partial sums), x += dx everywhere -- the landmarks' CVertexLandmark3D::Operator_Plus --, then
+// the composed poses written over their six entries
+double slam3d_update(spp_ctx *ctx, int64_t n, double *d_state, const double *d_dx, int64_t n_poses,
+	const int64_t *d_pose_off, bool apply)
+{
+	if(!n)
+		return 0;
+	const int64_t nwg = (n + 255) / 256;
+	ctx->geom_partial.reserve((size_t)(nwg + 1 + (apply ? 6 * n_poses : 0)));
+	hipLaunchKernelGGL(norm2_partial_kernel, dim3((unsigned)nwg), dim3(256), 0, ctx->stream, n, d_dx, ctx->geom_partial.p + 1);
+	hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, ctx->stream, nwg, ctx->geom_partial.p + 1, ctx->geom_partial.p);
+	if(apply) {
+		double *tmp = ctx->geom_partial.p + 1 + nwg;
+		if(n_poses)
+			hipLaunchKernelGGL(slam3d_pose_plus_kernel, dim3((unsigned)((n_poses + 255) / 256)), dim3(256), 0, ctx->stream,
+				n_poses, d_pose_off, d_state, d_dx, tmp);
+		hipLaunchKernelGGL(axpy1_kernel, dim3((unsigned)nwg), dim3(256), 0, ctx->stream, n, d_state, d_dx);
+		if(n_poses)
+			hipLaunchKernelGGL(slam3d_pose_store_kernel, dim3((unsigned)((6 * n_poses + 255) / 256)), dim3(256), 0, ctx->stream,
+				n_poses, d_pose_off, tmp, d_state);
 	}
 	SPP_HIP_CHECK(hipGetLastError());
 	double h = 0;

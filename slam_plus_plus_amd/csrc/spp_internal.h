@@ -385,6 +385,12 @@ void se2_rb_linearize(spp_ctx *ctx, int64_t ne, const int64_t *d_off0, const int
 	const double *d_meas, double *d_J0, double *d_J1, double *d_r);
 double slam2d_update(spp_ctx *ctx, int64_t n, double *d_state, const double *d_dx, int64_t n_angles,
 	const int64_t *d_angle_off, bool apply);
+void se3_linearize_at(spp_ctx *ctx, int64_t ne, const int64_t *d_off0, const int64_t *d_off1, const double *d_state,
+	const double *d_meas, double *d_J0, double *d_J1, double *d_r);
+void se3_xyz_linearize(spp_ctx *ctx, int64_t ne, const int64_t *d_pose_off, const int64_t *d_lm_off, const double *d_state,
+	const double *d_meas, double *d_J0, double *d_J1, double *d_r);
+double slam3d_update(spp_ctx *ctx, int64_t n, double *d_state, const double *d_dx, int64_t n_poses,
+	const int64_t *d_pose_off, bool apply);
 double edge_chi2(spp_ctx *ctx, int64_t ne, int rd, const double *d_r, const double *d_Om);
 void edge_robust_weights(spp_ctx *ctx, int64_t ne, int rd, int kind, double scale, double param, const double *d_r, double *d_w);
 double edge_hessian_maxdiag(spp_ctx *ctx, int64_t ne, int rd, int d0, int d1, const double *d_J0, const double *d_J1,

@@ -385,8 +385,16 @@ def problem_from_graph(path):
     """Graph file -> hot-path inputs (synth.Problem) at the file's initial estimate, plus a short description.
     2D / 3D pose graphs without VERTEX lines are initialized the way the reference's parse loop does it
     (CEdgePose2D / CEdgePose3D constructors: an unseen second vertex becomes first (+) measurement, in file order);
-    BA files use the reference's VERTEX_CAM convention (camera-to-world in the file)."""
+    BA files use the reference's VERTEX_CAM convention (camera-to-world in the file). A file with LANDMARK3:XYZ /
+    EDGE_SE3_XYZ lines goes to load_slam3d_graph and comes back as the PAIR of its edge groups (slam3d_linearize)."""
     from scipy.spatial.transform import Rotation
+    with open(path) as f:
+        has_lm3 = any(ln.split()[0].upper() in _LM3_XYZ_EDGE for ln in f if ln.split())
+    if has_lm3:  # 3D poses + landmarks: TWO edge groups over the same vertices (nonlinear.CSlam3D solves such a graph)
+        s = load_slam3d_graph(path)
+        groups = slam3d_linearize(s["dim"], s["state"], s["odo"], s["odo_info"], s["obs"], s["obs_info"])
+        return groups, "3D landmark SLAM graph file (%d poses, %d landmarks, %d odometry edges, %d observations)" % (
+            int((s["dim"] == 6).sum()), int((s["dim"] == 3).sum()), s["odo"].shape[0], s["obs"].shape[0])
     g = load_graph(path)
     if g["projections"].size:
         cams_f, pts_f, proj = g["cams"], g["points"], g["projections"]
@@ -630,3 +638,156 @@ def slam2d_linearize(dim, state, odo, odo_info, obs, obs_info, unary_vertex=0):
                     J1=np.ascontiguousarray(H1.transpose(0, 2, 1)).reshape(k, 4),
                     Om=np.asarray(obs_info, dtype=np.float64).reshape(k, 4), r=ro, unary_vertex=unary_vertex, damping=0.0)
     return g_odo, g_obs
+
+
+# --------------------------------------------------------------------------------------------------
+# 3D landmark SLAM: poses (6, [t | axis-angle]) + point landmarks (3), odometry + XYZ observations
+# --------------------------------------------------------------------------------------------------
+_LM3_XYZ_EDGE = {"LANDMARK3:XYZ", "EDGE_SE3_XYZ"}   # ParsePrimitives.h:639-640
+
+
+def slam3d_offsets(dim):
+    return slam2d_offsets(dim)
+
+
+def _rpy_to_rotvec(rpy):
+    """the parser's conversion of roll pitch yaw (ParsePrimitives.h:504-519): Q = Rz Ry Rx"""
+    from scipy.spatial.transform import Rotation
+    return Rotation.from_euler("ZYX", [rpy[2], rpy[1], rpy[0]]).as_rotvec()
+
+
+def load_slam3d_graph(path):
+    """A 3D landmark SLAM graph as the reference's parser and edge constructors would build it, line by line. Returns
+      dim (nv,) 6 for a pose / 3 for a landmark, state (flat, laid out by dim), vertex ids 0 .. nv - 1,
+      odo (m, 8) i j t (3) axis-angle (3) + odo_info (m, 6, 6) + odo_seq (m,) position among all edges of the file,
+      obs (k, 5) pose landmark x y z + obs_info (k, 3, 3) + obs_seq (k,).
+    Tokens: the pose edges and VERTEX3 lines of load_graph (roll-pitch-yaw converted unless the token ends in :AXISANGLE)
+    and LANDMARK3:XYZ / EDGE_SE3_XYZ: two ids, x y z, the 6 upper-triangular values of the information row by row
+    (ParsePrimitives.h:629-680). The first id is the pose (CEdgePoseLandmark3D swaps nothing). A vertex an edge meets
+    first is initialised from it: a pose by composing the odometry (the null vertex for the very first), a landmark at
+    t + R z of the observing pose (CRelative_to_Absolute_XYZ_Initializer, SE3_Types.h:449-478)."""
+    from scipy.spatial.transform import Rotation
+    state, dimof = {}, {}
+    odo, odo_info, odo_seq, obs, obs_info, obs_seq = [], [], [], [], [], []
+    n_edges = 0
+    with open(path) as f:
+        for ln in f:
+            t = ln.split()
+            if not t or t[0].startswith("#") or t[0].startswith("%"):
+                continue
+            tok, a = t[0].upper(), t[1:]
+            if tok in _SE3_VERTEX and len(a) >= 7:
+                v = [float(x) for x in a[:7]]
+                state[int(v[0])], dimof[int(v[0])] = np.concatenate([v[1:4], _rpy_to_rotvec(v[4:7])]), 6
+            elif tok in _SE3_EDGE and len(a) >= 29:
+                i, j = int(a[0]), int(a[1])
+                z = np.array([float(x) for x in a[2:8]])
+                if not tok.endswith(":AXISANGLE"):
+                    z[3:] = _rpy_to_rotvec(z[3:])
+                if i not in state:
+                    state[i], dimof[i] = np.zeros(6), 6           # CInitializeNullVertex
+                if j not in state:
+                    state[j], dimof[j] = se3_plus(state[i][None, :], z[None, :])[0], 6
+                odo.append([i, j, *z])
+                odo_info.append(_upper_to_full([float(x) for x in a[8:29]], 6))
+                odo_seq.append(n_edges)
+                n_edges += 1
+            elif tok in _LM3_XYZ_EDGE and len(a) >= 11:
+                i, j = int(a[0]), int(a[1])
+                z = np.array([float(x) for x in a[2:5]])
+                if i not in state:
+                    state[i], dimof[i] = np.zeros(6), 6
+                if j not in state:
+                    state[j], dimof[j] = state[i][:3] + Rotation.from_rotvec(state[i][3:]).apply(z), 3
+                obs.append([i, j, *z])
+                obs_info.append(_upper_to_full([float(x) for x in a[5:11]], 3))
+                obs_seq.append(n_edges)
+                n_edges += 1
+    nv = max(state) + 1 if state else 0
+    if sorted(state) != list(range(nv)):
+        raise ValueError("vertex ids are not 0 .. n-1: %s" % path)
+    for grp, col, d in ((odo, 0, 6), (odo, 1, 6), (obs, 0, 6), (obs, 1, 3)):
+        if any(dimof[int(e[col])] != d for e in grp):
+            raise ValueError("an edge joins vertices of the wrong widths: %s" % path)
+    dim = np.array([dimof[v] for v in range(nv)], dtype=np.int32)
+    return dict(dim=dim, state=np.concatenate([state[v] for v in range(nv)]) if nv else np.zeros(0),
+                odo=np.array(odo).reshape(-1, 8), odo_info=np.array(odo_info).reshape(-1, 6, 6),
+                odo_seq=np.array(odo_seq, dtype=np.int64), obs=np.array(obs).reshape(-1, 5),
+                obs_info=np.array(obs_info).reshape(-1, 3, 3), obs_seq=np.array(obs_seq, dtype=np.int64))
+
+
+def slam3d_lines(odo, odo_info, obs, obs_info, odo_seq=None, obs_seq=None, ids=None):
+    """EDGE3:AXISANGLE and EDGE_SE3_XYZ lines in the global edge order, everything with %.17g; ids: vertex id -> id written"""
+    m, k = len(odo), len(obs)
+    odo_seq = np.arange(m) if odo_seq is None else np.asarray(odo_seq)
+    obs_seq = m + np.arange(k) if obs_seq is None else np.asarray(obs_seq)
+    name = (lambda v: int(v)) if ids is None else (lambda v: ids[int(v)])
+    lines = [None] * (m + k)
+    for tok, d, edges, infos, seq in (("EDGE3:AXISANGLE", 6, odo, odo_info, odo_seq), ("EDGE_SE3_XYZ", 3, obs, obs_info, obs_seq)):
+        iu = np.triu_indices(d)
+        for e, mat, q in zip(edges, infos, seq):
+            lines[q] = "%s %d %d " % (tok, name(e[0]), name(e[1])) + " ".join("%.17g" % x for x in e[2:2 + d]) + " " + \
+                " ".join("%.17g" % x for x in np.asarray(mat)[iu])
+    return lines
+
+
+def save_slam3d_graph(path, dim, state, odo, odo_info, obs, obs_info, odo_seq=None, obs_seq=None):
+    """EDGE3:AXISANGLE and EDGE_SE3_XYZ lines in the global edge order. No vertex lines: VERTEX3 holds roll-pitch-yaw,
+    which would not bring an axis-angle back bit for bit, and landmarks have no vertex token here; the reader composes
+    the poses from the odometry and puts every landmark where its first observation sees it (dim and state only say
+    which graph this is)."""
+    with open(path, "w") as f:
+        f.write("\n".join(slam3d_lines(odo, odo_info, obs, obs_info, odo_seq, obs_seq)) + "\n")
+
+
+def slam3d_expectation(pose, lm):
+    """C3DJacobians::Absolute_to_Relative_Landmark (3DSolverBase.h:1528-1539): R(a)^T (l - t); pose (k, 6), lm (k, 3)"""
+    from scipy.spatial.transform import Rotation
+    return Rotation.from_rotvec(pose[:, 3:]).inv().apply(lm - pose[:, :3])
+
+
+def slam3d_linearize(dim, state, odo, odo_info, obs, obs_info, unary_vertex=0):
+    """The two edge groups of a 3D landmark SLAM graph at `state` (flat, laid out by dim), as synth.Problems over the
+    SAME vertices: odometry (6, 6, 6) -- se3_linearize above, CEdgePose3D -- and XYZ observations (6, 3, 3):
+    expectation e = R(a)^T (l - t), r = z - e without any wrapping (CEdgePoseLandmark3D, SE3_Types.h:568-586), Jacobians
+    w.r.t. the pose increment of Relative_to_Absolute (t' = t + R dt, R' = R exp(dr), 3DSolverBase.h:807-850) and w.r.t.
+    the landmark: e(t + R dt, R exp(dr)) = exp(dr)^T (e - dt), hence d e / d pose = [-I | [e]x], d e / d l = R^T --
+    analytic where the reference takes forward differences with delta = 1e-9 (:1602-1637)."""
+    from scipy.spatial.transform import Rotation
+    from .synth import Problem
+    dim = np.asarray(dim, dtype=np.int32)
+    x = np.asarray(state, dtype=np.float64)
+    base = slam3d_offsets(dim)
+    odo = np.asarray(odo, dtype=np.float64).reshape(-1, 8)
+    obs = np.asarray(obs, dtype=np.float64).reshape(-1, 5)
+    # odometry: se3_linearize over an array with a row per vertex (landmark rows are never addressed)
+    pose_v = np.flatnonzero(dim == 6)
+    rows = np.zeros((dim.size, 6))
+    rows[pose_v] = x[base[pose_v][:, None] + np.arange(6)]
+    g_odo = se3_linearize(rows, odo, np.asarray(odo_info, dtype=np.float64).reshape(-1, 6, 6))
+    g_odo["name"], g_odo["dim"], g_odo["unary_vertex"] = "slam3d_odometry", dim, unary_vertex
+    # observations
+    vp, vl = obs[:, 0].astype(np.int64), obs[:, 1].astype(np.int64)
+    k = vp.size
+    p = x[base[vp][:, None] + np.arange(6)]
+    l = x[base[vl][:, None] + np.arange(3)]
+    e = slam3d_expectation(p, l)
+    H0 = np.concatenate([np.tile(-np.eye(3), (k, 1, 1)), _hat(e)], axis=2)
+    H1 = Rotation.from_rotvec(p[:, 3:]).as_matrix().transpose(0, 2, 1)
+    g_obs = Problem(name="slam3d_observations", dim=dim, v0=vp, v1=vl, d0=6, d1=3, rd=3,
+                    J0=np.ascontiguousarray(H0.transpose(0, 2, 1)).reshape(k, 18),
+                    J1=np.ascontiguousarray(H1.transpose(0, 2, 1)).reshape(k, 9),
+                    Om=np.asarray(obs_info, dtype=np.float64).reshape(k, 9), r=obs[:, 2:5] - e, unary_vertex=unary_vertex,
+                    damping=0.0)
+    return g_odo, g_obs
+
+
+def slam3d_plus(dim, state, dx):
+    """x (+) dx over the flat state: poses by se3_plus (CVertexPose3D::Operator_Plus), landmarks by the plain sum
+    (CVertexLandmark3D::Operator_Plus, SE3_Types.h:110-113)"""
+    dim = np.asarray(dim)
+    base = slam3d_offsets(dim)
+    out = state + dx
+    idx = base[:-1][dim == 6][:, None] + np.arange(6)
+    out[idx] = se3_plus(state[idx], dx[idx])
+    return out

@@ -17,7 +17,8 @@ import math
 import numpy as np
 
 from . import api
-from .formats import se2_linearize, se3_linearize, se3_plus, ba_linearize, slam2d_linearize, slam2d_offsets
+from .formats import (se2_linearize, se3_linearize, se3_plus, ba_linearize, slam2d_linearize, slam2d_offsets,
+                      slam3d_linearize, slam3d_offsets, slam3d_plus)
 
 
 class CPoseGraph2D:
@@ -103,8 +104,47 @@ class CSlam2D:
         return float(sum(np.einsum("ei,eij,ej->", g.r, g.Om.reshape(-1, g.rd, g.rd), g.r) for g in self.linearize()))
 
 
+class CSlam3D:
+    """3D landmark SLAM 'system': 6-wide poses [t | axis-angle] and 3-wide landmarks in one flat state laid out by `dim`
+    (the layout of eta: the increment of a pose has 6 entries, too), odometry edges odo (m, 8) i j t axis-angle +
+    odo_info (m, 6, 6) (CEdgePose3D) and observations obs (k, 5) pose landmark x y z + obs_info (k, 3, 3)
+    (CEdgePoseLandmark3D). odo_seq / obs_seq: position of every edge in the graph's edge order (default: odometry, then
+    observations)."""
+
+    def __init__(self, dim, state, odo, odo_info, obs, obs_info, odo_seq=None, obs_seq=None, unary_vertex=0):
+        self.dim = np.asarray(dim, dtype=np.int32)
+        self.state = np.array(state, dtype=np.float64)
+        self.odo, self.odo_info = np.asarray(odo, dtype=np.float64), np.asarray(odo_info, dtype=np.float64)
+        self.obs, self.obs_info = np.asarray(obs, dtype=np.float64), np.asarray(obs_info, dtype=np.float64)
+        m, k = self.odo.shape[0], self.obs.shape[0]
+        self.odo_seq = np.arange(m, dtype=np.int64) if odo_seq is None else np.asarray(odo_seq, dtype=np.int64)
+        self.obs_seq = m + np.arange(k, dtype=np.int64) if obs_seq is None else np.asarray(obs_seq, dtype=np.int64)
+        self.unary_vertex = unary_vertex
+        self.base = slam3d_offsets(self.dim)
+        self.pose_off = self.base[:-1][self.dim == 6]
+
+    @classmethod
+    def from_problem(cls, p):
+        """from synth.slam3d_problem or formats.load_slam3d_graph"""
+        return cls(p["dim"], p["state"], p["odo"], p["odo_info"], p["obs"], p["obs_info"], p.get("odo_seq"), p.get("obs_seq"),
+                   p.get("unary_vertex", 0))
+
+    def linearize(self):
+        """the two edge groups (odometry, observations) as synth.Problems over the same vertices"""
+        return slam3d_linearize(self.dim, self.state, self.odo, self.odo_info, self.obs, self.obs_info, self.unary_vertex)
+
+    def groups(self):
+        return [(self.odo[:, 0], self.odo[:, 1], 6, 6, 6), (self.obs[:, 0], self.obs[:, 1], 6, 3, 3)]
+
+    def plus(self, dx):
+        self.state = slam3d_plus(self.dim, self.state, dx)  # poses composed, landmarks added (SE3_Types.h:44-47, :110-113)
+
+    def chi2(self):
+        return float(sum(np.einsum("ei,eij,ej->", g.r, g.Om.reshape(-1, g.rd, g.rd), g.r) for g in self.linearize()))
+
+
 class _DeviceGroupsPath:
-    """Jacobians on the host, multi-group device assembly + device solve (host_jacobians=True for CSlam2D)"""
+    """Jacobians on the host, multi-group device assembly + device solve (host_jacobians=True for CSlam2D / CSlam3D)"""
 
     def __init__(self, device=0, seq=None):
         self.ctx = api.Context(device)
@@ -186,6 +226,68 @@ class _ResidentSlam2DPath:
 
     def apply(self):
         self.ctx.slam2d_update_device(self.n, self.d_state.ptr, self.d_eta.ptr, self.n_angle, self.d_angle.ptr, apply=True)
+
+    def finish(self, system):
+        system.state[:] = self.d_state.download()
+
+    def close(self):
+        self.ctx.close()
+
+
+class _ResidentSlam3DPath:
+    """the whole Gauss-Newton iteration of a CSlam3D in HBM, as _ResidentSlam2DPath: spp_se3_linearize_at_device,
+    spp_se3_xyz_linearize_device, spp_assemble_groups_device over the groups (6,6,6) and (6,3,3), analyze once,
+    spp_factor_solve_device, spp_slam3d_update_device. Host traffic: the 8-byte norm per update call, two per applied
+    iteration."""
+
+    def __init__(self, device=0):
+        self.ctx = api.Context(device)
+
+    def begin(self, system):
+        ctx, s = self.ctx, system
+        up = lambda a: api.DeviceArray.from_host(ctx, np.ascontiguousarray(a).ravel())
+        self.m, self.k, self.n = s.odo.shape[0], s.obs.shape[0], s.state.size
+        self.st = ctx.assemble_analyze_groups(s.dim, s.groups(), [s.odo_seq, s.obs_seq], s.unary_vertex)
+        off = lambda col: up(s.base[col.astype(np.int64)])
+        self.d_off = [off(s.odo[:, 0]), off(s.odo[:, 1]), off(s.obs[:, 0]), off(s.obs[:, 1])]
+        self.d_meas = [up(s.odo[:, 2:8]), up(s.obs[:, 2:5])]
+        self.d_Om = [up(s.odo_info), up(s.obs_info)]
+        self.d_state, self.d_pose = up(s.state), up(s.pose_off.astype(np.int64))
+        self.n_pose = s.pose_off.size
+        self.d_J0 = [api.DeviceArray(ctx, 36 * self.m), api.DeviceArray(ctx, 18 * self.k)]
+        self.d_J1 = [api.DeviceArray(ctx, 36 * self.m), api.DeviceArray(ctx, 9 * self.k)]
+        self.d_r = [api.DeviceArray(ctx, 6 * self.m), api.DeviceArray(ctx, 3 * self.k)]
+        self.d_vals, self.d_eta = api.DeviceArray(ctx, self.st.nvals), api.DeviceArray(ctx, self.st.n)
+        self.analyzed = False
+
+    def linearize(self):
+        ctx = self.ctx
+        ctx.se3_linearize_at_device(self.m, self.d_off[0].ptr, self.d_off[1].ptr, self.d_state.ptr, self.d_meas[0].ptr,
+                                    self.d_J0[0].ptr, self.d_J1[0].ptr, self.d_r[0].ptr)
+        ctx.se3_xyz_linearize_device(self.k, self.d_off[2].ptr, self.d_off[3].ptr, self.d_state.ptr, self.d_meas[1].ptr,
+                                     self.d_J0[1].ptr, self.d_J1[1].ptr, self.d_r[1].ptr)
+
+    def chi2(self):
+        """error at the current state: the sum over the groups (re-linearizes)"""
+        self.linearize()
+        return (self.ctx.edge_chi2_device(self.m, 6, self.d_r[0].ptr, self.d_Om[0].ptr) +
+                self.ctx.edge_chi2_device(self.k, 3, self.d_r[1].ptr, self.d_Om[1].ptr))
+
+    def step(self):
+        ctx = self.ctx
+        self.linearize()
+        ptrs = lambda arrs: [a.ptr for a in arrs]
+        ctx.assemble_groups_device(ptrs(self.d_J0), ptrs(self.d_J1), ptrs(self.d_Om), ptrs(self.d_r), 0.0,
+                                   self.d_vals.ptr, self.d_eta.ptr)
+        if not self.analyzed:
+            ctx.analyze(self.st, api.MODE_AUTO)
+            self.analyzed = True
+        if ctx.factor_solve_device(self.d_vals.ptr, self.d_eta.ptr) != 0:
+            return False, 0.0
+        return True, ctx.slam3d_update_device(self.n, self.d_state.ptr, self.d_eta.ptr, self.n_pose, self.d_pose.ptr, apply=False)
+
+    def apply(self):
+        self.ctx.slam3d_update_device(self.n, self.d_state.ptr, self.d_eta.ptr, self.n_pose, self.d_pose.ptr, apply=True)
 
     def finish(self, system):
         system.state[:] = self.d_state.download()
@@ -278,9 +380,9 @@ class CNonlinearSolver_Lambda:
     def __init__(self, system, path=None, device=0, verbose=False, host_jacobians=False):
         self.system = system
         if path is None:  # the product paths need the GPU; host_jacobians keeps the linearization in numpy
-            if isinstance(system, CSlam2D):
-                path = (_DeviceGroupsPath(device, [system.odo_seq, system.obs_seq]) if host_jacobians
-                        else _ResidentSlam2DPath(device))
+            if isinstance(system, (CSlam2D, CSlam3D)):
+                resident = _ResidentSlam2DPath if isinstance(system, CSlam2D) else _ResidentSlam3DPath
+                path = _DeviceGroupsPath(device, [system.odo_seq, system.obs_seq]) if host_jacobians else resident(device)
             else:
                 path = _DevicePath(device) if host_jacobians else _ResidentPath(device)
         self.path = path

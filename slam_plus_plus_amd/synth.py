@@ -380,6 +380,118 @@ def slam2d_problem(n_poses=60, n_lm=90, seed=68, interleave=False, name="slam2d"
                    obs_seq=seq[oi.size:].copy(), truth=dict(poses=P, landmarks=Lm))
 
 
+def slam3d_problem(n_poses=40, n_lm=60, seed=71, interleave=False, name="slam3d", views=(2, 5), window=5, hubs=0):
+    """3D landmark SLAM: a trajectory along a helix with noisy odometry (CEdgePose3D) and n_poses // 5 loop closures,
+    landmarks each seen from views[0] .. views[1] nearby poses as noisy XYZ points in the pose's frame
+    (CEdgePoseLandmark3D) -- two edge groups, (6, 6, 6) and (6, 3, 3), over the same vertices. The measurements come from a
+    ground truth, the initial estimate is what a reader of the edge list builds: dead reckoning along the odometry, every
+    landmark where its first observation sees it (t + R z). interleave=True shuffles the vertex ids (vertex 0 stays the
+    first pose, which carries the unary factor), so that landmarks sit between the poses and about half of the
+    pose-landmark blocks are stored transposed. hubs > 0: landmark 0 is seen from `hubs` poses more and the middle pose
+    sees `hubs` landmarks more (vertices of both widths with a degree the sequential assembly kernel leaves to the wave
+    kernel). The edges are in the order of an incremental run: each when its later pose arrives.
+    Returns Problem(dim, state (flat, laid out by dim), odo (m, 8) i j t axis-angle, odo_info, odo_seq, obs (k, 5) pose
+    landmark x y z, obs_info, obs_seq, pose_id, lm_id, truth, unary_vertex)."""
+    from scipy.spatial.transform import Rotation
+    from .formats import se3_plus
+    rng = np.random.default_rng(seed)
+    nv = n_poses + n_lm
+    if interleave:
+        ids = 1 + rng.permutation(nv - 1)
+        pose_id, lm_id = np.concatenate([[0], ids[:n_poses - 1]]), ids[n_poses - 1:]
+    else:
+        pose_id, lm_id = np.arange(n_poses), n_poses + np.arange(n_lm)
+    # ground truth: a helix of radius 5 rising 0.15 per step, flown without turning into the curve: the attitude only
+    # wobbles by about 0.1 rad, so that the rotation between ANY two poses stays small. (CEdgePose3D pairs the Jacobian of
+    # the expectation with the error log(R(z) R(e)^T), SE3_Types.h:264-286, which is the error's own Jacobian only up to
+    # the rotation between the two poses; with loop closures across a quarter turn of a turning trajectory Gauss-Newton
+    # on that linearization does not settle.) Pose 0 is the origin (the reader starts the first vertex there)
+    a = 0.25 * np.arange(n_poses)
+    pos = np.stack([5 * np.cos(a) - 5, 5 * np.sin(a), 0.15 * np.arange(n_poses)], axis=1)
+    Rw = Rotation.from_euler("ZYX", np.stack([0.12 * np.sin(0.6 * a), 0.08 * np.sin(0.4 * a + 1), 0.05 * np.sin(0.8 * a)], axis=1))
+    R0i = Rw[0].inv()
+    pos, Rw = R0i.apply(pos - pos[0]), R0i * Rw
+    P = np.concatenate([pos, Rw.as_rotvec()], axis=1)
+
+    def rel(i, j):  # pose j in the frame of pose i
+        Ri = Rw[i].inv()
+        return np.concatenate([Ri.apply(pos[j] - pos[i]), (Ri * Rw[j]).as_rotvec()], axis=1)
+
+    oi = np.arange(n_poses - 1)
+    oj = oi + 1
+    lc = np.sort(np.stack([rng.choice(n_poses, size=2, replace=False) for _ in range(n_poses // 5)]), axis=1)
+    oi, oj = np.concatenate([oi, lc[:, 0]]), np.concatenate([oj, lc[:, 1]])
+    # odometry along the chain, loop closures from a ten times finer sensor: dead reckoning misses the closures by many
+    # of their sigmas while staying inside Gauss-Newton's basin
+    chain = (np.arange(oi.size) < n_poses - 1)[:, None]
+    sig = np.where(chain, np.array([0.02] * 3 + [0.004] * 3), np.array([0.002] * 3 + [0.0004] * 3))
+    z_odo = rel(oi, oj)
+    z_odo[:, :3] += rng.normal(0, 1, size=(oi.size, 3)) * sig[:, :3]
+    z_odo[:, 3:] = (Rotation.from_rotvec(z_odo[:, 3:]) * Rotation.from_rotvec(rng.normal(0, 1, size=(oi.size, 3)) * sig[:, 3:])).as_rotvec()
+    odo_info = np.zeros((oi.size, 6, 6))
+    odo_info[:, np.arange(6), np.arange(6)] = 1.0 / sig ** 2
+    # landmarks: 2 .. 5 m off a centre pose, seen from a few poses around it
+    centre = rng.integers(0, n_poses, size=n_lm)
+    off = rng.normal(size=(n_lm, 3))
+    Lm = pos[centre] + off / np.linalg.norm(off, axis=1, keepdims=True) * rng.uniform(2.0, 5.0, size=(n_lm, 1))
+    po, lo = [], []
+    for l in range(n_lm):
+        seen = np.unique(np.clip(centre[l] + rng.integers(-window, window + 1, size=rng.integers(views[0], views[1] + 1)), 0, n_poses - 1))
+        if seen.size < 2:
+            seen = np.unique(np.clip([centre[l] - 1, centre[l], centre[l] + 1], 0, n_poses - 1))[:2]
+        po.append(seen)
+        lo.append(np.full(seen.size, l))
+    if hubs:
+        extra = np.setdiff1d(np.arange(n_poses), po[0])[:hubs]            # landmark 0: `hubs` more poses
+        po.append(extra)
+        lo.append(np.zeros(extra.size, dtype=np.int64))
+        mid = n_poses // 2
+        more = np.array([l for l in range(1, n_lm) if mid not in po[l]][:hubs])   # pose mid: `hubs` more landmarks
+        po.append(np.full(more.size, mid))
+        lo.append(more)
+    po, lo = np.concatenate(po).astype(np.int64), np.concatenate(lo).astype(np.int64)
+    sig_obs = np.array([0.02, 0.03, 0.05])
+    z_obs = Rw[po].inv().apply(Lm[lo] - pos[po]) + rng.normal(0, 1, size=(po.size, 3)) * sig_obs
+    obs_info = np.tile(np.diag(1.0 / sig_obs ** 2), (po.size, 1, 1))
+    # global edge order: by the later pose of the edge, odometry before the observations made there
+    t_all = np.concatenate([np.maximum(oi, oj), po])
+    order = np.argsort(t_all, kind="stable")
+    seq = np.empty(order.size, dtype=np.int64)
+    seq[order] = np.arange(order.size)
+    # initial estimate: dead reckoning, landmarks from their first observation (in the global order)
+    est = np.zeros((n_poses, 6))
+    for i in range(n_poses - 1):
+        est[i + 1] = se3_plus(est[i:i + 1], z_odo[i:i + 1])[0]
+    first = np.full(n_lm, -1)
+    for k in np.argsort(seq[oi.size:], kind="stable"):
+        if first[lo[k]] < 0:
+            first[lo[k]] = k
+    lm_est = np.stack([est[po[k], :3] + Rotation.from_rotvec(est[po[k], 3:]).apply(z_obs[k]) for k in first])
+    dim = np.empty(nv, dtype=np.int32)
+    dim[pose_id], dim[lm_id] = 6, 3
+    base = np.zeros(nv + 1, dtype=np.int64)
+    np.cumsum(dim, out=base[1:])
+    state = np.empty(base[-1])
+    state[base[pose_id][:, None] + np.arange(6)] = est
+    state[base[lm_id][:, None] + np.arange(3)] = lm_est
+    f = lambda a: a.astype(np.float64)
+    return Problem(name=name, dim=dim, state=state, unary_vertex=0, pose_id=pose_id, lm_id=lm_id,
+                   odo=np.concatenate([f(pose_id[oi])[:, None], f(pose_id[oj])[:, None], z_odo], axis=1), odo_info=odo_info,
+                   odo_seq=seq[:oi.size].copy(),
+                   obs=np.concatenate([f(pose_id[po])[:, None], f(lm_id[lo])[:, None], z_obs], axis=1), obs_info=obs_info,
+                   obs_seq=seq[oi.size:].copy(), truth=dict(poses=P, landmarks=Lm))
+
+
+def landmark3d_problem(n_poses=40, n_lm=60, seed=72, name="lm3d_small"):
+    """the (6, 3, 3) observations of a slam3d_problem alone, linearized at its initial estimate, as ONE homogeneous edge
+    group for the one-group entry points (damped: without the odometry only the observations hold the poses)"""
+    from .formats import slam3d_linearize
+    p = slam3d_problem(n_poses, n_lm, seed, name=name)
+    g = slam3d_linearize(p.dim, p.state, p.odo, p.odo_info, p.obs, p.obs_info)[1]
+    g["name"], g["damping"] = name, 1e-2
+    return g
+
+
 def pose_graph_states(prob):
     """The same pose graph as states + measurements in the REFERENCE's parameterization, as input of
     spp_se2_/se3_linearize_device: poses (n, 3) x y theta or (n, 6) [t | axis-angle] at the noisy estimate,
@@ -418,6 +530,9 @@ CONFIGS = {
     "lm2d_interleaved": lambda: landmark2d_problem(60, 150, 33, interleave=True, name="lm2d_interleaved"),
     "slam2d_small": lambda: slam2d_problem(60, 90, 68, name="slam2d_small"),
     "slam2d_interleaved": lambda: slam2d_problem(150, 300, 62, interleave=True, name="slam2d_interleaved"),
+    "slam3d_small": lambda: slam3d_problem(40, 60, 71, name="slam3d_small"),
+    "slam3d_interleaved": lambda: slam3d_problem(150, 300, 73, interleave=True, name="slam3d_interleaved", hubs=26),
+    "lm3d_small": lambda: landmark3d_problem(40, 60, 72),
     "se2_small": lambda: se2_problem(300, 150, 12, name="se2_small"),
     "se3_small": lambda: se3_problem(8, 12, 13, name="se3_small"),
 }
