@@ -316,6 +316,24 @@ int spp_ba_update_device(spp_ctx *ctx, int64_t n_cams, double *d_cams, const int
 	int64_t n_points, double *d_points, const int64_t *d_pt_dxoff, const double *d_dx, int64_t n_dx, int apply,
 	double *h_dx_norm2);
 
+/* ---- on-device geometry of stereo bundle adjustment (CEdgeP2SC3D, include/slam/BA_Types.h:705-811) ----
+ * Cameras: 6 doubles each [t | axis-angle], world -> left camera, and 6 constant intrinsics each (fx fy cx cy d b, b the
+ * baseline: CVertexSCam, BA_Types.h:211-290); points: XYZ; measurements: 3 per observation (u v u_right).
+ * spp_ba_stereo_linearize_device replaces CBAJacobians::Project_P2SC (include/slam/BASolverBase.h:462-537, with Jacobians
+ * :781-841) as CEdgeP2SC3D::Calculate_Jacobians_Expectation_Error calls it: x = R X + t, p = (fx x0/x2 + cx,
+ * fy x1/x2 + cy), k = d / (0.5 (fx + fy)), rho = |p - c|, uv = c + (1 + rho k)(p - c); the right camera sees the point
+ * moved by -b (row 0 of R)^T, i.e. x - b e0 in the camera frame (the form evaluated), through the same projection and
+ * distortion with its own rho; expectation e = (uv0, uv1, uv_right0), r = z - e. Jacobians w.r.t. the camera increment of
+ * C3DJacobians::Relative_to_Absolute (t' = t + R dt, R' = R exp(dr), include/slam/3DSolverBase.h:807-850) and w.r.t. the
+ * point -- analytic, where the reference takes forward differences with delta = 1e-9; the distortion's derivative
+ * (1 + rho k) I + k (p - c)(p - c)^T / rho is evaluated with (p - c) / rho := 0 at rho = 0, so a point on the optical
+ * axis gives finite Jacobians. Output layout = input of spp_assemble_device for the (6,3,3) edge group: J0 no x (3x6)
+ * column-major, J1 no x (3x3), r no x 3. cam_of / pt_of: int32 indices into the camera / point arrays. The vertex update
+ * is spp_ba_update_device (CVertexSCam::Operator_Plus is the same Relative_to_Absolute). */
+int spp_ba_stereo_linearize_device(spp_ctx *ctx, int64_t n_obs, const int32_t *d_cam_of, const int32_t *d_pt_of,
+	const double *d_cams, const double *d_intrinsics, const double *d_points, const double *d_measurements,
+	double *d_J0, double *d_J1, double *d_r);
+
 /* ---- scalars of the Levenberg-Marquardt control (include/slam/NonlinearSolver_Lambda_LM.h) ----------
  * chi2 = sum_e r_e^T Omega_e r_e (f_Error, :1078-1095); the largest diagonal entry of any vertex Hessian
  * J_i^T Omega J_i over all edges (f_InitialDamping multiplies it by tau = 1e-3, :151-199); the denominator

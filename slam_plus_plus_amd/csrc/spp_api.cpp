@@ -892,6 +892,20 @@ int spp_ba_linearize_device(spp_ctx *ctx, int64_t n_obs, const int32_t *d_cam_of
 	SPP_CATCH(ctx)
 }
 
+int spp_ba_stereo_linearize_device(spp_ctx *ctx, int64_t n_obs, const int32_t *d_cam_of, const int32_t *d_pt_of,
+	const double *d_cams, const double *d_intrinsics, const double *d_points, const double *d_measurements,
+	double *d_J0, double *d_J1, double *d_r)
+{
+	if(!ctx || n_obs < 0 || !d_cam_of || !d_pt_of || !d_cams || !d_intrinsics || !d_points || !d_measurements ||
+	   !d_J0 || !d_J1 || !d_r)
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	ba_stereo_linearize(ctx, n_obs, d_cam_of, d_pt_of, d_cams, d_intrinsics, d_points, d_measurements, d_J0, d_J1, d_r);
+	return SPP_OK;
+	SPP_CATCH(ctx)
+}
+
 int spp_ba_update_device(spp_ctx *ctx, int64_t n_cams, double *d_cams, const int64_t *d_cam_dxoff,
 	int64_t n_points, double *d_points, const int64_t *d_pt_dxoff, const double *d_dx, int64_t n_dx, int apply,
 	double *h_dx_norm2)

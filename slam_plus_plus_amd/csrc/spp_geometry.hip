@@ -197,6 +197,80 @@ void ba_linearize_kernel(int64_t no, const int32_t *__restrict__ cam_of, const i
 	}
 }
 
+// --------------------------------------------------------------------------------------------------
+// Stereo bundle adjustment: projection edge CEdgeP2SC3D (include/slam/BA_Types.h:705-811) between a stereo camera
+// CVertexSCam (6D pose [t | axis-angle], world -> LEFT camera, + 6 constant intrinsics fx fy cx cy d b, b the baseline)
+// and a point XYZ. Reference (functional spec):
+//   CBAJacobians::Project_P2SC               include/slam/BASolverBase.h:462-537 (model), :781-841 (Jacobians)
+//     x = R X + t ; q = p - c = (fx x0 / x2, fy x1 / x2) ; k = d / ((fx + fy) / 2) ; rho = |q| ; uv = c + (1 + rho k) q
+//     (the distortion is LINEAR in rho here, where Project_P2C has rho^2); the right camera sees the point moved by
+//     -b (row 0 of R)^T through the same projection and distortion with its own rho; expectation (uv0, uv1, uv_right0).
+//   Since R (row 0 of R)^T = e0, the moved point in the camera frame is x - b e0: THAT form is evaluated here (one
+//   rotation instead of two), and it holds for the incremented camera too (R' R'^T e0 = e0), so the right camera
+//   shares d x / d increment with the left one.
+//   The reference's Jacobians are FORWARD DIFFERENCES (delta = 1e-9) over cam (+) delta = Relative_to_Absolute
+//   (t' = t + R dt, R' = R exp(dr), 3DSolverBase.h:807-850) and over an additive point increment. Here ANALYTIC:
+//     d uv / d q = (1 + rho k) I + k q n^T,  n = q / rho  and  n = 0 at rho = 0, where the term vanishes (|q n^T| = rho):
+//     a point on the optical axis gives finite Jacobians; d q / d x = [fx/x2 0 -fx x0/x2^2; 0 fy/x2 -fy x1/x2^2];
+//     P (3 x 3) = rows 0, 1 of the left chain and row 0 of the right one (at x - b e0);
+//     J_cam = P [ R | -R [X]x ],  J_pt = P R,  r = z - e.
+// One thread per observation: 12 + 3 gathered doubles + 24 B in, 240 B out (J0 3x6, J1 3x3 column-major, r 3):
+// the (6,3,3) group of spp_assemble_device.
+// --------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256)
+void ba_stereo_linearize_kernel(int64_t no, const int32_t *__restrict__ cam_of, const int32_t *__restrict__ pt_of,
+	const double *__restrict__ cams, const double *__restrict__ intr, const double *__restrict__ pts,
+	const double *__restrict__ meas, double *__restrict__ J0, double *__restrict__ J1, double *__restrict__ r)
+{
+	const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if(e >= no)
+		return;
+	const double *cam = cams + 6 * (int64_t)cam_of[e], *in = intr + 6 * (int64_t)cam_of[e], *X = pts + 3 * (int64_t)pt_of[e];
+	double R[9];
+	axis_angle_to_rot(cam + 3, R);
+	const double X0 = X[0], X1 = X[1], X2 = X[2];
+	const double x = R[0] * X0 + R[1] * X1 + R[2] * X2 + cam[0];
+	const double y = R[3] * X0 + R[4] * X1 + R[5] * X2 + cam[1];
+	const double z = R[6] * X0 + R[7] * X1 + R[8] * X2 + cam[2];
+	const double fx = in[0], fy = in[1], k = in[4] / (0.5 * (fx + fy)), xr = x - in[5];
+	const double iz = 1.0 / z, q0 = fx * x * iz, q1 = fy * y * iz, s0 = fx * xr * iz; // left q, right (s0, q1)
+	const double rho = sqrt(q0 * q0 + q1 * q1), rhor = sqrt(s0 * s0 + q1 * q1), g = 1.0 + rho * k, gr = 1.0 + rhor * k;
+	r[3 * e] = meas[3 * e] - (in[2] + g * q0);
+	r[3 * e + 1] = meas[3 * e + 1] - (in[3] + g * q1);
+	r[3 * e + 2] = meas[3 * e + 2] - (in[2] + gr * s0);
+	// unit vectors q / rho, 0 at rho = 0 (|q_i| <= rho: the quotient cannot overflow)
+	const double n0 = (rho > 0) ? q0 / rho : 0.0, n1 = (rho > 0) ? q1 / rho : 0.0;
+	const double m0 = (rhor > 0) ? s0 / rhor : 0.0, m1 = (rhor > 0) ? q1 / rhor : 0.0;
+	const double D00 = g + k * q0 * n0, D01 = k * q0 * n1, D11 = g + k * q1 * n1; // symmetric: q0 n1 = q1 n0
+	const double E0 = gr + k * s0 * m0, E1 = k * s0 * m1;                        // row 0 of the right camera's
+	const double a0 = fx * iz, a2 = -fx * x * iz * iz, b1 = fy * iz, b2 = -fy * y * iz * iz, c2 = -fx * xr * iz * iz;
+	const double P[9] = {D00 * a0, D01 * b1, D00 * a2 + D01 * b2,
+	                     D01 * a0, D11 * b1, D01 * a2 + D11 * b2,
+	                     E0 * a0,  E1 * b1,  E0 * c2 + E1 * b2};
+	double PR[9]; // P R = d e / d dt = d e / d X
+#pragma unroll
+	for(int i = 0; i < 3; ++ i)
+#pragma unroll
+		for(int j = 0; j < 3; ++ j)
+			PR[3 * i + j] = P[3 * i] * R[j] + P[3 * i + 1] * R[3 + j] + P[3 * i + 2] * R[6 + j];
+	double *a = J0 + 18 * e, *b = J1 + 9 * e;
+#pragma unroll
+	for(int j = 0; j < 3; ++ j)
+#pragma unroll
+		for(int i = 0; i < 3; ++ i) {
+			a[3 * j + i] = PR[3 * i + j];
+			b[3 * j + i] = PR[3 * i + j];
+		}
+	// d e / d dr = -PR [X]x, row by row as in ba_linearize_kernel
+#pragma unroll
+	for(int i = 0; i < 3; ++ i) {
+		const double p0 = PR[3 * i], p1 = PR[3 * i + 1], p2 = PR[3 * i + 2];
+		a[9 + i] = -(p1 * X2 - p2 * X1);
+		a[12 + i] = -(p2 * X0 - p0 * X2);
+		a[15 + i] = -(p0 * X1 - p1 * X0);
+	}
+}
+
 // camera (+): t' = t + R dt, R' = R exp(dr) through unit quaternions with w >= 0 (the reference's
 // AxisAngle_to_Quat / Quat_to_AxisAngle, 3DSolverBase.h:477-502,557+); one thread per camera
 __device__ __forceinline__ void aa_to_quat(const double *a, double *q) // q = (w, x, y, z)
@@ -636,6 +710,16 @@ void ba_linearize(spp_ctx *ctx, int64_t no, const int32_t *d_cam_of, const int32
 	if(!no)
 		return;
 	hipLaunchKernelGGL(ba_linearize_kernel, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, ctx->stream,
+		no, d_cam_of, d_pt_of, d_cams, d_intr, d_pts, d_meas, d_J0, d_J1, d_r);
+	SPP_HIP_CHECK(hipGetLastError());
+}
+
+void ba_stereo_linearize(spp_ctx *ctx, int64_t no, const int32_t *d_cam_of, const int32_t *d_pt_of, const double *d_cams,
+	const double *d_intr, const double *d_pts, const double *d_meas, double *d_J0, double *d_J1, double *d_r)
+{
+	if(!no)
+		return;
+	hipLaunchKernelGGL(ba_stereo_linearize_kernel, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, ctx->stream,
 		no, d_cam_of, d_pt_of, d_cams, d_intr, d_pts, d_meas, d_J0, d_J1, d_r);
 	SPP_HIP_CHECK(hipGetLastError());
 }

@@ -385,11 +385,20 @@ def problem_from_graph(path):
     """Graph file -> hot-path inputs (synth.Problem) at the file's initial estimate, plus a short description.
     2D / 3D pose graphs without VERTEX lines are initialized the way the reference's parse loop does it
     (CEdgePose2D / CEdgePose3D constructors: an unseen second vertex becomes first (+) measurement, in file order);
-    BA files use the reference's VERTEX_CAM convention (camera-to-world in the file). A file with LANDMARK3:XYZ /
-    EDGE_SE3_XYZ lines goes to load_slam3d_graph and comes back as the PAIR of its edge groups (slam3d_linearize)."""
+    BA files use the reference's VERTEX_CAM convention (camera-to-world in the file); a file with EDGE_PROJECT_P2SC /
+    EDGE_P2SC lines goes to load_stereo_graph and comes back as one (6, 3, 3) group (stereo_linearize). A file with
+    LANDMARK3:XYZ / EDGE_SE3_XYZ lines goes to load_slam3d_graph and comes back as the PAIR of its edge groups
+    (slam3d_linearize)."""
     from scipy.spatial.transform import Rotation
     with open(path) as f:
-        has_lm3 = any(ln.split()[0].upper() in _LM3_XYZ_EDGE for ln in f if ln.split())
+        toks = {ln.split()[0].upper() for ln in f if ln.split()}
+    has_lm3 = bool(toks & _LM3_XYZ_EDGE)
+    if toks & _P2SC_EDGE:  # stereo BA: ONE (6, 3, 3) group, cameras CVertexSCam
+        g = load_stereo_graph(path)
+        prob = stereo_linearize(g["cams"], g["intr"], g["points"], g["obs"], g["cam_id"], g["pt_id"], g["info"])
+        prob["nc"], prob["npts"] = g["cam_id"].size, g["pt_id"].size
+        return prob, "stereo BA graph file (%d cameras, %d points, %d observations)" % (
+            g["cam_id"].size, g["pt_id"].size, g["obs"].shape[0])
     if has_lm3:  # 3D poses + landmarks: TWO edge groups over the same vertices (nonlinear.CSlam3D solves such a graph)
         s = load_slam3d_graph(path)
         groups = slam3d_linearize(s["dim"], s["state"], s["odo"], s["odo_info"], s["obs"], s["obs_info"])
@@ -791,3 +800,163 @@ def slam3d_plus(dim, state, dx):
     idx = base[:-1][dim == 6][:, None] + np.arange(6)
     out[idx] = se3_plus(state[idx], dx[idx])
     return out
+
+
+# --------------------------------------------------------------------------------------------------
+# stereo bundle adjustment: cameras CVertexSCam (6, [t | axis-angle] + 6 intrinsics) + points (3), CEdgeP2SC3D
+# --------------------------------------------------------------------------------------------------
+_P2SC_EDGE = {"EDGE_PROJECT_P2SC", "EDGE_P2SC"}   # ParsePrimitives.h:1314-1315
+
+
+def stereo_expectation(cam, intr, X):
+    """CBAJacobians::Project_P2SC (include/slam/BASolverBase.h:462-537) as the reference writes it, one row per
+    observation: cam (k, 6) [t | axis-angle] world -> left camera, intr (k, 6) fx fy cx cy d b, X (k, 3) -> (k, 3)
+    u v u_right. x = R X + t, uv = A x / x2, k = d / (0.5 (fx + fy)), rho = |uv - c|, uv <- c + (1 + rho k)(uv - c); the
+    right camera sees the point moved by -b (row 0 of R)^T through the same steps with its own rho."""
+    from scipy.spatial.transform import Rotation
+    cam, intr, X = (np.asarray(a, dtype=np.float64) for a in (cam, intr, X))
+    R = Rotation.from_rotvec(cam[:, 3:6]).as_matrix()
+    fx, fy, cx, cy = (intr[:, i] for i in range(4))
+    k, b = intr[:, 4] / (0.5 * (fx + fy)), intr[:, 5]
+    c = np.stack([cx, cy], axis=1)
+
+    def project(Xw):
+        x = np.einsum("eij,ej->ei", R, Xw) + cam[:, :3]
+        uv = np.stack([fx * x[:, 0] + cx * x[:, 2], fy * x[:, 1] + cy * x[:, 2]], axis=1) / x[:, 2:3]   # A x / (A x)_2
+        rho = np.sqrt(((uv - c) ** 2).sum(axis=1))
+        return c + (1 + rho * k)[:, None] * (uv - c)
+
+    uv = project(X)
+    uv2 = project(X - b[:, None] * R[:, 0, :])
+    return np.stack([uv[:, 0], uv[:, 1], uv2[:, 0]], axis=1)
+
+
+def stereo_linearize(cams, intr, points, obs, cam_id=None, pt_id=None, info=None):
+    """Hot-path inputs (synth.Problem, like ba_linearize: one group, here (6, 3, 3)) of a stereo bundle adjustment at the
+    given estimate: cams (nc, 6) [t | axis-angle] world -> left camera, intr (nc, 6) fx fy cx cy d b, points (np, 3), obs
+    (no, 5) cam pt u v u_right, info (no, 3, 3) or None (identity). r = z - stereo_expectation. Jacobians w.r.t. the camera
+    increment of Relative_to_Absolute (t' = t + R dt, R' = R exp(dr), 3DSolverBase.h:807-850) and the point, analytic
+    where the reference takes forward differences with delta = 1e-9 (BASolverBase.h:781-841). With q = p - c,
+    rho = |q|: d uv / d q = (1 + rho k) I + k q n^T, n = q / rho and n = 0 at rho = 0 (the term's norm is rho k: it
+    vanishes there, a point on the optical axis has finite Jacobians); d q / d x = [fx/x2 0 -fx x0/x2^2; 0 fy/x2
+    -fy x1/x2^2]. Since R (row 0 of R)^T = e0 -- for the incremented R' as well -- the right camera's point in the camera
+    frame is x - b e0 and has d x / d increment of the left one: P = rows 0, 1 of the left chain, row 0 of the right one
+    at x - b e0; J_cam = P [R | -R [X]x], J_pt = P R. Vertex ids: cameras 0..nc-1, points nc.. unless cam_id / pt_id say
+    otherwise."""
+    from scipy.spatial.transform import Rotation
+    from .synth import Problem
+    cams, intr, points, obs = (np.asarray(a, dtype=np.float64) for a in (cams, intr, points, obs))
+    nc, npts, no = cams.shape[0], points.shape[0], obs.shape[0]
+    co, po = obs[:, 0].astype(np.int64), obs[:, 1].astype(np.int64)
+    cam_id = np.arange(nc) if cam_id is None else np.asarray(cam_id)
+    pt_id = nc + np.arange(npts) if pt_id is None else np.asarray(pt_id)
+    R = Rotation.from_rotvec(cams[:, 3:]).as_matrix()[co]
+    X = points[po]
+    x = np.einsum("eij,ej->ei", R, X) + cams[co, :3]
+    fx, fy = intr[co, 0], intr[co, 1]
+    k, b = intr[co, 4] / (0.5 * (fx + fy)), intr[co, 5]
+    iz = 1.0 / x[:, 2]
+
+    def chain(x0):
+        """D Jd (no, 2, 3) of one camera whose point has the first camera-frame coordinate x0"""
+        q = np.stack([fx * x0 * iz, fy * x[:, 1] * iz], axis=1)
+        rho = np.sqrt((q ** 2).sum(axis=1))
+        n = np.where(rho[:, None] > 0, q / np.where(rho > 0, rho, 1.0)[:, None], 0.0)
+        D = (1 + rho * k)[:, None, None] * np.eye(2)[None] + k[:, None, None] * np.einsum("ei,ej->eij", q, n)
+        Jd = np.zeros((no, 2, 3))
+        Jd[:, 0, 0], Jd[:, 0, 2] = fx * iz, -fx * x0 * iz * iz
+        Jd[:, 1, 1], Jd[:, 1, 2] = fy * iz, -fy * x[:, 1] * iz * iz
+        return np.einsum("eij,ejk->eik", D, Jd)
+
+    P = np.concatenate([chain(x[:, 0]), chain(x[:, 0] - b)[:, :1]], axis=1)
+    PR = np.einsum("eij,ejk->eik", P, R)
+    J0 = np.concatenate([PR, -np.einsum("eij,ejk->eik", PR, _hat(X))], axis=2)
+    dim = np.empty(nc + npts, dtype=np.int32)
+    dim[cam_id] = 6
+    dim[pt_id] = 3
+    Om = np.tile(np.eye(3), (no, 1, 1)) if info is None else np.asarray(info, dtype=np.float64)
+    return Problem(name="stereo_ba", dim=dim, v0=cam_id[co], v1=pt_id[po], d0=6, d1=3, rd=3,
+                   J0=np.ascontiguousarray(J0.transpose(0, 2, 1)).reshape(no, 18),
+                   J1=np.ascontiguousarray(PR.transpose(0, 2, 1)).reshape(no, 9),
+                   Om=np.ascontiguousarray(Om).reshape(no, 9), r=obs[:, 2:5] - stereo_expectation(cams[co], intr[co], X),
+                   unary_vertex=0, damping=0.0)
+
+
+def load_stereo_graph(path):
+    """A stereo BA graph as the reference's parser reads it: `VERTEX_SCAM id x y z qx qy qz qw fx fy cx cy d b` stores the
+    camera-to-world pose (centre + quaternion), which the parser inverts into the world-to-camera [t | axis-angle] it
+    optimizes, exactly as for VERTEX_CAM (include/slam_app/ParsePrimitives.h:984-1048: quat.inverse(), c = quat * -t,
+    Quat_to_AxisAngle); `VERTEX_XYZ id x y z`; `EDGE_PROJECT_P2SC` / `EDGE_P2SC point-id cam-id u v u_right` + the six
+    upper-triangular values of the information row by row (:1303-1358). The edge's first vertex is the camera, the
+    SECOND id (CEdgeP2SC3D, BA_Types.h:724-727). The d of the FILE is the distortion per pixel of radius: the parsed
+    vertex multiplies it by 0.5 (fx + fy) (TVertexSCam3D, include/slam/Parser.h:580-587) into the internal d that
+    Project_P2SC divides again, and so does this loader -- intr holds the internal value. Returns dict(cams (nc, 6),
+    intr (nc, 6), points (np, 3), obs (no, 5) camera INDEX, point INDEX, u v u_right, info (no, 3, 3), cam_id, pt_id: the
+    vertex ids, in file order)."""
+    from scipy.spatial.transform import Rotation
+    cams, pts, edges, info = [], [], [], []
+    with open(path) as f:
+        for ln in f:
+            t = ln.split()
+            if not t or t[0].startswith("#") or t[0].startswith("%"):
+                continue
+            tok, a = t[0].upper(), t[1:]
+            if tok == "VERTEX_SCAM" and len(a) >= 14:
+                cams.append([float(x) for x in a[:14]])
+            elif tok == "VERTEX_XYZ" and len(a) >= 4:
+                pts.append([float(x) for x in a[:4]])
+            elif tok in _P2SC_EDGE and len(a) >= 11:
+                edges.append([float(x) for x in a[:5]])
+                info.append(_upper_to_full([float(x) for x in a[5:11]], 3))
+    cams_f, pts_f, e = np.array(cams).reshape(-1, 14), np.array(pts).reshape(-1, 4), np.array(edges).reshape(-1, 5)
+    q = Rotation.from_quat(cams_f[:, 4:8]).inv()
+    cam_id, pt_id = cams_f[:, 0].astype(np.int64), pts_f[:, 0].astype(np.int64)
+    nv = int(max(cam_id.max(initial=-1), pt_id.max(initial=-1))) + 1
+    cam_index, pt_index = np.full(nv, -1, dtype=np.int64), np.full(nv, -1, dtype=np.int64)
+    cam_index[cam_id] = np.arange(cam_id.size)
+    pt_index[pt_id] = np.arange(pt_id.size)
+    ci, pi = cam_index[e[:, 1].astype(np.int64)], pt_index[e[:, 0].astype(np.int64)]
+    if (ci < 0).any() or (pi < 0).any():
+        raise ValueError("an EDGE_PROJECT_P2SC line names a vertex that is no VERTEX_SCAM / VERTEX_XYZ: %s" % path)
+    intr = cams_f[:, 8:14].copy()
+    intr[:, 4] *= 0.5 * (intr[:, 0] + intr[:, 1])   # TVertexSCam3D's constructor (include/slam/Parser.h:580-587)
+    return dict(cams=np.concatenate([q.apply(-cams_f[:, 1:4]), q.as_rotvec()], axis=1), intr=intr,
+                points=pts_f[:, 1:4].copy(), obs=np.concatenate([ci[:, None].astype(np.float64), pi[:, None].astype(np.float64),
+                                                                  e[:, 2:5]], axis=1),
+                info=np.array(info).reshape(-1, 3, 3), cam_id=cam_id, pt_id=pt_id)
+
+
+def stereo_lines(cams, intr, points, obs, info=None, cam_id=None, pt_id=None):
+    """the lines of save_stereo_graph: vertices in id order, then the edges as given, everything with %.17g"""
+    from scipy.spatial.transform import Rotation
+    cams, intr, points, obs = (np.asarray(a, dtype=np.float64) for a in (cams, intr, points, obs))
+    nc, npts = cams.shape[0], points.shape[0]
+    cam_id = np.arange(nc) if cam_id is None else np.asarray(cam_id)
+    pt_id = nc + np.arange(npts) if pt_id is None else np.asarray(pt_id)
+    R = Rotation.from_rotvec(cams[:, 3:6])
+    C = -R.inv().apply(cams[:, :3])            # camera centre in the world
+    q = R.inv().as_quat()                       # x y z w, camera-to-world
+    intr_f = intr.copy()
+    intr_f[:, 4] /= 0.5 * (intr[:, 0] + intr[:, 1])   # the file holds d per pixel of radius, the reader scales it back
+    lines = []
+    for v in np.argsort(np.concatenate([cam_id, pt_id]), kind="stable"):
+        if v < nc:
+            lines.append("VERTEX_SCAM %d " % cam_id[v] + " ".join("%.17g" % x for x in (*C[v], *q[v], *intr_f[v])))
+        else:
+            lines.append("VERTEX_XYZ %d " % pt_id[v - nc] + " ".join("%.17g" % x for x in points[v - nc]))
+    iu = np.triu_indices(3)
+    for k, o in enumerate(obs):
+        m = np.eye(3) if info is None else np.asarray(info[k])
+        lines.append("EDGE_PROJECT_P2SC %d %d " % (pt_id[int(o[1])], cam_id[int(o[0])]) +
+                     " ".join("%.17g" % x for x in (*o[2:5], *m[iu])))
+    return lines
+
+
+def save_stereo_graph(path, cams, intr, points, obs, info=None, cam_id=None, pt_id=None):
+    """Stereo BA graph in the reference's text format (tokens: load_stereo_graph). cams (nc, 6) world-to-camera [t |
+    axis-angle] (the reference's internal CVertexSCam state; the file gets centre + camera-to-world quaternion), intr
+    (nc, 6) fx fy cx cy d b (d the internal value; the file gets d / (0.5 (fx + fy))), points (np, 3), obs (no, 5)
+    camera index, point index, u v u_right (written point id first, as the parser wants), info (no, 3, 3) or None
+    (identity); cam_id / pt_id: vertex ids (default: cameras 0..nc-1, points nc..). Vertices are written in id order."""
+    with open(path, "w") as f:
+        f.write("\n".join(stereo_lines(cams, intr, points, obs, info, cam_id, pt_id)) + "\n")

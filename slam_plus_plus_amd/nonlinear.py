@@ -18,7 +18,7 @@ import numpy as np
 
 from . import api
 from .formats import (se2_linearize, se3_linearize, se3_plus, ba_linearize, slam2d_linearize, slam2d_offsets,
-                      slam3d_linearize, slam3d_offsets, slam3d_plus)
+                      slam3d_linearize, slam3d_offsets, slam3d_plus, stereo_linearize)
 
 
 class CPoseGraph2D:
@@ -458,23 +458,29 @@ class CBundleAdjustment:
 class _ResidentBAPath:
     """LM iteration pieces in HBM: spp_ba_linearize_device, spp_assemble_device (damping alpha),
     spp_factor_solve_device, spp_ba_update_device, chi2 / alpha0 / gain-ratio reductions."""
+    rd = 2                                  # residual dimension: the edge group is (6, 3, rd)
 
     def __init__(self, device=0):
         self.ctx = api.Context(device)
+
+    def _dx_offsets(self, s):
+        """scalar offsets of the cameras and of the points in the solution vector: cameras first"""
+        return 6 * np.arange(self.nc, dtype=np.int64), 6 * self.nc + 3 * np.arange(self.np, dtype=np.int64)
 
     def begin(self, system):
         ctx, s = self.ctx, system
         prob = s.linearize()   # structure only
         self.no, self.nc, self.np = s.obs.shape[0], s.cams.shape[0], s.points.shape[0]
-        self.st = ctx.assemble_analyze(prob.dim, prob.v0, prob.v1, 6, 3, 2, prob.unary_vertex)
+        rd = self.rd
+        self.st = ctx.assemble_analyze(prob.dim, prob.v0, prob.v1, 6, 3, rd, prob.unary_vertex)
         up = lambda a: api.DeviceArray.from_host(ctx, np.ascontiguousarray(a).ravel())
         self.d_cam_of, self.d_pt_of = up(s.obs[:, 0].astype(np.int32)), up(s.obs[:, 1].astype(np.int32))
         self.d_cams, self.d_intr, self.d_pts = up(s.cams), up(s.intr), up(s.points)
-        self.d_meas, self.d_Om = up(s.obs[:, 2:4]), up(prob.Om)
-        self.d_cam_off = up(6 * np.arange(self.nc, dtype=np.int64))
-        self.d_pt_off = up(6 * self.nc + 3 * np.arange(self.np, dtype=np.int64))
-        self.d_J0, self.d_J1 = api.DeviceArray(ctx, 12 * self.no), api.DeviceArray(ctx, 6 * self.no)
-        self.d_r = api.DeviceArray(ctx, 2 * self.no)
+        self.d_meas, self.d_Om = up(s.obs[:, 2:2 + rd]), up(prob.Om)
+        cam_off, pt_off = self._dx_offsets(s)
+        self.d_cam_off, self.d_pt_off = up(cam_off), up(pt_off)
+        self.d_J0, self.d_J1 = api.DeviceArray(ctx, 6 * rd * self.no), api.DeviceArray(ctx, 3 * rd * self.no)
+        self.d_r = api.DeviceArray(ctx, rd * self.no)
         self.d_vals, self.d_eta, self.d_dx = (api.DeviceArray(ctx, self.st.nvals), api.DeviceArray(ctx, self.st.n),
                                               api.DeviceArray(ctx, self.st.n))
         self.s_cams, self.s_pts = api.DeviceArray(ctx, 6 * self.nc), api.DeviceArray(ctx, 3 * self.np)
@@ -488,10 +494,10 @@ class _ResidentBAPath:
         """error at the CURRENT state (re-evaluates the residuals; J of the last linearization is overwritten too,
         which the loop accounts for by re-linearizing after a rejected step is rolled back)"""
         self.linearize()
-        return self.ctx.edge_chi2_device(self.no, 2, self.d_r.ptr, self.d_Om.ptr)
+        return self.ctx.edge_chi2_device(self.no, self.rd, self.d_r.ptr, self.d_Om.ptr)
 
     def max_hessian_diag(self):
-        return self.ctx.edge_hessian_maxdiag_device(self.no, 2, 6, 3, self.d_J0.ptr, self.d_J1.ptr, self.d_Om.ptr)
+        return self.ctx.edge_hessian_maxdiag_device(self.no, self.rd, 6, 3, self.d_J0.ptr, self.d_J1.ptr, self.d_Om.ptr)
 
     def solve(self, alpha):
         ctx = self.ctx
@@ -528,6 +534,66 @@ class _ResidentBAPath:
         self.ctx.close()
 
 
+class CStereoBundleAdjustment:
+    """Stereo BA 'system' (CVertexSCam + CVertexXYZ joined by CEdgeP2SC3D, src/slam_app/SolveBAStereoImpl.cpp), the
+    interface of CBundleAdjustment: cams (nc, 6) [t | axis-angle] world -> left camera, intr (nc, 6) fx fy cx cy d b,
+    points (np, 3), obs (no, 5) cam pt u v u_right; info (no, 3, 3) or None (identity). Vertex ids: cameras 0..nc-1, points
+    nc.. unless cam_id / pt_id say otherwise (a graph file may interleave them)."""
+
+    def __init__(self, cams, intr, points, obs, info=None, cam_id=None, pt_id=None):
+        self.cams = np.array(cams, dtype=np.float64)
+        self.intr = np.asarray(intr, dtype=np.float64)
+        self.points = np.array(points, dtype=np.float64)
+        self.obs = np.asarray(obs, dtype=np.float64)
+        self.info = None if info is None else np.asarray(info, dtype=np.float64)
+        nc, npts = self.cams.shape[0], self.points.shape[0]
+        self.cam_id = np.arange(nc) if cam_id is None else np.asarray(cam_id, dtype=np.int64)
+        self.pt_id = nc + np.arange(npts) if pt_id is None else np.asarray(pt_id, dtype=np.int64)
+        dim = np.empty(nc + npts, dtype=np.int64)
+        dim[self.cam_id], dim[self.pt_id] = 6, 3
+        base = slam3d_offsets(dim)
+        self.cam_off, self.pt_off = base[self.cam_id], base[self.pt_id]   # scalar offsets in the solution vector
+
+    @classmethod
+    def from_problem(cls, p):
+        """from synth.stereo_problem (its geometry) or formats.load_stereo_graph"""
+        g = p["geometry"] if "geometry" in p else p
+        return cls(g["cams"], g["intr"], g["points"], g["obs"], g["info"], g["cam_id"], g["pt_id"])
+
+    def linearize(self):
+        return stereo_linearize(self.cams, self.intr, self.points, self.obs, self.cam_id, self.pt_id, self.info)
+
+    def chi2(self):
+        p = self.linearize()
+        return float(np.einsum("ei,eij,ej->", p.r, p.Om.reshape(-1, 3, 3), p.r))
+
+    def state(self):
+        return self.cams.copy(), self.points.copy()
+
+    def set_state(self, st):
+        self.cams, self.points = st[0].copy(), st[1].copy()
+
+    def plus(self, dx):
+        """CVertexSCam::Operator_Plus is Relative_to_Absolute (BA_Types.h:264-267), CVertexXYZ's the plain sum"""
+        self.cams = se3_plus(self.cams, dx[self.cam_off[:, None] + np.arange(6)])
+        self.points = self.points + dx[self.pt_off[:, None] + np.arange(3)]
+
+
+class _ResidentStereoBAPath(_ResidentBAPath):
+    """the LM iteration pieces of a CStereoBundleAdjustment in HBM: _ResidentBAPath with the (6, 3, 3) group --
+    assemble_analyze(..., 6, 3, 3, ...), spp_ba_stereo_linearize_device, edge_chi2_device(no, 3, ...),
+    edge_hessian_maxdiag_device(no, 3, 6, 3, ...) -- and spp_ba_update_device as it is, the vertices at the system's
+    offsets."""
+    rd = 3
+
+    def _dx_offsets(self, s):
+        return s.cam_off.astype(np.int64), s.pt_off.astype(np.int64)
+
+    def linearize(self):
+        self.ctx.ba_stereo_linearize_device(self.no, self.d_cam_of.ptr, self.d_pt_of.ptr, self.d_cams.ptr, self.d_intr.ptr,
+                                            self.d_pts.ptr, self.d_meas.ptr, self.d_J0.ptr, self.d_J1.ptr, self.d_r.ptr)
+
+
 class CNonlinearSolver_Lambda_LM:
     """Mirror of CNonlinearSolver_Lambda_LM::Optimize (include/slam/NonlinearSolver_Lambda_LM.h:796-1135) with
     the Levenberg trust-region policy of :151-222:
@@ -537,7 +603,8 @@ class CNonlinearSolver_Lambda_LM:
               rho = (last - err) / (dx . (alpha dx + eta));
               rho > 0: alpha *= max(1/3, 1 - (2 rho - 1)^3), nu = 2, last = err
               else   : alpha *= nu, nu *= 2, restore x, and the iteration budget grows by one (at most 10 times)
-    `path`: _ResidentBAPath (default, GPU) or any object with the same methods (tests inject a host path)."""
+    `path`: _ResidentBAPath (default, GPU), _ResidentStereoBAPath for a CStereoBundleAdjustment, or any object with the
+    same methods (tests inject a host path)."""
 
     def __init__(self, system, path=None, device=0, verbose=False):
         self.system = system

@@ -492,6 +492,76 @@ def landmark3d_problem(n_poses=40, n_lm=60, seed=72, name="lm3d_small"):
     return g
 
 
+# ------------------------------------------------------------------------------------------------
+# stereo bundle adjustment: cameras CVertexSCam (6) + points (3), 3-d residuals (u, v, u_right), CEdgeP2SC3D
+# ------------------------------------------------------------------------------------------------
+def stereo_problem(nc=6, npts=40, seed=16, interleave=False, views=(2, 6), hubs=False, name="stereo"):
+    """nc stereo cameras on a circle of radius 10 looking at the origin (scene depth about 10, baseline 0.5 = 1/20 of it),
+    npts points in a cube, each seen by views[0] .. views[1] distinct cameras; fx 500, fy 505, c = (320, 240), the
+    distortion d = 0.1 on every odd camera and 0 on the even ones. hubs: point 0 is seen by ALL cameras and camera 0 sees
+    30 points more (vertices of both widths beyond the 24 entries the sequential assembly kernel takes).
+    interleave=True shuffles the vertex ids. The measurements come from the ground truth + pixel noise (sigma 0.5 / 0.5 /
+    0.7, information its inverse square), the estimate is the truth disturbed (cameras 0.03 / 0.004 rad, points 0.05), so
+    that Levenberg-Marquardt has work to do. Returns the (6, 3, 3) group linearized at the estimate (formats.
+    stereo_linearize: measurements = expectation + r) with geometry = the states (stereo_states)."""
+    from scipy.spatial.transform import Rotation
+    from .formats import stereo_expectation, stereo_linearize
+    rng = np.random.default_rng(seed)
+    k = rng.integers(views[0], min(views[1], nc) + 1, size=npts)
+    cam_of = np.concatenate([np.sort(rng.choice(nc, size=kk, replace=False)) for kk in k])
+    pt_of = np.repeat(np.arange(npts, dtype=np.int64), k)
+    if hubs:
+        more_c = np.setdiff1d(np.arange(nc), cam_of[pt_of == 0])                 # point 0: every camera
+        more_p = np.array([j for j in range(1, npts) if 0 not in cam_of[pt_of == j]][:30])   # camera 0: 30 points more
+        cam_of = np.concatenate([cam_of, more_c, np.zeros(more_p.size, dtype=np.int64)])
+        pt_of = np.concatenate([pt_of, np.zeros(more_c.size, dtype=np.int64), more_p])
+    nobs = cam_of.size
+    th = 2 * np.pi * np.arange(nc) / nc
+    C = np.stack([10 * np.cos(th), 10 * np.sin(th), 0.5 * np.sin(3 * th)], axis=1)
+    z = -C / np.linalg.norm(C, axis=1, keepdims=True)
+    x = np.cross(np.array([0.0, 0.0, 1.0])[None, :], z)
+    x /= np.linalg.norm(x, axis=1, keepdims=True)
+    R = np.stack([x, np.cross(z, x), z], axis=1)  # rows = camera axes (world -> camera)
+    cams = np.concatenate([-np.einsum("cij,cj->ci", R, C), Rotation.from_matrix(R).as_rotvec()], axis=1)
+    intr = np.tile(np.array([500.0, 505.0, 320.0, 240.0, 0.0, 0.5]), (nc, 1))
+    intr[1::2, 4] = 0.1
+    X = rng.uniform(-2, 2, size=(npts, 3))
+    sig = np.array([0.5, 0.5, 0.7])
+    meas = stereo_expectation(cams[cam_of], intr[cam_of], X[pt_of]) + rng.normal(0, 1, size=(nobs, 3)) * sig
+    info = np.tile(np.diag(1.0 / sig ** 2), (nobs, 1, 1))
+    est_c = np.concatenate([cams[:, :3] + rng.normal(0, 0.03, size=(nc, 3)),
+                            (Rotation.from_rotvec(cams[:, 3:]) * Rotation.from_rotvec(rng.normal(0, 0.004, size=(nc, 3)))).as_rotvec()], axis=1)
+    est_p = X + rng.normal(0, 0.05, size=X.shape)
+    nv = nc + npts
+    if interleave:
+        perm = rng.permutation(nv)
+        cam_id, pt_id = perm[:nc], perm[nc:]
+    else:
+        cam_id, pt_id = np.arange(nc), nc + np.arange(npts)
+    f = lambda a: a.astype(np.float64)
+    obs = np.concatenate([f(cam_of)[:, None], f(pt_of)[:, None], meas], axis=1)
+    prob = stereo_linearize(est_c, intr, est_p, obs, cam_id, pt_id, info)
+    J0, J1, Om = prob.J0.reshape(nobs, 6, 3), prob.J1.reshape(nobs, 3, 3), info
+    h0 = np.einsum("eci,eij,ecj->ec", J0, Om, J0).max()
+    h1 = np.einsum("eci,eij,ecj->ec", J1, Om, J1).max()
+    prob.update(name=name, damping=1e-3 * float(max(h0, h1)), nc=nc, npts=npts,
+                geometry=dict(cams=est_c, intr=intr, points=est_p, obs=obs, info=info, cam_of=cam_of, pt_of=pt_of,
+                              cam_id=cam_id, pt_id=pt_id, truth=dict(cams=cams, points=X)))
+    return prob
+
+
+def stereo_states(prob):
+    """The scene of a stereo_problem as input of spp_ba_stereo_linearize_device, like ba_states: dict(cams (nc,6), intr
+    (nc,6) fx fy cx cy d b, points (np,3), meas (no,3) = expectation + the problem's residual, cam_of, pt_of int32,
+    cam_dxoff, pt_dxoff int64: scalar offset of every vertex in the solution vector)."""
+    g = prob.geometry
+    base = np.zeros(prob.dim.size + 1, dtype=np.int64)
+    np.cumsum(prob.dim, out=base[1:])
+    return dict(cams=g["cams"].copy(), intr=g["intr"].copy(), points=g["points"].copy(), meas=g["obs"][:, 2:5].copy(),
+                cam_of=g["cam_of"].astype(np.int32), pt_of=g["pt_of"].astype(np.int32),
+                cam_dxoff=base[g["cam_id"]].copy(), pt_dxoff=base[g["pt_id"]].copy())
+
+
 def pose_graph_states(prob):
     """The same pose graph as states + measurements in the REFERENCE's parameterization, as input of
     spp_se2_/se3_linearize_device: poses (n, 3) x y theta or (n, 6) [t | axis-angle] at the noisy estimate,
@@ -533,6 +603,8 @@ CONFIGS = {
     "slam3d_small": lambda: slam3d_problem(40, 60, 71, name="slam3d_small"),
     "slam3d_interleaved": lambda: slam3d_problem(150, 300, 73, interleave=True, name="slam3d_interleaved", hubs=26),
     "lm3d_small": lambda: landmark3d_problem(40, 60, 72),
+    "stereo_small": lambda: stereo_problem(6, 40, 16, name="stereo_small"),
+    "stereo_interleaved": lambda: stereo_problem(30, 150, 17, interleave=True, hubs=True, name="stereo_interleaved"),
     "se2_small": lambda: se2_problem(300, 150, 12, name="se2_small"),
     "se3_small": lambda: se3_problem(8, 12, 13, name="se3_small"),
 }
