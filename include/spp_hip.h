@@ -119,6 +119,16 @@ int spp_set_shard(spp_ctx *ctx, int rank, int world_size);
 int spp_get_info(const spp_ctx *ctx, int what, int64_t *out);
 /* elimination order chosen by the analysis: order[k] = source block column eliminated k-th */
 int spp_get_ordering(const spp_ctx *ctx, int64_t *h_order);
+/* The front table of the sparse plan (diagnostics and tests; host copies only, nothing is launched). Returns the number
+ * of fronts (supernodes), 0 when the analysis built no sparse plan, and fills the first min(capacity, fronts) entries of
+ * every array that is not NULL, fronts in elimination (post-) order:
+ *   h, w     scalar height (right-hand-side slot included: a root has h = w + 1) and pivot width
+ *   pad      identity padding behind the pivot block in the front's HBM image (class 3: to 16, class 4: to 128, else 0)
+ *   cls      size class 0..4: LDS image of 32 / 64 / 128 rows, one workgroup in place in HBM, 128-padded big front
+ *   level    level in the assembly tree (leaves 0);  parent: front index, -1 for a root
+ *   team     workgroups of a big front inside the dependency-driven launch (1: none, or the front is host-driven) */
+int64_t spp_sparse_fronts(const spp_ctx *ctx, int64_t capacity, int32_t *h, int32_t *w, int32_t *pad, int32_t *cls, int32_t *level,
+	int32_t *parent, int32_t *team);
 
 /* Fill-reducing block ordering of an upper block pattern, host only (no context, no GPU): the job of
  * CMatrixOrdering::p_BlockOrdering (reference src/slam/OrderingMagic.cpp:701, live path :900-1031:

@@ -28,7 +28,7 @@ PHASES = ["permute", "schur_inv", "schur_gemm", "schur_rhs", "factor", "trisolve
 # every symbol include/spp_hip.h declares (tests/test_abi.py checks the .so exports them all)
 EXPORTS = [
     "spp_create", "spp_destroy", "spp_free_memory", "spp_last_error", "spp_host_staging", "spp_set_stream", "spp_synchronize",
-    "spp_analyze", "spp_set_shard", "spp_get_info", "spp_get_ordering", "spp_factor_solve",
+    "spp_analyze", "spp_set_shard", "spp_get_info", "spp_get_ordering", "spp_sparse_fronts", "spp_factor_solve",
     "spp_factor_solve_device", "spp_schur_buffer_size", "spp_schur_form", "spp_schur_finish",
     "spp_schur_packed_size", "spp_schur_pack", "spp_schur_unpack",
     "spp_assemble_analyze", "spp_assemble_get_structure", "spp_assemble_device", "spp_assemble_set_edge_weights",
@@ -73,6 +73,7 @@ def load_library():
         "spp_set_shard": (cint, [vp, cint, cint]),
         "spp_get_info": (cint, [vp, cint, _c_i64p]),
         "spp_get_ordering": (cint, [vp, vp]),
+        "spp_sparse_fronts": (i64, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
         "spp_factor_solve": (cint, [vp, vp, vp]),
         "spp_factor_solve_device": (cint, [vp, vp, vp]),
         "spp_schur_buffer_size": (cint, [vp, _c_i64p]),
@@ -342,6 +343,16 @@ class Context:
     def ordering(self, nb):
         out = np.empty(nb, dtype=np.int64)
         self._check(self.lib.spp_get_ordering(self.h, _ptr(out)))
+        return out
+
+    def sparse_fronts(self):
+        """the front table of the sparse plan (spp_sparse_fronts): a dict of int32 arrays h, w, pad, cls, level, parent, team,
+        one entry per front in elimination order; empty arrays when the analysis built no sparse plan"""
+        keys = ("h", "w", "pad", "cls", "level", "parent", "team")
+        ns = self._check(self.lib.spp_sparse_fronts(self.h, 0, None, None, None, None, None, None, None))
+        out = {k: np.zeros(ns, dtype=np.int32) for k in keys}
+        if ns:
+            self._check(self.lib.spp_sparse_fronts(self.h, ns, *[_ptr(out[k]) for k in keys]))
         return out
 
     def se2_linearize_device(self, n_edges, d_v0, d_v1, d_poses, d_meas, d_J0, d_J1, d_r):

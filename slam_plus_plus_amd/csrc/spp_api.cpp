@@ -413,6 +413,18 @@ int spp_get_ordering(const spp_ctx *ctx, int64_t *h_order)
 	return SPP_OK;
 }
 
+int64_t spp_sparse_fronts(const spp_ctx *ctx, int64_t capacity, int32_t *h, int32_t *w, int32_t *pad, int32_t *cls, int32_t *level,
+	int32_t *parent, int32_t *team)
+{
+	if(!ctx || capacity < 0)
+		return SPP_E_BADARG;
+#ifdef SPP_HAVE_SPARSE
+	if(ctx->sparse)
+		return sparse_fronts(ctx, capacity, h, w, pad, cls, level, parent, team);
+#endif
+	return 0;
+}
+
 int spp_block_ordering(int64_t nb, const int64_t *col_ptr, const int64_t *row_idx, int method, int64_t *h_order)
 {
 	if(nb <= 0 || !col_ptr || !row_idx || !h_order || (method != SPP_ORDER_AMD && method != SPP_ORDER_ND))

@@ -457,6 +457,8 @@ int sparse_factor_solve(spp_ctx *ctx, const double *d_vals, double *d_rhs);
 void sparse_release(spp_ctx *ctx);
 void sparse_dag_disable(spp_ctx *ctx); // after a timed-out flag wait: level-by-level launches from then on
 int64_t sparse_info(const spp_ctx *ctx, int what);
+int64_t sparse_fronts(const spp_ctx *ctx, int64_t capacity, int32_t *h, int32_t *w, int32_t *pad, int32_t *cls, int32_t *level,
+	int32_t *parent, int32_t *team);
 
 // ---- spp_schur.hip ----
 void schur_form(spp_ctx *ctx, const double *d_vals, const double *d_rhs, double *d_S_rhs);

@@ -50,6 +50,7 @@ struct SparsePlan {
 	std::vector<int32_t> h_front_ld, h_front_pad, h_front_cls;
 	std::vector<int32_t> h_cls_ptr;            // [n_levels * NCLS + 1]: fronts of (level, class) in level_fronts
 	std::vector<int32_t> h_child_ptr, h_child_list, h_asm_ptr;
+	std::vector<int32_t> h_front_level, h_front_parent, h_front_team; // per supernode (diagnostics: sparse_fronts)
 	// device
 	DevBuf<int32_t> level_fronts;              // fronts grouped by level
 	DevBuf<int64_t> front_off;                 // [ns] offset of F in `fronts`
@@ -187,6 +188,26 @@ int64_t sparse_info(const spp_ctx *ctx, int what)
 	if(what == SPP_INFO_N_SUPERNODES) return ctx->sparse->n_snodes;
 	if(what == SPP_INFO_N_LEVELS) return ctx->sparse->n_levels;
 	return 0;
+}
+
+// the front table of the plan, from its host copies (diagnostics and tests: nothing is launched)
+int64_t sparse_fronts(const spp_ctx *ctx, int64_t capacity, int32_t *h, int32_t *w, int32_t *pad, int32_t *cls, int32_t *level,
+	int32_t *parent, int32_t *team)
+{
+	if(!ctx->sparse)
+		return 0;
+	const SparsePlan &sp = *ctx->sparse;
+	const int64_t ns = sp.n_snodes, nc = std::min(ns, capacity);
+	for(int64_t q = 0; q < nc; ++ q) {
+		if(h) h[q] = sp.h_front_h[q];
+		if(w) w[q] = sp.h_front_w[q];
+		if(pad) pad[q] = sp.h_front_pad[q];
+		if(cls) cls[q] = sp.h_front_cls[q];
+		if(level) level[q] = sp.h_front_level[q];
+		if(parent) parent[q] = sp.h_front_parent[q];
+		if(team) team[q] = sp.h_front_team[q];
+	}
+	return ns;
 }
 
 static const int NCLS = 5;
@@ -601,6 +622,9 @@ void sparse_analyze(spp_ctx *ctx, const Structure &st)
 	sp->h_front_ld = front_ld;
 	sp->h_front_pad = front_pad;
 	sp->h_front_cls = front_cls;
+	sp->h_front_level = level;
+	sp->h_front_parent = sn_parent;
+	sp->h_front_team = front_team;
 	sp->front_doubles = foff;
 	sp->vbuf_doubles = voff;
 	sp->h_front_h = front_h;
