@@ -116,6 +116,9 @@ int spp_set_shard(spp_ctx *ctx, int rank, int world_size);
 #define SPP_INFO_DENSE_STREAMED 16 /* tile rows (of 128) the last dense factorization handed to the streamed launch (spp_dense_tail.h); 0: none */
 #define SPP_INFO_LM_STREAM      17 /* landmark-side Schur kernels the last spp_schur_form / solve launched: 0 one lane per block, 1 / 2 the streamed forms (SPP_LM_STREAM) */
 #define SPP_INFO_BS_GROUPS      18 /* Schur: landmark groups of the fused back-substitution; 0: a landmark has more than 256 observations, two launches */
+#define SPP_INFO_SCHUR_SIDE     19 /* the last spp_schur_form / solve ran the reduced right-hand side on the side stream (SPP_SCHUR_SIDE): 1, else 0 */
+#define SPP_INFO_S_CLEAR        20 /* what the last spp_schur_form / solve cleared of its S buffer: 0 all of it, 1 the tiles of the filled mask, 2 the right-hand side and padding columns (every block of S is written) */
+#define SPP_INFO_S_DEVICE_PTR   21 /* diagnostics, tests: device address of the S | rhs buffer spp_factor_solve owns (0: none yet) */
 int spp_get_info(const spp_ctx *ctx, int what, int64_t *out);
 /* elimination order chosen by the analysis: order[k] = source block column eliminated k-th */
 int spp_get_ordering(const spp_ctx *ctx, int64_t *h_order);

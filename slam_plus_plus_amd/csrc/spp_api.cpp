@@ -167,6 +167,11 @@ void spp_destroy(spp_ctx *ctx)
 		if(ctx->dense.ev_chain)
 			(void)hipEventDestroy(ctx->dense.ev_chain);
 	}
+	if(ctx->side_stream) {
+		(void)hipStreamDestroy(ctx->side_stream);
+		(void)hipEventDestroy(ctx->side_ev[0]);
+		(void)hipEventDestroy(ctx->side_ev[1]);
+	}
 	if(ctx->dense.h_chain_err)
 		(void)hipHostFree(ctx->dense.h_chain_err);
 	if(ctx->h_staging)
@@ -397,6 +402,9 @@ int spp_get_info(const spp_ctx *ctx, int what, int64_t *out)
 	case SPP_INFO_DENSE_STREAMED: *out = ctx->dense.tail_rows_last; break;
 	case SPP_INFO_LM_STREAM: *out = (ctx->mode == SPP_MODE_SCHUR) ? ctx->schur.lm_stream_last : 0; break;
 	case SPP_INFO_BS_GROUPS: *out = (ctx->mode == SPP_MODE_SCHUR) ? ctx->schur.n_bs : 0; break;
+	case SPP_INFO_SCHUR_SIDE: *out = (ctx->mode == SPP_MODE_SCHUR) ? ctx->schur.side_last : 0; break;
+	case SPP_INFO_S_CLEAR: *out = (ctx->mode == SPP_MODE_SCHUR) ? ctx->schur.clear_last : 0; break;
+	case SPP_INFO_S_DEVICE_PTR: *out = (ctx->mode == SPP_MODE_SCHUR) ? (int64_t)(uintptr_t)ctx->schur.S.p : 0; break;
 	default: return SPP_E_BADARG;
 	}
 	return SPP_OK;
@@ -660,8 +668,10 @@ int spp_factor_solve_device(spp_ctx *ctx, const double *d_vals, double *d_rhs)
 	if(ctx->mode == SPP_MODE_SCHUR) {
 		SPP_REQUIRE(ctx->shard_world == 1, SPP_E_STATE,
 			"sharded ctx: use spp_schur_form / all-reduce / spp_schur_finish");
+		if(!ctx->schur.S.p || ctx->schur.S.cap < (size_t)schur_buffer_doubles(ctx))
+			ctx->schur.unlisted_dirty = true; // a new allocation: nothing is known of its contents
 		ctx->schur.S.reserve((size_t)schur_buffer_doubles(ctx));
-		schur_form(ctx, d_vals, d_rhs, ctx->schur.S.p);
+		schur_form(ctx, d_vals, d_rhs, ctx->schur.S.p, true);
 		ret = schur_finish(ctx, d_vals, ctx->schur.S.p, d_rhs);
 	} else
 		ret = sparse_factor_solve(ctx, d_vals, d_rhs);

@@ -1132,10 +1132,15 @@ __global__ void pad_diag_kernel(double *S, int64_t ld, int64_t n)
 	}
 }
 
+void dense_set_padding_on(hipStream_t st, double *d_A, int64_t ld, int64_t n)
+{
+	hipLaunchKernelGGL(pad_diag_kernel, dim3((unsigned)((ld - n + 255) / 256)), dim3(256), 0, st,
+		d_A, ld, n);
+}
+
 void dense_set_padding(spp_ctx *ctx, double *d_A, int64_t ld, int64_t n)
 {
-	hipLaunchKernelGGL(pad_diag_kernel, dim3((unsigned)((ld - n + 255) / 256)), dim3(256), 0, ctx->stream,
-		d_A, ld, n);
+	dense_set_padding_on(ctx->stream, d_A, ld, n);
 }
 
 // --------------------------------------------------------------------------------------------------
@@ -1426,6 +1431,7 @@ void dense_factor_steps(spp_ctx *ctx, double *d_A, int64_t ld, int64_t n, int64_
 {
 	ensure_dense_work(ctx, nsteps);
 	ctx->dense.tail_rows_last = 0;
+	ctx->dense.tail_masked_whole = false;
 	const bool captured = capturing(ctx->stream);
 	if(!captured && la_usable(ctx, nsteps)) { // lookahead: persistent chain kernel + one bulk launch per step
 		dense_factor_lookahead(ctx, d_A, ld, n, rows, ncols, nsteps, has_rhs);
@@ -1618,6 +1624,7 @@ static bool launch_dense_tail(spp_ctx *ctx, double *d_A, int64_t ld, int64_t row
 		dom_end(ctx, m * m * m / 3.0 + (a.have_pre ? (double)NB * m * (m + 1.0) : 0.0) + 2.0 * m * m);
 	}
 	dw.tail_rows_last = Tr;
+	dw.tail_masked_whole = k < 0 && mask != nullptr;
 	SPP_HIP_CHECK(hipGetLastError());
 	if(a.trace) {
 		std::vector<long long> h((size_t)Tr * 8);
@@ -1884,10 +1891,20 @@ void dense_reserve(spp_ctx *ctx, int64_t nblk)
 	ensure_dense_work(ctx, nblk);
 }
 
+void dense_info_ensure(spp_ctx *ctx)
+{
+	ensure_info(ctx);
+}
+
+void dense_info_reset_on(spp_ctx *ctx, hipStream_t st)
+{
+	hipLaunchKernelGGL(set_info_kernel, dim3(1), dim3(1), 0, st, ctx->dense.info.p);
+}
+
 void dense_info_reset(spp_ctx *ctx)
 {
 	ensure_info(ctx);
-	hipLaunchKernelGGL(set_info_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->dense.info.p);
+	dense_info_reset_on(ctx, ctx->stream);
 }
 
 void dense_chain_check(spp_ctx *ctx)
@@ -1939,11 +1956,13 @@ int dense_info_fetch(spp_ctx *ctx, bool *dag_aborted)
 // factorization without the host round trip for the status: the caller enqueues what follows (solves, back-
 // substitution) and fetches the status with dense_info_fetch() at the end -- after a failed factorization
 // those kernels work on garbage, which is harmless (no data-dependent waits) and discarded by the caller
-void dense_potrf_upper_enqueue(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld)
+bool dense_potrf_upper_enqueue(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, bool info_reset)
 {
 	SPP_REQUIRE(ld % NB == 0 && n < ld, SPP_E_BADARG, "dense_potrf_upper: ld must be a multiple of 128 and > n");
-	dense_info_reset(ctx);
+	if(info_reset)
+		dense_info_reset(ctx);
 	dense_factor_steps(ctx, d_A, ld, n, n, n + 1, (n + NB - 1) / NB, true);
+	return ctx->dense.tail_masked_whole;
 }
 
 int dense_potrf_upper(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, bool /*keep_inverses*/)

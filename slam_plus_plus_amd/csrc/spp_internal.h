@@ -270,6 +270,14 @@ struct SchurPlan : SchurDims {
 	DevBuf<double> xw;             // [no * dp]      W l per observation
 	DevBuf<double> partial;        // [slots * dp*dp]
 	DevBuf<double> S;              // [ld*ld + ld] when the caller does not supply the buffer
+	// A tile of S outside the filled mask is zero whenever a factorization starts: true while that is NOT known of the
+	// buffer S (after its allocation, and after any factorization on it other than the fully masked streamed launch,
+	// which never writes a tile without a workgroup). schur_form then clears the whole buffer, else the listed tiles.
+	bool unlisted_dirty = true;
+	// the side stream of schur_form (SPP_SCHUR_SIDE) has work the ctx stream has not waited for yet; padding and status
+	// reset of the coming factorization are already enqueued there
+	bool side_pending = false, side_padded = false;
+	int side_last = 0, clear_last = 0; // diagnostics of the last schur_form: SPP_INFO_SCHUR_SIDE, SPP_INFO_S_CLEAR
 	void release_all();
 };
 
@@ -296,6 +304,7 @@ struct DenseWork {
 	// word per tile row of 128, bit j = tile (i, j) is nonzero after symbolic fill (tile_mask_close). nullptr or a size
 	// that does not match the factorization's tile rows: every tile is nonzero.
 	const std::vector<uint64_t> *tile_mask = nullptr;
+	bool tail_masked_whole = false; // the last factorization was ONE streamed launch (no per-step front) under the caller's tile mask
 	int tail_rows_last = 0;        // tile rows the last factorization streamed (diagnostics: SPP_INFO_DENSE_STREAMED)
 	bool tail_disabled = false;    // a streamed launch timed out on this ctx: later factorizations take the per-step schedule
 	DevBuf<double> trsv_m;         // M_b = Tinv_b R_{b, b+1} per block row (M form of the backward substitution)
@@ -348,6 +357,11 @@ struct spp_ctx {
 	int flags = 0;
 	hipStream_t stream = nullptr;
 	bool own_stream = false;
+	// Schur stage: what the S accumulation does not feed (reduced rhs, padding, status reset) runs here beside it; forked
+	// from / joined into `stream` by the two events (created on first use, spp_schur.hip). Not dense.aux: that one is
+	// CU-masked and belongs to the per-step schedule of the dense factor.
+	hipStream_t side_stream = nullptr;
+	hipEvent_t side_ev[2] = {nullptr, nullptr};
 	std::string last_error;
 	int mode = -1; // -1: not analyzed
 	int shard_rank = 0, shard_world = 1;
@@ -461,24 +475,36 @@ int64_t sparse_fronts(const spp_ctx *ctx, int64_t capacity, int32_t *h, int32_t 
 	int32_t *parent, int32_t *team);
 
 // ---- spp_schur.hip ----
-void schur_form(spp_ctx *ctx, const double *d_vals, const double *d_rhs, double *d_S_rhs);
+// Observations from which on schur_form forks the side stream (SPP_SCHUR_SIDE=1). The fork and the join are one barrier
+// packet each on the ctx stream, ~6 us apiece on this runtime, 12 us together; rhs_kernel takes 6.1 us
+// at 31 843 observations (Ladybug-49, profiles/r03_ladybug49_kernel_stats.csv: the launch floor) and 63.8 us at 2 838 740
+// (Venice-871, profiles/r08_venice871_kernel_stats.csv). Between the two it reaches the 12 us of the hand-overs near
+// 300 000 observations; the threshold keeps a margin above that.
+constexpr int64_t SCHUR_SIDE_MIN_OBS = 500000;
+// one_call: spp_factor_solve_device runs (schur_finish follows on the same stream and takes over the join with the side stream)
+void schur_form(spp_ctx *ctx, const double *d_vals, const double *d_rhs, double *d_S_rhs, bool one_call = false);
 int schur_finish(spp_ctx *ctx, const double *d_vals, double *d_S_rhs, double *d_rhs);
 void schur_pack(spp_ctx *ctx, double *S, double *packed, bool pack);
 
 // ---- spp_dense.hip ----
 constexpr int DENSE_NB = 128;
 int dense_potrf_upper(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, bool keep_inverses);
-void dense_potrf_upper_enqueue(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld);
+// returns whether the whole factorization went to the streamed launch under the caller's tile mask (the one schedule that
+// leaves every tile outside the mask untouched); info_reset false: the caller has enqueued dense_info_reset_on() itself
+bool dense_potrf_upper_enqueue(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, bool info_reset = true);
 int dense_info_fetch(spp_ctx *ctx, bool *dag_aborted = nullptr); // dag_aborted given: a timed-out sparse launch is reported there instead of thrown
 void dense_potrs_upper(spp_ctx *ctx, const double *d_R, int64_t n, int64_t ld, double *d_b);
 void dense_aux_park(int device, hipStream_t s); // hands the bulk stream of a closing context to the next one
 void dense_factor_steps(spp_ctx *ctx, double *d_A, int64_t ld, int64_t n, int64_t rows, int64_t ncols,
 	int64_t nsteps, bool has_rhs);
 void dense_info_reset(spp_ctx *ctx);
+void dense_info_ensure(spp_ctx *ctx); // the status words exist (created and zeroed on the ctx stream)
+void dense_info_reset_on(spp_ctx *ctx, hipStream_t st); // ... reset on a stream the caller orders against the ctx stream
 void dense_reserve(spp_ctx *ctx, int64_t nblk); // workspaces for nblk diagonal blocks (call at analyze time)
 
 void dense_chain_check(spp_ctx *ctx); // call after the stream was synchronized
 void dense_set_padding(spp_ctx *ctx, double *d_A, int64_t ld, int64_t n);
+void dense_set_padding_on(hipStream_t st, double *d_A, int64_t ld, int64_t n);
 struct TileMaskGuard { // hands a tile mask to the factorizations enqueued while it lives
 	DenseWork &d;
 	TileMaskGuard(DenseWork &dw, const std::vector<uint64_t> *m) : d(dw) { d.tile_mask = (m && !m->empty()) ? m : nullptr; }

@@ -1041,6 +1041,8 @@ void backsubst_fused_kernel(const int32_t *__restrict__ bs_ptr, const int32_t *_
 	}
 }
 
+constexpr int BS_SCATTER_PER = 2048; // entries of the poses' dx a scatter workgroup of backsubst_stream_kernel copies
+
 // The fused kernel, streamed (SPP_LM_STREAM, even block sizes): a workgroup works through `per` consecutive groups. The
 // U blocks of a group are fetched like those of obs_fact_stream_kernel (each wave the 64 observations its lanes own), and
 // the pieces and dx of group g + 1 are requested BEFORE the landmark step of group g -- whose own operands were requested
@@ -1051,17 +1053,26 @@ template <int DP, int DL>
 __global__ __launch_bounds__(256)
 void backsubst_stream_kernel(int32_t n_bs, int32_t per, const int32_t *__restrict__ bs_ptr, const int32_t *__restrict__ lm_ptr, const int32_t *__restrict__ obs_pose,
 	const int64_t *__restrict__ obs_off, const int64_t *__restrict__ lm_rbase, const double *__restrict__ cinv,
-	const int64_t *__restrict__ lm_coff, const double *__restrict__ vals, const double *__restrict__ dx, double *__restrict__ rhs)
+	const int64_t *__restrict__ lm_coff, const double *__restrict__ vals, const double *__restrict__ dx, double *__restrict__ rhs,
+	int32_t n_scatter, int64_t nc, const int64_t *__restrict__ pose_rbase)
 {
 	constexpr int BLK = DP * DL, ST = BLK | 1;
 	static_assert(BLK % 2 == 0, "16-byte pieces");
+	// the first n_scatter workgroups do what scatter_dx_kernel does (dx of the poses to its place in rhs, BS_SCATTER_PER
+	// entries each): no landmark step reads or writes a pose's entries of rhs
+	if((int32_t)blockIdx.x < n_scatter) {
+		const int64_t e0 = (int64_t)blockIdx.x * BS_SCATTER_PER, e1 = (e0 + BS_SCATTER_PER < nc * DP) ? e0 + BS_SCATTER_PER : nc * DP;
+		for(int64_t e = e0 + threadIdx.x; e < e1; e += 256)
+			rhs[pose_rbase[e / DP] + e % DP] = dx[e];
+		return;
+	}
 	__shared__ double img_all[4][64 * ST];
 	__shared__ int64_t off_all[4][64];
 	__shared__ double tq_all[2][256 * DL];
 	const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
 	double *img = img_all[wave];
 	int64_t *off = off_all[wave];
-	const int32_t g0 = blockIdx.x * per, g1 = (g0 + per < n_bs) ? g0 + per : n_bs;
+	const int32_t g0 = ((int32_t)blockIdx.x - n_scatter) * per, g1 = (g0 + per < n_bs) ? g0 + per : n_bs;
 	// the group in flight
 	dbl2_a8 pc[BLK / 2] = {};
 	double dv[DP];
@@ -1195,22 +1206,91 @@ static void launch_backsubst_stream(dim3 grid, hipStream_t s, Args... args)
 		hipLaunchKernelGGL((backsubst_stream_kernel<DP, DL>), grid, dim3(256), 0, s, args...);
 }
 
+// The clear of a dense S whose tiles outside the filled mask are known to be zero (SchurPlan::unlisted_dirty): one
+// workgroup per 128 x 128 tile of the upper triangle, which leaves at once when its tile is not listed; a listed tile is
+// zeroed as 128 column pieces of 1 KB (64 lanes x 16 bytes, four columns per pass). The tile column of the reduced
+// right-hand side and of the padding columns is listed in every row (tile_mask_close); tile rows behind the mask (a
+// reduced system that fills its last tile row exactly has one of padding alone) are cleared whole.
+struct ClearArgs {
+	uint64_t rowbits[64];
+	int n_rows; // tile rows the mask has
+};
+
+__global__ __launch_bounds__(256)
+void s_clear_tiles_kernel(double *__restrict__ S, int64_t ld, ClearArgs a)
+{
+	const int j = (int)blockIdx.x, i = (int)blockIdx.y;
+	if(j < i || (i < a.n_rows && !((a.rowbits[i] >> j) & 1)))
+		return;
+	double *T = S + (int64_t)i * 128 + (int64_t)j * 128 * ld;
+	const int t = threadIdx.x, r = 2 * (t & 63), c0 = t >> 6;
+	const dbl2_a8 z = {0.0, 0.0};
+#pragma unroll 4
+	for(int c = c0; c < 128; c += 4)
+		*(dbl2_a8*)(T + r + (int64_t)c * ld) = z;
+}
+
+// the side stream and its two events: created on first use, destroyed with the context
+static void side_stream_ensure(spp_ctx *ctx)
+{
+	if(ctx->side_stream)
+		return;
+	SPP_HIP_CHECK(hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking));
+	SPP_HIP_CHECK(hipEventCreateWithFlags(&ctx->side_ev[0], hipEventDisableTiming));
+	SPP_HIP_CHECK(hipEventCreateWithFlags(&ctx->side_ev[1], hipEventDisableTiming));
+}
+
+// the ctx stream waits for what schur_form put on the side stream (a no-op when there is nothing)
+static void side_stream_join(spp_ctx *ctx)
+{
+	if(!ctx->schur.side_pending)
+		return;
+	SPP_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->side_ev[1], 0));
+	ctx->schur.side_pending = false;
+}
+
+// (an error of the query counts as capturing: a fork under capture would create parallel graph branches)
+static bool stream_capturing(hipStream_t s)
+{
+	hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+	return hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+}
+
 template <int DP, int DL>
-static void schur_form_t(spp_ctx *ctx, const double *d_vals, const double *d_rhs, double *S)
+static void schur_form_t(spp_ctx *ctx, const double *d_vals, const double *d_rhs, double *S, bool one_call)
 {
 	SchurPlan &sp = ctx->schur;
 	hipStream_t s = ctx->stream;
 	const int64_t ld = sp.ld;
 	const int64_t *voff = sp.sparse_S ? sp.sblk_voff.p : nullptr;
 	double *xcol = sp.sparse_S ? S + sp.s_st.nvals : S + sp.n_red * ld; // reduced rhs
+	side_stream_join(ctx); // (left behind by a call that failed between its fork and its join)
+	sp.side_padded = false;
 	phase_begin(ctx, SPP_PHASE_SCHUR_INV);
 	// Every written block of S is ASSIGNED by the accumulation kernels. When the (dense, unsharded) reduced system lives in
 	// the solver's own buffer (not a caller's: the split API hands S to an all-reduce) and has all of its upper blocks written, only the padding columns -- which carry the reduced rhs -- need
 	// clearing: nothing below the diagonal is ever an operand (220 MB memset -> 1 MB on the Venice shape).
-	if(S == sp.S.p && !sp.sparse_S && ctx->shard_world == 1 && sp.n_sblk == sp.nc * (sp.nc + 1) / 2 && sp.n_red == sp.nc * DP)
+	const bool own_dense = S == sp.S.p && !sp.sparse_S && ctx->shard_world == 1;
+	const int64_t n_trows = ld / 128;
+	if(own_dense && sp.n_sblk == sp.nc * (sp.nc + 1) / 2 && sp.n_red == sp.nc * DP) {
 		SPP_HIP_CHECK(hipMemsetAsync(S + sp.n_red * ld, 0, (size_t)(schur_buffer_doubles(ctx) - sp.n_red * ld) * sizeof(double), s));
-	else
+		sp.clear_last = 2;
+	} else if(own_dense && !sp.unlisted_dirty && !sp.tile_mask.empty() && (int64_t)sp.tile_mask.size() <= n_trows && n_trows <= 64) {
+		// every tile outside the filled mask is zero (the invariant the fully masked streamed factor keeps, see
+		// SchurPlan::unlisted_dirty): the listed tiles alone are cleared (Venice: 662 of 861 tiles, 85 of 219 MB)
+		ClearArgs ca;
+		memset(ca.rowbits, 0, sizeof(ca.rowbits));
+		for(size_t q = 0; q < sp.tile_mask.size(); ++ q)
+			ca.rowbits[q] = sp.tile_mask[q];
+		ca.n_rows = (int)sp.tile_mask.size();
+		hipLaunchKernelGGL(s_clear_tiles_kernel, dim3((unsigned)n_trows, (unsigned)n_trows), dim3(256), 0, s, S, ld, ca);
+		sp.clear_last = 1;
+	} else {
 		SPP_HIP_CHECK(hipMemsetAsync(S, 0, (size_t)schur_buffer_doubles(ctx) * sizeof(double), s));
+		sp.clear_last = 0;
+		if(own_dense)
+			sp.unlisted_dirty = false; // (schur_finish sets it again from the schedule its factorization takes)
+	}
 	constexpr int VIL = VSplit<DP * DL>::IL;
 	double *Vm = sp.W.p, *Vs = sp.W.p + sp.no * VIL; // factored form: in-line rows, then the side array, in the one buffer W
 	const bool onfly = sp.factored && DL <= 3; // F and -(C^-1) formed where they are used: no cinv_kernel
@@ -1233,6 +1313,39 @@ static void schur_form_t(spp_ctx *ctx, const double *d_vals, const double *d_rhs
 		hipLaunchKernelGGL((obs_kernel<DP, DL>), obs_grid, dim3(256), 0, s,
 			sp.no, sp.obs_lm.p, sp.obs_off.p, sp.lm_rbase.p, d_vals, d_rhs, sp.cinv.p, sp.obs_wpos.p, sp.W.p, sp.Up.p, sp.xw.p, sp.u_landmark_major ? 1 : 0);
 	phase_end(ctx, SPP_PHASE_SCHUR_INV);
+	// What the S accumulation does not feed -- the reduced right-hand side (it needs xw and d_rhs alone), and in the one-call
+	// path the padding of S and the status reset -- goes to the side stream, enqueued BEFORE s_accum_kernel so that its few
+	// workgroups are seated at once: rhs_kernel is latency-bound on less than a workgroup per CU, s_accum_kernel is
+	// throughput-bound on all of them. Hand-overs are events. The serial order stays under stream capture, with profiling on
+	// (phase_ms keeps its meaning) and below SCHUR_SIDE_MIN_OBS observations.
+	const int side_sw = switches().schur_side;
+	const bool side = side_sw != 0 && sp.nc > 0 && (side_sw == 2 || sp.no >= SCHUR_SIDE_MIN_OBS) &&
+		!(ctx->flags & SPP_FLAG_PROFILE) && !stream_capturing(s);
+	sp.side_last = side ? 1 : 0;
+	auto launch_rhs = [&](hipStream_t st) {
+		if(sp.nc && lm_stream == 1)
+			hipLaunchKernelGGL((rhs_kernel<DP, true>), dim3((unsigned)((sp.nc + 3) / 4)), dim3(256), 0, st,
+				sp.nc, sp.cam_ptr.p, sp.cam_obs.p, sp.pose_rbase.p, sp.xw.p, d_rhs, sp.add_A ? 1 : 0, xcol);
+		else if(sp.nc)
+			hipLaunchKernelGGL((rhs_kernel<DP, false>), dim3((unsigned)((sp.nc + 3) / 4)), dim3(256), 0, st,
+				sp.nc, sp.cam_ptr.p, sp.cam_obs.p, sp.pose_rbase.p, sp.xw.p, d_rhs, sp.add_A ? 1 : 0, xcol);
+	};
+	if(side) {
+		side_stream_ensure(ctx);
+		const bool pad_here = one_call && own_dense;
+		if(pad_here)
+			dense_info_ensure(ctx);
+		SPP_HIP_CHECK(hipEventRecord(ctx->side_ev[0], s));
+		SPP_HIP_CHECK(hipStreamWaitEvent(ctx->side_stream, ctx->side_ev[0], 0));
+		launch_rhs(ctx->side_stream);
+		if(pad_here) {
+			dense_set_padding_on(ctx->side_stream, S, ld, sp.n_red);
+			dense_info_reset_on(ctx, ctx->side_stream);
+			sp.side_padded = true;
+		}
+		SPP_HIP_CHECK(hipEventRecord(ctx->side_ev[1], ctx->side_stream));
+		sp.side_pending = true;
+	}
 	phase_begin(ctx, SPP_PHASE_SCHUR_GEMM);
 	if(sp.n_items) {
 		int chunk = switches().sacc_chunk; // items per wave
@@ -1252,12 +1365,10 @@ static void schur_form_t(spp_ctx *ctx, const double *d_vals, const double *d_rhs
 			sp.partial.p, d_vals, sp.add_A ? 1 : 0, S, ld, voff);
 	phase_end(ctx, SPP_PHASE_SCHUR_GEMM);
 	phase_begin(ctx, SPP_PHASE_SCHUR_RHS);
-	if(sp.nc && lm_stream == 1)
-		hipLaunchKernelGGL((rhs_kernel<DP, true>), dim3((unsigned)((sp.nc + 3) / 4)), dim3(256), 0, s,
-			sp.nc, sp.cam_ptr.p, sp.cam_obs.p, sp.pose_rbase.p, sp.xw.p, d_rhs, sp.add_A ? 1 : 0, xcol);
-	else if(sp.nc)
-		hipLaunchKernelGGL((rhs_kernel<DP, false>), dim3((unsigned)((sp.nc + 3) / 4)), dim3(256), 0, s,
-			sp.nc, sp.cam_ptr.p, sp.cam_obs.p, sp.pose_rbase.p, sp.xw.p, d_rhs, sp.add_A ? 1 : 0, xcol);
+	if(!side)
+		launch_rhs(s);
+	else if(!one_call)
+		side_stream_join(ctx); // split API: schur_pack reads S | rhs on the ctx stream next (one call: schur_finish joins in front of the factor)
 	phase_end(ctx, SPP_PHASE_SCHUR_RHS);
 	SPP_HIP_CHECK(hipGetLastError());
 }
@@ -1269,6 +1380,7 @@ static int schur_finish_t(spp_ctx *ctx, const double *d_vals, double *S, double 
 	hipStream_t s = ctx->stream;
 	const int64_t ld = sp.ld;
 	double *xcol;
+	side_stream_join(ctx); // the reduced rhs (and padding, status reset) of a one-call schur_form
 	if(sp.sparse_S) {
 		// supernodal multifrontal factorization + solves of the sparse reduced camera system (the
 		// reference's CLinearSolver_Schur with a sparse inner solver, LinearSolver_Schur.h:1844-1853)
@@ -1278,15 +1390,25 @@ static int schur_finish_t(spp_ctx *ctx, const double *d_vals, double *S, double 
 			return ret;
 	} else {
 		phase_begin(ctx, SPP_PHASE_FACTOR);
-		dense_set_padding(ctx, S, ld, sp.n_red);
+		if(!sp.side_padded)
+			dense_set_padding(ctx, S, ld, sp.n_red);
 		// the status of the factorization is fetched at the very end: a host round trip here would leave the GPU
 		// idle for ~40 us before the solves (after a failure they run on garbage and the result is discarded)
 		{
 			// S is a band plus what elimination fills: the streamed launch skips the tiles that stay zero. The mask covers the
 			// landmarks of every shard, so it also holds for an S summed over the ranks.
 			TileMaskGuard guard(ctx->dense, &sp.tile_mask);
-			dense_potrf_upper_enqueue(ctx, S, sp.n_red, ld);
+			// any schedule but the fully masked streamed launch (per-step, unmasked, a row panel in front of the streamed
+			// launch) writes tiles outside the mask: the next schur_form on this buffer then clears all of it. (Set first: a
+			// call that fails halfway leaves the buffer marked.)
+			const bool own = S == sp.S.p;
+			if(own)
+				sp.unlisted_dirty = true;
+			const bool masked_whole = dense_potrf_upper_enqueue(ctx, S, sp.n_red, ld, !sp.side_padded);
+			if(own && masked_whole)
+				sp.unlisted_dirty = false;
 		}
+		sp.side_padded = false;
 		phase_end(ctx, SPP_PHASE_FACTOR);
 		xcol = S + sp.n_red * ld;
 		phase_begin(ctx, SPP_PHASE_TRISOLVE);
@@ -1300,10 +1422,14 @@ static int schur_finish_t(spp_ctx *ctx, const double *d_vals, double *S, double 
 	// consecutive groups per workgroup of the streamed kernel: 4 where that still leaves every CU a workgroup, else 1 (a
 	// small problem wants all of its groups side by side, not a pipeline: Ladybug-49 has 130 groups)
 	const int32_t bs_per = (sp.n_bs >= 1024) ? 4 : 1;
-	if(bs_fused && sp.n_bs > 0 && lm_stream_form<DP, DL>(sp))
-		launch_backsubst_stream<DP, DL>(dim3((unsigned)((sp.n_bs + bs_per - 1) / bs_per)), s,
+	// the streamed kernel copies the poses' dx itself (its first bs_scatter workgroups): no scatter_dx launch behind it
+	const bool bs_stream = bs_fused && sp.n_bs > 0 && lm_stream_form<DP, DL>(sp);
+	const int32_t bs_scatter = bs_stream ? (int32_t)((sp.nc * DP + BS_SCATTER_PER - 1) / BS_SCATTER_PER) : 0;
+	if(bs_stream)
+		launch_backsubst_stream<DP, DL>(dim3((unsigned)((sp.n_bs + bs_per - 1) / bs_per + bs_scatter)), s,
 			(int32_t)sp.n_bs, bs_per, (const int32_t*)sp.bs_ptr.p, (const int32_t*)sp.lm_ptr.p, (const int32_t*)sp.obs_pose.p, (const int64_t*)sp.obs_off.p,
-			(const int64_t*)sp.lm_rbase.p, cinv_arg, (const int64_t*)sp.lm_coff.p, d_vals, (const double*)xcol, d_rhs);
+			(const int64_t*)sp.lm_rbase.p, cinv_arg, (const int64_t*)sp.lm_coff.p, d_vals, (const double*)xcol, d_rhs,
+			bs_scatter, (int64_t)sp.nc, (const int64_t*)sp.pose_rbase.p);
 	else if(bs_fused && sp.n_bs > 0)
 		hipLaunchKernelGGL((backsubst_fused_kernel<DP, DL>), dim3((unsigned)sp.n_bs), dim3(256), 0, s,
 			sp.bs_ptr.p, sp.lm_ptr.p, sp.obs_pose.p, sp.obs_off.p, sp.lm_rbase.p, cinv_arg, sp.lm_coff.p, d_vals, xcol, d_rhs);
@@ -1315,7 +1441,7 @@ static int schur_finish_t(spp_ctx *ctx, const double *d_vals, double *S, double 
 			hipLaunchKernelGGL((backsubst_lm_kernel<DL>), dim3((unsigned)((sp.nl + 255) / 256)), dim3(256), 0, s,
 				sp.nl, sp.lm_ptr.p, sp.lm_rbase.p, sp.xw.p, cinv_arg, sp.lm_coff.p, d_vals, d_rhs);
 	}
-	if(sp.nc)
+	if(sp.nc && !bs_stream)
 		hipLaunchKernelGGL((scatter_dx_kernel<DP>), dim3((unsigned)((sp.nc * DP + 255) / 256)), dim3(256), 0, s,
 			sp.nc, sp.pose_rbase.p, xcol, d_rhs);
 	phase_end(ctx, SPP_PHASE_BACKSUBST);
@@ -1356,13 +1482,13 @@ void schur_pack(spp_ctx *ctx, double *S, double *packed, bool pack)
 	SPP_HIP_CHECK(hipGetLastError());
 }
 
-void schur_form(spp_ctx *ctx, const double *d_vals, const double *d_rhs, double *d_S_rhs)
+void schur_form(spp_ctx *ctx, const double *d_vals, const double *d_rhs, double *d_S_rhs, bool one_call)
 {
 	const int dp = ctx->schur.dp, dl = ctx->schur.dl;
-	if(dp == 6 && dl == 3) schur_form_t<6, 3>(ctx, d_vals, d_rhs, d_S_rhs);
-	else if(dp == 3 && dl == 2) schur_form_t<3, 2>(ctx, d_vals, d_rhs, d_S_rhs);
-	else if(dp == 3 && dl == 3) schur_form_t<3, 3>(ctx, d_vals, d_rhs, d_S_rhs);
-	else if(dp == 6 && dl == 6) schur_form_t<6, 6>(ctx, d_vals, d_rhs, d_S_rhs);
+	if(dp == 6 && dl == 3) schur_form_t<6, 3>(ctx, d_vals, d_rhs, d_S_rhs, one_call);
+	else if(dp == 3 && dl == 2) schur_form_t<3, 2>(ctx, d_vals, d_rhs, d_S_rhs, one_call);
+	else if(dp == 3 && dl == 3) schur_form_t<3, 3>(ctx, d_vals, d_rhs, d_S_rhs, one_call);
+	else if(dp == 6 && dl == 6) schur_form_t<6, 6>(ctx, d_vals, d_rhs, d_S_rhs, one_call);
 	else throw Error(SPP_E_UNSUPPORTED, "Schur kernels: block widths not instantiated");
 }
 

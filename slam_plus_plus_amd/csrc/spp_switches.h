@@ -59,6 +59,7 @@ struct Switches {
 	int sacc_chunk;           // SPP_SACC_CHUNK (1): items per wave (<= 0 = one persistent set of workgroups). Measured on the Venice shape: 1 -> 0.86 ms, 4...16 -> 0.98 ms, persistent 1.5 ms: the hardware's dynamic dispatch of one-item waves balances the uneven items (1 ... 2048 pairs) better than the software pipeline across items hides latency
 	int schur_cam_order;      // SPP_SCHUR_CAM_ORDER (1): dense S with a tile mask: the cameras of a closed loop are ordered arc, arc, separators (tile-aligned dissection, schur_cam_order) when the cost model of the streamed factor gains 10 %; 0: the natural order always
 	int backsubst_fused;      // SPP_BACKSUBST_FUSED (1): 0: the products U^T dx through memory, two launches (rounds 1-3)
+	int schur_side;           // SPP_SCHUR_SIDE (1): the reduced right-hand side, the padding of S and the status reset run on a side stream beside the S accumulation, from SCHUR_SIDE_MIN_OBS observations on; 0: the serial order on the one stream; 2: the side stream whatever the size (tests)
 	int lm_stream;            // SPP_LM_STREAM (1): (factored form, 6 x 3 blocks) the landmark-side kernels fetch U cooperatively in 16-byte pieces, xw in observation order, the fused back-substitution with the next group's fetch in flight; 2: the same with xw camera-major in 16-byte pieces (measured slower: Venice step 2.675 against 2.618 ms); 0: one lane per block (rounds 3-7)
 
 	// ---- sparse path (spp_sparse.hip)
@@ -130,6 +131,7 @@ inline Switches parse_switches()
 	w.sacc_chunk = env_int("SPP_SACC_CHUNK", 1);
 	w.schur_cam_order = env_int("SPP_SCHUR_CAM_ORDER", 1);
 	w.backsubst_fused = env_int("SPP_BACKSUBST_FUSED", 1);
+	w.schur_side = env_int("SPP_SCHUR_SIDE", 1);
 	w.lm_stream = env_int("SPP_LM_STREAM", 1);
 
 	w.mid_front_max = std::max(128, std::min(MID_FRONT_MAX, env_int("SPP_MID_FRONT_MAX", 320)));
