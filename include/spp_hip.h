@@ -119,6 +119,7 @@ int spp_set_shard(spp_ctx *ctx, int rank, int world_size);
 #define SPP_INFO_SCHUR_SIDE     19 /* the last spp_schur_form / solve ran the reduced right-hand side on the side stream (SPP_SCHUR_SIDE): 1, else 0 */
 #define SPP_INFO_S_CLEAR        20 /* what the last spp_schur_form / solve cleared of its S buffer: 0 all of it, 1 the tiles of the filled mask, 2 the right-hand side and padding columns (every block of S is written) */
 #define SPP_INFO_S_DEVICE_PTR   21 /* diagnostics, tests: device address of the S | rhs buffer spp_factor_solve owns (0: none yet) */
+#define SPP_INFO_ASM_HUB_CHUNK   22 /* assembly of ternary edges: edges one workgroup of the hub reduction sums (C); a constant, needs no analysis */
 int spp_get_info(const spp_ctx *ctx, int what, int64_t *out);
 /* elimination order chosen by the analysis: order[k] = source block column eliminated k-th */
 int spp_get_ordering(const spp_ctx *ctx, int64_t *h_order);
@@ -235,6 +236,29 @@ int spp_assemble_analyze_groups(spp_ctx *ctx, int64_t nv, const int32_t *h_dim, 
 int spp_assemble_groups_device(spp_ctx *ctx, const double *const *d_J0, const double *const *d_J1,
 	const double *const *d_Omega, const double *const *d_r, double damping, double *d_vals_out, double *d_eta_out);
 int spp_assemble_set_group_edge_weights(spp_ctx *ctx, int group, const double *d_w);
+/* Ternary edges: self-calibrating bundle adjustment, one residual of CEdgeP2CI3D (include/slam/BA_Types.h:562-700) feeding
+ * a camera v0 (6), a point v1 (3) and an intrinsics vertex v2 (CVertexIntrinsics, :141-206: 5 coordinates fx fy cx cy kappa).
+ * replaces, for an n-ary edge: Alloc_HessianBlocks_v2 (symbolic; include/slam/BaseTypes.h:1540-1767: one upper block per
+ * pair of the edge's vertices, transposed when the ids are reversed) and Calculate_Hessians_v2 (numeric; :1981-2130) + the
+ * reduction plan (NonlinearSolver_Lambda_Base.h:563-607, 152-197).
+ * Inside this library an intrinsics vertex is d2 = 6 WIDE with live2 = 5 live coordinates and one inert one: h_dim[v2] is 6,
+ * J2 is ne x (2x6) column-major with a zero last column, the assembly puts 1.0 on the inert diagonal entry (before the
+ * damping), its row and column are otherwise exact zeros and its eta entry is 0 -- the solution's inert entry is exactly
+ * +-0, and Lambda keeps the two widths {6, 3} of the guided Schur mode, with "poses" = cameras + intrinsics.
+ * One instantiated shape: (d0, d1, d2, rd) = (6,3,6,2) with live2 = 5; anything else is SPP_E_UNSUPPORTED. SPP_E_BADARG: a
+ * bad index, a vertex width that does not match, two equal vertices in one edge, a vertex that is the camera of one edge
+ * and the intrinsics of another; the ctx then holds no assembly plan. Structure (spp_assemble_get_structure): every
+ * diagonal block and one upper block per connected pair among (v0, v1), (v0, v2), (v1, v2). Every destination is summed
+ * in edge order: H00, H01, H11, g0, g1 by the kernels of spp_assemble_device on the (6,3,2) edges (v0, v1), bit for bit;
+ * what touches an intrinsics vertex -- H02, H12, H22, g2 -- sequentially (first assigned, rest added) up to 24 edges, beyond
+ * that by a two-stage reduction over chunks of SPP_INFO_ASM_HUB_CHUNK edges whose result depends on that constant alone
+ * (DESIGN section 20). The unary factor is the identity on the LIVE coordinates of unary_vertex when that is an
+ * intrinsics vertex; `damping` is added to every diagonal entry. Robust weights: SPP_E_UNSUPPORTED on such a plan.
+ * SPP_E_STATE: spp_assemble_ternary_device without a ternary plan, spp_assemble_device / _groups_device on one. */
+int spp_assemble_analyze_ternary(spp_ctx *ctx, int64_t nv, const int32_t *h_dim, int64_t ne, const int64_t *h_v0,
+	const int64_t *h_v1, const int64_t *h_v2, int d0, int d1, int d2, int live2, int rd, int64_t unary_vertex);
+int spp_assemble_ternary_device(spp_ctx *ctx, const double *d_J0, const double *d_J1, const double *d_J2,
+	const double *d_Omega, const double *d_r, double damping, double *d_vals_out, double *d_eta_out);
 /* the weights themselves, on the device: w_e = kernel(||r_e|| / scale) -- CRobustify_ErrorNorm_Default::f_RobustWeight
  * (include/slam/RobustUtils.h:396-400) with kind 0 = Huber, w = 1 for x <= param, param / x beyond (CHuberLoss::operator (),
  * include/geometry/RobustLoss.h:100-104; the reference's default param is 1.345). Asynchronous on the ctx stream. */
@@ -346,6 +370,27 @@ int spp_ba_update_device(spp_ctx *ctx, int64_t n_cams, double *d_cams, const int
 int spp_ba_stereo_linearize_device(spp_ctx *ctx, int64_t n_obs, const int32_t *d_cam_of, const int32_t *d_pt_of,
 	const double *d_cams, const double *d_intrinsics, const double *d_points, const double *d_measurements,
 	double *d_J0, double *d_J1, double *d_r);
+
+/* ---- on-device geometry of self-calibrating bundle adjustment (CEdgeP2CI3D, include/slam/BA_Types.h:562-700) ----
+ * Cameras: 6 doubles each [t | axis-angle], world -> camera; intrinsics VERTICES: 5 doubles each (fx fy cx cy kappa:
+ * CVertexIntrinsics, BA_Types.h:141-206), observation e uses d_intrinsics + 5 intr_of[e]; points: XYZ.
+ * spp_ba_intrinsics_linearize_device evaluates CBAJacobians::Project_P2C (include/slam/BASolverBase.h:260-327): p - c =
+ * (fx x0/x2, fy x1/x2), k = kappa / (0.5 (fx + fy)), uv = c + (1 + r^2 k)(p - c), r = |p - c|; residual z - uv. J0, J1 and
+ * the residual come from the device function of spp_ba_linearize_device and are bit-identical to its output for the
+ * gathered per-camera intrinsics. J2 (no x (2x6) column-major, last column zeros: the inert coordinate) is analytic
+ * w.r.t. the plain increment of Relative_to_Absolute_Intrinsics (BASolverBase.h:204-212), where the reference takes
+ * forward differences with delta = 1e-9 (:690-759); nothing is divided by r, a point on the optical axis gives finite
+ * Jacobians. Output = input of spp_assemble_ternary_device.
+ * spp_ba_intrinsics_update_device: ||dx||^2 over the 5 LIVE entries dx[intr_dxoff[i] .. +5) of every intrinsics vertex ->
+ * *h_dx_norm2 and, if `apply`, CVertexIntrinsics::Operator_Plus AS WRITTEN (BA_Types.h:170-185): fx fy cx cy plain sums,
+ * kappa' = (kappa + dkappa) / (0.5 fx fy) * (0.5 fx' fy') -- renormalised through the PRODUCT of the focal lengths of the old
+ * and of the new state. Cameras and points keep spp_ba_update_device (whose norm over the padded dx already holds the
+ * intrinsics' share: the inert entries are zero). Synchronizes the stream. */
+int spp_ba_intrinsics_linearize_device(spp_ctx *ctx, int64_t n_obs, const int32_t *d_cam_of, const int32_t *d_pt_of,
+	const int32_t *d_intr_of, const double *d_cams, const double *d_intrinsics, const double *d_points,
+	const double *d_measurements, double *d_J0, double *d_J1, double *d_J2, double *d_r);
+int spp_ba_intrinsics_update_device(spp_ctx *ctx, int64_t n_intrinsics, double *d_intrinsics, const int64_t *d_intr_dxoff,
+	const double *d_dx, int apply, double *h_dx_norm2);
 
 /* ---- scalars of the Levenberg-Marquardt control (include/slam/NonlinearSolver_Lambda_LM.h) ----------
  * chi2 = sum_e r_e^T Omega_e r_e (f_Error, :1078-1095); the largest diagonal entry of any vertex Hessian

@@ -22,7 +22,7 @@ MODE_AUTO, MODE_SPARSE, MODE_SCHUR, MODE_SCHUR_SPARSE, MODE_SCHUR_MIS = 0, 1, 2,
 FLAG_PROFILE = 1
 INFO = dict(MODE=0, N=1, NNZB=2, NVALS=3, FACTOR_NNZ=4, FACTOR_FLOPS=5, N_REDUCED=6, N_POSES=7,
             N_LANDMARKS=8, SCHUR_PAIRS=9, N_OBS=10, SOLVE_BYTES=11, N_SUPERNODES=12, N_LEVELS=13, S_LD=14, S_NNZB=15, DENSE_STREAMED=16,
-            LM_STREAM=17, BS_GROUPS=18, SCHUR_SIDE=19, S_CLEAR=20, S_DEVICE_PTR=21)
+            LM_STREAM=17, BS_GROUPS=18, SCHUR_SIDE=19, S_CLEAR=20, S_DEVICE_PTR=21, ASM_HUB_CHUNK=22)
 PHASES = ["permute", "schur_inv", "schur_gemm", "schur_rhs", "factor", "trisolve", "backsubst", "assemble", "total"]
 
 # every symbol include/spp_hip.h declares (tests/test_abi.py checks the .so exports them all)
@@ -33,6 +33,8 @@ EXPORTS = [
     "spp_schur_packed_size", "spp_schur_pack", "spp_schur_unpack",
     "spp_assemble_analyze", "spp_assemble_get_structure", "spp_assemble_device", "spp_assemble_set_edge_weights",
     "spp_assemble_analyze_groups", "spp_assemble_groups_device", "spp_assemble_set_group_edge_weights",
+    "spp_assemble_analyze_ternary", "spp_assemble_ternary_device", "spp_ba_intrinsics_linearize_device",
+    "spp_ba_intrinsics_update_device",
     "spp_se2_linearize_at_device", "spp_se2_rb_linearize_device", "spp_slam2d_update_device",
     "spp_se3_linearize_at_device", "spp_se3_xyz_linearize_device", "spp_slam3d_update_device", "spp_device_malloc",
     "spp_device_free", "spp_memcpy_h2d", "spp_memcpy_d2h", "spp_memcpy_d2d", "spp_get_phase_ms", "spp_get_dominant_kernel",
@@ -89,6 +91,10 @@ def load_library():
         "spp_assemble_analyze_groups": (cint, [vp, i64, vp, cint, vp, vp, vp, vp, vp, vp, vp, i64]),
         "spp_assemble_groups_device": (cint, [vp, vp, vp, vp, vp, dbl, vp, vp]),
         "spp_assemble_set_group_edge_weights": (cint, [vp, cint, vp]),
+        "spp_assemble_analyze_ternary": (cint, [vp, i64, vp, i64, vp, vp, vp, cint, cint, cint, cint, cint, i64]),
+        "spp_assemble_ternary_device": (cint, [vp, vp, vp, vp, vp, vp, dbl, vp, vp]),
+        "spp_ba_intrinsics_linearize_device": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "spp_ba_intrinsics_update_device": (cint, [vp, i64, vp, vp, vp, cint, _c_f64p]),
         "spp_se2_linearize_at_device": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
         "spp_se2_rb_linearize_device": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
         "spp_slam2d_update_device": (cint, [vp, i64, vp, vp, i64, vp, cint, _c_f64p]),
@@ -436,6 +442,20 @@ class Context:
                                                   d_dx, n_dx, 1 if apply else 0, ctypes.byref(out)))
         return out.value ** 0.5
 
+    def ba_intrinsics_linearize_device(self, n_obs, d_cam_of, d_pt_of, d_intr_of, d_cams, d_intr, d_points, d_meas,
+                                       d_J0, d_J1, d_J2, d_r):
+        """CEdgeP2CI3D: intr 5 per intrinsics VERTEX (fx fy cx cy kappa), intr_of int32 per observation; J0 2x6, J1 2x3,
+        J2 2x6 (last column zeros), r 2"""
+        return self._check(self.lib.spp_ba_intrinsics_linearize_device(self.h, n_obs, d_cam_of, d_pt_of, d_intr_of, d_cams,
+                                                                       d_intr, d_points, d_meas, d_J0, d_J1, d_J2, d_r))
+
+    def ba_intrinsics_update_device(self, n_intr, d_intr, d_intr_dxoff, d_dx, apply=True):
+        """returns ||dx|| over the live coordinates of the intrinsics vertices; when `apply`, CVertexIntrinsics::Operator_Plus"""
+        out = ctypes.c_double()
+        self._check(self.lib.spp_ba_intrinsics_update_device(self.h, n_intr, d_intr, d_intr_dxoff, d_dx, 1 if apply else 0,
+                                                             ctypes.byref(out)))
+        return out.value ** 0.5
+
     def set_profiling(self, on):
         return self._check(self.lib.spp_set_profiling(self.h, 1 if on else 0))
 
@@ -518,6 +538,18 @@ class Context:
                                                           None if seq is None else parr(sq), _ptr(d0), _ptr(d1), _ptr(rd),
                                                           int(unary_vertex)))
         return self._assemble_structure(dim)
+
+    def assemble_analyze_ternary(self, dim, v0, v1, v2, unary_vertex=-1, shape=(6, 3, 6, 2), live2=5):
+        """ternary edges (camera v0, point v1, intrinsics v2; the intrinsics vertices 6 wide in dim). Returns the union
+        structure, as assemble_analyze does."""
+        dim = np.ascontiguousarray(dim, dtype=np.int32)
+        v0, v1, v2 = (np.ascontiguousarray(v, dtype=np.int64) for v in (v0, v1, v2))
+        self._check(self.lib.spp_assemble_analyze_ternary(self.h, dim.size, _ptr(dim), v0.size, _ptr(v0), _ptr(v1), _ptr(v2),
+                                                           shape[0], shape[1], shape[2], live2, shape[3], int(unary_vertex)))
+        return self._assemble_structure(dim)
+
+    def assemble_ternary_device(self, d_J0, d_J1, d_J2, d_Om, d_r, damping, d_vals, d_eta):
+        return self._check(self.lib.spp_assemble_ternary_device(self.h, d_J0, d_J1, d_J2, d_Om, d_r, float(damping), d_vals, d_eta))
 
     def assemble_groups_device(self, d_J0, d_J1, d_Om, d_r, damping, d_vals, d_eta):
         """d_J0 ... d_r: one device pointer per group"""

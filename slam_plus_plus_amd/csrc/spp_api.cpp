@@ -379,7 +379,8 @@ int spp_get_info(const spp_ctx *ctx, int what, int64_t *out)
 {
 	if(!ctx || !out)
 		return SPP_E_BADARG;
-	if(ctx->mode < 0 && what != SPP_INFO_NNZB && what != SPP_INFO_NVALS && what != SPP_INFO_N && what != SPP_INFO_DENSE_STREAMED)
+	if(ctx->mode < 0 && what != SPP_INFO_NNZB && what != SPP_INFO_NVALS && what != SPP_INFO_N && what != SPP_INFO_DENSE_STREAMED &&
+	   what != SPP_INFO_ASM_HUB_CHUNK)
 		return SPP_E_STATE;
 	switch(what) {
 	case SPP_INFO_MODE: *out = (ctx->mode != SPP_MODE_SCHUR) ? ctx->mode : ctx->schur.mis ? SPP_MODE_SCHUR_MIS :
@@ -405,6 +406,7 @@ int spp_get_info(const spp_ctx *ctx, int what, int64_t *out)
 	case SPP_INFO_SCHUR_SIDE: *out = (ctx->mode == SPP_MODE_SCHUR) ? ctx->schur.side_last : 0; break;
 	case SPP_INFO_S_CLEAR: *out = (ctx->mode == SPP_MODE_SCHUR) ? ctx->schur.clear_last : 0; break;
 	case SPP_INFO_S_DEVICE_PTR: *out = (ctx->mode == SPP_MODE_SCHUR) ? (int64_t)(uintptr_t)ctx->schur.S.p : 0; break;
+	case SPP_INFO_ASM_HUB_CHUNK: *out = ASM_HUB_CHUNK; break;
 	default: return SPP_E_BADARG;
 	}
 	return SPP_OK;
@@ -757,6 +759,7 @@ int spp_assemble_device(spp_ctx *ctx, const double *d_J0, const double *d_J1, co
 	SPP_TRY(ctx)
 	SPP_REQUIRE(ctx->assemble, SPP_E_STATE, "spp_assemble_device: call spp_assemble_analyze first");
 	SPP_REQUIRE(assemble_n_groups(ctx) == 1, SPP_E_STATE, "spp_assemble_device: the plan has several edge groups (spp_assemble_groups_device)");
+	SPP_REQUIRE(!assemble_is_ternary(ctx), SPP_E_STATE, "spp_assemble_device: the plan is one of ternary edges (spp_assemble_ternary_device)");
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	phases_reset(ctx);
 	phase_begin(ctx, SPP_PHASE_ASSEMBLE);
@@ -774,6 +777,7 @@ int spp_assemble_groups_device(spp_ctx *ctx, const double *const *d_J0, const do
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
 	SPP_REQUIRE(ctx->assemble, SPP_E_STATE, "spp_assemble_groups_device: call spp_assemble_analyze_groups first");
+	SPP_REQUIRE(!assemble_is_ternary(ctx), SPP_E_STATE, "spp_assemble_groups_device: the plan is one of ternary edges (spp_assemble_ternary_device)");
 	for(int g = 0; g < assemble_n_groups(ctx); ++ g) // (a group without edges needs no arrays)
 		SPP_REQUIRE(!assemble_group_edges(ctx, g) || (d_J0[g] && d_J1[g] && d_Omega[g] && d_r[g]), SPP_E_BADARG,
 			"spp_assemble_groups_device: null array of an edge group");
@@ -787,12 +791,76 @@ int spp_assemble_groups_device(spp_ctx *ctx, const double *const *d_J0, const do
 	SPP_CATCH(ctx)
 }
 
+int spp_assemble_analyze_ternary(spp_ctx *ctx, int64_t nv, const int32_t *h_dim, int64_t ne, const int64_t *h_v0,
+	const int64_t *h_v1, const int64_t *h_v2, int d0, int d1, int d2, int live2, int rd, int64_t unary_vertex)
+{
+	if(!ctx)
+		return SPP_E_BADARG;
+	assemble_release(ctx); // whatever happens below: after a rejected call the ctx holds no assembly plan
+	if(!h_dim || !h_v0 || !h_v1 || !h_v2 || nv <= 0 || ne <= 0)
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	SPP_REQUIRE(d0 == 6 && d1 == 3 && d2 == 6 && live2 == 5 && rd == 2, SPP_E_UNSUPPORTED,
+		"ternary edge shape (d0, d1, d2, rd) / live2 not instantiated: (6,3,6,2) / 5");
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	assemble_analyze_ternary(ctx, nv, h_dim, ne, h_v0, h_v1, h_v2, unary_vertex);
+	return SPP_OK;
+	SPP_CATCH(ctx)
+}
+
+int spp_assemble_ternary_device(spp_ctx *ctx, const double *d_J0, const double *d_J1, const double *d_J2,
+	const double *d_Omega, const double *d_r, double damping, double *d_vals_out, double *d_eta_out)
+{
+	if(!ctx || !d_J0 || !d_J1 || !d_J2 || !d_Omega || !d_r || !d_vals_out || !d_eta_out)
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	SPP_REQUIRE(ctx->assemble && assemble_is_ternary(ctx), SPP_E_STATE, "spp_assemble_ternary_device: call spp_assemble_analyze_ternary first");
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	phases_reset(ctx);
+	phase_begin(ctx, SPP_PHASE_ASSEMBLE);
+	assemble_ternary_run(ctx, d_J0, d_J1, d_J2, d_Omega, d_r, damping, d_vals_out, d_eta_out);
+	phase_end(ctx, SPP_PHASE_ASSEMBLE);
+	phases_collect(ctx);
+	return SPP_OK;
+	SPP_CATCH(ctx)
+}
+
+int spp_ba_intrinsics_linearize_device(spp_ctx *ctx, int64_t n_obs, const int32_t *d_cam_of, const int32_t *d_pt_of,
+	const int32_t *d_intr_of, const double *d_cams, const double *d_intrinsics, const double *d_points,
+	const double *d_measurements, double *d_J0, double *d_J1, double *d_J2, double *d_r)
+{
+	if(!ctx || n_obs < 0 || !d_cam_of || !d_pt_of || !d_intr_of || !d_cams || !d_intrinsics || !d_points || !d_measurements ||
+	   !d_J0 || !d_J1 || !d_J2 || !d_r)
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	ba_intrinsics_linearize(ctx, n_obs, d_cam_of, d_pt_of, d_intr_of, d_cams, d_intrinsics, d_points, d_measurements, d_J0, d_J1,
+		d_J2, d_r);
+	return SPP_OK;
+	SPP_CATCH(ctx)
+}
+
+int spp_ba_intrinsics_update_device(spp_ctx *ctx, int64_t n_intrinsics, double *d_intrinsics, const int64_t *d_intr_dxoff,
+	const double *d_dx, int apply, double *h_dx_norm2)
+{
+	if(!ctx || n_intrinsics < 0 || !d_dx || (n_intrinsics && (!d_intrinsics || !d_intr_dxoff)))
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	const double n2 = ba_intrinsics_update(ctx, n_intrinsics, d_intrinsics, d_intr_dxoff, d_dx, apply != 0);
+	if(h_dx_norm2)
+		*h_dx_norm2 = n2;
+	return SPP_OK;
+	SPP_CATCH(ctx)
+}
+
 int spp_assemble_set_edge_weights(spp_ctx *ctx, const double *d_w)
 {
 	if(!ctx)
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
 	SPP_REQUIRE(ctx->assemble, SPP_E_STATE, "spp_assemble_set_edge_weights: call spp_assemble_analyze first");
+	SPP_REQUIRE(!assemble_is_ternary(ctx), SPP_E_UNSUPPORTED, "robust weights on ternary edges");
 	assemble_set_edge_weights(ctx, 0, d_w);
 	return SPP_OK;
 	SPP_CATCH(ctx)
@@ -805,6 +873,7 @@ int spp_assemble_set_group_edge_weights(spp_ctx *ctx, int group, const double *d
 	SPP_TRY(ctx)
 	SPP_REQUIRE(ctx->assemble, SPP_E_STATE, "spp_assemble_set_group_edge_weights: call spp_assemble_analyze_groups first");
 	SPP_REQUIRE(group >= 0 && group < assemble_n_groups(ctx), SPP_E_BADARG, "spp_assemble_set_group_edge_weights: no such edge group");
+	SPP_REQUIRE(!assemble_is_ternary(ctx), SPP_E_UNSUPPORTED, "robust weights on ternary edges");
 	assemble_set_edge_weights(ctx, group, d_w);
 	return SPP_OK;
 	SPP_CATCH(ctx)

@@ -21,43 +21,14 @@
 //                    fixed butterfly reduction => reproducible, order differs from sequential in the
 //                    last bits only
 // All three are HBM-bound: 192 B read + 144 B written per BA observation for the off-diagonal part.
+// The plan (AssemblePlan) and the per-edge bodies jt_omega / vertex_contrib live in spp_assemble_plan.h: spp_assemble3.hip
+// (ternary edges) runs these kernels on its (camera, point) part and adds the kernels of what touches an intrinsics vertex.
 
-#include "spp_internal.h"
+#include "spp_assemble_plan.h"
 #include <algorithm>
 #include <cstdint>
 
 namespace spp {
-
-// One plan type for one edge group and for several: edges are numbered through the concatenation of the groups
-// (group g holds the indices gstart[g] .. gstart[g + 1)), every list below holds such indices in ascending GLOBAL position
-// (h_seq of spp_assemble_analyze_groups; the concatenation itself without it). With one group and no h_seq that is the
-// edge index itself: the lists are then those the one-group kernels have always read.
-static const int MAX_WIDTH_CLASSES = 3; // distinct vertex widths of the instantiated shapes: 6, 3, 2
-
-struct AssemblePlan {
-	int n_groups = 1;
-	int d0[SPP_MAX_EDGE_GROUPS] = {0}, d1[SPP_MAX_EDGE_GROUPS] = {0}, rd[SPP_MAX_EDGE_GROUPS] = {0};
-	int64_t gstart[SPP_MAX_EDGE_GROUPS + 1] = {0};
-	int n_cls = 0, cls_dim[MAX_WIDTH_CLASSES] = {0}; // vertex width classes, in order of first appearance (d0, d1 of group 0, ...)
-	int n_shapes = 0, shape_group[SPP_MAX_EDGE_GROUPS] = {0}; // distinct (d0, d1, rd): the first group of each
-	int64_t nv = 0, ne = 0, unary_vertex = -1;
-	Structure st;
-	int64_t n_ob = 0;
-	DevBuf<unsigned char> index_store; // the one allocation behind the index arrays below (UploadArena)
-	DevBuf<int32_t> ob_ptr;     // [n_ob+1]
-	DevBuf<int32_t> ob_edge;    // edge | reversed << 31
-	DevBuf<int64_t> ob_off;     // [n_ob] offset of the block in vals
-	DevBuf<int32_t> vl_ptr;     // [nv+1]
-	DevBuf<int32_t> vl_entry;   // edge << 1 | side
-	DevBuf<int64_t> v_doff;     // [nv] offset of the diagonal block
-	DevBuf<int64_t> v_base;     // [nv] scalar offset in eta
-	DevBuf<int32_t> vlist_seq[MAX_WIDTH_CLASSES], vlist_wave[MAX_WIDTH_CLASSES];
-	int64_t n_seq[MAX_WIDTH_CLASSES] = {0}, n_wave[MAX_WIDTH_CLASSES] = {0};
-	DevBuf<int32_t> oblist[SPP_MAX_EDGE_GROUPS]; // off-diagonal blocks of each shape (more than one shape only; else all of them)
-	int64_t n_oblist[SPP_MAX_EDGE_GROUPS] = {0};
-	// device, one robust weight per edge of the group, or null (assemble_set_edge_weights; not owned)
-	const double *edge_weights[SPP_MAX_EDGE_GROUPS] = {nullptr};
-};
 
 void assemble_release(spp_ctx *ctx)
 {
@@ -78,6 +49,11 @@ void assemble_set_edge_weights(spp_ctx *ctx, int group, const double *d_w)
 	ctx->assemble->edge_weights[group] = d_w;
 }
 
+bool assemble_is_ternary(const spp_ctx *ctx)
+{
+	return ctx->assemble->ternary != nullptr;
+}
+
 int assemble_n_groups(const spp_ctx *ctx)
 {
 	return ctx->assemble->n_groups;
@@ -87,8 +63,6 @@ int64_t assemble_group_edges(const spp_ctx *ctx, int group)
 {
 	return ctx->assemble->gstart[group + 1] - ctx->assemble->gstart[group];
 }
-
-static const int SEQ_MAX_DEGREE = 24;
 
 static bool same_shape(const AssemblePlan *ap, int ga, int gb)
 {
@@ -103,7 +77,7 @@ static bool shape_instantiated(int d0, int d1, int rd)
 
 void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int n_groups, const int64_t *g_ne,
 	const int64_t *const *g_v0, const int64_t *const *g_v1, const int64_t *const *g_seq, const int *g_d0, const int *g_d1,
-	const int *g_rd, int64_t unary_vertex)
+	const int *g_rd, int64_t unary_vertex, const uint8_t *skip_vertex)
 {
 	assemble_release(ctx); // after a rejected call the ctx has NO assembly plan (spp_assemble_device then fails its state check)
 	SPP_REQUIRE(n_groups >= 1 && n_groups <= SPP_MAX_EDGE_GROUPS, SPP_E_UNSUPPORTED, "more than SPP_MAX_EDGE_GROUPS edge groups");
@@ -321,6 +295,8 @@ void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int n_groups
 	for(int64_t v = 0; v < nv; ++ v) {
 		const int cls = (int)(std::find(ap->cls_dim, ap->cls_dim + ap->n_cls, dim[v]) - ap->cls_dim);
 		SPP_REQUIRE(cls < ap->n_cls, SPP_E_BADARG, "vertex width outside of the edge group");
+		if(skip_vertex && skip_vertex[v])
+			continue; // in no list: another kernel writes its diagonal block and eta segment (spp_assemble3.hip)
 		if(vl_ptr[v + 1] - vl_ptr[v] <= SEQ_MAX_DEGREE)
 			lseq[cls].push_back((int32_t)v);
 		else
@@ -378,22 +354,6 @@ void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int n_groups
 // --------------------------------------------------------------------------------------------------
 // device helpers
 // --------------------------------------------------------------------------------------------------
-// T = J^T Omega  (D x RD), J is RD x D column-major
-template <int D, int RD>
-__device__ __forceinline__ void jt_omega(const double *__restrict__ J, const double *__restrict__ Om, double *T)
-{
-#pragma unroll
-	for(int c = 0; c < RD; ++ c)
-#pragma unroll
-		for(int i = 0; i < D; ++ i) {
-			double s = 0;
-#pragma unroll
-			for(int l = 0; l < RD; ++ l)
-				s += J[l + i * RD] * Om[l + c * RD];
-			T[i + c * D] = s;
-		}
-}
-
 template <int D0, int D1, int RD>
 __global__ __launch_bounds__(256)
 void offdiag_kernel(int64_t n_ob, const int32_t *__restrict__ ob_ptr, const int32_t *__restrict__ ob_edge,
@@ -441,61 +401,6 @@ void offdiag_kernel(int64_t n_ob, const int32_t *__restrict__ ob_ptr, const int3
 #pragma unroll
 	for(int i = 0; i < D0 * D1; ++ i)
 		o[i] = acc[i];
-}
-
-// contribution of one (edge, side) to the vertex: H (D x D, upper computed, mirrored) and g (D)
-template <int D, int RD, int SIDE>
-__device__ __forceinline__ void vertex_contrib(const double *__restrict__ J, const double *__restrict__ Om,
-	const double *__restrict__ r, double wgt, double *H, double *g)
-{
-	// wgt: the robust weight of the edge (1 for a plain edge: the products below are then exact), applied where the
-	// reference applies it (BaseTypes_Binary.h:768-848): side 0 through T = J0^T Omega w -- H00 carries it once, g0 = T r w
-	// TWICE --, side 1 on the finished H11 and g1
-	double T[D * RD];
-	jt_omega<D, RD>(J, Om, T);
-	if(SIDE == 0) {
-#pragma unroll
-		for(int i = 0; i < D * RD; ++ i)
-			T[i] *= wgt;
-	}
-#pragma unroll
-	for(int c = 0; c < D; ++ c)
-#pragma unroll
-		for(int i = 0; i <= c; ++ i) {
-			double s = 0;
-#pragma unroll
-			for(int l = 0; l < RD; ++ l)
-				s += T[i + l * D] * J[l + c * RD];
-			H[i + c * D] = (SIDE == 0) ? s : s * wgt;
-		}
-	if(SIDE == 0) { // g0 = (J0^T Omega) r
-#pragma unroll
-		for(int i = 0; i < D; ++ i) {
-			double s = 0;
-#pragma unroll
-			for(int l = 0; l < RD; ++ l)
-				s += T[i + l * D] * r[l];
-			g[i] = s * wgt;
-		}
-	} else {        // g1 = J1^T (Omega r)
-		double orr[RD];
-#pragma unroll
-		for(int l = 0; l < RD; ++ l) {
-			double s = 0;
-#pragma unroll
-			for(int m = 0; m < RD; ++ m)
-				s += Om[l + m * RD] * r[m];
-			orr[l] = s;
-		}
-#pragma unroll
-		for(int i = 0; i < D; ++ i) {
-			double s = 0;
-#pragma unroll
-			for(int l = 0; l < RD; ++ l)
-				s += J[l + i * RD] * orr[l];
-			g[i] = s * wgt;
-		}
-	}
 }
 
 // D = width of the vertices handled; when D0 == D1 a vertex may sit on either side of its edges

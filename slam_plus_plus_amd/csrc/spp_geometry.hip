@@ -147,15 +147,12 @@ __device__ __forceinline__ void axis_angle_to_rot(const double *a, double *R) //
 	R[6] = B * x * z - A * y;       R[7] = B * y * z + A * x;       R[8] = 1 - B * (x * x + y * y);
 }
 
-__global__ __launch_bounds__(256)
-void ba_linearize_kernel(int64_t no, const int32_t *__restrict__ cam_of, const int32_t *__restrict__ pt_of,
-	const double *__restrict__ cams, const double *__restrict__ intr, const double *__restrict__ pts,
-	const double *__restrict__ meas, double *__restrict__ J0, double *__restrict__ J1, double *__restrict__ r)
+// one observation of Project_P2C: a = J0 (2x6), b = J1 (2x3), both column-major, r = z - uv; xyz (may be dead) <- the point in
+// the camera frame as (x, y, 1 / z). ONE body for spp_ba_linearize_device and spp_ba_intrinsics_linearize_device.
+__device__ __forceinline__ void ba_p2c_edge(const double *__restrict__ cam, const double *__restrict__ in,
+	const double *__restrict__ X, const double *__restrict__ meas, double *__restrict__ a, double *__restrict__ b,
+	double *__restrict__ r, double *xyz)
 {
-	const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if(e >= no)
-		return;
-	const double *cam = cams + 6 * (int64_t)cam_of[e], *in = intr + 5 * (int64_t)cam_of[e], *X = pts + 3 * (int64_t)pt_of[e];
 	double R[9];
 	axis_angle_to_rot(cam + 3, R);
 	const double X0 = X[0], X1 = X[1], X2 = X[2];
@@ -164,8 +161,8 @@ void ba_linearize_kernel(int64_t no, const int32_t *__restrict__ cam_of, const i
 	const double z = R[6] * X0 + R[7] * X1 + R[8] * X2 + cam[2];
 	const double fx = in[0], fy = in[1], k = in[4] / (0.5 * (fx + fy));
 	const double iz = 1.0 / z, d0 = fx * x * iz, d1 = fy * y * iz, r2 = d0 * d0 + d1 * d1, g = 1.0 + r2 * k;
-	r[2 * e] = meas[2 * e] - (in[2] + g * d0);
-	r[2 * e + 1] = meas[2 * e + 1] - (in[3] + g * d1);
+	r[0] = meas[0] - (in[2] + g * d0);
+	r[1] = meas[1] - (in[3] + g * d1);
 	// d uv / d x (2 x 3): D * Jd
 	const double D00 = g + 2 * k * d0 * d0, D01 = 2 * k * d0 * d1, D11 = g + 2 * k * d1 * d1;
 	const double a0 = fx * iz, a2 = -fx * x * iz * iz, b1 = fy * iz, b2 = -fy * y * iz * iz; // Jd = [a0 0 a2; 0 b1 b2]
@@ -178,7 +175,6 @@ void ba_linearize_kernel(int64_t no, const int32_t *__restrict__ cam_of, const i
 #pragma unroll
 		for(int j = 0; j < 3; ++ j)
 			PR[3 * i + j] = P[3 * i] * R[j] + P[3 * i + 1] * R[3 + j] + P[3 * i + 2] * R[6 + j];
-	double *a = J0 + 12 * e, *b = J1 + 6 * e;
 #pragma unroll
 	for(int j = 0; j < 3; ++ j) {
 		a[2 * j] = PR[j];
@@ -195,6 +191,108 @@ void ba_linearize_kernel(int64_t no, const int32_t *__restrict__ cam_of, const i
 		a[8 + i] = -(p2 * X0 - p0 * X2);
 		a[10 + i] = -(p0 * X1 - p1 * X0);
 	}
+	xyz[0] = x; xyz[1] = y; xyz[2] = iz;
+}
+
+__global__ __launch_bounds__(256)
+void ba_linearize_kernel(int64_t no, const int32_t *__restrict__ cam_of, const int32_t *__restrict__ pt_of,
+	const double *__restrict__ cams, const double *__restrict__ intr, const double *__restrict__ pts,
+	const double *__restrict__ meas, double *__restrict__ J0, double *__restrict__ J1, double *__restrict__ r)
+{
+	const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if(e >= no)
+		return;
+	double xyz[3];
+	ba_p2c_edge(cams + 6 * (int64_t)cam_of[e], intr + 5 * (int64_t)cam_of[e], pts + 3 * (int64_t)pt_of[e], meas + 2 * e,
+		J0 + 12 * e, J1 + 6 * e, r + 2 * e, xyz);
+}
+
+// --------------------------------------------------------------------------------------------------
+// Self-calibrating bundle adjustment: the ternary edge CEdgeP2CI3D (include/slam/BA_Types.h:562-700) between a camera
+// CVertexCam (6), a point CVertexXYZ (3) and an intrinsics vertex CVertexIntrinsics (5: fx fy cx cy kappa, :141-206) that
+// several cameras may share. Projection, r, J0 and J1 are those of Project_P2C above -- the same device function, with the
+// intrinsics taken from the edge's third vertex. J2 = d uv / d (fx fy cx cy kappa) w.r.t. the plain increment of
+// Relative_to_Absolute_Intrinsics (BASolverBase.h:204-212), analytic where the reference takes forward differences with
+// delta = 1e-9 (:690-759). With p = (x/z, y/z), d = (fx p0, fy p1), F = fx + fy, k = kappa / (0.5 F), r2 = |d|^2, g = 1 + r2 k:
+//   d uv / d fx = g (p0, 0) + d (2 k d0 p0 - r2 k / F)      d uv / d cx = (1, 0)
+//   d uv / d fy = g (0, p1) + d (2 k d1 p1 - r2 k / F)      d uv / d cy = (0, 1)      d uv / d kappa = d r2 / (0.5 F)
+// Nothing is divided by r: a point on the optical axis gives finite (zero) columns. Inside the library the vertex is 6 wide:
+// J2 is 2x6 column-major and its last column, the inert coordinate, is written as zeros.
+// J2 reads x, y, 1/z through an empty asm statement: its arithmetic then shares no subexpression with the body above,
+// which is therefore contracted into the same FMAs in both kernels (J0, J1, r bit-identical between them).
+// --------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double opaque_copy(double x)
+{
+	asm volatile("" : "+v"(x));
+	return x;
+}
+
+__global__ __launch_bounds__(256)
+void ba_intrinsics_linearize_kernel(int64_t no, const int32_t *__restrict__ cam_of, const int32_t *__restrict__ pt_of,
+	const int32_t *__restrict__ intr_of, const double *__restrict__ cams, const double *__restrict__ intr,
+	const double *__restrict__ pts, const double *__restrict__ meas, double *__restrict__ J0, double *__restrict__ J1,
+	double *__restrict__ J2, double *__restrict__ r)
+{
+	const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if(e >= no)
+		return;
+	const double *in = intr + 5 * (int64_t)intr_of[e];
+	double xyz[3];
+	ba_p2c_edge(cams + 6 * (int64_t)cam_of[e], in, pts + 3 * (int64_t)pt_of[e], meas + 2 * e, J0 + 12 * e, J1 + 6 * e, r + 2 * e, xyz);
+	const double x = opaque_copy(xyz[0]), y = opaque_copy(xyz[1]), iz = opaque_copy(xyz[2]);
+	const double fx = opaque_copy(in[0]), fy = opaque_copy(in[1]), kappa = opaque_copy(in[4]);
+	const double p0 = x * iz, p1 = y * iz, d0 = fx * p0, d1 = fy * p1, F = fx + fy, k = kappa / (0.5 * F);
+	const double r2 = d0 * d0 + d1 * d1, g = 1.0 + r2 * k, kF = r2 * k / F;
+	const double sx = 2.0 * k * d0 * p0 - kF, sy = 2.0 * k * d1 * p1 - kF, sk = r2 / (0.5 * F);
+	double *c = J2 + 12 * e;
+	c[0] = g * p0 + d0 * sx; c[1] = d1 * sx;          // fx
+	c[2] = d0 * sy;          c[3] = g * p1 + d1 * sy; // fy
+	c[4] = 1.0; c[5] = 0.0;                           // cx
+	c[6] = 0.0; c[7] = 1.0;                           // cy
+	c[8] = d0 * sk; c[9] = d1 * sk;                   // kappa
+	c[10] = 0.0; c[11] = 0.0;                         // inert
+}
+
+// CVertexIntrinsics::Operator_Plus AS WRITTEN (BA_Types.h:170-185): fx fy cx cy are plain sums; kappa is divided by
+// 0.5 fx fy -- the PRODUCT, not the 0.5 (fx + fy) of the projection -- of the old state, incremented by its delta divided
+// alike, and multiplied by 0.5 fx fy of the new state. One thread per intrinsics vertex; dx at dxoff[i] .. + 5.
+__global__ __launch_bounds__(256)
+void ba_update_intrinsics_kernel(int64_t ni, double *__restrict__ intr, const int64_t *__restrict__ dxoff, const double *__restrict__ dx)
+{
+	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if(i >= ni)
+		return;
+	double *v = intr + 5 * i;
+	const double *d = dx + dxoff[i];
+	const double den = 0.5 * (v[0] * v[1]);
+	const double dn = v[4] / den + d[4] / den;
+	const double fx = v[0] + d[0], fy = v[1] + d[1];
+	v[0] = fx;
+	v[1] = fy;
+	v[2] += d[2];
+	v[3] += d[3];
+	v[4] = dn * (0.5 * (fx * fy));
+}
+
+// ||dx||^2 over the 5 live coordinates of every intrinsics vertex: one workgroup, fixed assignment, fixed tree
+__global__ __launch_bounds__(256)
+void intrinsics_norm2_kernel(int64_t ni, const int64_t *__restrict__ dxoff, const double *__restrict__ dx, double *__restrict__ out)
+{
+	__shared__ double red[256];
+	double s = 0;
+	for(int64_t q = threadIdx.x; q < 5 * ni; q += 256) {
+		const double v = dx[dxoff[q / 5] + q % 5];
+		s += v * v;
+	}
+	red[threadIdx.x] = s;
+	__syncthreads();
+	for(int off = 128; off > 0; off >>= 1) {
+		if((int)threadIdx.x < off)
+			red[threadIdx.x] += red[threadIdx.x + off];
+		__syncthreads();
+	}
+	if(threadIdx.x == 0)
+		out[0] = red[0];
 }
 
 // --------------------------------------------------------------------------------------------------
@@ -722,6 +820,33 @@ void ba_stereo_linearize(spp_ctx *ctx, int64_t no, const int32_t *d_cam_of, cons
 	hipLaunchKernelGGL(ba_stereo_linearize_kernel, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, ctx->stream,
 		no, d_cam_of, d_pt_of, d_cams, d_intr, d_pts, d_meas, d_J0, d_J1, d_r);
 	SPP_HIP_CHECK(hipGetLastError());
+}
+
+void ba_intrinsics_linearize(spp_ctx *ctx, int64_t no, const int32_t *d_cam_of, const int32_t *d_pt_of, const int32_t *d_intr_of,
+	const double *d_cams, const double *d_intr, const double *d_pts, const double *d_meas, double *d_J0, double *d_J1, double *d_J2,
+	double *d_r)
+{
+	if(!no)
+		return;
+	hipLaunchKernelGGL(ba_intrinsics_linearize_kernel, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, ctx->stream,
+		no, d_cam_of, d_pt_of, d_intr_of, d_cams, d_intr, d_pts, d_meas, d_J0, d_J1, d_J2, d_r);
+	SPP_HIP_CHECK(hipGetLastError());
+}
+
+double ba_intrinsics_update(spp_ctx *ctx, int64_t ni, double *d_intr, const int64_t *d_intr_dxoff, const double *d_dx, bool apply)
+{
+	if(!ni)
+		return 0.0;
+	ctx->geom_partial.reserve(2);
+	hipLaunchKernelGGL(intrinsics_norm2_kernel, dim3(1), dim3(256), 0, ctx->stream, ni, d_intr_dxoff, d_dx, ctx->geom_partial.p);
+	if(apply)
+		hipLaunchKernelGGL(ba_update_intrinsics_kernel, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, ctx->stream, ni, d_intr,
+			d_intr_dxoff, d_dx);
+	SPP_HIP_CHECK(hipGetLastError());
+	double h = 0;
+	SPP_HIP_CHECK(hipMemcpyAsync(&h, ctx->geom_partial.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	SPP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+	return h;
 }
 
 double ba_update(spp_ctx *ctx, int64_t nc, double *d_cams, const int64_t *d_cam_dxoff, int64_t np, double *d_pts,

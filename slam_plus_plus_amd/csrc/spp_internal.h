@@ -417,6 +417,10 @@ void ba_linearize(spp_ctx *ctx, int64_t no, const int32_t *d_cam_of, const int32
 	const double *d_intr, const double *d_pts, const double *d_meas, double *d_J0, double *d_J1, double *d_r);
 void ba_stereo_linearize(spp_ctx *ctx, int64_t no, const int32_t *d_cam_of, const int32_t *d_pt_of, const double *d_cams,
 	const double *d_intr, const double *d_pts, const double *d_meas, double *d_J0, double *d_J1, double *d_r);
+void ba_intrinsics_linearize(spp_ctx *ctx, int64_t no, const int32_t *d_cam_of, const int32_t *d_pt_of, const int32_t *d_intr_of,
+	const double *d_cams, const double *d_intr, const double *d_pts, const double *d_meas, double *d_J0, double *d_J1, double *d_J2,
+	double *d_r);
+double ba_intrinsics_update(spp_ctx *ctx, int64_t ni, double *d_intr, const int64_t *d_intr_dxoff, const double *d_dx, bool apply);
 double ba_update(spp_ctx *ctx, int64_t nc, double *d_cams, const int64_t *d_cam_dxoff, int64_t np, double *d_pts,
 	const int64_t *d_pt_dxoff, const double *d_dx, int64_t n_dx, bool apply);
 
@@ -525,7 +529,7 @@ double microbench_update(spp_ctx *ctx, int64_t m, int iters);
 // one plan type: spp_assemble_analyze is the one-group case (g_seq null: the groups concatenated in group order)
 void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int n_groups, const int64_t *g_ne,
 	const int64_t *const *g_v0, const int64_t *const *g_v1, const int64_t *const *g_seq, const int *g_d0, const int *g_d1,
-	const int *g_rd, int64_t unary_vertex);
+	const int *g_rd, int64_t unary_vertex, const uint8_t *skip_vertex = nullptr); // skip_vertex[v]: v enters no vertex list
 int assemble_n_groups(const spp_ctx *ctx);
 int64_t assemble_group_edges(const spp_ctx *ctx, int group);
 void assemble_run(spp_ctx *ctx, const double *J0, const double *J1, const double *Om, const double *r,
@@ -534,6 +538,13 @@ void assemble_groups_run(spp_ctx *ctx, const double *const *J0, const double *co
 	const double *const *r, double damping, double *vals, double *eta); // host arrays of n_groups device pointers
 void assemble_set_edge_weights(spp_ctx *ctx, int group, const double *d_w); // null: plain edges
 void assemble_release(spp_ctx *ctx);
+bool assemble_is_ternary(const spp_ctx *ctx);
+// ---- spp_assemble3.hip ----
+constexpr int ASM_HUB_CHUNK = 4096; // edges one workgroup of the hub reduction sums (SPP_INFO_ASM_HUB_CHUNK)
+void assemble_analyze_ternary(spp_ctx *ctx, int64_t nv, const int32_t *dim, int64_t ne, const int64_t *v0, const int64_t *v1,
+	const int64_t *v2, int64_t unary_vertex);
+void assemble_ternary_run(spp_ctx *ctx, const double *J0, const double *J1, const double *J2, const double *Om, const double *r,
+	double damping, double *vals, double *eta);
 void assemble_get_structure(const spp_ctx *ctx, int64_t *col_ptr, int64_t *row_idx, int64_t *blk_off);
 
 // ---- profiling helpers (spp_api.cpp) ----

@@ -960,3 +960,220 @@ def save_stereo_graph(path, cams, intr, points, obs, info=None, cam_id=None, pt_
     (identity); cam_id / pt_id: vertex ids (default: cameras 0..nc-1, points nc..). Vertices are written in id order."""
     with open(path, "w") as f:
         f.write("\n".join(stereo_lines(cams, intr, points, obs, info, cam_id, pt_id)) + "\n")
+
+
+# --------------------------------------------------------------------------------------------------
+# self-calibrating bundle adjustment: cameras CVertexCam (6), points CVertexXYZ (3), intrinsics CVertexIntrinsics (5),
+# one ternary edge CEdgeP2CI3D per observation (include/slam/BA_Types.h:141-206, 562-700)
+# --------------------------------------------------------------------------------------------------
+_P2CI_EDGE = {"EDGE_PROJECT_P2MCI", "EDGE_P2MCI", "EDGE_P2CI"}   # ParsePrimitives.h:1252-1254
+BAI_INTR_WIDTH = 6   # width of an intrinsics vertex inside the library: 5 live coordinates + 1 inert (DESIGN section 20)
+
+
+def bai_expectation(cam, intr, X):
+    """CBAJacobians::Project_P2C (include/slam/BASolverBase.h:260-327) as the reference writes it, one row per observation:
+    cam (k, 6) [t | axis-angle] world -> camera, intr (k, 5) fx fy cx cy kappa, X (k, 3) -> (k, 2). x = R X + t,
+    uv = A x / (A x)_2, k = kappa / (0.5 (fx + fy)), r = |uv - c|, uv <- c + (1 + r r k)(uv - c)."""
+    from scipy.spatial.transform import Rotation
+    cam, intr, X = (np.asarray(a, dtype=np.float64) for a in (cam, intr, X))
+    R = Rotation.from_rotvec(cam[:, 3:6]).as_matrix()
+    fx, fy, cx, cy = (intr[:, i] for i in range(4))
+    k = intr[:, 4] / (0.5 * (fx + fy))
+    c = np.stack([cx, cy], axis=1)
+    x = np.einsum("eij,ej->ei", R, X) + cam[:, :3]
+    uv = np.stack([fx * x[:, 0] + cx * x[:, 2], fy * x[:, 1] + cy * x[:, 2]], axis=1) / x[:, 2:3]
+    r = np.sqrt(((uv - c) ** 2).sum(axis=1))
+    return c + (1 + r * r * k)[:, None] * (uv - c)
+
+
+def bai_ids(nc, npts, ni, cam_id=None, pt_id=None, intr_id=None):
+    """default vertex ids: intrinsics 0..ni-1, cameras after them, points last"""
+    intr_id = np.arange(ni) if intr_id is None else np.asarray(intr_id, dtype=np.int64)
+    cam_id = ni + np.arange(nc) if cam_id is None else np.asarray(cam_id, dtype=np.int64)
+    pt_id = ni + nc + np.arange(npts) if pt_id is None else np.asarray(pt_id, dtype=np.int64)
+    return cam_id, pt_id, intr_id
+
+
+def bai_linearize(cams, intr, points, obs, cam_id=None, pt_id=None, intr_id=None, info=None):
+    """Hot-path inputs (synth.Problem) of a bundle adjustment with intrinsics vertices at the given estimate: the float64
+    mirror of spp_ba_intrinsics_linearize_device. cams (nc, 6) [t | axis-angle] world -> camera, intr (ni, 5) fx fy cx cy
+    kappa, points (np, 3), obs (no, 5) camera index, point index, intrinsics index, u v; info (no, 2, 2) or None (identity).
+    r = z - uv with the projection of CBAJacobians::Project_P2C (BASolverBase.h:260-327); J0, J1 as ba_linearize (the camera
+    increment of Relative_to_Absolute, the point); J2 w.r.t. the plain increment of Relative_to_Absolute_Intrinsics
+    (:204-212), analytic where the reference takes forward differences (:690-759): with p = (x0/x2, x1/x2), d = (fx p0,
+    fy p1), F = fx + fy, k = kappa / (0.5 F), r2 = |d|^2, g = 1 + r2 k:
+        d uv / d fx = g (p0, 0) + d (2 k d0 p0 - r2 k / F),  d uv / d fy = g (0, p1) + d (2 k d1 p1 - r2 k / F),
+        d uv / d cx = (1, 0),  d uv / d cy = (0, 1),  d uv / d kappa = d r2 / (0.5 F).
+    The intrinsics vertex is BAI_INTR_WIDTH = 6 wide here: J2 is (no, 12), 2x6 column-major with a zero last column, and
+    dim holds 6 for it. Extra keys of the Problem: v2, d2 = 6, live2 = 5, J2. Vertex ids: bai_ids."""
+    from scipy.spatial.transform import Rotation
+    from .synth import Problem
+    cams, intr, points, obs = (np.asarray(a, dtype=np.float64) for a in (cams, intr, points, obs))
+    nc, npts, ni, no = cams.shape[0], points.shape[0], intr.shape[0], obs.shape[0]
+    co, po, io = (obs[:, i].astype(np.int64) for i in range(3))
+    cam_id, pt_id, intr_id = bai_ids(nc, npts, ni, cam_id, pt_id, intr_id)
+    R = Rotation.from_rotvec(cams[:, 3:]).as_matrix()[co]
+    X = points[po]
+    x = np.einsum("eij,ej->ei", R, X) + cams[co, :3]
+    fx, fy, cx, cy, kappa = (intr[io, i] for i in range(5))
+    F = fx + fy
+    k = kappa / (0.5 * F)
+    iz = 1.0 / x[:, 2]
+    p = x[:, :2] * iz[:, None]
+    d = np.stack([fx * x[:, 0] * iz, fy * x[:, 1] * iz], axis=1)
+    r2 = (d ** 2).sum(axis=1)
+    g = 1 + r2 * k
+    uv = np.stack([cx, cy], axis=1) + g[:, None] * d
+    Jd = np.zeros((no, 2, 3))
+    Jd[:, 0, 0], Jd[:, 0, 2] = fx * iz, -fx * x[:, 0] * iz * iz
+    Jd[:, 1, 1], Jd[:, 1, 2] = fy * iz, -fy * x[:, 1] * iz * iz
+    D = g[:, None, None] * np.eye(2)[None] + 2 * k[:, None, None] * np.einsum("ei,ej->eij", d, d)
+    PR = np.einsum("eij,ejk,ekl->eil", D, Jd, R)
+    J0 = np.concatenate([PR, -np.einsum("eij,ejk->eik", PR, _hat(X))], axis=2)
+    kF = r2 * k / F
+    sx, sy, sk = 2 * k * d[:, 0] * p[:, 0] - kF, 2 * k * d[:, 1] * p[:, 1] - kF, r2 / (0.5 * F)
+    J2 = np.zeros((no, 2, BAI_INTR_WIDTH))
+    J2[:, :, 0] = d * sx[:, None]
+    J2[:, 0, 0] += g * p[:, 0]
+    J2[:, :, 1] = d * sy[:, None]
+    J2[:, 1, 1] += g * p[:, 1]
+    J2[:, 0, 2] = 1.0
+    J2[:, 1, 3] = 1.0
+    J2[:, :, 4] = d * sk[:, None]
+    dim = np.empty(nc + npts + ni, dtype=np.int32)
+    dim[cam_id], dim[pt_id], dim[intr_id] = 6, 3, BAI_INTR_WIDTH
+    Om = np.tile(np.eye(2), (no, 1, 1)) if info is None else np.asarray(info, dtype=np.float64)
+    return Problem(name="bai", dim=dim, v0=cam_id[co], v1=pt_id[po], v2=intr_id[io], d0=6, d1=3, d2=BAI_INTR_WIDTH, live2=5, rd=2,
+                   J0=np.ascontiguousarray(J0.transpose(0, 2, 1)).reshape(no, 12),
+                   J1=np.ascontiguousarray(PR.transpose(0, 2, 1)).reshape(no, 6),
+                   J2=np.ascontiguousarray(J2.transpose(0, 2, 1)).reshape(no, 12),
+                   Om=np.ascontiguousarray(Om).reshape(no, 4), r=obs[:, 3:5] - uv, unary_vertex=0, damping=0.0)
+
+
+def bai_intrinsics_plus(intr, d):
+    """CVertexIntrinsics::Operator_Plus AS WRITTEN (BA_Types.h:170-185), rows of intr (ni, 5) and of the increment d (ni, 5):
+    fx fy cx cy plain sums; kappa divided by 0.5 fx fy (the PRODUCT) of the old state, incremented by its delta divided
+    alike, multiplied by 0.5 fx fy of the new state."""
+    intr, d = np.asarray(intr, dtype=np.float64), np.asarray(d, dtype=np.float64)
+    out = intr.copy()
+    den = 0.5 * (intr[:, 0] * intr[:, 1])
+    dn = intr[:, 4] / den + d[:, 4] / den
+    out[:, :4] = intr[:, :4] + d[:, :4]
+    out[:, 4] = dn * (0.5 * (out[:, 0] * out[:, 1]))
+    return out
+
+
+def bai_assemble_dense(prob, damping=0.0):
+    """float64 mirror of spp_assemble_ternary_device as one dense matrix: Lambda (n, n) and eta (n) of a bai_linearize
+    Problem in the padded layout -- J^T Omega J + unary factor (identity on the live coordinates of an intrinsics vertex)
+    + damping on every diagonal entry + 1.0 on the inert diagonal entries."""
+    dim = np.asarray(prob.dim, dtype=np.int64)
+    base = np.concatenate([[0], np.cumsum(dim)])
+    n, no = int(base[-1]), prob.v0.size
+    lam, eta = np.zeros((n, n)), np.zeros(n)
+    Om = prob.Om.reshape(no, 2, 2)
+    Js = [(prob.v0, prob.J0.reshape(no, 6, 2).transpose(0, 2, 1)), (prob.v1, prob.J1.reshape(no, 3, 2).transpose(0, 2, 1)),
+          (prob.v2, prob.J2.reshape(no, 6, 2).transpose(0, 2, 1))]
+    for e in range(no):
+        for va, Ja in Js:
+            ia = slice(base[va[e]], base[va[e] + 1])
+            eta[ia] += Ja[e].T @ (Om[e] @ prob.r[e])
+            for vb, Jb in Js:
+                lam[ia, slice(base[vb[e]], base[vb[e] + 1])] += Ja[e].T @ Om[e] @ Jb[e]
+    is_intr = np.zeros(dim.size, dtype=bool)
+    is_intr[prob.v2] = True
+    u = prob.unary_vertex
+    if u is not None and u >= 0:
+        live = 5 if is_intr[u] else int(dim[u])
+        lam[base[u] + np.arange(live), base[u] + np.arange(live)] += 1.0
+    inert = base[:-1][is_intr] + 5
+    lam[inert, inert] += 1.0
+    lam[np.arange(n), np.arange(n)] += damping
+    return lam, eta
+
+
+def load_bai_graph(path):
+    """A bundle adjustment graph with intrinsics vertices as the reference's parser reads it: `VERTEX_CAM id x y z qx qy qz
+    qw fx fy cx cy d` (camera-to-world centre + quaternion, inverted by the parser into the world-to-camera [t |
+    axis-angle] it optimizes, include/slam_app/ParsePrimitives.h:861-931; the five intrinsics of the line are not used by
+    CEdgeP2CI3D); `VERTEX_XYZ id x y z`; `VERTEX_INTRINSICS id fx fy cx cy d` (:932-976), d the distortion per pixel of radius
+    which the parsed vertex multiplies by 0.5 (fx + fy) into the internal kappa (TVertexIntrinsics, include/slam/Parser.h:
+    543-549) -- intr holds the internal value; `EDGE_P2CI point-id cam-id intrinsics-id u v xx xy yy` (:1241-1297; the edge's
+    vertices are camera, point, intrinsics: BA_Types.h:583-587). Returns dict(cams (nc, 6), intr (ni, 5), points (np, 3),
+    obs (no, 5) camera INDEX, point INDEX, intrinsics INDEX, u v, info (no, 2, 2), cam_id, pt_id, intr_id: vertex ids in
+    file order)."""
+    from scipy.spatial.transform import Rotation
+    cams, pts, intrs, edges, info = [], [], [], [], []
+    with open(path) as f:
+        for ln in f:
+            t = ln.split()
+            if not t or t[0].startswith("#") or t[0].startswith("%"):
+                continue
+            tok, a = t[0].upper(), t[1:]
+            if tok == "VERTEX_CAM" and len(a) >= 13:
+                cams.append([float(x) for x in a[:13]])
+            elif tok == "VERTEX_XYZ" and len(a) >= 4:
+                pts.append([float(x) for x in a[:4]])
+            elif tok == "VERTEX_INTRINSICS" and len(a) >= 6:
+                intrs.append([float(x) for x in a[:6]])
+            elif tok in _P2CI_EDGE and len(a) >= 8:
+                edges.append([float(x) for x in a[:5]])
+                info.append(_upper_to_full([float(x) for x in a[5:8]], 2))
+    cams_f, pts_f = np.array(cams).reshape(-1, 13), np.array(pts).reshape(-1, 4)
+    intr_f, e = np.array(intrs).reshape(-1, 6), np.array(edges).reshape(-1, 5)
+    q = Rotation.from_quat(cams_f[:, 4:8]).inv()
+    cam_id, pt_id, intr_id = (a[:, 0].astype(np.int64) for a in (cams_f, pts_f, intr_f))
+    nv = int(max(cam_id.max(initial=-1), pt_id.max(initial=-1), intr_id.max(initial=-1))) + 1
+    index = []
+    for ids in (cam_id, pt_id, intr_id):
+        ix = np.full(nv, -1, dtype=np.int64)
+        ix[ids] = np.arange(ids.size)
+        index.append(ix)
+    ci, pi, ii = index[0][e[:, 1].astype(np.int64)], index[1][e[:, 0].astype(np.int64)], index[2][e[:, 2].astype(np.int64)]
+    if (ci < 0).any() or (pi < 0).any() or (ii < 0).any():
+        raise ValueError("an EDGE_P2CI line names a vertex that is no VERTEX_CAM / VERTEX_XYZ / VERTEX_INTRINSICS: %s" % path)
+    intr = intr_f[:, 1:6].copy()
+    intr[:, 4] *= 0.5 * (intr[:, 0] + intr[:, 1])
+    f64 = lambda a: a[:, None].astype(np.float64)
+    return dict(cams=np.concatenate([q.apply(-cams_f[:, 1:4]), q.as_rotvec()], axis=1), intr=intr, points=pts_f[:, 1:4].copy(),
+                obs=np.concatenate([f64(ci), f64(pi), f64(ii), e[:, 3:5]], axis=1), info=np.array(info).reshape(-1, 2, 2),
+                cam_id=cam_id, pt_id=pt_id, intr_id=intr_id)
+
+
+def bai_lines(cams, intr, points, obs, info=None, cam_id=None, pt_id=None, intr_id=None):
+    """the lines of save_bai_graph: vertices in id order, then the edges as given, everything with %.17g. A camera's line
+    carries the intrinsics of the vertex its first observation names (the application does not read them)."""
+    from scipy.spatial.transform import Rotation
+    cams, intr, points, obs = (np.asarray(a, dtype=np.float64) for a in (cams, intr, points, obs))
+    nc, npts, ni = cams.shape[0], points.shape[0], intr.shape[0]
+    cam_id, pt_id, intr_id = bai_ids(nc, npts, ni, cam_id, pt_id, intr_id)
+    R = Rotation.from_rotvec(cams[:, 3:6])
+    C = -R.inv().apply(cams[:, :3])
+    q = R.inv().as_quat()
+    intr_f = intr.copy()
+    intr_f[:, 4] /= 0.5 * (intr[:, 0] + intr[:, 1])   # the file holds d per pixel of radius, the reader scales it back
+    first = np.zeros(nc, dtype=np.int64)
+    co = obs[:, 0].astype(np.int64)
+    first[co[::-1]] = obs[::-1, 2].astype(np.int64)
+    lines = []
+    for v in np.argsort(np.concatenate([cam_id, pt_id, intr_id]), kind="stable"):
+        if v < nc:
+            lines.append("VERTEX_CAM %d " % cam_id[v] + " ".join("%.17g" % x for x in (*C[v], *q[v], *intr_f[first[v]])))
+        elif v < nc + npts:
+            lines.append("VERTEX_XYZ %d " % pt_id[v - nc] + " ".join("%.17g" % x for x in points[v - nc]))
+        else:
+            lines.append("VERTEX_INTRINSICS %d " % intr_id[v - nc - npts] + " ".join("%.17g" % x for x in intr_f[v - nc - npts]))
+    for k, o in enumerate(obs):
+        m = np.eye(2) if info is None else np.asarray(info[k])
+        lines.append("EDGE_P2CI %d %d %d " % (pt_id[int(o[1])], cam_id[int(o[0])], intr_id[int(o[2])]) +
+                     " ".join("%.17g" % x for x in (o[3], o[4], m[0, 0], m[0, 1], m[1, 1])))
+    return lines
+
+
+def save_bai_graph(path, cams, intr, points, obs, info=None, cam_id=None, pt_id=None, intr_id=None):
+    """Bundle adjustment graph with intrinsics vertices in the reference's text format (tokens: load_bai_graph). cams
+    (nc, 6) world-to-camera [t | axis-angle], intr (ni, 5) fx fy cx cy kappa (the internal value; the file gets kappa /
+    (0.5 (fx + fy))), points (np, 3), obs (no, 5) camera index, point index, intrinsics index, u v (written point id
+    first, as the parser wants), info (no, 2, 2) or None. Vertices are written in id order, in front of the edges."""
+    with open(path, "w") as f:
+        f.write("\n".join(bai_lines(cams, intr, points, obs, info, cam_id, pt_id, intr_id)) + "\n")

@@ -18,7 +18,8 @@ import numpy as np
 
 from . import api
 from .formats import (se2_linearize, se3_linearize, se3_plus, ba_linearize, slam2d_linearize, slam2d_offsets,
-                      slam3d_linearize, slam3d_offsets, slam3d_plus, stereo_linearize)
+                      slam3d_linearize, slam3d_offsets, slam3d_plus, stereo_linearize, bai_linearize, bai_intrinsics_plus,
+                      bai_ids, BAI_INTR_WIDTH)
 
 
 class CPoseGraph2D:
@@ -594,6 +595,119 @@ class _ResidentStereoBAPath(_ResidentBAPath):
                                             self.d_pts.ptr, self.d_meas.ptr, self.d_J0.ptr, self.d_J1.ptr, self.d_r.ptr)
 
 
+class CBundleAdjustmentIntrinsics:
+    """Self-calibrating BA 'system' (CVertexCam + CVertexXYZ + CVertexIntrinsics joined by the ternary CEdgeP2CI3D,
+    src/slam_app/SolveBAIntrinsicsImpl.cpp), the interface of CBundleAdjustment: cams (nc, 6) [t | axis-angle] world ->
+    camera, intr (ni, 5) fx fy cx cy kappa, points (np, 3), obs (no, 5) cam pt intr u v; info (no, 2, 2) or None (identity).
+    Vertex ids: formats.bai_ids unless cam_id / pt_id / intr_id say otherwise. The increment is PADDED: an intrinsics vertex
+    takes 6 entries of dx, the last of them inert (zero)."""
+
+    def __init__(self, cams, intr, points, obs, info=None, cam_id=None, pt_id=None, intr_id=None):
+        self.cams = np.array(cams, dtype=np.float64)
+        self.intr = np.array(intr, dtype=np.float64)
+        self.points = np.array(points, dtype=np.float64)
+        self.obs = np.asarray(obs, dtype=np.float64)
+        self.info = None if info is None else np.asarray(info, dtype=np.float64)
+        nc, npts, ni = self.cams.shape[0], self.points.shape[0], self.intr.shape[0]
+        self.cam_id, self.pt_id, self.intr_id = bai_ids(nc, npts, ni, cam_id, pt_id, intr_id)
+        dim = np.empty(nc + npts + ni, dtype=np.int64)
+        dim[self.cam_id], dim[self.pt_id], dim[self.intr_id] = 6, 3, BAI_INTR_WIDTH
+        base = slam3d_offsets(dim)
+        self.cam_off, self.pt_off, self.intr_off = base[self.cam_id], base[self.pt_id], base[self.intr_id]
+
+    @classmethod
+    def from_problem(cls, p):
+        """from synth.bai_problem (its geometry) or formats.load_bai_graph"""
+        g = p["geometry"] if "geometry" in p else p
+        return cls(g["cams"], g["intr"], g["points"], g["obs"], g["info"], g["cam_id"], g["pt_id"], g["intr_id"])
+
+    def linearize(self):
+        return bai_linearize(self.cams, self.intr, self.points, self.obs, self.cam_id, self.pt_id, self.intr_id, self.info)
+
+    def chi2(self):
+        p = self.linearize()
+        return float(np.einsum("ei,eij,ej->", p.r, p.Om.reshape(-1, 2, 2), p.r))
+
+    def state(self):
+        return self.cams.copy(), self.points.copy(), self.intr.copy()
+
+    def set_state(self, st):
+        self.cams, self.points, self.intr = st[0].copy(), st[1].copy(), st[2].copy()
+
+    def plus(self, dx):
+        """cameras: Relative_to_Absolute; points: the plain sum; intrinsics: CVertexIntrinsics::Operator_Plus as written
+        (formats.bai_intrinsics_plus) on the 5 live entries"""
+        self.cams = se3_plus(self.cams, dx[self.cam_off[:, None] + np.arange(6)])
+        self.points = self.points + dx[self.pt_off[:, None] + np.arange(3)]
+        self.intr = bai_intrinsics_plus(self.intr, dx[self.intr_off[:, None] + np.arange(5)])
+
+
+class _ResidentBAIPath(_ResidentBAPath):
+    """the LM iteration pieces of a CBundleAdjustmentIntrinsics in HBM: states, J0 / J1 / J2, Lambda and the padded dx stay
+    on the device -- spp_ba_intrinsics_linearize_device, spp_assemble_ternary_device (damping alpha), spp_factor_solve_device
+    (AUTO: the dense Schur mode, poses = cameras + intrinsics), spp_ba_update_device for cameras and points (its norm runs
+    over the padded dx, whose inert entries are zero) and spp_ba_intrinsics_update_device; chi2 and the gain denominator as
+    in _ResidentBAPath, the initial damping from the larger of the (J0, J1) and (J2, J1) vertex Hessian diagonals. A rejected
+    step restores cameras, points and intrinsics."""
+    rd = 2
+
+    def begin(self, system):
+        ctx, s = self.ctx, system
+        prob = s.linearize()   # structure only
+        self.no, self.nc, self.np, self.ni = s.obs.shape[0], s.cams.shape[0], s.points.shape[0], s.intr.shape[0]
+        self.st = ctx.assemble_analyze_ternary(prob.dim, prob.v0, prob.v1, prob.v2, prob.unary_vertex)
+        up = lambda a: api.DeviceArray.from_host(ctx, np.ascontiguousarray(a).ravel())
+        self.d_cam_of, self.d_pt_of, self.d_intr_of = (up(s.obs[:, i].astype(np.int32)) for i in range(3))
+        self.d_cams, self.d_intr, self.d_pts = up(s.cams), up(s.intr), up(s.points)
+        self.d_meas, self.d_Om = up(s.obs[:, 3:5]), up(prob.Om)
+        self.d_cam_off, self.d_pt_off, self.d_intr_off = (up(a.astype(np.int64)) for a in (s.cam_off, s.pt_off, s.intr_off))
+        self.d_J0, self.d_J1, self.d_J2 = (api.DeviceArray(ctx, w * self.no) for w in (12, 6, 12))
+        self.d_r = api.DeviceArray(ctx, 2 * self.no)
+        self.d_vals, self.d_eta, self.d_dx = (api.DeviceArray(ctx, self.st.nvals), api.DeviceArray(ctx, self.st.n),
+                                              api.DeviceArray(ctx, self.st.n))
+        self.s_cams, self.s_pts, self.s_intr = (api.DeviceArray(ctx, 6 * self.nc), api.DeviceArray(ctx, 3 * self.np),
+                                                api.DeviceArray(ctx, 5 * self.ni))
+        self.analyzed = False
+
+    def linearize(self):
+        self.ctx.ba_intrinsics_linearize_device(self.no, self.d_cam_of.ptr, self.d_pt_of.ptr, self.d_intr_of.ptr, self.d_cams.ptr,
+                                                self.d_intr.ptr, self.d_pts.ptr, self.d_meas.ptr, self.d_J0.ptr, self.d_J1.ptr,
+                                                self.d_J2.ptr, self.d_r.ptr)
+
+    def max_hessian_diag(self):
+        f = lambda d_J: self.ctx.edge_hessian_maxdiag_device(self.no, 2, 6, 3, d_J.ptr, self.d_J1.ptr, self.d_Om.ptr)
+        return max(f(self.d_J0), f(self.d_J2))
+
+    def solve(self, alpha):
+        ctx = self.ctx
+        ctx.assemble_ternary_device(self.d_J0.ptr, self.d_J1.ptr, self.d_J2.ptr, self.d_Om.ptr, self.d_r.ptr, alpha,
+                                    self.d_vals.ptr, self.d_eta.ptr)
+        if not self.analyzed:
+            ctx.analyze(self.st, api.MODE_AUTO)
+            self.analyzed = True
+        self.d_dx.copy_from(self.d_eta)
+        if ctx.factor_solve_device(self.d_vals.ptr, self.d_dx.ptr) != 0:
+            return False, 0.0
+        return True, ctx.ba_update_device(self.nc, self.d_cams.ptr, self.d_cam_off.ptr, self.np, self.d_pts.ptr,
+                                          self.d_pt_off.ptr, self.d_dx.ptr, self.st.n, apply=False)
+
+    def save(self):
+        super().save()
+        self.s_intr.copy_from(self.d_intr)
+
+    def restore(self):
+        super().restore()
+        self.d_intr.copy_from(self.s_intr)
+
+    def apply(self):
+        super().apply()
+        self.ctx.ba_intrinsics_update_device(self.ni, self.d_intr.ptr, self.d_intr_off.ptr, self.d_dx.ptr, apply=True)
+
+    def finish(self, system):
+        super().finish(system)
+        system.intr = self.d_intr.download().reshape(-1, 5)
+
+
 class CNonlinearSolver_Lambda_LM:
     """Mirror of CNonlinearSolver_Lambda_LM::Optimize (include/slam/NonlinearSolver_Lambda_LM.h:796-1135) with
     the Levenberg trust-region policy of :151-222:
@@ -603,7 +717,8 @@ class CNonlinearSolver_Lambda_LM:
               rho = (last - err) / (dx . (alpha dx + eta));
               rho > 0: alpha *= max(1/3, 1 - (2 rho - 1)^3), nu = 2, last = err
               else   : alpha *= nu, nu *= 2, restore x, and the iteration budget grows by one (at most 10 times)
-    `path`: _ResidentBAPath (default, GPU), _ResidentStereoBAPath for a CStereoBundleAdjustment, or any object with the
+    `path`: _ResidentBAPath (default, GPU), _ResidentStereoBAPath for a CStereoBundleAdjustment, _ResidentBAIPath for a
+    CBundleAdjustmentIntrinsics, or any object with the
     same methods (tests inject a host path)."""
 
     def __init__(self, system, path=None, device=0, verbose=False):

@@ -562,6 +562,94 @@ def stereo_states(prob):
                 cam_dxoff=base[g["cam_id"]].copy(), pt_dxoff=base[g["pt_id"]].copy())
 
 
+# ------------------------------------------------------------------------------------------------
+# self-calibrating bundle adjustment: cameras (6) + points (3) + intrinsics vertices (5, stored 6 wide), ternary
+# CEdgeP2CI3D observations with 2-d residuals
+# ------------------------------------------------------------------------------------------------
+def bai_problem(ni=1, nc=3, npts=12, seed=20, views=(2, 3), layout="first", name="bai"):
+    """nc cameras on a circle of radius 10 looking at the origin, camera j using intrinsics vertex j % ni (the cameras
+    alternate between them); intrinsics vertex i: fx 500 + 20 i, fy 505 + 20 i (fx != fy), c = (320 + 5 i, 240 - 3 i), kappa
+    = 0.02 (0.5 (fx + fy)) / 70^2 -- the distortion reaches 2 % at 70 pixels from the centre, the edge of what the cameras see
+    of the scene; npts points in the cube [-1, 1]^3, each
+    seen by views[0] .. views[1] distinct cameras. layout: where the intrinsics vertices get their ids -- "first" (0 ..
+    ni - 1, cameras and points after them: ids the reference application accepts), "last", or "interleaved" (all ids
+    shuffled). Measurements: the truth + pixel noise of sigma 0.5 (information 4 I). Estimate: the truth disturbed by 0.03 /
+    0.004 rad (cameras), 0.05 (points), 2 / 2 / 1 / 1 pixels on fx fy cx cy and 10 % of kappa: the host float64
+    Levenberg-Marquardt loop brings chi2 monotonically below 0.05 of its initial value within 5 iterations
+    (tests/test_bai_host.py). Returns the ternary group linearized at the estimate (formats.bai_linearize) with geometry
+    = the states."""
+    from scipy.spatial.transform import Rotation
+    from .formats import bai_expectation, bai_linearize
+    rng = np.random.default_rng(seed)
+    k = rng.integers(views[0], min(views[1], nc) + 1, size=npts)
+    cam_of = np.concatenate([np.sort(rng.choice(nc, size=kk, replace=False)) for kk in k])
+    pt_of = np.repeat(np.arange(npts, dtype=np.int64), k)
+    intr_of = cam_of % ni
+    nobs = cam_of.size
+    th = 2 * np.pi * np.arange(nc) / nc
+    C = np.stack([10 * np.cos(th), 10 * np.sin(th), 0.5 * np.sin(3 * th)], axis=1)
+    z = -C / np.linalg.norm(C, axis=1, keepdims=True)
+    x = np.cross(np.array([0.0, 0.0, 1.0])[None, :], z)
+    x /= np.linalg.norm(x, axis=1, keepdims=True)
+    R = np.stack([x, np.cross(z, x), z], axis=1)  # rows = camera axes (world -> camera)
+    cams = np.concatenate([-np.einsum("cij,cj->ci", R, C), Rotation.from_matrix(R).as_rotvec()], axis=1)
+    i = np.arange(ni, dtype=np.float64)
+    intr = np.stack([500 + 20 * i, 505 + 20 * i, 320 + 5 * i, 240 - 3 * i, np.zeros(ni)], axis=1)
+    intr[:, 4] = 0.02 * (0.5 * (intr[:, 0] + intr[:, 1])) / 70.0 ** 2
+    X = rng.uniform(-1, 1, size=(npts, 3))
+    meas = bai_expectation(cams[cam_of], intr[intr_of], X[pt_of]) + rng.normal(0, 0.5, size=(nobs, 2))
+    info = np.tile(4.0 * np.eye(2), (nobs, 1, 1))
+    est_c = np.concatenate([cams[:, :3] + rng.normal(0, 0.03, size=(nc, 3)),
+                            (Rotation.from_rotvec(cams[:, 3:]) * Rotation.from_rotvec(rng.normal(0, 0.004, size=(nc, 3)))).as_rotvec()], axis=1)
+    est_p = X + rng.normal(0, 0.05, size=X.shape)
+    est_i = intr + rng.normal(0, 1, size=intr.shape) * np.array([2.0, 2.0, 1.0, 1.0, 0.0])
+    est_i[:, 4] = intr[:, 4] * (1 + 0.1 * rng.normal(0, 1, size=ni))
+    nv = ni + nc + npts
+    if layout == "first":
+        intr_id, cam_id, pt_id = np.arange(ni), ni + np.arange(nc), ni + nc + np.arange(npts)
+    elif layout == "last":
+        cam_id, pt_id, intr_id = np.arange(nc), nc + np.arange(npts), nc + npts + np.arange(ni)
+    else:
+        perm = rng.permutation(nv)
+        intr_id, cam_id, pt_id = perm[:ni], perm[ni:ni + nc], perm[ni + nc:]
+    f = lambda a: a.astype(np.float64)
+    obs = np.concatenate([f(cam_of)[:, None], f(pt_of)[:, None], f(intr_of)[:, None], meas], axis=1)
+    prob = bai_linearize(est_c, est_i, est_p, obs, cam_id, pt_id, intr_id, info)
+    prob.update(name=name, ni=ni, nc=nc, npts=npts,
+                geometry=dict(cams=est_c, intr=est_i, points=est_p, obs=obs, info=info, cam_of=cam_of, pt_of=pt_of, intr_of=intr_of,
+                              cam_id=cam_id, pt_id=pt_id, intr_id=intr_id, truth=dict(cams=cams, intr=intr, points=X)))
+    return prob
+
+
+def bai_tiny(layout="first"):
+    """1 intrinsics vertex, 3 cameras, 12 points"""
+    return bai_problem(1, 3, 12, 20, views=(2, 3), layout=layout, name="bai_tiny")
+
+
+def bai_small(layout="first"):
+    """2 intrinsics vertices, 6 cameras alternating between them, 40 points seen by 2 .. 6 cameras: a point has two (point,
+    intrinsics) blocks"""
+    return bai_problem(2, 6, 40, 21, views=(2, 6), layout=layout, name="bai_small")
+
+
+def bai_hub(layout="first"):
+    """1 intrinsics vertex, 40 cameras, 3000 points seen by 2 .. 6 cameras: the intrinsics' block of S is split over several
+    work items of the Schur plan (n_multi >= 1), its H22 and its blocks against the cameras go through the hub reduction"""
+    return bai_problem(1, 40, 3000, 22, views=(2, 6), layout=layout, name="bai_hub")
+
+
+def bai_states(prob):
+    """The scene of a bai_problem as input of spp_ba_intrinsics_linearize_device: dict(cams (nc,6), intr (ni,5), points
+    (np,3), meas (no,2), cam_of, pt_of, intr_of int32, cam_dxoff, pt_dxoff, intr_dxoff int64: scalar offset of every vertex in
+    the padded solution vector)."""
+    g = prob.geometry
+    base = np.zeros(prob.dim.size + 1, dtype=np.int64)
+    np.cumsum(prob.dim, out=base[1:])
+    return dict(cams=g["cams"].copy(), intr=g["intr"].copy(), points=g["points"].copy(), meas=g["obs"][:, 3:5].copy(),
+                cam_of=g["cam_of"].astype(np.int32), pt_of=g["pt_of"].astype(np.int32), intr_of=g["intr_of"].astype(np.int32),
+                cam_dxoff=base[g["cam_id"]].copy(), pt_dxoff=base[g["pt_id"]].copy(), intr_dxoff=base[g["intr_id"]].copy())
+
+
 def pose_graph_states(prob):
     """The same pose graph as states + measurements in the REFERENCE's parameterization, as input of
     spp_se2_/se3_linearize_device: poses (n, 3) x y theta or (n, 6) [t | axis-angle] at the noisy estimate,
@@ -605,6 +693,9 @@ CONFIGS = {
     "lm3d_small": lambda: landmark3d_problem(40, 60, 72),
     "stereo_small": lambda: stereo_problem(6, 40, 16, name="stereo_small"),
     "stereo_interleaved": lambda: stereo_problem(30, 150, 17, interleave=True, hubs=True, name="stereo_interleaved"),
+    "bai_tiny": lambda: bai_tiny(),
+    "bai_small": lambda: bai_small(),
+    "bai_hub": lambda: bai_hub(),
     "se2_small": lambda: se2_problem(300, 150, 12, name="se2_small"),
     "se3_small": lambda: se3_problem(8, 12, 13, name="se3_small"),
 }
