@@ -85,6 +85,23 @@ void dom_end(spp_ctx *ctx, double flops)
 	catch(const std::bad_alloc &) { if(ctx) (ctx)->last_error = "host allocation failed"; return SPP_E_NOMEM; } \
 	catch(const std::exception &e) { if(ctx) (ctx)->last_error = e.what(); return SPP_E_HIP; }
 
+static inline void store_if(double *h_out, double value) // the update entry points' norm is optional
+{
+	if(h_out)
+		*h_out = value;
+}
+
+// what a geometry entry point does after its argument check: select the device, run the body, translate exceptions
+template <class Body>
+static int geometry_call(spp_ctx *ctx, Body body)
+{
+	SPP_TRY(ctx)
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	body();
+	return SPP_OK;
+	SPP_CATCH(ctx)
+}
+
 extern "C" {
 
 const char *spp_version(void)
@@ -832,12 +849,10 @@ int spp_ba_intrinsics_linearize_device(spp_ctx *ctx, int64_t n_obs, const int32_
 	if(!ctx || n_obs < 0 || !d_cam_of || !d_pt_of || !d_intr_of || !d_cams || !d_intrinsics || !d_points || !d_measurements ||
 	   !d_J0 || !d_J1 || !d_J2 || !d_r)
 		return SPP_E_BADARG;
-	SPP_TRY(ctx)
-	SPP_HIP_CHECK(hipSetDevice(ctx->device));
-	ba_intrinsics_linearize(ctx, n_obs, d_cam_of, d_pt_of, d_intr_of, d_cams, d_intrinsics, d_points, d_measurements, d_J0, d_J1,
-		d_J2, d_r);
-	return SPP_OK;
-	SPP_CATCH(ctx)
+	return geometry_call(ctx, [&] {
+		ba_intrinsics_linearize(ctx, n_obs, d_cam_of, d_pt_of, d_intr_of, d_cams, d_intrinsics, d_points, d_measurements, d_J0, d_J1,
+			d_J2, d_r);
+	});
 }
 
 int spp_ba_intrinsics_update_device(spp_ctx *ctx, int64_t n_intrinsics, double *d_intrinsics, const int64_t *d_intr_dxoff,
@@ -845,13 +860,7 @@ int spp_ba_intrinsics_update_device(spp_ctx *ctx, int64_t n_intrinsics, double *
 {
 	if(!ctx || n_intrinsics < 0 || !d_dx || (n_intrinsics && (!d_intrinsics || !d_intr_dxoff)))
 		return SPP_E_BADARG;
-	SPP_TRY(ctx)
-	SPP_HIP_CHECK(hipSetDevice(ctx->device));
-	const double n2 = ba_intrinsics_update(ctx, n_intrinsics, d_intrinsics, d_intr_dxoff, d_dx, apply != 0);
-	if(h_dx_norm2)
-		*h_dx_norm2 = n2;
-	return SPP_OK;
-	SPP_CATCH(ctx)
+	return geometry_call(ctx, [&] { store_if(h_dx_norm2, ba_intrinsics_update(ctx, n_intrinsics, d_intrinsics, d_intr_dxoff, d_dx, apply != 0)); });
 }
 
 int spp_assemble_set_edge_weights(spp_ctx *ctx, const double *d_w)
@@ -884,11 +893,7 @@ int spp_se2_linearize_device(spp_ctx *ctx, int64_t n_edges, const int32_t *d_v0,
 {
 	if(!ctx || n_edges < 0 || !d_v0 || !d_v1 || !d_poses || !d_measurements || !d_J0 || !d_J1 || !d_r)
 		return SPP_E_BADARG;
-	SPP_TRY(ctx)
-	SPP_HIP_CHECK(hipSetDevice(ctx->device));
-	se2_linearize(ctx, n_edges, d_v0, d_v1, d_poses, d_measurements, d_J0, d_J1, d_r);
-	return SPP_OK;
-	SPP_CATCH(ctx)
+	return geometry_call(ctx, [&] { se2_linearize(ctx, n_edges, d_v0, d_v1, d_poses, d_measurements, d_J0, d_J1, d_r); });
 }
 
 int spp_se2_update_device(spp_ctx *ctx, int64_t n_vertices, double *d_poses, const double *d_dx, int apply,
@@ -896,13 +901,7 @@ int spp_se2_update_device(spp_ctx *ctx, int64_t n_vertices, double *d_poses, con
 {
 	if(!ctx || n_vertices < 0 || !d_poses || !d_dx)
 		return SPP_E_BADARG;
-	SPP_TRY(ctx)
-	SPP_HIP_CHECK(hipSetDevice(ctx->device));
-	const double n2 = se2_update(ctx, n_vertices, d_poses, d_dx, apply != 0);
-	if(h_dx_norm2)
-		*h_dx_norm2 = n2;
-	return SPP_OK;
-	SPP_CATCH(ctx)
+	return geometry_call(ctx, [&] { store_if(h_dx_norm2, se2_update(ctx, n_vertices, d_poses, d_dx, apply != 0)); });
 }
 
 int spp_se2_linearize_at_device(spp_ctx *ctx, int64_t n_edges, const int64_t *d_off0, const int64_t *d_off1,
@@ -910,11 +909,7 @@ int spp_se2_linearize_at_device(spp_ctx *ctx, int64_t n_edges, const int64_t *d_
 {
 	if(!ctx || n_edges < 0 || !d_off0 || !d_off1 || !d_state || !d_measurements || !d_J0 || !d_J1 || !d_r)
 		return SPP_E_BADARG;
-	SPP_TRY(ctx)
-	SPP_HIP_CHECK(hipSetDevice(ctx->device));
-	se2_linearize_at(ctx, n_edges, d_off0, d_off1, d_state, d_measurements, d_J0, d_J1, d_r);
-	return SPP_OK;
-	SPP_CATCH(ctx)
+	return geometry_call(ctx, [&] { se2_linearize_at(ctx, n_edges, d_off0, d_off1, d_state, d_measurements, d_J0, d_J1, d_r); });
 }
 
 int spp_se2_rb_linearize_device(spp_ctx *ctx, int64_t n_edges, const int64_t *d_pose_off, const int64_t *d_lm_off,
@@ -922,11 +917,7 @@ int spp_se2_rb_linearize_device(spp_ctx *ctx, int64_t n_edges, const int64_t *d_
 {
 	if(!ctx || n_edges < 0 || !d_pose_off || !d_lm_off || !d_state || !d_measurements || !d_J0 || !d_J1 || !d_r)
 		return SPP_E_BADARG;
-	SPP_TRY(ctx)
-	SPP_HIP_CHECK(hipSetDevice(ctx->device));
-	se2_rb_linearize(ctx, n_edges, d_pose_off, d_lm_off, d_state, d_measurements, d_J0, d_J1, d_r);
-	return SPP_OK;
-	SPP_CATCH(ctx)
+	return geometry_call(ctx, [&] { se2_rb_linearize(ctx, n_edges, d_pose_off, d_lm_off, d_state, d_measurements, d_J0, d_J1, d_r); });
 }
 
 int spp_slam2d_update_device(spp_ctx *ctx, int64_t n, double *d_state, const double *d_dx, int64_t n_pose_angles,
@@ -934,13 +925,7 @@ int spp_slam2d_update_device(spp_ctx *ctx, int64_t n, double *d_state, const dou
 {
 	if(!ctx || n < 0 || n_pose_angles < 0 || !d_state || !d_dx || (n_pose_angles && !d_angle_off))
 		return SPP_E_BADARG;
-	SPP_TRY(ctx)
-	SPP_HIP_CHECK(hipSetDevice(ctx->device));
-	const double n2 = slam2d_update(ctx, n, d_state, d_dx, n_pose_angles, d_angle_off, apply != 0);
-	if(h_dx_norm2)
-		*h_dx_norm2 = n2;
-	return SPP_OK;
-	SPP_CATCH(ctx)
+	return geometry_call(ctx, [&] { store_if(h_dx_norm2, slam2d_update(ctx, n, d_state, d_dx, n_pose_angles, d_angle_off, apply != 0)); });
 }
 
 int spp_se3_linearize_device(spp_ctx *ctx, int64_t n_edges, const int32_t *d_v0, const int32_t *d_v1,
@@ -948,11 +933,7 @@ int spp_se3_linearize_device(spp_ctx *ctx, int64_t n_edges, const int32_t *d_v0,
 {
 	if(!ctx || n_edges < 0 || !d_v0 || !d_v1 || !d_poses || !d_measurements || !d_J0 || !d_J1 || !d_r)
 		return SPP_E_BADARG;
-	SPP_TRY(ctx)
-	SPP_HIP_CHECK(hipSetDevice(ctx->device));
-	se3_linearize(ctx, n_edges, d_v0, d_v1, d_poses, d_measurements, d_J0, d_J1, d_r);
-	return SPP_OK;
-	SPP_CATCH(ctx)
+	return geometry_call(ctx, [&] { se3_linearize(ctx, n_edges, d_v0, d_v1, d_poses, d_measurements, d_J0, d_J1, d_r); });
 }
 
 int spp_se3_update_device(spp_ctx *ctx, int64_t n_vertices, double *d_poses, const double *d_dx, int apply,
@@ -960,13 +941,7 @@ int spp_se3_update_device(spp_ctx *ctx, int64_t n_vertices, double *d_poses, con
 {
 	if(!ctx || n_vertices < 0 || !d_poses || !d_dx)
 		return SPP_E_BADARG;
-	SPP_TRY(ctx)
-	SPP_HIP_CHECK(hipSetDevice(ctx->device));
-	const double n2 = se3_update(ctx, n_vertices, d_poses, d_dx, apply != 0);
-	if(h_dx_norm2)
-		*h_dx_norm2 = n2;
-	return SPP_OK;
-	SPP_CATCH(ctx)
+	return geometry_call(ctx, [&] { store_if(h_dx_norm2, se3_update(ctx, n_vertices, d_poses, d_dx, apply != 0)); });
 }
 
 int spp_ba_linearize_device(spp_ctx *ctx, int64_t n_obs, const int32_t *d_cam_of, const int32_t *d_pt_of,
@@ -976,11 +951,7 @@ int spp_ba_linearize_device(spp_ctx *ctx, int64_t n_obs, const int32_t *d_cam_of
 	if(!ctx || n_obs < 0 || !d_cam_of || !d_pt_of || !d_cams || !d_intrinsics || !d_points || !d_measurements ||
 	   !d_J0 || !d_J1 || !d_r)
 		return SPP_E_BADARG;
-	SPP_TRY(ctx)
-	SPP_HIP_CHECK(hipSetDevice(ctx->device));
-	ba_linearize(ctx, n_obs, d_cam_of, d_pt_of, d_cams, d_intrinsics, d_points, d_measurements, d_J0, d_J1, d_r);
-	return SPP_OK;
-	SPP_CATCH(ctx)
+	return geometry_call(ctx, [&] { ba_linearize(ctx, n_obs, d_cam_of, d_pt_of, d_cams, d_intrinsics, d_points, d_measurements, d_J0, d_J1, d_r); });
 }
 
 int spp_ba_stereo_linearize_device(spp_ctx *ctx, int64_t n_obs, const int32_t *d_cam_of, const int32_t *d_pt_of,
@@ -990,11 +961,7 @@ int spp_ba_stereo_linearize_device(spp_ctx *ctx, int64_t n_obs, const int32_t *d
 	if(!ctx || n_obs < 0 || !d_cam_of || !d_pt_of || !d_cams || !d_intrinsics || !d_points || !d_measurements ||
 	   !d_J0 || !d_J1 || !d_r)
 		return SPP_E_BADARG;
-	SPP_TRY(ctx)
-	SPP_HIP_CHECK(hipSetDevice(ctx->device));
-	ba_stereo_linearize(ctx, n_obs, d_cam_of, d_pt_of, d_cams, d_intrinsics, d_points, d_measurements, d_J0, d_J1, d_r);
-	return SPP_OK;
-	SPP_CATCH(ctx)
+	return geometry_call(ctx, [&] { ba_stereo_linearize(ctx, n_obs, d_cam_of, d_pt_of, d_cams, d_intrinsics, d_points, d_measurements, d_J0, d_J1, d_r); });
 }
 
 int spp_ba_update_device(spp_ctx *ctx, int64_t n_cams, double *d_cams, const int64_t *d_cam_dxoff,
@@ -1004,13 +971,7 @@ int spp_ba_update_device(spp_ctx *ctx, int64_t n_cams, double *d_cams, const int
 	if(!ctx || n_cams < 0 || n_points < 0 || n_dx < 0 || !d_dx || (n_cams && (!d_cams || !d_cam_dxoff)) ||
 	   (n_points && (!d_points || !d_pt_dxoff)))
 		return SPP_E_BADARG;
-	SPP_TRY(ctx)
-	SPP_HIP_CHECK(hipSetDevice(ctx->device));
-	const double n2 = ba_update(ctx, n_cams, d_cams, d_cam_dxoff, n_points, d_points, d_pt_dxoff, d_dx, n_dx, apply != 0);
-	if(h_dx_norm2)
-		*h_dx_norm2 = n2;
-	return SPP_OK;
-	SPP_CATCH(ctx)
+	return geometry_call(ctx, [&] { store_if(h_dx_norm2, ba_update(ctx, n_cams, d_cams, d_cam_dxoff, n_points, d_points, d_pt_dxoff, d_dx, n_dx, apply != 0)); });
 }
 
 int spp_edge_robust_weights_device(spp_ctx *ctx, int64_t n_edges, int rd, int kind, double scale, double param,
@@ -1018,11 +979,7 @@ int spp_edge_robust_weights_device(spp_ctx *ctx, int64_t n_edges, int rd, int ki
 {
 	if(!ctx || n_edges < 0 || !d_r || !d_w_out)
 		return SPP_E_BADARG;
-	SPP_TRY(ctx)
-	SPP_HIP_CHECK(hipSetDevice(ctx->device));
-	edge_robust_weights(ctx, n_edges, rd, kind, scale, param, d_r, d_w_out);
-	return SPP_OK;
-	SPP_CATCH(ctx)
+	return geometry_call(ctx, [&] { edge_robust_weights(ctx, n_edges, rd, kind, scale, param, d_r, d_w_out); });
 }
 
 int spp_se3_linearize_at_device(spp_ctx *ctx, int64_t n_edges, const int64_t *d_off0, const int64_t *d_off1,
@@ -1030,11 +987,7 @@ int spp_se3_linearize_at_device(spp_ctx *ctx, int64_t n_edges, const int64_t *d_
 {
 	if(!ctx || n_edges < 0 || !d_off0 || !d_off1 || !d_state || !d_measurements || !d_J0 || !d_J1 || !d_r)
 		return SPP_E_BADARG;
-	SPP_TRY(ctx)
-	SPP_HIP_CHECK(hipSetDevice(ctx->device));
-	se3_linearize_at(ctx, n_edges, d_off0, d_off1, d_state, d_measurements, d_J0, d_J1, d_r);
-	return SPP_OK;
-	SPP_CATCH(ctx)
+	return geometry_call(ctx, [&] { se3_linearize_at(ctx, n_edges, d_off0, d_off1, d_state, d_measurements, d_J0, d_J1, d_r); });
 }
 
 int spp_se3_xyz_linearize_device(spp_ctx *ctx, int64_t n_edges, const int64_t *d_pose_off, const int64_t *d_lm_off,
@@ -1042,11 +995,7 @@ int spp_se3_xyz_linearize_device(spp_ctx *ctx, int64_t n_edges, const int64_t *d
 {
 	if(!ctx || n_edges < 0 || !d_pose_off || !d_lm_off || !d_state || !d_measurements || !d_J0 || !d_J1 || !d_r)
 		return SPP_E_BADARG;
-	SPP_TRY(ctx)
-	SPP_HIP_CHECK(hipSetDevice(ctx->device));
-	se3_xyz_linearize(ctx, n_edges, d_pose_off, d_lm_off, d_state, d_measurements, d_J0, d_J1, d_r);
-	return SPP_OK;
-	SPP_CATCH(ctx)
+	return geometry_call(ctx, [&] { se3_xyz_linearize(ctx, n_edges, d_pose_off, d_lm_off, d_state, d_measurements, d_J0, d_J1, d_r); });
 }
 
 int spp_slam3d_update_device(spp_ctx *ctx, int64_t n, double *d_state, const double *d_dx, int64_t n_poses,
@@ -1054,24 +1003,14 @@ int spp_slam3d_update_device(spp_ctx *ctx, int64_t n, double *d_state, const dou
 {
 	if(!ctx || n < 0 || n_poses < 0 || !d_state || !d_dx || (n_poses && !d_pose_off))
 		return SPP_E_BADARG;
-	SPP_TRY(ctx)
-	SPP_HIP_CHECK(hipSetDevice(ctx->device));
-	const double n2 = slam3d_update(ctx, n, d_state, d_dx, n_poses, d_pose_off, apply != 0);
-	if(h_dx_norm2)
-		*h_dx_norm2 = n2;
-	return SPP_OK;
-	SPP_CATCH(ctx)
+	return geometry_call(ctx, [&] { store_if(h_dx_norm2, slam3d_update(ctx, n, d_state, d_dx, n_poses, d_pose_off, apply != 0)); });
 }
 
 int spp_edge_chi2_device(spp_ctx *ctx, int64_t n_edges, int rd, const double *d_r, const double *d_Omega, double *h_chi2)
 {
 	if(!ctx || n_edges < 0 || !d_r || !d_Omega || !h_chi2)
 		return SPP_E_BADARG;
-	SPP_TRY(ctx)
-	SPP_HIP_CHECK(hipSetDevice(ctx->device));
-	*h_chi2 = edge_chi2(ctx, n_edges, rd, d_r, d_Omega);
-	return SPP_OK;
-	SPP_CATCH(ctx)
+	return geometry_call(ctx, [&] { *h_chi2 = edge_chi2(ctx, n_edges, rd, d_r, d_Omega); });
 }
 
 int spp_edge_hessian_maxdiag_device(spp_ctx *ctx, int64_t n_edges, int rd, int d0, int d1, const double *d_J0,
@@ -1079,11 +1018,7 @@ int spp_edge_hessian_maxdiag_device(spp_ctx *ctx, int64_t n_edges, int rd, int d
 {
 	if(!ctx || n_edges < 0 || !d_J0 || !d_J1 || !d_Omega || !h_max)
 		return SPP_E_BADARG;
-	SPP_TRY(ctx)
-	SPP_HIP_CHECK(hipSetDevice(ctx->device));
-	*h_max = edge_hessian_maxdiag(ctx, n_edges, rd, d0, d1, d_J0, d_J1, d_Omega);
-	return SPP_OK;
-	SPP_CATCH(ctx)
+	return geometry_call(ctx, [&] { *h_max = edge_hessian_maxdiag(ctx, n_edges, rd, d0, d1, d_J0, d_J1, d_Omega); });
 }
 
 int spp_lm_gain_denominator_device(spp_ctx *ctx, int64_t n, const double *d_dx, const double *d_eta, double alpha,
@@ -1091,11 +1026,7 @@ int spp_lm_gain_denominator_device(spp_ctx *ctx, int64_t n, const double *d_dx, 
 {
 	if(!ctx || n < 0 || !d_dx || !d_eta || !h_out)
 		return SPP_E_BADARG;
-	SPP_TRY(ctx)
-	SPP_HIP_CHECK(hipSetDevice(ctx->device));
-	*h_out = lm_gain_denominator(ctx, n, d_dx, d_eta, alpha);
-	return SPP_OK;
-	SPP_CATCH(ctx)
+	return geometry_call(ctx, [&] { *h_out = lm_gain_denominator(ctx, n, d_dx, d_eta, alpha); });
 }
 
 int spp_device_malloc(spp_ctx *ctx, size_t bytes, void **d_ptr)

@@ -1,19 +1,34 @@
-// spp_geometry.hip -- on-device edge linearization: Jacobians, expectation and error
-// of the 2D relative-pose edge (CEdgePose2D) and of the BA projection edge (CEdgeP2C3D), the vertex
-// updates x <- x (+) dx and ||dx||, so that a whole Gauss-Newton / LM iteration stays in HBM.
-// gfx950 only.
+// spp_geometry.hip -- everything a Gauss-Newton / Levenberg-Marquardt iteration needs besides assembly and the solve,
+// so that the whole iteration stays in HBM. gfx950 only, fp64, one thread per edge / vertex / entry.
 //
-// Reference (functional spec, nothing is ported):
+// Edge linearization (Jacobians column-major, r = error), each section headed by its reference and its formulas:
+//   SE(2) pose-pose          CEdgePose2D           se2_linearize_kernel (vertex ids), se2_linearize_at_kernel (offsets)
+//   SE(2) range-bearing      CEdgePoseLandmark2D   se2_rb_linearize_kernel
+//   SE(3) pose-pose          CEdgePose3D           se3_linearize_kernel (vertex ids), se3_linearize_at_kernel (offsets)
+//   SE(3) pose-landmark      CEdgePoseLandmark3D   se3_xyz_linearize_kernel
+//   BA projection            CEdgeP2C3D            ba_linearize_kernel
+//   BA, shared intrinsics    CEdgeP2CI3D (ternary) ba_intrinsics_linearize_kernel
+//   stereo BA projection     CEdgeP2SC3D           ba_stereo_linearize_kernel
+// The two addressings of an edge share one __device__ body (se2_linearize_edge, se3_linearize_edge), the two mono BA
+// edges share ba_p2c_edge. The kernels themselves stay named and non-templated: profiles are read by kernel name.
+// Vertex updates x <- x (+) dx, each returning ||dx||^2: se2_update, se3_update, ba_update (cameras as se3_plus, points),
+// ba_intrinsics_update, slam2d_update, slam3d_update (flat states addressed by scalar offsets).
+// LM scalars: edge_chi2, edge_hessian_maxdiag, lm_gain_denominator; robust (Huber) edge weights.
+//
+// Every scalar is a deterministic two-stage reduction: block_reduce_256 inside each workgroup (one fixed LDS tree, sum or
+// max), the partials into ctx->geom_partial, one workgroup over the partials, 8 bytes to the host (fetch_scalar). The host
+// wrappers at the end of each part go through one launcher (launch_per_item).
+//
+// The reference (functional spec, nothing is ported) has analytic Jacobians in 2D, so the device values agree with it to
+// rounding; its BA and SE(3) edges use forward differences with delta = 1e-9, against which the analytic Jacobians here
+// agree to the quotients' noise. tests/test_gpu_geometry_edges.py pins every kernel to a 50-digit reference instead.
+// 2D helpers:
 //   C2DJacobians::Absolute_to_Relative with Jacobians   include/slam/2DSolverBase.h:373-418
 //   C2DJacobians::f_ClampAngle_2Pi / f_ClampAngularError_2Pi  :44-94
 //   CEdgePose2D::Calculate_Jacobians_Expectation_Error  include/slam/SE2_Types.h (error = z - h(x))
 //   CVertexPose2D::Operator_Plus                        include/slam/SE2_Types.h:70-74
-// The reference's 2D Jacobians are analytic, so the device values agree with it to rounding (the BA
-// and SE(3) edges use forward differences with delta = 1e-9 there: SURVEY 8f rank 2 explains why
-// those need a Delta-x-level tolerance instead).
-//
-// Layout = what spp_assemble_device consumes: J0, J1: ne x (3 x 3) column-major, r: ne x 3.
-// One thread per edge: 2 x 24 B of gathered poses + 24 B measurement in, 168 B out; HBM-bound.
+// SE(2) pose-pose layout = what spp_assemble_device consumes: J0, J1: ne x (3 x 3) column-major, r: ne x 3;
+// 2 x 24 B of gathered poses + 24 B measurement in, 168 B out; HBM-bound.
 
 #include "spp_internal.h"
 #include <math.h>
@@ -35,15 +50,30 @@ __device__ __forceinline__ double clamp_angular_error_2pi(double e)
 	return m;
 }
 
-__global__ __launch_bounds__(256)
-void se2_linearize_kernel(int64_t ne, const int32_t *__restrict__ v0, const int32_t *__restrict__ v1,
-	const double *__restrict__ poses, const double *__restrict__ meas, double *__restrict__ J0,
-	double *__restrict__ J1, double *__restrict__ r)
+// one block reduction for every kernel of this file: 256 threads, the LDS tree with offsets 128 ... 1; every thread
+// returns the total, thread 0 stores it. The ORDER is fixed (thread t combines t and t + off): sums are bit-reproducible and
+// tests/test_gpu_geometry_scalars.py derives its error bounds from this tree. Each kernel calls it once.
+struct SumOp { __device__ __forceinline__ double operator ()(double a, double b) const { return a + b; } };
+struct MaxOp { __device__ __forceinline__ double operator ()(double a, double b) const { return fmax(a, b); } };
+
+template <class Op>
+__device__ __forceinline__ double block_reduce_256(double v, Op op)
 {
-	const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if(e >= ne)
-		return;
-	const double *p1 = poses + 3 * (int64_t)v0[e], *p2 = poses + 3 * (int64_t)v1[e];
+	__shared__ double red[256];
+	red[threadIdx.x] = v;
+	__syncthreads();
+	for(int off = 128; off > 0; off >>= 1) {
+		if((int)threadIdx.x < off)
+			red[threadIdx.x] = op(red[threadIdx.x], red[threadIdx.x + off]);
+		__syncthreads();
+	}
+	return red[0];
+}
+
+// the edge e between the poses at p1 and p2 (se2_linearize_kernel: poses + 3 id; se2_linearize_at_kernel: state + offset)
+__device__ __forceinline__ void se2_linearize_edge(int64_t e, const double *__restrict__ p1, const double *__restrict__ p2,
+	const double *__restrict__ meas, double *__restrict__ J0, double *__restrict__ J1, double *__restrict__ r)
+{
 	const double p1e = p1[0], p1n = p1[1], p1a = p1[2];
 	const double de = p2[0] - p1e, dn = p2[1] - p1n;
 	double s, c;
@@ -68,12 +98,22 @@ void se2_linearize_kernel(int64_t ne, const int32_t *__restrict__ v0, const int3
 	b[6] = 0;   b[7] = 0;   b[8] = 1;
 }
 
+__global__ __launch_bounds__(256)
+void se2_linearize_kernel(int64_t ne, const int32_t *__restrict__ v0, const int32_t *__restrict__ v1,
+	const double *__restrict__ poses, const double *__restrict__ meas, double *__restrict__ J0,
+	double *__restrict__ J1, double *__restrict__ r)
+{
+	const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if(e >= ne)
+		return;
+	se2_linearize_edge(e, poses + 3 * (int64_t)v0[e], poses + 3 * (int64_t)v1[e], meas, J0, J1, r);
+}
+
 // x <- x (+) dx for 2D poses (add, clamp the angle); per-workgroup partial sums of dx^2 in a FIXED order
 __global__ __launch_bounds__(256)
 void se2_update_kernel(int64_t nv, double *__restrict__ poses, const double *__restrict__ dx, int apply,
 	double *__restrict__ partial)
 {
-	__shared__ double red[256];
 	const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	double s = 0;
 	if(v < nv) {
@@ -85,33 +125,20 @@ void se2_update_kernel(int64_t nv, double *__restrict__ poses, const double *__r
 			poses[3 * v + 2] = clamp_angle_2pi(poses[3 * v + 2] + d2);
 		}
 	}
-	red[threadIdx.x] = s;
-	__syncthreads();
-	for(int off = 128; off > 0; off >>= 1) {
-		if((int)threadIdx.x < off)
-			red[threadIdx.x] += red[threadIdx.x + off];
-		__syncthreads();
-	}
+	s = block_reduce_256(s, SumOp());
 	if(threadIdx.x == 0 && partial)
-		partial[blockIdx.x] = red[0];
+		partial[blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(256)
 void sum_partials_kernel(int64_t n, const double *__restrict__ partial, double *__restrict__ out)
 {
-	__shared__ double red[256];
 	double s = 0;
 	for(int64_t i = threadIdx.x; i < n; i += 256) // fixed assignment, fixed order: bit-reproducible
 		s += partial[i];
-	red[threadIdx.x] = s;
-	__syncthreads();
-	for(int off = 128; off > 0; off >>= 1) {
-		if((int)threadIdx.x < off)
-			red[threadIdx.x] += red[threadIdx.x + off];
-		__syncthreads();
-	}
+	s = block_reduce_256(s, SumOp());
 	if(threadIdx.x == 0)
-		out[0] = red[0];
+		out[0] = s;
 }
 
 // --------------------------------------------------------------------------------------------------
@@ -278,21 +305,14 @@ void ba_update_intrinsics_kernel(int64_t ni, double *__restrict__ intr, const in
 __global__ __launch_bounds__(256)
 void intrinsics_norm2_kernel(int64_t ni, const int64_t *__restrict__ dxoff, const double *__restrict__ dx, double *__restrict__ out)
 {
-	__shared__ double red[256];
 	double s = 0;
 	for(int64_t q = threadIdx.x; q < 5 * ni; q += 256) {
 		const double v = dx[dxoff[q / 5] + q % 5];
 		s += v * v;
 	}
-	red[threadIdx.x] = s;
-	__syncthreads();
-	for(int off = 128; off > 0; off >>= 1) {
-		if((int)threadIdx.x < off)
-			red[threadIdx.x] += red[threadIdx.x + off];
-		__syncthreads();
-	}
+	s = block_reduce_256(s, SumOp());
 	if(threadIdx.x == 0)
-		out[0] = red[0];
+		out[0] = s;
 }
 
 // --------------------------------------------------------------------------------------------------
@@ -369,8 +389,8 @@ void ba_stereo_linearize_kernel(int64_t no, const int32_t *__restrict__ cam_of, 
 	}
 }
 
-// camera (+): t' = t + R dt, R' = R exp(dr) through unit quaternions with w >= 0 (the reference's
-// AxisAngle_to_Quat / Quat_to_AxisAngle, 3DSolverBase.h:477-502,557+); one thread per camera
+// camera and 6D pose (+): t' = t + R dt, R' = R exp(dr) through unit quaternions with w >= 0 (the reference's
+// AxisAngle_to_Quat / Quat_to_AxisAngle, 3DSolverBase.h:477-502,557+); se3_plus serves se3_update_kernel and slam3d_pose_plus_kernel
 __device__ __forceinline__ void aa_to_quat(const double *a, double *q) // q = (w, x, y, z)
 {
 	const double th = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
@@ -390,25 +410,58 @@ __device__ __forceinline__ void aa_to_quat(const double *a, double *q) // q = (w
 	q[0] = c; q[1] = a[0] * s_over; q[2] = a[1] * s_over; q[3] = a[2] * s_over;
 }
 
+__device__ __forceinline__ void quat_to_aa(double w, double vx, double vy, double vz, double *a)
+{
+	if(w < 0) {
+		w = -w; vx = -vx; vy = -vy; vz = -vz;
+	}
+	const double vn = sqrt(vx * vx + vy * vy + vz * vz);
+	const double scale = (vn < 1e-12) ? 2.0 : 2.0 * atan2(vn, w) / vn;
+	a[0] = vx * scale; a[1] = vy * scale; a[2] = vz * scale;
+}
+
+__device__ __forceinline__ void quat_mul(const double *p, const double *q, double *o) // o = p q, (w, x, y, z)
+{
+	o[0] = p[0] * q[0] - p[1] * q[1] - p[2] * q[2] - p[3] * q[3];
+	o[1] = p[0] * q[1] + p[1] * q[0] + p[2] * q[3] - p[3] * q[2];
+	o[2] = p[0] * q[2] - p[1] * q[3] + p[2] * q[0] + p[3] * q[1];
+	o[3] = p[0] * q[3] + p[1] * q[2] - p[2] * q[1] + p[3] * q[0];
+}
+
+// 6D pose (+): t' = t + R dt, R' = R exp(dr) (CVertexPose3D::Operator_Plus, SE3_Types.h:44-47); o may be p
+__device__ __forceinline__ void se3_plus(const double *p, const double *d, double *o)
+{
+	double R[9], q1[4], q2[4], q[4];
+	axis_angle_to_rot(p + 3, R);
+	const double t0 = p[0] + (R[0] * d[0] + R[1] * d[1] + R[2] * d[2]);
+	const double t1 = p[1] + (R[3] * d[0] + R[4] * d[1] + R[5] * d[2]);
+	const double t2 = p[2] + (R[6] * d[0] + R[7] * d[1] + R[8] * d[2]);
+	aa_to_quat(p + 3, q1);
+	aa_to_quat(d + 3, q2);
+	quat_mul(q1, q2, q);
+	o[0] = t0; o[1] = t1; o[2] = t2;
+	quat_to_aa(q[0], q[1], q[2], q[3], o + 3);
+}
+
 __global__ __launch_bounds__(256)
 void ba_update_cams_kernel(int64_t nc, double *__restrict__ cams, const int64_t *__restrict__ dxoff, const double *__restrict__ dx)
 {
 	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if(i >= nc)
 		return;
+	// se3_plus written out, apart from the quaternion product: the compiler contracts vx^2 + vy^2 + vz^2 into other FMAs
+	// behind se3_plus / quat_to_aa than it does here, and a camera would move by an ulp against earlier builds
 	double *cam = cams + 6 * i;
 	const double *d = dx + dxoff[i];
-	double R[9], q1[4], q2[4];
+	double R[9], q1[4], q2[4], q[4];
 	axis_angle_to_rot(cam + 3, R);
 	cam[0] += R[0] * d[0] + R[1] * d[1] + R[2] * d[2];
 	cam[1] += R[3] * d[0] + R[4] * d[1] + R[5] * d[2];
 	cam[2] += R[6] * d[0] + R[7] * d[1] + R[8] * d[2];
 	aa_to_quat(cam + 3, q1);
 	aa_to_quat(d + 3, q2);
-	double w = q1[0] * q2[0] - q1[1] * q2[1] - q1[2] * q2[2] - q1[3] * q2[3];
-	double vx = q1[0] * q2[1] + q1[1] * q2[0] + q1[2] * q2[3] - q1[3] * q2[2];
-	double vy = q1[0] * q2[2] - q1[1] * q2[3] + q1[2] * q2[0] + q1[3] * q2[1];
-	double vz = q1[0] * q2[3] + q1[1] * q2[2] - q1[2] * q2[1] + q1[3] * q2[0];
+	quat_mul(q1, q2, q);
+	double w = q[0], vx = q[1], vy = q[2], vz = q[3];
 	if(w < 0) {
 		w = -w; vx = -vx; vy = -vy; vz = -vz;
 	}
@@ -434,17 +487,10 @@ void ba_update_points_kernel(int64_t np, double *__restrict__ pts, const int64_t
 __global__ __launch_bounds__(256)
 void norm2_partial_kernel(int64_t n, const double *__restrict__ v, double *__restrict__ partial)
 {
-	__shared__ double red[256];
 	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	red[threadIdx.x] = (i < n) ? v[i] * v[i] : 0.0;
-	__syncthreads();
-	for(int off = 128; off > 0; off >>= 1) {
-		if((int)threadIdx.x < off)
-			red[threadIdx.x] += red[threadIdx.x + off];
-		__syncthreads();
-	}
+	const double s = block_reduce_256((i < n) ? v[i] * v[i] : 0.0, SumOp());
 	if(threadIdx.x == 0)
-		partial[blockIdx.x] = red[0];
+		partial[blockIdx.x] = s;
 }
 
 // --------------------------------------------------------------------------------------------------
@@ -458,24 +504,6 @@ void norm2_partial_kernel(int64_t n, const double *__restrict__ v, double *__res
 // agreeing with the reference's difference quotients to their noise (tests/test_gpu_se3_geometry.py).
 // One thread per edge; J0, J1: 6 x 6 column-major, r: 6.
 // --------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void quat_to_aa(double w, double vx, double vy, double vz, double *a)
-{
-	if(w < 0) {
-		w = -w; vx = -vx; vy = -vy; vz = -vz;
-	}
-	const double vn = sqrt(vx * vx + vy * vy + vz * vz);
-	const double scale = (vn < 1e-12) ? 2.0 : 2.0 * atan2(vn, w) / vn;
-	a[0] = vx * scale; a[1] = vy * scale; a[2] = vz * scale;
-}
-
-__device__ __forceinline__ void quat_mul(const double *p, const double *q, double *o) // o = p q, (w, x, y, z)
-{
-	o[0] = p[0] * q[0] - p[1] * q[1] - p[2] * q[2] - p[3] * q[3];
-	o[1] = p[0] * q[1] + p[1] * q[0] + p[2] * q[3] - p[3] * q[2];
-	o[2] = p[0] * q[2] - p[1] * q[3] + p[2] * q[0] + p[3] * q[1];
-	o[3] = p[0] * q[3] + p[1] * q[2] - p[2] * q[1] + p[3] * q[0];
-}
-
 // the edge e between the poses at p1 and p2 (se3_linearize_kernel: poses + 6 id; se3_linearize_at_kernel: state + offset)
 __device__ __forceinline__ void se3_linearize_edge(int64_t e, const double *__restrict__ p1, const double *__restrict__ p2,
 	const double *__restrict__ meas, double *__restrict__ J0, double *__restrict__ J1, double *__restrict__ r)
@@ -556,21 +584,6 @@ void se3_linearize_kernel(int64_t ne, const int32_t *__restrict__ v0, const int3
 	se3_linearize_edge(e, poses + 6 * (int64_t)v0[e], poses + 6 * (int64_t)v1[e], meas, J0, J1, r);
 }
 
-// 6D pose (+): t' = t + R dt, R' = R exp(dr) (CVertexPose3D::Operator_Plus, SE3_Types.h:44-47); o may be p
-__device__ __forceinline__ void se3_plus(const double *p, const double *d, double *o)
-{
-	double R[9], q1[4], q2[4], q[4];
-	axis_angle_to_rot(p + 3, R);
-	const double t0 = p[0] + (R[0] * d[0] + R[1] * d[1] + R[2] * d[2]);
-	const double t1 = p[1] + (R[3] * d[0] + R[4] * d[1] + R[5] * d[2]);
-	const double t2 = p[2] + (R[6] * d[0] + R[7] * d[1] + R[8] * d[2]);
-	aa_to_quat(p + 3, q1);
-	aa_to_quat(d + 3, q2);
-	quat_mul(q1, q2, q);
-	o[0] = t0; o[1] = t1; o[2] = t2;
-	quat_to_aa(q[0], q[1], q[2], q[3], o + 3);
-}
-
 __global__ __launch_bounds__(256)
 void se3_update_kernel(int64_t nv, double *__restrict__ poses, const double *__restrict__ dx)
 {
@@ -591,7 +604,6 @@ template <int RD>
 __global__ __launch_bounds__(256)
 void edge_chi2_kernel(int64_t ne, const double *__restrict__ r, const double *__restrict__ Om, double *__restrict__ partial)
 {
-	__shared__ double red[256];
 	const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	double s = 0;
 	if(e < ne) {
@@ -605,15 +617,9 @@ void edge_chi2_kernel(int64_t ne, const double *__restrict__ r, const double *__
 			s += re[i] * t;
 		}
 	}
-	red[threadIdx.x] = s;
-	__syncthreads();
-	for(int off = 128; off > 0; off >>= 1) {
-		if((int)threadIdx.x < off)
-			red[threadIdx.x] += red[threadIdx.x + off];
-		__syncthreads();
-	}
+	s = block_reduce_256(s, SumOp());
 	if(threadIdx.x == 0)
-		partial[blockIdx.x] = red[0];
+		partial[blockIdx.x] = s;
 }
 
 template <int RD, int D>
@@ -641,55 +647,83 @@ __global__ __launch_bounds__(256)
 void edge_maxdiag_kernel(int64_t ne, const double *__restrict__ J0, const double *__restrict__ J1,
 	const double *__restrict__ Om, double *__restrict__ partial)
 {
-	__shared__ double red[256];
 	const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	double m = 0;
 	if(e < ne)
 		m = fmax(max_hdiag<RD, D0>(J0 + RD * D0 * e, Om + RD * RD * e), max_hdiag<RD, D1>(J1 + RD * D1 * e, Om + RD * RD * e));
-	red[threadIdx.x] = m;
-	__syncthreads();
-	for(int off = 128; off > 0; off >>= 1) {
-		if((int)threadIdx.x < off)
-			red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + off]);
-		__syncthreads();
-	}
+	m = block_reduce_256(m, MaxOp());
 	if(threadIdx.x == 0)
-		partial[blockIdx.x] = red[0];
+		partial[blockIdx.x] = m;
 }
 
 __global__ __launch_bounds__(256)
 void max_partials_kernel(int64_t n, const double *__restrict__ partial, double *__restrict__ out)
 {
-	__shared__ double red[256];
 	double m = 0;
 	for(int64_t i = threadIdx.x; i < n; i += 256)
 		m = fmax(m, partial[i]);
-	red[threadIdx.x] = m;
-	__syncthreads();
-	for(int off = 128; off > 0; off >>= 1) {
-		if((int)threadIdx.x < off)
-			red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + off]);
-		__syncthreads();
-	}
+	m = block_reduce_256(m, MaxOp());
 	if(threadIdx.x == 0)
-		out[0] = red[0];
+		out[0] = m;
 }
 
 __global__ __launch_bounds__(256)
 void gain_partial_kernel(int64_t n, const double *__restrict__ dx, const double *__restrict__ rhs, double alpha,
 	double *__restrict__ partial)
 {
-	__shared__ double red[256];
 	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	red[threadIdx.x] = (i < n) ? dx[i] * (alpha * dx[i] + rhs[i]) : 0.0;
-	__syncthreads();
-	for(int off = 128; off > 0; off >>= 1) {
-		if((int)threadIdx.x < off)
-			red[threadIdx.x] += red[threadIdx.x + off];
-		__syncthreads();
-	}
+	const double s = block_reduce_256((i < n) ? dx[i] * (alpha * dx[i] + rhs[i]) : 0.0, SumOp());
 	if(threadIdx.x == 0)
-		partial[blockIdx.x] = red[0];
+		partial[blockIdx.x] = s;
+}
+
+// --------------------------------------------------------------------------------------------------
+// Host side. ONE launcher, ONE second stage, ONE read-back:
+//   launch_per_item   kernel(n, ...) over ceil(n / 256) workgroups of 256 on ctx->stream; nothing for n = 0
+//   geom_partial      p[0] = the scalar, p[1 .. nwg] = the first stage's partials, anything else behind them
+//   reduce_partials   sum_partials_kernel / max_partials_kernel over the partials into p[0] (enqueued)
+//   enqueue_norm2     ||v||^2 of a flat vector into p[0] (enqueued), `extra` doubles kept behind the partials
+//   fetch_scalar      p[0] to the host: the one stream synchronisation of an entry point that returns a scalar
+// --------------------------------------------------------------------------------------------------
+static inline int64_t n_workgroups(int64_t n)
+{
+	return (n + 255) / 256;
+}
+
+template <class Kernel, class... Args>
+static void launch_over(spp_ctx *ctx, Kernel kernel, int64_t n_threads, Args... args)
+{
+	if(!n_threads)
+		return;
+	hipLaunchKernelGGL(kernel, dim3((unsigned)n_workgroups(n_threads)), dim3(256), 0, ctx->stream, args...);
+	SPP_HIP_CHECK(hipGetLastError());
+}
+
+template <class Kernel, class... Args>
+static void launch_per_item(spp_ctx *ctx, Kernel kernel, int64_t n, Args... args)
+{
+	launch_over(ctx, kernel, n, n, args...);
+}
+
+static double *reserve_partials(spp_ctx *ctx, int64_t n, size_t extra = 0)
+{
+	ctx->geom_partial.reserve((size_t)n_workgroups(n) + 1 + extra);
+	return ctx->geom_partial.p + 1;
+}
+
+static void reduce_partials(spp_ctx *ctx, int64_t n, bool take_max = false)
+{
+	hipLaunchKernelGGL(take_max ? max_partials_kernel : sum_partials_kernel, dim3(1), dim3(256), 0, ctx->stream, n_workgroups(n),
+		ctx->geom_partial.p + 1, ctx->geom_partial.p);
+}
+
+static void enqueue_norm2(spp_ctx *ctx, int64_t n, const double *d_v, size_t extra = 0)
+{
+	double *part = reserve_partials(ctx, n, extra);
+	if(!n)
+		return;
+	launch_per_item(ctx, norm2_partial_kernel, n, d_v, part);
+	reduce_partials(ctx, n);
 }
 
 static double fetch_scalar(spp_ctx *ctx)
@@ -722,26 +756,19 @@ void edge_robust_weights(spp_ctx *ctx, int64_t ne, int rd, int kind, double scal
 {
 	SPP_REQUIRE(kind == 0, SPP_E_UNSUPPORTED, "robust weights: only the Huber kernel (kind 0) is instantiated");
 	SPP_REQUIRE(scale > 0 && param > 0 && rd > 0, SPP_E_BADARG, "robust weights: scale, parameter and residual dimension must be positive");
-	if(!ne)
-		return;
-	hipLaunchKernelGGL(edge_robust_weight_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, ctx->stream, ne, rd, kind,
-		scale, param, d_r, d_w);
-	SPP_HIP_CHECK(hipGetLastError());
+	launch_per_item(ctx, edge_robust_weight_kernel, ne, rd, kind, scale, param, d_r, d_w);
 }
 
 double edge_chi2(spp_ctx *ctx, int64_t ne, int rd, const double *d_r, const double *d_Om)
 {
 	if(!ne)
 		return 0;
-	const int64_t nwg = (ne + 255) / 256;
-	ctx->geom_partial.reserve((size_t)nwg + 1);
-	double *part = ctx->geom_partial.p + 1;
-	const dim3 g((unsigned)nwg), b(256);
-	if(rd == 2) hipLaunchKernelGGL((edge_chi2_kernel<2>), g, b, 0, ctx->stream, ne, d_r, d_Om, part);
-	else if(rd == 3) hipLaunchKernelGGL((edge_chi2_kernel<3>), g, b, 0, ctx->stream, ne, d_r, d_Om, part);
-	else if(rd == 6) hipLaunchKernelGGL((edge_chi2_kernel<6>), g, b, 0, ctx->stream, ne, d_r, d_Om, part);
+	double *part = reserve_partials(ctx, ne);
+	if(rd == 2) launch_per_item(ctx, edge_chi2_kernel<2>, ne, d_r, d_Om, part);
+	else if(rd == 3) launch_per_item(ctx, edge_chi2_kernel<3>, ne, d_r, d_Om, part);
+	else if(rd == 6) launch_per_item(ctx, edge_chi2_kernel<6>, ne, d_r, d_Om, part);
 	else throw Error(SPP_E_UNSUPPORTED, "chi2: residual dimension must be 2, 3 or 6");
-	hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, ctx->stream, nwg, part, ctx->geom_partial.p);
+	reduce_partials(ctx, ne);
 	return fetch_scalar(ctx);
 }
 
@@ -750,16 +777,13 @@ double edge_hessian_maxdiag(spp_ctx *ctx, int64_t ne, int rd, int d0, int d1, co
 {
 	if(!ne)
 		return 0;
-	const int64_t nwg = (ne + 255) / 256;
-	ctx->geom_partial.reserve((size_t)nwg + 1);
-	double *part = ctx->geom_partial.p + 1;
-	const dim3 g((unsigned)nwg), b(256);
-	if(rd == 2 && d0 == 6 && d1 == 3) hipLaunchKernelGGL((edge_maxdiag_kernel<2, 6, 3>), g, b, 0, ctx->stream, ne, d_J0, d_J1, d_Om, part);
-	else if(rd == 3 && d0 == 3 && d1 == 3) hipLaunchKernelGGL((edge_maxdiag_kernel<3, 3, 3>), g, b, 0, ctx->stream, ne, d_J0, d_J1, d_Om, part);
-	else if(rd == 6 && d0 == 6 && d1 == 6) hipLaunchKernelGGL((edge_maxdiag_kernel<6, 6, 6>), g, b, 0, ctx->stream, ne, d_J0, d_J1, d_Om, part);
-	else if(rd == 3 && d0 == 6 && d1 == 3) hipLaunchKernelGGL((edge_maxdiag_kernel<3, 6, 3>), g, b, 0, ctx->stream, ne, d_J0, d_J1, d_Om, part);
+	double *part = reserve_partials(ctx, ne);
+	if(rd == 2 && d0 == 6 && d1 == 3) launch_per_item(ctx, edge_maxdiag_kernel<2, 6, 3>, ne, d_J0, d_J1, d_Om, part);
+	else if(rd == 3 && d0 == 3 && d1 == 3) launch_per_item(ctx, edge_maxdiag_kernel<3, 3, 3>, ne, d_J0, d_J1, d_Om, part);
+	else if(rd == 6 && d0 == 6 && d1 == 6) launch_per_item(ctx, edge_maxdiag_kernel<6, 6, 6>, ne, d_J0, d_J1, d_Om, part);
+	else if(rd == 3 && d0 == 6 && d1 == 3) launch_per_item(ctx, edge_maxdiag_kernel<3, 6, 3>, ne, d_J0, d_J1, d_Om, part);
 	else throw Error(SPP_E_UNSUPPORTED, "max Hessian diagonal: edge group must be (2,6,3), (3,3,3), (6,6,6) or (3,6,3)");
-	hipLaunchKernelGGL(max_partials_kernel, dim3(1), dim3(256), 0, ctx->stream, nwg, part, ctx->geom_partial.p);
+	reduce_partials(ctx, ne, true);
 	return fetch_scalar(ctx);
 }
 
@@ -767,70 +791,45 @@ double lm_gain_denominator(spp_ctx *ctx, int64_t n, const double *d_dx, const do
 {
 	if(!n)
 		return 0;
-	const int64_t nwg = (n + 255) / 256;
-	ctx->geom_partial.reserve((size_t)nwg + 1);
-	double *part = ctx->geom_partial.p + 1;
-	hipLaunchKernelGGL(gain_partial_kernel, dim3((unsigned)nwg), dim3(256), 0, ctx->stream, n, d_dx, d_rhs, alpha, part);
-	hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, ctx->stream, nwg, part, ctx->geom_partial.p);
+	launch_per_item(ctx, gain_partial_kernel, n, d_dx, d_rhs, alpha, reserve_partials(ctx, n));
+	reduce_partials(ctx, n);
 	return fetch_scalar(ctx);
 }
 
 void se3_linearize(spp_ctx *ctx, int64_t ne, const int32_t *d_v0, const int32_t *d_v1, const double *d_poses,
 	const double *d_meas, double *d_J0, double *d_J1, double *d_r)
 {
-	if(!ne)
-		return;
-	hipLaunchKernelGGL(se3_linearize_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, ctx->stream,
-		ne, d_v0, d_v1, d_poses, d_meas, d_J0, d_J1, d_r);
-	SPP_HIP_CHECK(hipGetLastError());
+	launch_per_item(ctx, se3_linearize_kernel, ne, d_v0, d_v1, d_poses, d_meas, d_J0, d_J1, d_r);
 }
 
 double se3_update(spp_ctx *ctx, int64_t nv, double *d_poses, const double *d_dx, bool apply)
 {
 	if(!nv)
 		return 0;
-	const int64_t n = 6 * nv, nwg = (n + 255) / 256;
-	ctx->geom_partial.reserve((size_t)nwg + 1);
-	hipLaunchKernelGGL(norm2_partial_kernel, dim3((unsigned)nwg), dim3(256), 0, ctx->stream, n, d_dx, ctx->geom_partial.p + 1);
-	hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, ctx->stream, nwg, ctx->geom_partial.p + 1, ctx->geom_partial.p);
+	enqueue_norm2(ctx, 6 * nv, d_dx);
 	if(apply)
-		hipLaunchKernelGGL(se3_update_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, ctx->stream, nv, d_poses, d_dx);
-	SPP_HIP_CHECK(hipGetLastError());
-	double h = 0;
-	SPP_HIP_CHECK(hipMemcpyAsync(&h, ctx->geom_partial.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-	SPP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-	return h;
+		launch_per_item(ctx, se3_update_kernel, nv, d_poses, d_dx);
+	return fetch_scalar(ctx);
 }
 
 void ba_linearize(spp_ctx *ctx, int64_t no, const int32_t *d_cam_of, const int32_t *d_pt_of, const double *d_cams,
 	const double *d_intr, const double *d_pts, const double *d_meas, double *d_J0, double *d_J1, double *d_r)
 {
-	if(!no)
-		return;
-	hipLaunchKernelGGL(ba_linearize_kernel, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, ctx->stream,
-		no, d_cam_of, d_pt_of, d_cams, d_intr, d_pts, d_meas, d_J0, d_J1, d_r);
-	SPP_HIP_CHECK(hipGetLastError());
+	launch_per_item(ctx, ba_linearize_kernel, no, d_cam_of, d_pt_of, d_cams, d_intr, d_pts, d_meas, d_J0, d_J1, d_r);
 }
 
 void ba_stereo_linearize(spp_ctx *ctx, int64_t no, const int32_t *d_cam_of, const int32_t *d_pt_of, const double *d_cams,
 	const double *d_intr, const double *d_pts, const double *d_meas, double *d_J0, double *d_J1, double *d_r)
 {
-	if(!no)
-		return;
-	hipLaunchKernelGGL(ba_stereo_linearize_kernel, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, ctx->stream,
-		no, d_cam_of, d_pt_of, d_cams, d_intr, d_pts, d_meas, d_J0, d_J1, d_r);
-	SPP_HIP_CHECK(hipGetLastError());
+	launch_per_item(ctx, ba_stereo_linearize_kernel, no, d_cam_of, d_pt_of, d_cams, d_intr, d_pts, d_meas, d_J0, d_J1, d_r);
 }
 
 void ba_intrinsics_linearize(spp_ctx *ctx, int64_t no, const int32_t *d_cam_of, const int32_t *d_pt_of, const int32_t *d_intr_of,
 	const double *d_cams, const double *d_intr, const double *d_pts, const double *d_meas, double *d_J0, double *d_J1, double *d_J2,
 	double *d_r)
 {
-	if(!no)
-		return;
-	hipLaunchKernelGGL(ba_intrinsics_linearize_kernel, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, ctx->stream,
-		no, d_cam_of, d_pt_of, d_intr_of, d_cams, d_intr, d_pts, d_meas, d_J0, d_J1, d_J2, d_r);
-	SPP_HIP_CHECK(hipGetLastError());
+	launch_per_item(ctx, ba_intrinsics_linearize_kernel, no, d_cam_of, d_pt_of, d_intr_of, d_cams, d_intr, d_pts, d_meas, d_J0, d_J1,
+		d_J2, d_r);
 }
 
 double ba_intrinsics_update(spp_ctx *ctx, int64_t ni, double *d_intr, const int64_t *d_intr_dxoff, const double *d_dx, bool apply)
@@ -840,44 +839,30 @@ double ba_intrinsics_update(spp_ctx *ctx, int64_t ni, double *d_intr, const int6
 	ctx->geom_partial.reserve(2);
 	hipLaunchKernelGGL(intrinsics_norm2_kernel, dim3(1), dim3(256), 0, ctx->stream, ni, d_intr_dxoff, d_dx, ctx->geom_partial.p);
 	if(apply)
-		hipLaunchKernelGGL(ba_update_intrinsics_kernel, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, ctx->stream, ni, d_intr,
-			d_intr_dxoff, d_dx);
-	SPP_HIP_CHECK(hipGetLastError());
-	double h = 0;
-	SPP_HIP_CHECK(hipMemcpyAsync(&h, ctx->geom_partial.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-	SPP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-	return h;
+		launch_per_item(ctx, ba_update_intrinsics_kernel, ni, d_intr, d_intr_dxoff, d_dx);
+	return fetch_scalar(ctx);
 }
 
+// n_dx = 0: there is no norm to copy, and the stream is synchronized all the same
 double ba_update(spp_ctx *ctx, int64_t nc, double *d_cams, const int64_t *d_cam_dxoff, int64_t np, double *d_pts,
 	const int64_t *d_pt_dxoff, const double *d_dx, int64_t n_dx, bool apply)
 {
-	const int64_t nwg = (n_dx + 255) / 256;
-	ctx->geom_partial.reserve((size_t)nwg + 1);
-	if(n_dx) {
-		hipLaunchKernelGGL(norm2_partial_kernel, dim3((unsigned)nwg), dim3(256), 0, ctx->stream, n_dx, d_dx, ctx->geom_partial.p + 1);
-		hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, ctx->stream, nwg, ctx->geom_partial.p + 1, ctx->geom_partial.p);
+	enqueue_norm2(ctx, n_dx, d_dx);
+	if(apply) {
+		launch_per_item(ctx, ba_update_cams_kernel, nc, d_cams, d_cam_dxoff, d_dx);
+		launch_per_item(ctx, ba_update_points_kernel, np, d_pts, d_pt_dxoff, d_dx);
 	}
-	if(apply && nc)
-		hipLaunchKernelGGL(ba_update_cams_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, ctx->stream, nc, d_cams, d_cam_dxoff, d_dx);
-	if(apply && np)
-		hipLaunchKernelGGL(ba_update_points_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, ctx->stream, np, d_pts, d_pt_dxoff, d_dx);
-	SPP_HIP_CHECK(hipGetLastError());
-	double h = 0;
 	if(n_dx)
-		SPP_HIP_CHECK(hipMemcpyAsync(&h, ctx->geom_partial.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+		return fetch_scalar(ctx);
+	SPP_HIP_CHECK(hipGetLastError());
 	SPP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-	return h;
+	return 0;
 }
 
 void se2_linearize(spp_ctx *ctx, int64_t ne, const int32_t *d_v0, const int32_t *d_v1, const double *d_poses,
 	const double *d_meas, double *d_J0, double *d_J1, double *d_r)
 {
-	if(!ne)
-		return;
-	hipLaunchKernelGGL(se2_linearize_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, ctx->stream,
-		ne, d_v0, d_v1, d_poses, d_meas, d_J0, d_J1, d_r);
-	SPP_HIP_CHECK(hipGetLastError());
+	launch_per_item(ctx, se2_linearize_kernel, ne, d_v0, d_v1, d_poses, d_meas, d_J0, d_J1, d_r);
 }
 
 // returns ||dx||^2 (synchronizes the stream: the caller needs the value for the stopping test, as the
@@ -886,17 +871,9 @@ double se2_update(spp_ctx *ctx, int64_t nv, double *d_poses, const double *d_dx,
 {
 	if(!nv)
 		return 0;
-	const int64_t nwg = (nv + 255) / 256;
-	ctx->geom_partial.reserve((size_t)nwg + 1);
-	hipLaunchKernelGGL(se2_update_kernel, dim3((unsigned)nwg), dim3(256), 0, ctx->stream, nv, d_poses, d_dx,
-		apply ? 1 : 0, ctx->geom_partial.p + 1);
-	hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, ctx->stream, nwg, ctx->geom_partial.p + 1,
-		ctx->geom_partial.p);
-	SPP_HIP_CHECK(hipGetLastError());
-	double h = 0;
-	SPP_HIP_CHECK(hipMemcpyAsync(&h, ctx->geom_partial.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-	SPP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-	return h;
+	launch_per_item(ctx, se2_update_kernel, nv, d_poses, d_dx, apply ? 1 : 0, reserve_partials(ctx, nv));
+	reduce_partials(ctx, nv);
+	return fetch_scalar(ctx);
 }
 
 // --------------------------------------------------------------------------------------------------
@@ -916,27 +893,7 @@ void se2_linearize_at_kernel(int64_t ne, const int64_t *__restrict__ off0, const
 	const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if(e >= ne)
 		return;
-	// the body of se2_linearize_kernel, the two poses at their given offsets
-	const double *p1 = state + off0[e], *p2 = state + off1[e];
-	const double p1e = p1[0], p1n = p1[1], p1a = p1[2];
-	const double de = p2[0] - p1e, dn = p2[1] - p1n;
-	double s, c;
-	sincos(p1a, &s, &c);
-	const double hf = c * de + s * dn, hl = -s * de + c * dn, ha = clamp_angle_2pi(p2[2] - p1a);
-	const double *z = meas + 3 * e;
-	r[3 * e + 0] = z[0] - hf;
-	r[3 * e + 1] = z[1] - hl;
-	r[3 * e + 2] = clamp_angular_error_2pi(z[2] - ha);
-	double *a = J0 + 9 * e;
-	a[0] = -c;  a[1] = s;   a[2] = 0;
-	a[3] = -s;  a[4] = -c;  a[5] = 0;
-	a[6] = -s * de + c * dn;
-	a[7] = -c * de - s * dn;
-	a[8] = -1;
-	double *b = J1 + 9 * e;
-	b[0] = c;   b[1] = -s;  b[2] = 0;
-	b[3] = s;   b[4] = c;   b[5] = 0;
-	b[6] = 0;   b[7] = 0;   b[8] = 1;
+	se2_linearize_edge(e, state + off0[e], state + off1[e], meas, J0, J1, r);
 }
 
 __global__ __launch_bounds__(256)
@@ -984,21 +941,13 @@ void clamp_angles_kernel(int64_t na, const int64_t *__restrict__ off, double *__
 void se2_linearize_at(spp_ctx *ctx, int64_t ne, const int64_t *d_off0, const int64_t *d_off1, const double *d_state,
 	const double *d_meas, double *d_J0, double *d_J1, double *d_r)
 {
-	if(!ne)
-		return;
-	hipLaunchKernelGGL(se2_linearize_at_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, ctx->stream,
-		ne, d_off0, d_off1, d_state, d_meas, d_J0, d_J1, d_r);
-	SPP_HIP_CHECK(hipGetLastError());
+	launch_per_item(ctx, se2_linearize_at_kernel, ne, d_off0, d_off1, d_state, d_meas, d_J0, d_J1, d_r);
 }
 
 void se2_rb_linearize(spp_ctx *ctx, int64_t ne, const int64_t *d_pose_off, const int64_t *d_lm_off, const double *d_state,
 	const double *d_meas, double *d_J0, double *d_J1, double *d_r)
 {
-	if(!ne)
-		return;
-	hipLaunchKernelGGL(se2_rb_linearize_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, ctx->stream,
-		ne, d_pose_off, d_lm_off, d_state, d_meas, d_J0, d_J1, d_r);
-	SPP_HIP_CHECK(hipGetLastError());
+	launch_per_item(ctx, se2_rb_linearize_kernel, ne, d_pose_off, d_lm_off, d_state, d_meas, d_J0, d_J1, d_r);
 }
 
 // ||dx||^2 (two-stage sum, as se3_update) and, if apply, x += dx over the flat state, then the pose angles clamped: the sum
@@ -1008,21 +957,12 @@ double slam2d_update(spp_ctx *ctx, int64_t n, double *d_state, const double *d_d
 {
 	if(!n)
 		return 0;
-	const int64_t nwg = (n + 255) / 256;
-	ctx->geom_partial.reserve((size_t)nwg + 1);
-	hipLaunchKernelGGL(norm2_partial_kernel, dim3((unsigned)nwg), dim3(256), 0, ctx->stream, n, d_dx, ctx->geom_partial.p + 1);
-	hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, ctx->stream, nwg, ctx->geom_partial.p + 1, ctx->geom_partial.p);
+	enqueue_norm2(ctx, n, d_dx);
 	if(apply) {
-		hipLaunchKernelGGL(axpy1_kernel, dim3((unsigned)nwg), dim3(256), 0, ctx->stream, n, d_state, d_dx);
-		if(n_angles)
-			hipLaunchKernelGGL(clamp_angles_kernel, dim3((unsigned)((n_angles + 255) / 256)), dim3(256), 0, ctx->stream,
-				n_angles, d_angle_off, d_state);
+		launch_per_item(ctx, axpy1_kernel, n, d_state, d_dx);
+		launch_per_item(ctx, clamp_angles_kernel, n_angles, d_angle_off, d_state);
 	}
-	SPP_HIP_CHECK(hipGetLastError());
-	double h = 0;
-	SPP_HIP_CHECK(hipMemcpyAsync(&h, ctx->geom_partial.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-	SPP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-	return h;
+	return fetch_scalar(ctx);
 }
 
 // --------------------------------------------------------------------------------------------------
@@ -1101,21 +1041,13 @@ void slam3d_pose_store_kernel(int64_t np, const int64_t *__restrict__ pose_off, 
 void se3_linearize_at(spp_ctx *ctx, int64_t ne, const int64_t *d_off0, const int64_t *d_off1, const double *d_state,
 	const double *d_meas, double *d_J0, double *d_J1, double *d_r)
 {
-	if(!ne)
-		return;
-	hipLaunchKernelGGL(se3_linearize_at_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, ctx->stream,
-		ne, d_off0, d_off1, d_state, d_meas, d_J0, d_J1, d_r);
-	SPP_HIP_CHECK(hipGetLastError());
+	launch_per_item(ctx, se3_linearize_at_kernel, ne, d_off0, d_off1, d_state, d_meas, d_J0, d_J1, d_r);
 }
 
 void se3_xyz_linearize(spp_ctx *ctx, int64_t ne, const int64_t *d_pose_off, const int64_t *d_lm_off, const double *d_state,
 	const double *d_meas, double *d_J0, double *d_J1, double *d_r)
 {
-	if(!ne)
-		return;
-	hipLaunchKernelGGL(se3_xyz_linearize_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, ctx->stream,
-		ne, d_pose_off, d_lm_off, d_state, d_meas, d_J0, d_J1, d_r);
-	SPP_HIP_CHECK(hipGetLastError());
+	launch_per_item(ctx, se3_xyz_linearize_kernel, ne, d_pose_off, d_lm_off, d_state, d_meas, d_J0, d_J1, d_r);
 }
 
 // ||dx||^2 over the flat increment (two-stage sum, as se3_update) and, if apply: the listed poses composed (se3_plus on the
@@ -1126,25 +1058,14 @@ double slam3d_update(spp_ctx *ctx, int64_t n, double *d_state, const double *d_d
 {
 	if(!n)
 		return 0;
-	const int64_t nwg = (n + 255) / 256;
-	ctx->geom_partial.reserve((size_t)(nwg + 1 + (apply ? 6 * n_poses : 0)));
-	hipLaunchKernelGGL(norm2_partial_kernel, dim3((unsigned)nwg), dim3(256), 0, ctx->stream, n, d_dx, ctx->geom_partial.p + 1);
-	hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, ctx->stream, nwg, ctx->geom_partial.p + 1, ctx->geom_partial.p);
+	enqueue_norm2(ctx, n, d_dx, apply ? (size_t)(6 * n_poses) : 0);
 	if(apply) {
-		double *tmp = ctx->geom_partial.p + 1 + nwg;
-		if(n_poses)
-			hipLaunchKernelGGL(slam3d_pose_plus_kernel, dim3((unsigned)((n_poses + 255) / 256)), dim3(256), 0, ctx->stream,
-				n_poses, d_pose_off, d_state, d_dx, tmp);
-		hipLaunchKernelGGL(axpy1_kernel, dim3((unsigned)nwg), dim3(256), 0, ctx->stream, n, d_state, d_dx);
-		if(n_poses)
-			hipLaunchKernelGGL(slam3d_pose_store_kernel, dim3((unsigned)((6 * n_poses + 255) / 256)), dim3(256), 0, ctx->stream,
-				n_poses, d_pose_off, tmp, d_state);
+		double *tmp = ctx->geom_partial.p + 1 + n_workgroups(n);
+		launch_per_item(ctx, slam3d_pose_plus_kernel, n_poses, d_pose_off, d_state, d_dx, tmp);
+		launch_per_item(ctx, axpy1_kernel, n, d_state, d_dx);
+		launch_over(ctx, slam3d_pose_store_kernel, 6 * n_poses, n_poses, d_pose_off, tmp, d_state);
 	}
-	SPP_HIP_CHECK(hipGetLastError());
-	double h = 0;
-	SPP_HIP_CHECK(hipMemcpyAsync(&h, ctx->geom_partial.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-	SPP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-	return h;
+	return fetch_scalar(ctx);
 }
 
 } // namespace spp

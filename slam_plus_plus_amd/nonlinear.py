@@ -12,6 +12,7 @@ Per iteration, exactly in the reference's order (:605-664):
     if the factorization failed: stop, estimate unchanged
 Defaults are slam_app's: 5 iterations, threshold 0.01 (src/slam_app/Main.cpp:706-707).
 """
+import collections
 import math
 
 import numpy as np
@@ -66,11 +67,22 @@ class CPoseGraph3D:
         return float(np.einsum("ei,eij,ej->", prob.r, prob.Om.reshape(-1, 6, 6), prob.r))
 
 
-class CSlam2D:
-    """2D landmark SLAM 'system': 3-wide poses and 2-wide landmarks in one flat state laid out by `dim` (the layout of
-    eta: in 2D state and increment coincide), odometry edges odo (m, 5) i j dx dy dtheta + odo_info (m, 3, 3)
-    (CEdgePose2D) and observations obs (k, 4) pose landmark range bearing + obs_info (k, 2, 2) (CEdgePoseLandmark2D).
-    odo_seq / obs_seq: position of every edge in the graph's edge order (default: odometry, then observations)."""
+class _SlamKind(collections.namedtuple("_SlamKind", "pose_w lm_w lin_odo lin_obs update listed")):
+    """what tells 2D landmark SLAM from 3D: the widths of a pose and of a landmark (a measurement is as wide as what it
+    measures: odometry pose_w columns, an observation lm_w, both after the two vertex ids), the api.Context methods that
+    linearize the two edge groups and update the state, and the offsets the update lists beside the flat state (the
+    system's attribute of that name)."""
+
+
+_SLAM2D = _SlamKind(3, 2, "se2_linearize_at_device", "se2_rb_linearize_device", "slam2d_update_device", "angle_off")
+_SLAM3D = _SlamKind(6, 3, "se3_linearize_at_device", "se3_xyz_linearize_device", "slam3d_update_device", "pose_off")
+
+
+class _CSlam:
+    """landmark SLAM 'system': poses and landmarks in one flat state laid out by `dim` (the layout of eta), odometry edges
+    odo (m, 2 + pose_w) i j measurement + odo_info (m, pose_w, pose_w) and observations obs (k, 2 + lm_w) pose landmark
+    measurement + obs_info (k, lm_w, lm_w). odo_seq / obs_seq: position of every edge in the graph's edge order (default:
+    odometry, then observations). A subclass names its kind, its host linearization and its plus."""
 
     def __init__(self, dim, state, odo, odo_info, obs, obs_info, odo_seq=None, obs_seq=None, unary_vertex=0):
         self.dim = np.asarray(dim, dtype=np.int32)
@@ -82,73 +94,72 @@ class CSlam2D:
         self.obs_seq = m + np.arange(k, dtype=np.int64) if obs_seq is None else np.asarray(obs_seq, dtype=np.int64)
         self.unary_vertex = unary_vertex
         self.base = slam2d_offsets(self.dim)
-        self.angle_off = self.base[:-1][self.dim == 3] + 2
+        self.pose_off = self.base[:-1][self.dim == self.kind.pose_w]
 
     @classmethod
     def from_problem(cls, p):
-        """from synth.slam2d_problem or formats.load_slam2d_graph"""
+        """from synth.slam2d_problem / slam3d_problem or formats.load_slam2d_graph / load_slam3d_graph"""
         return cls(p["dim"], p["state"], p["odo"], p["odo_info"], p["obs"], p["obs_info"], p.get("odo_seq"), p.get("obs_seq"),
                    p.get("unary_vertex", 0))
 
     def linearize(self):
         """the two edge groups (odometry, observations) as synth.Problems over the same vertices"""
-        return slam2d_linearize(self.dim, self.state, self.odo, self.odo_info, self.obs, self.obs_info, self.unary_vertex)
+        return self._linearize(self.dim, self.state, self.odo, self.odo_info, self.obs, self.obs_info, self.unary_vertex)
 
     def groups(self):
-        return [(self.odo[:, 0], self.odo[:, 1], 3, 3, 3), (self.obs[:, 0], self.obs[:, 1], 3, 2, 2)]
+        p, l = self.kind.pose_w, self.kind.lm_w
+        return [(self.odo[:, 0], self.odo[:, 1], p, p, p), (self.obs[:, 0], self.obs[:, 1], p, l, l)]
+
+    def chi2(self):
+        return float(sum(np.einsum("ei,eij,ej->", g.r, g.Om.reshape(-1, g.rd, g.rd), g.r) for g in self.linearize()))
+
+
+class CSlam2D(_CSlam):
+    """2D landmark SLAM: 3-wide poses and 2-wide landmarks (in 2D state and increment coincide), odometry dx dy dtheta
+    (CEdgePose2D), observations range bearing (CEdgePoseLandmark2D)"""
+    kind, _linearize = _SLAM2D, staticmethod(slam2d_linearize)
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.angle_off = self.pose_off + 2
 
     def plus(self, dx):
         self.state += dx
         self.state[self.angle_off] = np.fmod(self.state[self.angle_off], 2 * math.pi)  # poses only (SE2_Types.h:70-74, :89)
 
-    def chi2(self):
-        return float(sum(np.einsum("ei,eij,ej->", g.r, g.Om.reshape(-1, g.rd, g.rd), g.r) for g in self.linearize()))
 
-
-class CSlam3D:
-    """3D landmark SLAM 'system': 6-wide poses [t | axis-angle] and 3-wide landmarks in one flat state laid out by `dim`
-    (the layout of eta: the increment of a pose has 6 entries, too), odometry edges odo (m, 8) i j t axis-angle +
-    odo_info (m, 6, 6) (CEdgePose3D) and observations obs (k, 5) pose landmark x y z + obs_info (k, 3, 3)
-    (CEdgePoseLandmark3D). odo_seq / obs_seq: position of every edge in the graph's edge order (default: odometry, then
-    observations)."""
-
-    def __init__(self, dim, state, odo, odo_info, obs, obs_info, odo_seq=None, obs_seq=None, unary_vertex=0):
-        self.dim = np.asarray(dim, dtype=np.int32)
-        self.state = np.array(state, dtype=np.float64)
-        self.odo, self.odo_info = np.asarray(odo, dtype=np.float64), np.asarray(odo_info, dtype=np.float64)
-        self.obs, self.obs_info = np.asarray(obs, dtype=np.float64), np.asarray(obs_info, dtype=np.float64)
-        m, k = self.odo.shape[0], self.obs.shape[0]
-        self.odo_seq = np.arange(m, dtype=np.int64) if odo_seq is None else np.asarray(odo_seq, dtype=np.int64)
-        self.obs_seq = m + np.arange(k, dtype=np.int64) if obs_seq is None else np.asarray(obs_seq, dtype=np.int64)
-        self.unary_vertex = unary_vertex
-        self.base = slam3d_offsets(self.dim)
-        self.pose_off = self.base[:-1][self.dim == 6]
-
-    @classmethod
-    def from_problem(cls, p):
-        """from synth.slam3d_problem or formats.load_slam3d_graph"""
-        return cls(p["dim"], p["state"], p["odo"], p["odo_info"], p["obs"], p["obs_info"], p.get("odo_seq"), p.get("obs_seq"),
-                   p.get("unary_vertex", 0))
-
-    def linearize(self):
-        """the two edge groups (odometry, observations) as synth.Problems over the same vertices"""
-        return slam3d_linearize(self.dim, self.state, self.odo, self.odo_info, self.obs, self.obs_info, self.unary_vertex)
-
-    def groups(self):
-        return [(self.odo[:, 0], self.odo[:, 1], 6, 6, 6), (self.obs[:, 0], self.obs[:, 1], 6, 3, 3)]
+class CSlam3D(_CSlam):
+    """3D landmark SLAM: 6-wide poses [t | axis-angle] (the increment of a pose has 6 entries, too) and 3-wide landmarks,
+    odometry t axis-angle (CEdgePose3D), observations x y z (CEdgePoseLandmark3D)"""
+    kind, _linearize = _SLAM3D, staticmethod(slam3d_linearize)
 
     def plus(self, dx):
         self.state = slam3d_plus(self.dim, self.state, dx)  # poses composed, landmarks added (SE3_Types.h:44-47, :110-113)
 
-    def chi2(self):
-        return float(sum(np.einsum("ei,eij,ej->", g.r, g.Om.reshape(-1, g.rd, g.rd), g.r) for g in self.linearize()))
+
+class _Path:
+    """what every product path has: its own api.Context, close(), and the symbolic analysis of self.st before the first
+    factorization (FinalBlockStructure + symbolic: once per Optimize, the structure is fixed within it)"""
+
+    def __init__(self, device=0):
+        self.ctx = api.Context(device)
+        self.st = None
+        self.analyzed = False
+
+    def _analyze_once(self):
+        if not self.analyzed:
+            self.ctx.analyze(self.st, api.MODE_AUTO)
+            self.analyzed = True
+
+    def close(self):
+        self.ctx.close()
 
 
-class _DeviceGroupsPath:
-    """Jacobians on the host, multi-group device assembly + device solve (host_jacobians=True for CSlam2D / CSlam3D)"""
+class _DeviceGroupsPath(_Path):
+    """Jacobians on the host, multi-group device assembly + device solve (host_jacobians=True)"""
 
     def __init__(self, device=0, seq=None):
-        self.ctx = api.Context(device)
+        super().__init__(device)
         self.seq = seq   # per group: the position of every edge in the graph's edge order (None: groups concatenated)
 
     def solve(self, groups, first):
@@ -158,180 +169,96 @@ class _DeviceGroupsPath:
                                                   self.seq, groups[0].unary_vertex)
             self.d_vals, self.d_eta = api.DeviceArray(ctx, self.st.nvals), api.DeviceArray(ctx, self.st.n)
             self.d_in = [[api.DeviceArray(ctx, a.size) for a in (g.J0, g.J1, g.Om, g.r)] for g in groups]
+            self.analyzed = False
         for d4, g in zip(self.d_in, groups):
             for d, a in zip(d4, (g.J0, g.J1, g.Om, g.r)):
                 d.upload(np.ascontiguousarray(a).ravel())
-        ctx.assemble_groups_device(*[[d4[k].ptr for d4 in self.d_in] for k in range(4)], 0.0, self.d_vals.ptr, self.d_eta.ptr)
-        if first:
-            ctx.analyze(self.st, api.MODE_AUTO)
+        ctx.assemble_groups_device(*[[d4[k].ptr for d4 in self.d_in] for k in range(4)], groups[0].damping, self.d_vals.ptr,
+                                   self.d_eta.ptr)
+        self._analyze_once()
         if ctx.factor_solve_device(self.d_vals.ptr, self.d_eta.ptr) != 0:
             return False, None
         return True, self.d_eta.download()
 
-    def close(self):
-        self.ctx.close()
 
-
-class _ResidentSlam2DPath:
-    """the whole Gauss-Newton iteration of a CSlam2D in HBM: both linearize kernels (spp_se2_linearize_at_device,
-    spp_se2_rb_linearize_device), spp_assemble_groups_device, analyze once, spp_factor_solve_device,
-    spp_slam2d_update_device. Host traffic: the 8-byte norm per spp_slam2d_update_device call -- one in step() (the
-    stopping test), one in apply() (the kernel's sibling entry points return it whenever they run), so 16 bytes and two
-    stream synchronisations per applied iteration, as in _ResidentPath."""
-
-    def __init__(self, device=0):
-        self.ctx = api.Context(device)
-
-    def begin(self, system):
-        ctx, s = self.ctx, system
-        up = lambda a: api.DeviceArray.from_host(ctx, np.ascontiguousarray(a).ravel())
-        self.m, self.k, self.n = s.odo.shape[0], s.obs.shape[0], s.state.size
-        self.st = ctx.assemble_analyze_groups(s.dim, s.groups(), [s.odo_seq, s.obs_seq], s.unary_vertex)
-        off = lambda col: up(s.base[col.astype(np.int64)])
-        self.d_off = [off(s.odo[:, 0]), off(s.odo[:, 1]), off(s.obs[:, 0]), off(s.obs[:, 1])]
-        self.d_meas = [up(s.odo[:, 2:5]), up(s.obs[:, 2:4])]
-        self.d_Om = [up(s.odo_info), up(s.obs_info)]
-        self.d_state, self.d_angle = up(s.state), up(s.angle_off.astype(np.int64))
-        self.n_angle = s.angle_off.size
-        self.d_J0 = [api.DeviceArray(ctx, 9 * self.m), api.DeviceArray(ctx, 6 * self.k)]
-        self.d_J1 = [api.DeviceArray(ctx, 9 * self.m), api.DeviceArray(ctx, 4 * self.k)]
-        self.d_r = [api.DeviceArray(ctx, 3 * self.m), api.DeviceArray(ctx, 2 * self.k)]
-        self.d_vals, self.d_eta = api.DeviceArray(ctx, self.st.nvals), api.DeviceArray(ctx, self.st.n)
-        self.analyzed = False
-
-    def linearize(self):
-        ctx = self.ctx
-        ctx.se2_linearize_at_device(self.m, self.d_off[0].ptr, self.d_off[1].ptr, self.d_state.ptr, self.d_meas[0].ptr,
-                                    self.d_J0[0].ptr, self.d_J1[0].ptr, self.d_r[0].ptr)
-        ctx.se2_rb_linearize_device(self.k, self.d_off[2].ptr, self.d_off[3].ptr, self.d_state.ptr, self.d_meas[1].ptr,
-                                    self.d_J0[1].ptr, self.d_J1[1].ptr, self.d_r[1].ptr)
-
-    def chi2(self):
-        """error at the current state: the sum over the groups (re-linearizes)"""
-        self.linearize()
-        return (self.ctx.edge_chi2_device(self.m, 3, self.d_r[0].ptr, self.d_Om[0].ptr) +
-                self.ctx.edge_chi2_device(self.k, 2, self.d_r[1].ptr, self.d_Om[1].ptr))
-
-    def step(self):
-        ctx = self.ctx
-        self.linearize()
-        ptrs = lambda arrs: [a.ptr for a in arrs]
-        ctx.assemble_groups_device(ptrs(self.d_J0), ptrs(self.d_J1), ptrs(self.d_Om), ptrs(self.d_r), 0.0,
-                                   self.d_vals.ptr, self.d_eta.ptr)
-        if not self.analyzed:
-            ctx.analyze(self.st, api.MODE_AUTO)
-            self.analyzed = True
-        if ctx.factor_solve_device(self.d_vals.ptr, self.d_eta.ptr) != 0:
-            return False, 0.0
-        return True, ctx.slam2d_update_device(self.n, self.d_state.ptr, self.d_eta.ptr, self.n_angle, self.d_angle.ptr, apply=False)
-
-    def apply(self):
-        self.ctx.slam2d_update_device(self.n, self.d_state.ptr, self.d_eta.ptr, self.n_angle, self.d_angle.ptr, apply=True)
-
-    def finish(self, system):
-        system.state[:] = self.d_state.download()
-
-    def close(self):
-        self.ctx.close()
-
-
-class _ResidentSlam3DPath:
-    """the whole Gauss-Newton iteration of a CSlam3D in HBM, as _ResidentSlam2DPath: spp_se3_linearize_at_device,
-    spp_se3_xyz_linearize_device, spp_assemble_groups_device over the groups (6,6,6) and (6,3,3), analyze once,
-    spp_factor_solve_device, spp_slam3d_update_device. Host traffic: the 8-byte norm per update call, two per applied
-    iteration."""
-
-    def __init__(self, device=0):
-        self.ctx = api.Context(device)
-
-    def begin(self, system):
-        ctx, s = self.ctx, system
-        up = lambda a: api.DeviceArray.from_host(ctx, np.ascontiguousarray(a).ravel())
-        self.m, self.k, self.n = s.odo.shape[0], s.obs.shape[0], s.state.size
-        self.st = ctx.assemble_analyze_groups(s.dim, s.groups(), [s.odo_seq, s.obs_seq], s.unary_vertex)
-        off = lambda col: up(s.base[col.astype(np.int64)])
-        self.d_off = [off(s.odo[:, 0]), off(s.odo[:, 1]), off(s.obs[:, 0]), off(s.obs[:, 1])]
-        self.d_meas = [up(s.odo[:, 2:8]), up(s.obs[:, 2:5])]
-        self.d_Om = [up(s.odo_info), up(s.obs_info)]
-        self.d_state, self.d_pose = up(s.state), up(s.pose_off.astype(np.int64))
-        self.n_pose = s.pose_off.size
-        self.d_J0 = [api.DeviceArray(ctx, 36 * self.m), api.DeviceArray(ctx, 18 * self.k)]
-        self.d_J1 = [api.DeviceArray(ctx, 36 * self.m), api.DeviceArray(ctx, 9 * self.k)]
-        self.d_r = [api.DeviceArray(ctx, 6 * self.m), api.DeviceArray(ctx, 3 * self.k)]
-        self.d_vals, self.d_eta = api.DeviceArray(ctx, self.st.nvals), api.DeviceArray(ctx, self.st.n)
-        self.analyzed = False
-
-    def linearize(self):
-        ctx = self.ctx
-        ctx.se3_linearize_at_device(self.m, self.d_off[0].ptr, self.d_off[1].ptr, self.d_state.ptr, self.d_meas[0].ptr,
-                                    self.d_J0[0].ptr, self.d_J1[0].ptr, self.d_r[0].ptr)
-        ctx.se3_xyz_linearize_device(self.k, self.d_off[2].ptr, self.d_off[3].ptr, self.d_state.ptr, self.d_meas[1].ptr,
-                                     self.d_J0[1].ptr, self.d_J1[1].ptr, self.d_r[1].ptr)
-
-    def chi2(self):
-        """error at the current state: the sum over the groups (re-linearizes)"""
-        self.linearize()
-        return (self.ctx.edge_chi2_device(self.m, 6, self.d_r[0].ptr, self.d_Om[0].ptr) +
-                self.ctx.edge_chi2_device(self.k, 3, self.d_r[1].ptr, self.d_Om[1].ptr))
-
-    def step(self):
-        ctx = self.ctx
-        self.linearize()
-        ptrs = lambda arrs: [a.ptr for a in arrs]
-        ctx.assemble_groups_device(ptrs(self.d_J0), ptrs(self.d_J1), ptrs(self.d_Om), ptrs(self.d_r), 0.0,
-                                   self.d_vals.ptr, self.d_eta.ptr)
-        if not self.analyzed:
-            ctx.analyze(self.st, api.MODE_AUTO)
-            self.analyzed = True
-        if ctx.factor_solve_device(self.d_vals.ptr, self.d_eta.ptr) != 0:
-            return False, 0.0
-        return True, ctx.slam3d_update_device(self.n, self.d_state.ptr, self.d_eta.ptr, self.n_pose, self.d_pose.ptr, apply=False)
-
-    def apply(self):
-        self.ctx.slam3d_update_device(self.n, self.d_state.ptr, self.d_eta.ptr, self.n_pose, self.d_pose.ptr, apply=True)
-
-    def finish(self, system):
-        system.state[:] = self.d_state.download()
-
-    def close(self):
-        self.ctx.close()
-
-
-class _DevicePath:
-    """device assembly + device solve through the C ABI (the product path; needs the GPU)"""
-
-    def __init__(self, device=0):
-        self.ctx = api.Context(device)
-        self.st = None
+class _DevicePath(_DeviceGroupsPath):
+    """_DeviceGroupsPath over the one edge group of a pose graph: spp_assemble_groups_device on a one-group plan runs the
+    kernels of spp_assemble_device and returns their bits (tests/test_gpu_assemble_groups.py asserts it)"""
 
     def solve(self, prob, first):
+        return super().solve([prob], first)
+
+
+class _ResidentSlamPath(_Path):
+    """the whole Gauss-Newton iteration of a CSlam2D / CSlam3D in HBM: the kind's two linearize kernels,
+    spp_assemble_groups_device, analyze once, spp_factor_solve_device, the kind's update. Host traffic: the 8-byte norm per
+    update call -- one in step() (the stopping test), one in apply() (the kernel's sibling entry points return it whenever
+    they run), so 16 bytes and two stream synchronisations per applied iteration, as in _ResidentPath."""
+    kind = None
+
+    def begin(self, system):
+        ctx, s, (pw, lw) = self.ctx, system, self.kind[:2]
+        up = lambda a: api.DeviceArray.from_host(ctx, np.ascontiguousarray(a).ravel())
+        self.m, self.k, self.n = s.odo.shape[0], s.obs.shape[0], s.state.size
+        self.st = ctx.assemble_analyze_groups(s.dim, s.groups(), [s.odo_seq, s.obs_seq], s.unary_vertex)
+        off = lambda col: up(s.base[col.astype(np.int64)])
+        self.d_off = [off(s.odo[:, 0]), off(s.odo[:, 1]), off(s.obs[:, 0]), off(s.obs[:, 1])]
+        self.d_meas = [up(s.odo[:, 2:2 + pw]), up(s.obs[:, 2:2 + lw])]
+        self.d_Om = [up(s.odo_info), up(s.obs_info)]
+        listed = getattr(s, self.kind.listed)
+        self.d_state, self.d_listed, self.n_listed = up(s.state), up(listed.astype(np.int64)), listed.size
+        self.d_J0 = [api.DeviceArray(ctx, pw * pw * self.m), api.DeviceArray(ctx, lw * pw * self.k)]
+        self.d_J1 = [api.DeviceArray(ctx, pw * pw * self.m), api.DeviceArray(ctx, lw * lw * self.k)]
+        self.d_r = [api.DeviceArray(ctx, pw * self.m), api.DeviceArray(ctx, lw * self.k)]
+        self.d_vals, self.d_eta = api.DeviceArray(ctx, self.st.nvals), api.DeviceArray(ctx, self.st.n)
+        self._lin, self._upd = (getattr(ctx, self.kind.lin_odo), getattr(ctx, self.kind.lin_obs)), getattr(ctx, self.kind.update)
+        self.analyzed = False
+
+    def linearize(self):
+        for g, (lin, n) in enumerate(zip(self._lin, (self.m, self.k))):
+            lin(n, self.d_off[2 * g].ptr, self.d_off[2 * g + 1].ptr, self.d_state.ptr, self.d_meas[g].ptr,
+                self.d_J0[g].ptr, self.d_J1[g].ptr, self.d_r[g].ptr)
+
+    def chi2(self):
+        """error at the current state: the sum over the groups (re-linearizes)"""
+        self.linearize()
+        return (self.ctx.edge_chi2_device(self.m, self.kind.pose_w, self.d_r[0].ptr, self.d_Om[0].ptr) +
+                self.ctx.edge_chi2_device(self.k, self.kind.lm_w, self.d_r[1].ptr, self.d_Om[1].ptr))
+
+    def _update(self, apply):
+        return self._upd(self.n, self.d_state.ptr, self.d_eta.ptr, self.n_listed, self.d_listed.ptr, apply=apply)
+
+    def step(self):
         ctx = self.ctx
-        if first:
-            self.st = ctx.assemble_analyze(prob.dim, prob.v0, prob.v1, prob.d0, prob.d1, prob.rd, prob.unary_vertex)
-            self.d_vals = api.DeviceArray(ctx, self.st.nvals)
-            self.d_eta = api.DeviceArray(ctx, self.st.n)
-            self.d_in = [api.DeviceArray(ctx, a.size) for a in (prob.J0, prob.J1, prob.Om, prob.r)]
-        for d, a in zip(self.d_in, (prob.J0, prob.J1, prob.Om, prob.r)):
-            d.upload(np.ascontiguousarray(a).ravel())
-        ctx.assemble_device(self.d_in[0].ptr, self.d_in[1].ptr, self.d_in[2].ptr, self.d_in[3].ptr, prob.damping,
-                            self.d_vals.ptr, self.d_eta.ptr)
-        if first:
-            ctx.analyze(self.st, api.MODE_AUTO)  # FinalBlockStructure + symbolic: once per Optimize
-        code = ctx.factor_solve_device(self.d_vals.ptr, self.d_eta.ptr)
-        if code != 0:
-            return False, None
-        return True, self.d_eta.download()
+        self.linearize()
+        ptrs = lambda arrs: [a.ptr for a in arrs]
+        ctx.assemble_groups_device(ptrs(self.d_J0), ptrs(self.d_J1), ptrs(self.d_Om), ptrs(self.d_r), 0.0,
+                                   self.d_vals.ptr, self.d_eta.ptr)
+        self._analyze_once()
+        if ctx.factor_solve_device(self.d_vals.ptr, self.d_eta.ptr) != 0:
+            return False, 0.0
+        return True, self._update(False)
 
-    def close(self):
-        self.ctx.close()
+    def apply(self):
+        self._update(True)
+
+    def finish(self, system):
+        system.state[:] = self.d_state.download()
 
 
-class _ResidentPath:
+class _ResidentSlam2DPath(_ResidentSlamPath):
+    """(3,3,3) odometry and (3,2,2) range-bearing groups; the update lists the pose angles it clamps"""
+    kind = _SLAM2D
+
+
+class _ResidentSlam3DPath(_ResidentSlamPath):
+    """(6,6,6) odometry and (6,3,3) landmark groups; the update lists the poses it composes"""
+    kind = _SLAM3D
+
+
+class _ResidentPath(_Path):
     """the whole Gauss-Newton iteration in HBM: linearization (spp_se2_linearize_device), assembly, solve,
     ||dx|| and the vertex update (spp_se2_update_device). Host traffic per iteration: 8 bytes (the norm)."""
-
-    def __init__(self, device=0):
-        self.ctx = api.Context(device)
 
     def begin(self, system):
         ctx = self.ctx
@@ -357,9 +284,7 @@ class _ResidentPath:
         self._lin(self.ne, self.d_v0.ptr, self.d_v1.ptr, self.d_poses.ptr, self.d_meas.ptr,
                   self.d_J0.ptr, self.d_J1.ptr, self.d_r.ptr)
         ctx.assemble_device(self.d_J0.ptr, self.d_J1.ptr, self.d_Om.ptr, self.d_r.ptr, 0.0, self.d_vals.ptr, self.d_eta.ptr)
-        if not self.analyzed:
-            ctx.analyze(self.st, api.MODE_AUTO)
-            self.analyzed = True
+        self._analyze_once()
         if ctx.factor_solve_device(self.d_vals.ptr, self.d_eta.ptr) != 0:
             return False, 0.0
         return True, self._upd(self.nv, self.d_poses.ptr, self.d_eta.ptr, apply=False)
@@ -370,9 +295,6 @@ class _ResidentPath:
     def finish(self, system):
         system.poses[:] = self.d_poses.download().reshape(-1, self.dof)
 
-    def close(self):
-        self.ctx.close()
-
 
 class CNonlinearSolver_Lambda:
     """mirror of the reference class for CPoseGraph2D systems. `path` may be replaced by any object with
@@ -381,7 +303,7 @@ class CNonlinearSolver_Lambda:
     def __init__(self, system, path=None, device=0, verbose=False, host_jacobians=False):
         self.system = system
         if path is None:  # the product paths need the GPU; host_jacobians keeps the linearization in numpy
-            if isinstance(system, (CSlam2D, CSlam3D)):
+            if isinstance(system, _CSlam):
                 resident = _ResidentSlam2DPath if isinstance(system, CSlam2D) else _ResidentSlam3DPath
                 path = _DeviceGroupsPath(device, [system.odo_seq, system.obs_seq]) if host_jacobians else resident(device)
             else:
@@ -456,28 +378,34 @@ class CBundleAdjustment:
         self.points = self.points + dx[6 * nc:].reshape(-1, 3)
 
 
-class _ResidentBAPath:
+class _ResidentBAPath(_Path):
     """LM iteration pieces in HBM: spp_ba_linearize_device, spp_assemble_device (damping alpha),
-    spp_factor_solve_device, spp_ba_update_device, chi2 / alpha0 / gain-ratio reductions."""
+    spp_factor_solve_device, spp_ba_update_device, chi2 / alpha0 / gain-ratio reductions. A subclass overrides what its
+    edge differs in: rd / n_ids, _analyze_structure, _dx_offsets, _begin_extra, linearize, _assemble, max_hessian_diag, and
+    extends save / restore / apply / finish for a further vertex set."""
     rd = 2                                  # residual dimension: the edge group is (6, 3, rd)
+    n_ids = 2                               # obs starts with that many vertex ids (cam pt); the measurement follows
 
-    def __init__(self, device=0):
-        self.ctx = api.Context(device)
+    def _analyze_structure(self, prob):
+        return self.ctx.assemble_analyze(prob.dim, prob.v0, prob.v1, 6, 3, self.rd, prob.unary_vertex)
 
     def _dx_offsets(self, s):
         """scalar offsets of the cameras and of the points in the solution vector: cameras first"""
         return 6 * np.arange(self.nc, dtype=np.int64), 6 * self.nc + 3 * np.arange(self.np, dtype=np.int64)
+
+    def _begin_extra(self, s, up):
+        """device arrays of a further vertex set"""
 
     def begin(self, system):
         ctx, s = self.ctx, system
         prob = s.linearize()   # structure only
         self.no, self.nc, self.np = s.obs.shape[0], s.cams.shape[0], s.points.shape[0]
         rd = self.rd
-        self.st = ctx.assemble_analyze(prob.dim, prob.v0, prob.v1, 6, 3, rd, prob.unary_vertex)
+        self.st = self._analyze_structure(prob)
         up = lambda a: api.DeviceArray.from_host(ctx, np.ascontiguousarray(a).ravel())
         self.d_cam_of, self.d_pt_of = up(s.obs[:, 0].astype(np.int32)), up(s.obs[:, 1].astype(np.int32))
         self.d_cams, self.d_intr, self.d_pts = up(s.cams), up(s.intr), up(s.points)
-        self.d_meas, self.d_Om = up(s.obs[:, 2:2 + rd]), up(prob.Om)
+        self.d_meas, self.d_Om = up(s.obs[:, self.n_ids:self.n_ids + rd]), up(prob.Om)
         cam_off, pt_off = self._dx_offsets(s)
         self.d_cam_off, self.d_pt_off = up(cam_off), up(pt_off)
         self.d_J0, self.d_J1 = api.DeviceArray(ctx, 6 * rd * self.no), api.DeviceArray(ctx, 3 * rd * self.no)
@@ -485,6 +413,7 @@ class _ResidentBAPath:
         self.d_vals, self.d_eta, self.d_dx = (api.DeviceArray(ctx, self.st.nvals), api.DeviceArray(ctx, self.st.n),
                                               api.DeviceArray(ctx, self.st.n))
         self.s_cams, self.s_pts = api.DeviceArray(ctx, 6 * self.nc), api.DeviceArray(ctx, 3 * self.np)
+        self._begin_extra(s, up)
         self.analyzed = False
 
     def linearize(self):
@@ -500,17 +429,22 @@ class _ResidentBAPath:
     def max_hessian_diag(self):
         return self.ctx.edge_hessian_maxdiag_device(self.no, self.rd, 6, 3, self.d_J0.ptr, self.d_J1.ptr, self.d_Om.ptr)
 
+    def _assemble(self, alpha):
+        self.ctx.assemble_device(self.d_J0.ptr, self.d_J1.ptr, self.d_Om.ptr, self.d_r.ptr, alpha, self.d_vals.ptr,
+                                 self.d_eta.ptr)
+
+    def _update(self, apply):
+        """cameras and points (+) dx; returns ||dx|| over the whole solution vector"""
+        return self.ctx.ba_update_device(self.nc, self.d_cams.ptr, self.d_cam_off.ptr, self.np, self.d_pts.ptr,
+                                         self.d_pt_off.ptr, self.d_dx.ptr, self.st.n, apply=apply)
+
     def solve(self, alpha):
-        ctx = self.ctx
-        ctx.assemble_device(self.d_J0.ptr, self.d_J1.ptr, self.d_Om.ptr, self.d_r.ptr, alpha, self.d_vals.ptr, self.d_eta.ptr)
-        if not self.analyzed:
-            ctx.analyze(self.st, api.MODE_AUTO)
-            self.analyzed = True
+        self._assemble(alpha)
+        self._analyze_once()
         self.d_dx.copy_from(self.d_eta)
-        if ctx.factor_solve_device(self.d_vals.ptr, self.d_dx.ptr) != 0:
+        if self.ctx.factor_solve_device(self.d_vals.ptr, self.d_dx.ptr) != 0:
             return False, 0.0
-        return True, ctx.ba_update_device(self.nc, self.d_cams.ptr, self.d_cam_off.ptr, self.np, self.d_pts.ptr,
-                                          self.d_pt_off.ptr, self.d_dx.ptr, self.st.n, apply=False)
+        return True, self._update(False)
 
     def gain_denominator(self, alpha):
         return self.ctx.lm_gain_denominator_device(self.st.n, self.d_dx.ptr, self.d_eta.ptr, alpha)
@@ -524,15 +458,11 @@ class _ResidentBAPath:
         self.d_pts.copy_from(self.s_pts)
 
     def apply(self):
-        self.ctx.ba_update_device(self.nc, self.d_cams.ptr, self.d_cam_off.ptr, self.np, self.d_pts.ptr, self.d_pt_off.ptr,
-                                  self.d_dx.ptr, self.st.n, apply=True)
+        self._update(True)
 
     def finish(self, system):
         system.cams = self.d_cams.download().reshape(-1, 6)
         system.points = self.d_pts.download().reshape(-1, 3)
-
-    def close(self):
-        self.ctx.close()
 
 
 class CStereoBundleAdjustment:
@@ -649,25 +579,17 @@ class _ResidentBAIPath(_ResidentBAPath):
     over the padded dx, whose inert entries are zero) and spp_ba_intrinsics_update_device; chi2 and the gain denominator as
     in _ResidentBAPath, the initial damping from the larger of the (J0, J1) and (J2, J1) vertex Hessian diagonals. A rejected
     step restores cameras, points and intrinsics."""
-    rd = 2
+    rd, n_ids = 2, 3                        # obs: cam pt intr u v
 
-    def begin(self, system):
-        ctx, s = self.ctx, system
-        prob = s.linearize()   # structure only
-        self.no, self.nc, self.np, self.ni = s.obs.shape[0], s.cams.shape[0], s.points.shape[0], s.intr.shape[0]
-        self.st = ctx.assemble_analyze_ternary(prob.dim, prob.v0, prob.v1, prob.v2, prob.unary_vertex)
-        up = lambda a: api.DeviceArray.from_host(ctx, np.ascontiguousarray(a).ravel())
-        self.d_cam_of, self.d_pt_of, self.d_intr_of = (up(s.obs[:, i].astype(np.int32)) for i in range(3))
-        self.d_cams, self.d_intr, self.d_pts = up(s.cams), up(s.intr), up(s.points)
-        self.d_meas, self.d_Om = up(s.obs[:, 3:5]), up(prob.Om)
-        self.d_cam_off, self.d_pt_off, self.d_intr_off = (up(a.astype(np.int64)) for a in (s.cam_off, s.pt_off, s.intr_off))
-        self.d_J0, self.d_J1, self.d_J2 = (api.DeviceArray(ctx, w * self.no) for w in (12, 6, 12))
-        self.d_r = api.DeviceArray(ctx, 2 * self.no)
-        self.d_vals, self.d_eta, self.d_dx = (api.DeviceArray(ctx, self.st.nvals), api.DeviceArray(ctx, self.st.n),
-                                              api.DeviceArray(ctx, self.st.n))
-        self.s_cams, self.s_pts, self.s_intr = (api.DeviceArray(ctx, 6 * self.nc), api.DeviceArray(ctx, 3 * self.np),
-                                                api.DeviceArray(ctx, 5 * self.ni))
-        self.analyzed = False
+    def _analyze_structure(self, prob):
+        return self.ctx.assemble_analyze_ternary(prob.dim, prob.v0, prob.v1, prob.v2, prob.unary_vertex)
+
+    _dx_offsets = _ResidentStereoBAPath._dx_offsets   # the vertices at the system's offsets
+
+    def _begin_extra(self, s, up):
+        self.ni = s.intr.shape[0]
+        self.d_intr_of, self.d_intr_off = up(s.obs[:, 2].astype(np.int32)), up(s.intr_off.astype(np.int64))
+        self.d_J2, self.s_intr = api.DeviceArray(self.ctx, 12 * self.no), api.DeviceArray(self.ctx, 5 * self.ni)
 
     def linearize(self):
         self.ctx.ba_intrinsics_linearize_device(self.no, self.d_cam_of.ptr, self.d_pt_of.ptr, self.d_intr_of.ptr, self.d_cams.ptr,
@@ -678,18 +600,9 @@ class _ResidentBAIPath(_ResidentBAPath):
         f = lambda d_J: self.ctx.edge_hessian_maxdiag_device(self.no, 2, 6, 3, d_J.ptr, self.d_J1.ptr, self.d_Om.ptr)
         return max(f(self.d_J0), f(self.d_J2))
 
-    def solve(self, alpha):
-        ctx = self.ctx
-        ctx.assemble_ternary_device(self.d_J0.ptr, self.d_J1.ptr, self.d_J2.ptr, self.d_Om.ptr, self.d_r.ptr, alpha,
-                                    self.d_vals.ptr, self.d_eta.ptr)
-        if not self.analyzed:
-            ctx.analyze(self.st, api.MODE_AUTO)
-            self.analyzed = True
-        self.d_dx.copy_from(self.d_eta)
-        if ctx.factor_solve_device(self.d_vals.ptr, self.d_dx.ptr) != 0:
-            return False, 0.0
-        return True, ctx.ba_update_device(self.nc, self.d_cams.ptr, self.d_cam_off.ptr, self.np, self.d_pts.ptr,
-                                          self.d_pt_off.ptr, self.d_dx.ptr, self.st.n, apply=False)
+    def _assemble(self, alpha):
+        self.ctx.assemble_ternary_device(self.d_J0.ptr, self.d_J1.ptr, self.d_J2.ptr, self.d_Om.ptr, self.d_r.ptr, alpha,
+                                         self.d_vals.ptr, self.d_eta.ptr)
 
     def save(self):
         super().save()

@@ -1,6 +1,6 @@
 """spp_ba_intrinsics_linearize_device / spp_ba_intrinsics_update_device on the device: the ternary edge CEdgeP2CI3D against
 the 50-digit golden (tests/golden/bai_edges.npz, tests/bai_ref.py) within C eps scale, J0 / J1 / r bit for bit those of
-spp_ba_linearize_device, the inert column, launch sizes, and CVertexIntrinsics::Operator_Plus as written."""
+spp_ba_linearize_device, the inert column, launch sizes of both, and CVertexIntrinsics::Operator_Plus as written."""
 import functools
 import os
 
@@ -111,3 +111,29 @@ def test_intrinsics_update():
     assert np.all(np.abs(got - want) <= 4 * bc.EPS * np.abs(want)), np.abs(got - want).max()
     assert np.all(np.abs(got - formats.bai_intrinsics_plus(v, d)) <= 4 * bc.EPS * np.abs(want))
     assert np.array_equal(got[3], v[3])                                # a zero increment: kappa / den * den' with den' = den
+
+
+def _apply_intrinsics_update(ctx, v, d, seed):
+    """v (+) d through spp_ba_intrinsics_update_device, vertex i at a shuffled offset 6 j of a padded dx"""
+    ni = v.shape[0]
+    off = 6 * np.random.default_rng(seed).permutation(ni).astype(np.int64)
+    dx = np.full(6 * ni, 1e3)                                          # the inert entries: never read
+    dx[off[:, None] + np.arange(5)] = d
+    up = lambda a: api.DeviceArray.from_host(ctx, np.ascontiguousarray(a).ravel())
+    d_v = up(v)
+    ctx.ba_intrinsics_update_device(ni, d_v.ptr, up(off).ptr, up(dx).ptr, apply=True)
+    return d_v.download().reshape(ni, 5)
+
+
+@pytest.mark.parametrize("ni", [1, 255, 256, 257])
+def test_every_intrinsics_vertex_keeps_its_bits_at_every_update_size(ni):
+    """ni vertices drawn from the four golden update cases in a shuffled order: every row bit-identical to the same case
+    in the four-vertex launch (one workgroup, a full one, a tail of one thread)"""
+    g = gold()
+    ctx = api.Context(0)
+    small = _apply_intrinsics_update(ctx, g["upd_v"], g["upd_d"], 0)
+    src = np.random.default_rng(ni).permutation(np.arange(ni) % g["upd_v"].shape[0])
+    got = _apply_intrinsics_update(ctx, g["upd_v"][src], g["upd_d"][src], ni + 1)
+    ctx.close()
+    assert np.all(np.abs(small - g["upd_out"]) <= 4 * bc.EPS * np.abs(g["upd_out"]))   # the four-vertex launch is the golden's
+    assert np.array_equal(got, small[src])

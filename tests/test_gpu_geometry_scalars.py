@@ -1,5 +1,5 @@
 """The Levenberg-Marquardt scalars and robust weights of spp_geometry.hip -- edge_chi2, edge_hessian_maxdiag,
-lm_gain_denominator, edge_robust_weights and the ||dx|| of the five update entry points -- against longdouble / exactly summed
+lm_gain_denominator, edge_robust_weights and the ||dx|| of the six update entry points -- against longdouble / exactly summed
 references at n = 1, 255, 256, 257 and 65537 (one workgroup, a full one, a tail of one, and more than 256 partials, where the
 second stage of the reduction makes a second pass), each called twice and required to return the same bits.
 
@@ -200,27 +200,41 @@ def test_robust_weights_reject_a_non_positive_scale_or_parameter(ctx, scale, par
     d.free()
 
 
+N_INTRINSICS = {1: 1, 255: 51, 256: 52, 257: 257, 65537: 13108}   # 5, 255, 260, 1285 and 65540 live entries
+
+
 @pytest.mark.parametrize("n", SIZES)
 def test_update_norms(ctx, n):
-    """||dx|| from the five update entry points: se2_update and se3_update over n poses (3 n and 6 n entries), slam2d_update,
-    slam3d_update and ba_update over n entries. apply=False: the states are placeholders and must come back untouched. The
-    entry points return the root of the device's sum: compared as squares, which adds the root's rounding and the squaring's
-    (3 eps). se2_update reduces one value per pose (three squares: 3 roundings), the others one square per entry."""
+    """||dx|| from the six update entry points: se2_update and se3_update over n poses (3 n and 6 n entries), slam2d_update,
+    slam3d_update and ba_update over n entries, ba_intrinsics_update over N_INTRINSICS[n] vertices. apply=False: the states
+    are placeholders and must come back untouched. The entry points return the root of the device's sum: compared as squares,
+    which adds the root's rounding and the squaring's (3 eps). se2_update reduces one value per pose (three squares: 3
+    roundings), the others one square per entry.
+    ba_intrinsics_update sums the 5 live entries of every vertex in ONE workgroup: below, at and past one pass of its 256
+    threads, and many passes. Thread t adds its ceil(5 ni / 256) squares in order, then the tree of depth 8:
+    |got^2 - exact| <= (1 + 8 + ceil(5 ni / 256) + 3) eps exact. The vertices sit at 6 i in a padded dx whose inert sixth
+    entries hold 1e3: a kernel that counted them would miss the bound by orders of magnitude."""
     rng = np.random.default_rng(n % 71)
     dx = rng.normal(size=6 * n) * np.exp(rng.normal(size=6 * n))
     d, st, off = _up(ctx, dx), _up(ctx, np.ones(6 * n)), _up(ctx, np.zeros(1), np.int64)
-    calls = {"se2": (lambda: ctx.se2_update_device(n, st.ptr, d.ptr, False), 3 * n, n, 3),
-             "se3": (lambda: ctx.se3_update_device(n, st.ptr, d.ptr, False), 6 * n, 6 * n, 1),
-             "slam2d": (lambda: ctx.slam2d_update_device(n, st.ptr, d.ptr, 0, off.ptr, False), n, n, 1),
-             "slam3d": (lambda: ctx.slam3d_update_device(n, st.ptr, d.ptr, 0, off.ptr, False), n, n, 1),
-             "ba": (lambda: ctx.ba_update_device(0, st.ptr, off.ptr, 0, st.ptr, off.ptr, d.ptr, n, False), n, n, 1)}
-    for name, (fn, m, items, per_item) in calls.items():
-        ref = _fsum_ld(dx[:m].astype(LD) ** 2)
+    ni = N_INTRINSICS[n]
+    live = rng.normal(size=(ni, 5)) * np.exp(rng.normal(size=(ni, 5)))
+    padded = np.concatenate([live, np.full((ni, 1), 1e3)], axis=1)
+    di, ioff = _up(ctx, padded), _up(ctx, 6 * np.arange(ni), np.int64)
+    calls = {"se2": (lambda: ctx.se2_update_device(n, st.ptr, d.ptr, False), dx[:3 * n], 3 + _passes(n)),
+             "se3": (lambda: ctx.se3_update_device(n, st.ptr, d.ptr, False), dx[:6 * n], 1 + _passes(6 * n)),
+             "slam2d": (lambda: ctx.slam2d_update_device(n, st.ptr, d.ptr, 0, off.ptr, False), dx[:n], 1 + _passes(n)),
+             "slam3d": (lambda: ctx.slam3d_update_device(n, st.ptr, d.ptr, 0, off.ptr, False), dx[:n], 1 + _passes(n)),
+             "ba": (lambda: ctx.ba_update_device(0, st.ptr, off.ptr, 0, st.ptr, off.ptr, d.ptr, n, False), dx[:n], 1 + _passes(n)),
+             "ba_intrinsics": (lambda: ctx.ba_intrinsics_update_device(ni, st.ptr, ioff.ptr, di.ptr, apply=False), live,
+                               1 + 8 + (5 * ni + 255) // 256)}
+    for name, (fn, entries, roundings) in calls.items():
+        ref = _fsum_ld(entries.astype(LD) ** 2)
         got = fn()
         assert got == fn(), name
-        bound = (per_item + _passes(items) + 3) * EPS * ref
+        bound = (roundings + 3) * EPS * ref
         print("%s n %d: |got^2 - exact| / exact = %.3g, bound %.3g" % (name, n, abs(got * got - ref) / ref, bound / ref))
         assert abs(got * got - ref) <= bound, name
     assert np.array_equal(st.download(), np.ones(6 * n))
-    for b in (d, st, off):
+    for b in (d, st, off, di, ioff):
         b.free()
