@@ -190,7 +190,9 @@ int spp_schur_unpack(spp_ctx *ctx, const double *d_packed, double *d_S_rhs);
  * One homogeneous binary-edge group (several: spp_assemble_analyze_groups below): residual dimension rd, vertex 0 width d0, vertex 1 width d1.
  * J0: ne x (rd x d0) col-major, J1: ne x (rd x d1), Omega: ne x (rd x rd), r: ne x rd.
  * Instantiated shapes (d0, d1, rd): (6,3,2) projections, (3,3,3) 2D odometry, (6,6,6) 3D odometry, (3,2,2) 2D landmark
- * observations, (6,3,3) 3D landmark (XYZ) observations; any other is SPP_E_UNSUPPORTED.
+ * observations, (6,3,3) 3D landmark (XYZ) observations, (6,3,1) ranges from a position-velocity vertex to a landmark
+ * (CEdgePosVel_Landmark3D, include/slam/ROCV_Types.h:77-223: J0 ne x (1x6), J1 ne x (1x3), Omega ne x 1, r ne x 1); any other
+ * is SPP_E_UNSUPPORTED.
  * The unary factor (identity, FlatSystem.h:441,467) is added to the diagonal block of vertex
  * `unary_vertex` (pass -1 for none). The reference's default build puts it on vertex 0 whatever its type
  * (__AUTO_UNARY_FACTOR_ON_VERTEX_ZERO, FlatSystem.h:331-337, _Lambda_Base.h:1903-1924; without that macro: on the
@@ -215,9 +217,19 @@ int spp_assemble_set_edge_weights(spp_ctx *ctx, const double *d_w);
  * (6,6,6) beside projections (6,3,2) -- the reference's AddEntriesInSparseSystem / Refresh_Lambda run over an edge pool of
  * several types alike (NonlinearSolver_Lambda_Base.h:1852-1931, 1658-1688; the reduction plan sums a destination's sources
  * in the order the edges were added, whatever their types: :563-607, 152-197; BaseTypes_Binary.h:759-848 per edge).
- * Group g: h_ne[g] edges h_v0[g] -> h_v1[g] of shape (h_d0[g], h_d1[g], h_rd[g]), one of the five above; two groups may
- * share a shape, but (6,3,2) and (6,3,3) may not appear in one plan: they share their widths, so one off-diagonal block
- * could be fed by both, and a block is summed by the kernel of ONE shape (SPP_E_UNSUPPORTED). h_seq[g][e]: position of that edge in the graph's global edge order (all of them a permutation of
+ * Group g: h_ne[g] edges h_v0[g] -> h_v1[g] of shape (h_d0[g], h_d1[g], h_rd[g]), one of the six above; two groups may
+ * share a shape, but no two of (6,3,1), (6,3,2) and (6,3,3) may appear in one plan: they share their widths, so one
+ * off-diagonal block could be fed by both, and a block is summed by the kernel of ONE shape (SPP_E_UNSUPPORTED).
+ * UNARY edges (priors: GPS fixes, anchors, surveyed beacons; CBaseEdgeImpl with ONE vertex, include/slam/BaseTypes_Unary.h,
+ * e.g. CEdgeLandmark3DPrior, ROCV_Types.h:228-320): a group with h_d1[g] == 0 and h_v1[g] == NULL holds unary edges on
+ * h_v0[g], of shape (d0, rd) = (3,3) or (6,6) (anything else SPP_E_UNSUPPORTED). Per edge H00 = J0^T Omega J0 is added to the
+ * vertex's diagonal block and g0 = J0^T (Omega r) to its eta segment (Calculate_Hessians_v2, BaseTypes_Unary.h:547-587);
+ * there is no off-diagonal block, the structure does not change, d_J1[g] is ignored and may be NULL, and no self-edge check
+ * applies. A unary edge takes its place among the sources of its vertex by its h_seq position like any other edge. Robust
+ * weights on a unary group: the reference HAS the branch (:554-569) -- H00 and g0 carry w ONCE each (g0 = J0^T (Omega r w)),
+ * and so they do here. The built-in identity factor `unary_vertex` is independent of these groups (ROCV passes -1,
+ * CNullUnaryFactorFactory, src/slam_app/SolveROCVImpl.cpp:42-43). A plan holding a unary group is assembled by
+ * spp_assemble_groups_device (spp_assemble_device: SPP_E_STATE), also when it is the only group. h_seq[g][e]: position of that edge in the graph's global edge order (all of them a permutation of
  * 0 .. sum(ne) - 1; h_seq, or h_seq[g], NULL: the position in the concatenation of the groups). Every destination -- diagonal
  * block, eta segment, off-diagonal block, also one fed by several groups -- sums its contributions in ascending position,
  * first assigned, rest added (vertices of degree > 24: the fixed butterfly of the wave kernel over that order). The
@@ -226,7 +238,7 @@ int spp_assemble_set_edge_weights(spp_ctx *ctx, const double *d_w);
  * spp_assemble_groups_device (host arrays of n_groups device pointers) accepts any plan and gives the same bits on a
  * one-group plan.
  * Unary factor and damping as above; robust weights per group (NULL: plain), reset by either analyze call.
- * SPP_E_UNSUPPORTED: a shape not instantiated, (6,3,2) beside (6,3,3), more than SPP_MAX_EDGE_GROUPS groups. SPP_E_BADARG: a vertex width that does
+ * SPP_E_UNSUPPORTED: a shape not instantiated, two of (6,3,1) (6,3,2) (6,3,3) side by side, more than SPP_MAX_EDGE_GROUPS groups. SPP_E_BADARG: a vertex width that does
  * not match its group, a bad index, a self edge, h_seq not a permutation; the ctx then holds no assembly plan.
  * SPP_E_STATE: spp_assemble_device on a plan of several groups, spp_assemble_groups_device without a plan. */
 #define SPP_MAX_EDGE_GROUPS 4
@@ -333,6 +345,24 @@ int spp_se3_xyz_linearize_device(spp_ctx *ctx, int64_t n_edges, const int64_t *d
 int spp_slam3d_update_device(spp_ctx *ctx, int64_t n, double *d_state, const double *d_dx, int64_t n_poses,
 	const int64_t *d_pose_off, int apply, double *h_dx_norm2);
 
+/* ---- on-device geometry of range-only constant-velocity SLAM (ROCV, include/slam/ROCV_Types.h) ---------
+ * Receivers [p | v] (6, CVertexPositionVelocity3D :31-72) and transmitters XYZ (3, CVertexLandmark3D) live in ONE flat state
+ * laid out like eta; vertices are addressed by scalar offset (int64), as in spp_se3_xyz_linearize_device.
+ * spp_rocv_range_linearize_device: CEdgePosVel_Landmark3D<false>::Calculate_Jacobians_Expectation_Error (:163-205):
+ * e = |p - l|, r = z - e, J0 = [(p - l)^T / e | 0 0 0], J1 = -J0[0:3]; layout of the (6,3,1) group. The distance is formed
+ * from the differences, where the reference writes the expanded polynomial (which cancels). DEVIATION: at e = 0 the
+ * reference divides 0 by 0; here both Jacobians are exact zeros and r = z -- nothing is divided by e.
+ * spp_rocv_cv_linearize_device: CEdgeConstVelocity3D<false> (:543-614), d_dt the measured time step per edge: expectation
+ * (p0 + v0 dt, v0), r = -(x1 - expectation) -- the reversed sign the reference chose (:608) --, J0 = -[I, dt I; 0, I], J1 = I;
+ * layout of the (6,6,6) group (Omega: the upper-left 6x6 of the parsed matrix, :394).
+ * The transmitter prior CEdgeLandmark3DPrior (:228-320) needs no kernel: J = I, r = 0 whatever the state (:302-310), chi2 0;
+ * a unary (3,3) group whose constants are uploaded once. Both vertex types add plainly (:60-63): the update is
+ * spp_slam2d_update_device with n_pose_angles = 0; chi2: spp_edge_chi2_device with rd 1 and rd 6. */
+int spp_rocv_range_linearize_device(spp_ctx *ctx, int64_t n_edges, const int64_t *d_recv_off, const int64_t *d_lm_off,
+	const double *d_state, const double *d_measurements, double *d_J0, double *d_J1, double *d_r);
+int spp_rocv_cv_linearize_device(spp_ctx *ctx, int64_t n_edges, const int64_t *d_off0, const int64_t *d_off1,
+	const double *d_state, const double *d_dt, double *d_J0, double *d_J1, double *d_r);
+
 /* ---- on-device geometry of bundle adjustment (CEdgeP2C3D) -------------------------
  * Cameras: 6 doubles each [t | axis-angle], world -> camera, and 5 constant intrinsics each (fx fy cx cy k:
  * CVertexCam, include/slam/BA_Types.h); points: XYZ. spp_ba_linearize_device evaluates per observation the
@@ -396,8 +426,8 @@ int spp_ba_intrinsics_update_device(spp_ctx *ctx, int64_t n_intrinsics, double *
  * chi2 = sum_e r_e^T Omega_e r_e (f_Error, :1078-1095); the largest diagonal entry of any vertex Hessian
  * J_i^T Omega J_i over all edges (f_InitialDamping multiplies it by tau = 1e-3, :151-199); the denominator
  * dx . (alpha dx + eta) of the gain ratio (Aftermath, :204-222). Device inputs, host outputs, deterministic
- * reductions; each call synchronizes the stream. rd / (d0, d1): the edge group of spp_assemble_analyze (chi2: rd 2, 3
- * or 6; max diagonal: (rd, d0, d1) = (2,6,3), (3,3,3), (6,6,6) or (3,6,3), the XYZ observations). */
+ * reductions; each call synchronizes the stream. rd / (d0, d1): the edge group of spp_assemble_analyze (chi2: rd 1, 2, 3
+ * or 6; max diagonal: (rd, d0, d1) = (2,6,3), (3,3,3), (6,6,6), (3,6,3), the XYZ observations, or (1,6,3), the ranges). */
 int spp_edge_chi2_device(spp_ctx *ctx, int64_t n_edges, int rd, const double *d_r, const double *d_Omega, double *h_chi2);
 int spp_edge_hessian_maxdiag_device(spp_ctx *ctx, int64_t n_edges, int rd, int d0, int d1, const double *d_J0,
 	const double *d_J1, const double *d_Omega, double *h_max);

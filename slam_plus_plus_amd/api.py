@@ -36,7 +36,8 @@ EXPORTS = [
     "spp_assemble_analyze_ternary", "spp_assemble_ternary_device", "spp_ba_intrinsics_linearize_device",
     "spp_ba_intrinsics_update_device",
     "spp_se2_linearize_at_device", "spp_se2_rb_linearize_device", "spp_slam2d_update_device",
-    "spp_se3_linearize_at_device", "spp_se3_xyz_linearize_device", "spp_slam3d_update_device", "spp_device_malloc",
+    "spp_se3_linearize_at_device", "spp_se3_xyz_linearize_device", "spp_slam3d_update_device", "spp_rocv_range_linearize_device",
+    "spp_rocv_cv_linearize_device", "spp_device_malloc",
     "spp_device_free", "spp_memcpy_h2d", "spp_memcpy_d2h", "spp_memcpy_d2d", "spp_get_phase_ms", "spp_get_dominant_kernel",
     "spp_microbench_copy", "spp_microbench_mfma_f64", "spp_microbench_ctile", "spp_microbench_update", "spp_block_ordering", "spp_schur_plan_host", "spp_set_profiling", "spp_se2_linearize_device", "spp_se2_update_device", "spp_ba_linearize_device", "spp_ba_stereo_linearize_device", "spp_ba_update_device", "spp_se3_linearize_device", "spp_se3_update_device", "spp_edge_chi2_device", "spp_edge_robust_weights_device", "spp_edge_hessian_maxdiag_device",
     "spp_lm_gain_denominator_device", "spp_dense_potrf_upper", "spp_dense_posv",
@@ -101,6 +102,8 @@ def load_library():
         "spp_se3_linearize_at_device": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
         "spp_se3_xyz_linearize_device": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
         "spp_slam3d_update_device": (cint, [vp, i64, vp, vp, i64, vp, cint, _c_f64p]),
+        "spp_rocv_range_linearize_device": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+        "spp_rocv_cv_linearize_device": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
         "spp_device_malloc": (cint, [vp, ctypes.c_size_t, ctypes.POINTER(vp)]),
         "spp_device_free": (cint, [vp, vp]),
         "spp_memcpy_h2d": (cint, [vp, vp, vp, ctypes.c_size_t]),
@@ -400,6 +403,14 @@ class Context:
                                                       ctypes.byref(out)))
         return out.value ** 0.5
 
+    def rocv_range_linearize_device(self, n_edges, d_recv_off, d_lm_off, d_state, d_meas, d_J0, d_J1, d_r):
+        """ranges from a position-velocity receiver to a transmitter (CEdgePosVel_Landmark3D): the (6, 3, 1) group's J0, J1, r"""
+        return self._check(self.lib.spp_rocv_range_linearize_device(self.h, n_edges, d_recv_off, d_lm_off, d_state, d_meas, d_J0, d_J1, d_r))
+
+    def rocv_cv_linearize_device(self, n_edges, d_off0, d_off1, d_state, d_dt, d_J0, d_J1, d_r):
+        """constant-velocity edges between receivers (CEdgeConstVelocity3D), d_dt the time step of each: a (6, 6, 6) group"""
+        return self._check(self.lib.spp_rocv_cv_linearize_device(self.h, n_edges, d_off0, d_off1, d_state, d_dt, d_J0, d_J1, d_r))
+
     def se3_linearize_device(self, n_edges, d_v0, d_v1, d_poses, d_meas, d_J0, d_J1, d_r):
         return self._check(self.lib.spp_se3_linearize_device(self.h, n_edges, d_v0, d_v1, d_poses, d_meas, d_J0, d_J1, d_r))
 
@@ -524,12 +535,13 @@ class Context:
         return BlockCSC(dim, col_ptr, row_idx, blk_off, None, nvals=self.info("NVALS"))
 
     def assemble_analyze_groups(self, dim, groups, seq=None, unary_vertex=-1):
-        """several edge groups in one Lambda. groups: a list of (v0, v1, d0, d1, rd); seq: None, or per group the global
-        position of each edge (or None). Returns the union structure, as assemble_analyze does."""
+        """several edge groups in one Lambda. groups: a list of (v0, v1, d0, d1, rd) -- unary edges (priors) as
+        (v0, None, d0, 0, rd); seq: None, or per group the global position of each edge (or None). Returns the union
+        structure, as assemble_analyze does."""
         dim = np.ascontiguousarray(dim, dtype=np.int32)
         ng = len(groups)
         v0 = [np.ascontiguousarray(g[0], dtype=np.int64) for g in groups]
-        v1 = [np.ascontiguousarray(g[1], dtype=np.int64) for g in groups]
+        v1 = [None if g[1] is None else np.ascontiguousarray(g[1], dtype=np.int64) for g in groups]
         sq = [None if (seq is None or q is None) else np.ascontiguousarray(q, dtype=np.int64) for q in (seq or [None] * ng)]
         parr = lambda arrs: (ctypes.c_void_p * ng)(*[None if a is None else a.ctypes.data for a in arrs])
         ne = np.array([a.size for a in v0], dtype=np.int64)

@@ -751,7 +751,7 @@ int spp_assemble_analyze_groups(spp_ctx *ctx, int64_t nv, const int32_t *h_dim, 
 	SPP_REQUIRE(n_groups <= SPP_MAX_EDGE_GROUPS, SPP_E_UNSUPPORTED, "more than SPP_MAX_EDGE_GROUPS edge groups");
 	int64_t total = 0;
 	for(int g = 0; g < n_groups; ++ g) {
-		SPP_REQUIRE(h_ne[g] >= 0 && (!h_ne[g] || (h_v0[g] && h_v1[g])), SPP_E_BADARG, "edge group without vertex arrays");
+		SPP_REQUIRE(h_ne[g] >= 0 && (!h_ne[g] || (h_v0[g] && (h_v1[g] || h_d1[g] == 0))), SPP_E_BADARG, "edge group without vertex arrays"); // (d1 = 0 and no v1: unary edges)
 		total += h_ne[g];
 	}
 	SPP_REQUIRE(total > 0, SPP_E_BADARG, "no edges");
@@ -777,6 +777,7 @@ int spp_assemble_device(spp_ctx *ctx, const double *d_J0, const double *d_J1, co
 	SPP_REQUIRE(ctx->assemble, SPP_E_STATE, "spp_assemble_device: call spp_assemble_analyze first");
 	SPP_REQUIRE(assemble_n_groups(ctx) == 1, SPP_E_STATE, "spp_assemble_device: the plan has several edge groups (spp_assemble_groups_device)");
 	SPP_REQUIRE(!assemble_is_ternary(ctx), SPP_E_STATE, "spp_assemble_device: the plan is one of ternary edges (spp_assemble_ternary_device)");
+	SPP_REQUIRE(!assemble_group_is_unary(ctx, 0), SPP_E_STATE, "spp_assemble_device: the plan is one of unary edges (spp_assemble_groups_device)");
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	phases_reset(ctx);
 	phase_begin(ctx, SPP_PHASE_ASSEMBLE);
@@ -796,7 +797,7 @@ int spp_assemble_groups_device(spp_ctx *ctx, const double *const *d_J0, const do
 	SPP_REQUIRE(ctx->assemble, SPP_E_STATE, "spp_assemble_groups_device: call spp_assemble_analyze_groups first");
 	SPP_REQUIRE(!assemble_is_ternary(ctx), SPP_E_STATE, "spp_assemble_groups_device: the plan is one of ternary edges (spp_assemble_ternary_device)");
 	for(int g = 0; g < assemble_n_groups(ctx); ++ g) // (a group without edges needs no arrays)
-		SPP_REQUIRE(!assemble_group_edges(ctx, g) || (d_J0[g] && d_J1[g] && d_Omega[g] && d_r[g]), SPP_E_BADARG,
+		SPP_REQUIRE(!assemble_group_edges(ctx, g) || (d_J0[g] && (d_J1[g] || assemble_group_is_unary(ctx, g)) && d_Omega[g] && d_r[g]), SPP_E_BADARG,
 			"spp_assemble_groups_device: null array of an edge group");
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	phases_reset(ctx);
@@ -1004,6 +1005,22 @@ int spp_slam3d_update_device(spp_ctx *ctx, int64_t n, double *d_state, const dou
 	if(!ctx || n < 0 || n_poses < 0 || !d_state || !d_dx || (n_poses && !d_pose_off))
 		return SPP_E_BADARG;
 	return geometry_call(ctx, [&] { store_if(h_dx_norm2, slam3d_update(ctx, n, d_state, d_dx, n_poses, d_pose_off, apply != 0)); });
+}
+
+int spp_rocv_range_linearize_device(spp_ctx *ctx, int64_t n_edges, const int64_t *d_recv_off, const int64_t *d_lm_off,
+	const double *d_state, const double *d_measurements, double *d_J0, double *d_J1, double *d_r)
+{
+	if(!ctx || n_edges < 0 || !d_recv_off || !d_lm_off || !d_state || !d_measurements || !d_J0 || !d_J1 || !d_r)
+		return SPP_E_BADARG;
+	return geometry_call(ctx, [&] { rocv_range_linearize(ctx, n_edges, d_recv_off, d_lm_off, d_state, d_measurements, d_J0, d_J1, d_r); });
+}
+
+int spp_rocv_cv_linearize_device(spp_ctx *ctx, int64_t n_edges, const int64_t *d_off0, const int64_t *d_off1,
+	const double *d_state, const double *d_dt, double *d_J0, double *d_J1, double *d_r)
+{
+	if(!ctx || n_edges < 0 || !d_off0 || !d_off1 || !d_state || !d_dt || !d_J0 || !d_J1 || !d_r)
+		return SPP_E_BADARG;
+	return geometry_call(ctx, [&] { rocv_cv_linearize(ctx, n_edges, d_off0, d_off1, d_state, d_dt, d_J0, d_J1, d_r); });
 }
 
 int spp_edge_chi2_device(spp_ctx *ctx, int64_t n_edges, int rd, const double *d_r, const double *d_Omega, double *h_chi2)

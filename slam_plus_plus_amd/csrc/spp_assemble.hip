@@ -64,6 +64,11 @@ int64_t assemble_group_edges(const spp_ctx *ctx, int group)
 	return ctx->assemble->gstart[group + 1] - ctx->assemble->gstart[group];
 }
 
+bool assemble_group_is_unary(const spp_ctx *ctx, int group)
+{
+	return ctx->assemble->d1[group] == 0;
+}
+
 static bool same_shape(const AssemblePlan *ap, int ga, int gb)
 {
 	return ap->d0[ga] == ap->d0[gb] && ap->d1[ga] == ap->d1[gb] && ap->rd[ga] == ap->rd[gb];
@@ -72,7 +77,13 @@ static bool same_shape(const AssemblePlan *ap, int ga, int gb)
 static bool shape_instantiated(int d0, int d1, int rd)
 {
 	return (d0 == 6 && d1 == 3 && rd == 2) || (d0 == 3 && d1 == 3 && rd == 3) || (d0 == 6 && d1 == 6 && rd == 6) ||
-		(d0 == 3 && d1 == 2 && rd == 2) || (d0 == 6 && d1 == 3 && rd == 3);
+		(d0 == 3 && d1 == 2 && rd == 2) || (d0 == 6 && d1 == 3 && rd == 3) || (d0 == 6 && d1 == 3 && rd == 1);
+}
+
+// a group of unary edges (d1 = 0, no second vertex array): (d0, rd) = (3,3) landmark / 2D pose prior, (6,6) pose prior
+static bool unary_shape_instantiated(int d0, int rd)
+{
+	return (d0 == 3 && rd == 3) || (d0 == 6 && rd == 6);
 }
 
 void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int n_groups, const int64_t *g_ne,
@@ -82,9 +93,16 @@ void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int n_groups
 	assemble_release(ctx); // after a rejected call the ctx has NO assembly plan (spp_assemble_device then fails its state check)
 	SPP_REQUIRE(n_groups >= 1 && n_groups <= SPP_MAX_EDGE_GROUPS, SPP_E_UNSUPPORTED, "more than SPP_MAX_EDGE_GROUPS edge groups");
 	int64_t ne = 0;
+	bool any_unary = false;
 	for(int g = 0; g < n_groups; ++ g) {
-		SPP_REQUIRE(shape_instantiated(g_d0[g], g_d1[g], g_rd[g]), SPP_E_UNSUPPORTED,
-			"edge group (d0, d1, rd) not instantiated: (6,3,2) (3,3,3) (6,6,6) (3,2,2) (6,3,3)");
+		if(g_d1[g] == 0 && !g_v1[g]) { // unary edges on v0 (BaseTypes_Unary.h): no second vertex, no off-diagonal block
+			SPP_REQUIRE(unary_shape_instantiated(g_d0[g], g_rd[g]), SPP_E_UNSUPPORTED,
+				"unary edge group (d0, rd) not instantiated: (3,3) (6,6)");
+			any_unary = true;
+		} else {
+			SPP_REQUIRE(shape_instantiated(g_d0[g], g_d1[g], g_rd[g]), SPP_E_UNSUPPORTED,
+				"edge group (d0, d1, rd) not instantiated: (6,3,2) (3,3,3) (6,6,6) (3,2,2) (6,3,3) (6,3,1)");
+		}
 		ne += g_ne[g];
 	}
 	SPP_REQUIRE(ne < (int64_t(1) << 30), SPP_E_UNSUPPORTED, "too many edges for 31-bit edge indices");
@@ -93,6 +111,15 @@ void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int n_groups
 	for(int g = 0; g < n_groups; ++ g) {
 		const int64_t *v0 = g_v0[g], *v1 = g_v1[g], gne = g_ne[g];
 		const int d0 = g_d0[g], d1 = g_d1[g];
+		if(!v1) { // unary: one vertex, nothing to be equal to
+			run_threads(nt, [&](int t) {
+				for(int64_t e = gne * t / nt, e1 = gne * (t + 1) / nt; e < e1; ++ e) {
+					SPP_REQUIRE(v0[e] >= 0 && v0[e] < nv, SPP_E_BADARG, "bad edge");
+					SPP_REQUIRE(dim[v0[e]] == d0, SPP_E_BADARG, "vertex width does not match the edge group");
+				}
+			});
+			continue;
+		}
 		run_threads(nt, [&](int t) {
 			for(int64_t e = gne * t / nt, e1 = gne * (t + 1) / nt; e < e1; ++ e) {
 				SPP_REQUIRE(v0[e] >= 0 && v0[e] < nv && v1[e] >= 0 && v1[e] < nv && v0[e] != v1[e], SPP_E_BADARG, "bad edge");
@@ -109,7 +136,7 @@ void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int n_groups
 		ap->d0[g] = g_d0[g]; ap->d1[g] = g_d1[g]; ap->rd[g] = g_rd[g];
 		ap->gstart[g + 1] = ap->gstart[g] + g_ne[g];
 		for(int w : {g_d0[g], g_d1[g]}) {
-			if(std::find(ap->cls_dim, ap->cls_dim + ap->n_cls, w) == ap->cls_dim + ap->n_cls)
+			if(w && std::find(ap->cls_dim, ap->cls_dim + ap->n_cls, w) == ap->cls_dim + ap->n_cls)
 				ap->cls_dim[ap->n_cls ++] = w;
 		}
 		int s = 0; // a shape is (d0, d1, rd): (6,3,2) and (6,3,3) share their widths
@@ -124,7 +151,7 @@ void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int n_groups
 		for(int b = a + 1; b < ap->n_shapes; ++ b) {
 			const int ga = ap->shape_group[a], gb = ap->shape_group[b];
 			SPP_REQUIRE(ap->d0[ga] != ap->d0[gb] || ap->d1[ga] != ap->d1[gb], SPP_E_UNSUPPORTED,
-				"edge groups (6,3,2) and (6,3,3) in one plan: their off-diagonal blocks could mix two shapes");
+				"two of the edge groups (6,3,1), (6,3,2), (6,3,3) in one plan: their off-diagonal blocks could mix two shapes");
 		}
 	}
 	// ---- the edges in the order of their global positions: everything below walks positions, v0[q] / v1[q] are the vertices
@@ -133,7 +160,7 @@ void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int n_groups
 	const int64_t *v0 = g_v0[0], *v1 = g_v1[0];
 	HVec<int64_t> pv0, pv1;
 	HVec<int32_t> pedge;
-	const bool identity = n_groups == 1 && !(g_seq && g_seq[0]);
+	const bool identity = n_groups == 1 && !(g_seq && g_seq[0]) && !any_unary;
 	if(!identity) {
 		pv0.resize(ne);
 		pv1.resize(ne);
@@ -145,7 +172,7 @@ void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int n_groups
 				SPP_REQUIRE(q >= 0 && q < ne && pedge[q] < 0, SPP_E_BADARG, "h_seq is not a permutation of the edge positions");
 				pedge[q] = (int32_t)(ap->gstart[g] + e);
 				pv0[q] = g_v0[g][e];
-				pv1[q] = g_v1[g][e];
+				pv1[q] = g_v1[g] ? g_v1[g][e] : -1; // unary: no second vertex
 			}
 		}
 		v0 = pv0.data();
@@ -157,13 +184,14 @@ void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int n_groups
 	HVec<std::pair<int64_t, int64_t> > key(ne); // (col, row)
 	run_threads(nt, [&](int t) {
 		for(int64_t e = ne * t / nt, e1 = ne * (t + 1) / nt; e < e1; ++ e)
-			key[e] = std::make_pair(std::max(v0[e], v1[e]), std::min(v0[e], v1[e]));
+			key[e] = v1[e] < 0 ? std::make_pair(nv, v0[e]) : std::make_pair(std::max(v0[e], v1[e]), std::min(v0[e], v1[e]));
 	});
+	// (a unary edge has no block: it is filed under a column past the last, which the loops over the columns never visit)
 	// edges in (column, row, edge index) order: a counting sort by column, then (row, edge) inside each column -- a handful
 	// per landmark column -- by insertion, longer runs by std::sort (a comparison sort of all the edges was most of this
 	// function on a Venice-sized graph)
 	HVec<int64_t> eorder(ne);
-	std::vector<int64_t> cstart(nv + 1, 0); // edges of column c: eorder[cstart[c] .. cstart[c + 1])
+	std::vector<int64_t> cstart(nv + 1 + (any_unary ? 1 : 0), 0); // edges of column c: eorder[cstart[c] .. cstart[c + 1])
 	std::vector<int64_t> ccut; // ranges of columns with about equal numbers of edges (+ 1 per column)
 	{
 		// counted and scattered by all threads with atomic increments; the scatter is then in no particular order, the sort
@@ -280,7 +308,8 @@ void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int n_groups
 	// 16 threads on them measured 125 ms against 7 ms for this loop)
 	for(int64_t e = 0; e < ne; ++ e) {
 		++ vl_ptr[v0[e] + 1];
-		++ vl_ptr[v1[e] + 1];
+		if(v1[e] >= 0)
+			++ vl_ptr[v1[e] + 1];
 	}
 	for(int64_t v = 0; v < nv; ++ v)
 		vl_ptr[v + 1] += vl_ptr[v];
@@ -288,7 +317,8 @@ void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int n_groups
 		HVec<int32_t> fill(vl_ptr.begin(), vl_ptr.end() - 1);
 		for(int64_t e = 0; e < ne; ++ e) { // within an edge vertex 0 registers before vertex 1
 			vl_entry[fill[v0[e]] ++] = edge_at(e) << 1;
-			vl_entry[fill[v1[e]] ++] = (edge_at(e) << 1) | 1;
+			if(v1[e] >= 0)
+				vl_entry[fill[v1[e]] ++] = (edge_at(e) << 1) | 1;
 		}
 	}
 	std::vector<int32_t> lseq[MAX_WIDTH_CLASSES], lwave[MAX_WIDTH_CLASSES];
@@ -431,6 +461,47 @@ __device__ __forceinline__ void load_contrib(int32_t entry, const double *__rest
 	}
 }
 
+// a unary edge's contribution to its one vertex (Calculate_Hessians_v2, BaseTypes_Unary.h:547-587): H00 = J0^T Omega J0 w,
+// g0 = J0^T (Omega r w) -- the robust weight ONCE on each, where the reference applies it (:560-569; 1 for a plain edge)
+template <int D, int RD>
+__device__ __forceinline__ void load_unary(int64_t e, const double *__restrict__ J0, const double *__restrict__ Om,
+	const double *__restrict__ r, const double *__restrict__ wts, double *H, double *g)
+{
+	const double wgt = wts ? wts[e] : 1.0;
+	double om[RD * RD], j[RD * D], T[D * RD], orr[RD];
+#pragma unroll
+	for(int i = 0; i < RD * RD; ++ i) om[i] = Om[e * RD * RD + i];
+#pragma unroll
+	for(int i = 0; i < RD * D; ++ i) j[i] = J0[e * RD * D + i];
+	jt_omega<D, RD>(j, om, T);
+#pragma unroll
+	for(int c = 0; c < D; ++ c)
+#pragma unroll
+		for(int i = 0; i <= c; ++ i) {
+			double s = 0;
+#pragma unroll
+			for(int l = 0; l < RD; ++ l)
+				s += T[i + l * D] * j[l + c * RD];
+			H[i + c * D] = s * wgt;
+		}
+#pragma unroll
+	for(int l = 0; l < RD; ++ l) {
+		double s = 0;
+#pragma unroll
+		for(int m = 0; m < RD; ++ m)
+			s += om[l + m * RD] * r[e * RD + m];
+		orr[l] = s * wgt;
+	}
+#pragma unroll
+	for(int i = 0; i < D; ++ i) {
+		double s = 0;
+#pragma unroll
+		for(int l = 0; l < RD; ++ l)
+			s += j[l + i * RD] * orr[l];
+		g[i] = s;
+	}
+}
+
 template <int D>
 __device__ __forceinline__ void store_vertex(const double *H, const double *g, bool unary, double damping,
 	double *__restrict__ hd, double *__restrict__ gd)
@@ -554,8 +625,11 @@ void vertex_wave_kernel(int64_t nlist, const int32_t *__restrict__ vlist, const 
 // sums may differ from the one-group kernels' in the last bit; a plan of ONE group therefore runs the one-group kernels
 // (assemble_groups_run), and the two entry points agree bit for bit on it whatever the weights. Traffic is unchanged: each edge's J / Omega / r is read by
 // the three destinations it feeds; what the groups share is the launches.
+// A group of UNARY edges (d1 = 0, no second vertex array: priors, reference include/slam/BaseTypes_Unary.h:547-587) feeds
+// ONE destination, its vertex: an entry of side 0 in that vertex's list at the edge's position, no off-diagonal block
+// (assemble_analyze files it under a column past the last), the body load_unary; its J1 pointer is never read.
 // --------------------------------------------------------------------------------------------------
-enum { SHAPE_632 = 0, SHAPE_333 = 1, SHAPE_666 = 2, SHAPE_322 = 3, SHAPE_633 = 4 };
+enum { SHAPE_632 = 0, SHAPE_333 = 1, SHAPE_666 = 2, SHAPE_322 = 3, SHAPE_633 = 4, SHAPE_631 = 5, SHAPE_U33 = 6, SHAPE_U66 = 7 };
 
 struct GroupPtrs {
 	const double *J0, *J1, *Om, *r, *w;
@@ -647,8 +721,9 @@ void offdiag_groups_kernel(int64_t n, const int32_t *__restrict__ oblist, const 
 // contribution of one list entry to a vertex of width D: the body of the entry's shape (a shape without a D-wide side
 // cannot occur in the list of such a vertex). W633: the plan holds a (6,3,3) group; without one the switch is the four-way
 // switch the kernels had before that shape existed, instruction for instruction (measured: with the fifth case compiled
-// in, the 2D odometry + observation assembly of tools/slam2d_time.py took 46.7 us instead of 45.9 us)
-template <int D, bool W633>
+// in, the 2D odometry + observation assembly of tools/slam2d_time.py took 46.7 us instead of 45.9 us). WEXT, likewise: the
+// plan holds a (6,3,1) group or a group of unary edges (W633 is then set, too); without one the switch is the one above
+template <int D, bool W633, bool WEXT>
 __device__ __forceinline__ void load_contrib_groups(int32_t entry, const GroupArgs &ga, double *H, double *g)
 {
 	const EdgeRef x = edge_ref(ga, entry >> 1);
@@ -667,7 +742,16 @@ __device__ __forceinline__ void load_contrib_groups(int32_t entry, const GroupAr
 			load_contrib<D, 6, 6, 6>(le, x.J0, x.J1, x.Om, x.r, x.w, H, g);
 		break;
 	default:
-		if(W633 && x.shape == SHAPE_633) {
+		if(WEXT && x.shape >= SHAPE_631) {
+			if(x.shape == SHAPE_631) {
+				if(D == 6 || D == 3)
+					load_contrib<D, 6, 3, 1>(le, x.J0, x.J1, x.Om, x.r, x.w, H, g);
+			} else if(x.shape == SHAPE_U33) {
+				if(D == 3)
+					load_unary<3, 3>(x.e, x.J0, x.Om, x.r, x.w, H, g);
+			} else if(D == 6)
+				load_unary<6, 6>(x.e, x.J0, x.Om, x.r, x.w, H, g);
+		} else if(W633 && x.shape == SHAPE_633) {
 			if(D == 6 || D == 3)
 				load_contrib<D, 6, 3, 3>(le, x.J0, x.J1, x.Om, x.r, x.w, H, g);
 		} else if(D == 3 || D == 2)
@@ -676,7 +760,7 @@ __device__ __forceinline__ void load_contrib_groups(int32_t entry, const GroupAr
 	}
 }
 
-template <int D, bool W633>
+template <int D, bool W633, bool WEXT = false>
 __global__ __launch_bounds__(256)
 void vertex_seq_groups_kernel(int64_t nlist, const int32_t *__restrict__ vlist, const int32_t *__restrict__ vl_ptr,
 	const int32_t *__restrict__ vl_entry, const int64_t *__restrict__ v_doff, const int64_t *__restrict__ v_base,
@@ -694,7 +778,7 @@ void vertex_seq_groups_kernel(int64_t nlist, const int32_t *__restrict__ vlist, 
 	bool first = true;
 	for(int32_t q = vl_ptr[v]; q < vl_ptr[v + 1]; ++ q) {
 		double Hc[D * D], gc[D];
-		load_contrib_groups<D, W633>(vl_entry[q], ga, Hc, gc);
+		load_contrib_groups<D, W633, WEXT>(vl_entry[q], ga, Hc, gc);
 		if(first) { // the first source is assigned, the others are added (_Lambda_Base.h:598-604)
 #pragma unroll
 			for(int c = 0; c < D; ++ c)
@@ -715,7 +799,7 @@ void vertex_seq_groups_kernel(int64_t nlist, const int32_t *__restrict__ vlist, 
 	store_vertex<D>(H, g, v == unary_vertex, damping, vals + v_doff[v], eta + v_base[v]);
 }
 
-template <int D, bool W633>
+template <int D, bool W633, bool WEXT = false>
 __global__ __launch_bounds__(256)
 void vertex_wave_groups_kernel(int64_t nlist, const int32_t *__restrict__ vlist, const int32_t *__restrict__ vl_ptr,
 	const int32_t *__restrict__ vl_entry, const int64_t *__restrict__ v_doff, const int64_t *__restrict__ v_base,
@@ -733,7 +817,7 @@ void vertex_wave_groups_kernel(int64_t nlist, const int32_t *__restrict__ vlist,
 	for(int i = 0; i < D; ++ i) g[i] = 0;
 	for(int32_t q = vl_ptr[v] + lane; q < vl_ptr[v + 1]; q += 64) {
 		double Hc[D * D], gc[D];
-		load_contrib_groups<D, W633>(vl_entry[q], ga, Hc, gc);
+		load_contrib_groups<D, W633, WEXT>(vl_entry[q], ga, Hc, gc);
 #pragma unroll
 		for(int c = 0; c < D; ++ c)
 #pragma unroll
@@ -765,8 +849,10 @@ void vertex_wave_groups_kernel(int64_t nlist, const int32_t *__restrict__ vlist,
 
 static int shape_id(int d0, int d1, int rd)
 {
+	if(d1 == 0)
+		return d0 == 6 ? SHAPE_U66 : SHAPE_U33;
 	if(d0 == 6)
-		return d1 == 6 ? SHAPE_666 : (rd == 3 ? SHAPE_633 : SHAPE_632);
+		return d1 == 6 ? SHAPE_666 : (rd == 3 ? SHAPE_633 : rd == 1 ? SHAPE_631 : SHAPE_632);
 	return d1 == 3 ? SHAPE_333 : SHAPE_322;
 }
 
@@ -775,7 +861,7 @@ void assemble_groups_run(spp_ctx *ctx, const double *const *J0, const double *co
 	const double *const *r, double damping, double *vals, double *eta)
 {
 	AssemblePlan *ap = ctx->assemble;
-	if(ap->n_groups == 1) { // the one-group case IS spp_assemble_device: same kernels, same bits
+	if(ap->n_groups == 1 && ap->d1[0]) { // the one-group case IS spp_assemble_device: same kernels, same bits
 		assemble_run(ctx, J0[0], J1[0], Om[0], r[0], damping, vals, eta);
 		return;
 	}
@@ -801,30 +887,37 @@ void assemble_groups_run(spp_ctx *ctx, const double *const *J0, const double *co
 		case SHAPE_333: SPP_OFFDIAG_LAUNCH(3, 3, 3); break;
 		case SHAPE_666: SPP_OFFDIAG_LAUNCH(6, 6, 6); break;
 		case SHAPE_633: SPP_OFFDIAG_LAUNCH(6, 3, 3); break;
-		default: SPP_OFFDIAG_LAUNCH(3, 2, 2); break;
+		case SHAPE_631: SPP_OFFDIAG_LAUNCH(6, 3, 1); break;
+		case SHAPE_322: SPP_OFFDIAG_LAUNCH(3, 2, 2); break;
+		default: break; // unary edges: no block
 		}
 #undef SPP_OFFDIAG_LAUNCH
 	}
-	bool with_633 = false;
-	for(int g = 0; g < ap->n_groups; ++ g)
+	bool with_633 = false, with_ext = false;
+	for(int g = 0; g < ap->n_groups; ++ g) {
 		with_633 = with_633 || gp[g]->shape == SHAPE_633;
+		with_ext = with_ext || gp[g]->shape >= SHAPE_631;
+	}
 	for(int cls = 0; cls < ap->n_cls; ++ cls) {
-#define SPP_VERTEX_LAUNCH(D, W633) \
+#define SPP_VERTEX_LAUNCH(D, W633, ...) \
 		if(ap->n_seq[cls]) \
-			hipLaunchKernelGGL((vertex_seq_groups_kernel<D, W633>), dim3((unsigned)((ap->n_seq[cls] + 255) / 256)), dim3(256), 0, s, \
+			hipLaunchKernelGGL((vertex_seq_groups_kernel<D, W633, ##__VA_ARGS__>), dim3((unsigned)((ap->n_seq[cls] + 255) / 256)), dim3(256), 0, s, \
 				ap->n_seq[cls], ap->vlist_seq[cls].p, ap->vl_ptr.p, ap->vl_entry.p, ap->v_doff.p, ap->v_base.p, ga, \
 				ap->unary_vertex, damping, vals, eta); \
 		if(ap->n_wave[cls]) \
-			hipLaunchKernelGGL((vertex_wave_groups_kernel<D, W633>), dim3((unsigned)((ap->n_wave[cls] + 3) / 4)), dim3(256), 0, s, \
+			hipLaunchKernelGGL((vertex_wave_groups_kernel<D, W633, ##__VA_ARGS__>), dim3((unsigned)((ap->n_wave[cls] + 3) / 4)), dim3(256), 0, s, \
 				ap->n_wave[cls], ap->vlist_wave[cls].p, ap->vl_ptr.p, ap->vl_entry.p, ap->v_doff.p, ap->v_base.p, ga, \
 				ap->unary_vertex, damping, vals, eta);
-		switch(ap->cls_dim[cls] + (with_633 ? 10 : 0)) {
+		switch(ap->cls_dim[cls] + (with_ext ? 20 : with_633 ? 10 : 0)) {
 		case 6: SPP_VERTEX_LAUNCH(6, false) break;
 		case 3: SPP_VERTEX_LAUNCH(3, false) break;
 		case 2: SPP_VERTEX_LAUNCH(2, false) break;
 		case 16: SPP_VERTEX_LAUNCH(6, true) break;
 		case 13: SPP_VERTEX_LAUNCH(3, true) break;
-		default: SPP_VERTEX_LAUNCH(2, true) break;
+		case 12: SPP_VERTEX_LAUNCH(2, true) break;
+		case 26: SPP_VERTEX_LAUNCH(6, true, true) break;
+		case 23: SPP_VERTEX_LAUNCH(3, true, true) break;
+		default: SPP_VERTEX_LAUNCH(2, true, true) break;
 		}
 #undef SPP_VERTEX_LAUNCH
 	}
@@ -866,6 +959,7 @@ void assemble_run(spp_ctx *ctx, const double *J0, const double *J1, const double
 	case SHAPE_333: assemble_t<3, 3, 3>(ctx, J0, J1, Om, r, damping, vals, eta); break;
 	case SHAPE_666: assemble_t<6, 6, 6>(ctx, J0, J1, Om, r, damping, vals, eta); break;
 	case SHAPE_633: assemble_t<6, 3, 3>(ctx, J0, J1, Om, r, damping, vals, eta); break;
+	case SHAPE_631: assemble_t<6, 3, 1>(ctx, J0, J1, Om, r, damping, vals, eta); break;
 	default: assemble_t<3, 2, 2>(ctx, J0, J1, Om, r, damping, vals, eta); break;
 	}
 }

@@ -39,7 +39,7 @@ struct AssemblePlan {
 	TernaryPlan *ternary = nullptr; // the plan is one of ternary edges: the lists below are those of its (camera, point) part
 	~AssemblePlan() { delete ternary; }
 	int n_groups = 1;
-	int d0[SPP_MAX_EDGE_GROUPS] = {0}, d1[SPP_MAX_EDGE_GROUPS] = {0}, rd[SPP_MAX_EDGE_GROUPS] = {0};
+	int d0[SPP_MAX_EDGE_GROUPS] = {0}, d1[SPP_MAX_EDGE_GROUPS] = {0}, rd[SPP_MAX_EDGE_GROUPS] = {0}; // d1 = 0: a group of unary edges
 	int64_t gstart[SPP_MAX_EDGE_GROUPS + 1] = {0};
 	int n_cls = 0, cls_dim[MAX_WIDTH_CLASSES] = {0}; // vertex width classes, in order of first appearance (d0, d1 of group 0, ...)
 	int n_shapes = 0, shape_group[SPP_MAX_EDGE_GROUPS] = {0}; // distinct (d0, d1, rd): the first group of each

@@ -764,10 +764,11 @@ double edge_chi2(spp_ctx *ctx, int64_t ne, int rd, const double *d_r, const doub
 	if(!ne)
 		return 0;
 	double *part = reserve_partials(ctx, ne);
-	if(rd == 2) launch_per_item(ctx, edge_chi2_kernel<2>, ne, d_r, d_Om, part);
+	if(rd == 1) launch_per_item(ctx, edge_chi2_kernel<1>, ne, d_r, d_Om, part);
+	else if(rd == 2) launch_per_item(ctx, edge_chi2_kernel<2>, ne, d_r, d_Om, part);
 	else if(rd == 3) launch_per_item(ctx, edge_chi2_kernel<3>, ne, d_r, d_Om, part);
 	else if(rd == 6) launch_per_item(ctx, edge_chi2_kernel<6>, ne, d_r, d_Om, part);
-	else throw Error(SPP_E_UNSUPPORTED, "chi2: residual dimension must be 2, 3 or 6");
+	else throw Error(SPP_E_UNSUPPORTED, "chi2: residual dimension must be 1, 2, 3 or 6");
 	reduce_partials(ctx, ne);
 	return fetch_scalar(ctx);
 }
@@ -782,7 +783,8 @@ double edge_hessian_maxdiag(spp_ctx *ctx, int64_t ne, int rd, int d0, int d1, co
 	else if(rd == 3 && d0 == 3 && d1 == 3) launch_per_item(ctx, edge_maxdiag_kernel<3, 3, 3>, ne, d_J0, d_J1, d_Om, part);
 	else if(rd == 6 && d0 == 6 && d1 == 6) launch_per_item(ctx, edge_maxdiag_kernel<6, 6, 6>, ne, d_J0, d_J1, d_Om, part);
 	else if(rd == 3 && d0 == 6 && d1 == 3) launch_per_item(ctx, edge_maxdiag_kernel<3, 6, 3>, ne, d_J0, d_J1, d_Om, part);
-	else throw Error(SPP_E_UNSUPPORTED, "max Hessian diagonal: edge group must be (2,6,3), (3,3,3), (6,6,6) or (3,6,3)");
+	else if(rd == 1 && d0 == 6 && d1 == 3) launch_per_item(ctx, edge_maxdiag_kernel<1, 6, 3>, ne, d_J0, d_J1, d_Om, part);
+	else throw Error(SPP_E_UNSUPPORTED, "max Hessian diagonal: edge group must be (2,6,3), (3,3,3), (6,6,6), (3,6,3) or (1,6,3)");
 	reduce_partials(ctx, ne, true);
 	return fetch_scalar(ctx);
 }
@@ -1066,6 +1068,78 @@ double slam3d_update(spp_ctx *ctx, int64_t n, double *d_state, const double *d_d
 		launch_over(ctx, slam3d_pose_store_kernel, 6 * n_poses, n_poses, d_pose_off, tmp, d_state);
 	}
 	return fetch_scalar(ctx);
+}
+
+// --------------------------------------------------------------------------------------------------
+// Range-only constant-velocity SLAM (ROCV): 6-wide receivers [p | v] and 3-wide transmitters in ONE flat state laid out
+// like eta, vertices addressed by their scalar offset; both vertex types add their increment plainly
+// (CVertexPositionVelocity3D::Operator_Plus, include/slam/ROCV_Types.h:60-63; CVertexLandmark3D), so the update is
+// slam2d_update with no angles. Reference (functional spec):
+//   CEdgePosVel_Landmark3D<false>::Calculate_Jacobians_Expectation_Error   ROCV_Types.h:163-205
+//     e = |p - l|, r = z - e, J0 = [(p - l)^T / e | 0 0 0], J1 = -J0[0:3]. The reference divides by the square root of the
+//     EXPANDED polynomial lx^2 - 2 lx x + x^2 + ..., which cancels when p is near l; here e is formed from the differences
+//     (as its own expectation is, :200). At e = 0 the reference divides 0 by 0; here both Jacobians are exact zeros and
+//     r = z: nothing is divided by e.
+//   CEdgeConstVelocity3D<false>::Calculate_Jacobians_Expectation_Error     ROCV_Types.h:543-614
+//     expectation = (p0 + v0 dt, v0), r = -(x1 - expectation) (the reversed sign of :608), J0 = -[I, dt I; 0, I], J1 = I,
+//     in the layout of the (6,6,6) group.
+// One thread per edge. Range: 6 gathered doubles, 8 B measurement, 16 B offsets in; 80 B out (J0 1 x 6, J1 1 x 3, r 1).
+// Constant velocity: 12 gathered doubles, 8 B dt, 16 B offsets in; 624 B out, all but 3 + 6 of them constants.
+// --------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256)
+void rocv_range_linearize_kernel(int64_t ne, const int64_t *__restrict__ recv_off, const int64_t *__restrict__ lm_off,
+	const double *__restrict__ state, const double *__restrict__ meas, double *__restrict__ J0,
+	double *__restrict__ J1, double *__restrict__ r)
+{
+	const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if(e >= ne)
+		return;
+	const double *p = state + recv_off[e], *l = state + lm_off[e];
+	const double d0 = p[0] - l[0], d1 = p[1] - l[1], d2 = p[2] - l[2];
+	const double dist = sqrt(d0 * d0 + d1 * d1 + d2 * d2);
+	const double u0 = dist > 0 ? d0 / dist : 0.0, u1 = dist > 0 ? d1 / dist : 0.0, u2 = dist > 0 ? d2 / dist : 0.0;
+	r[e] = meas[e] - dist;
+	double *a = J0 + 6 * e;
+	a[0] = u0; a[1] = u1; a[2] = u2; a[3] = 0; a[4] = 0; a[5] = 0;
+	double *b = J1 + 3 * e;
+	b[0] = -u0; b[1] = -u1; b[2] = -u2;
+}
+
+__global__ __launch_bounds__(256)
+void rocv_cv_linearize_kernel(int64_t ne, const int64_t *__restrict__ off0, const int64_t *__restrict__ off1,
+	const double *__restrict__ state, const double *__restrict__ dts, double *__restrict__ J0,
+	double *__restrict__ J1, double *__restrict__ r)
+{
+	const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if(e >= ne)
+		return;
+	const double *x0 = state + off0[e], *x1 = state + off1[e];
+	const double dt = dts[e];
+	double *ro = r + 6 * e, *a = J0 + 36 * e, *b = J1 + 36 * e;
+#pragma unroll
+	for(int i = 0; i < 3; ++ i) {
+		ro[i] = -(x1[i] - (x0[i] + x0[3 + i] * dt));
+		ro[3 + i] = -(x1[3 + i] - x0[3 + i]);
+	}
+#pragma unroll
+	for(int c = 0; c < 6; ++ c)
+#pragma unroll
+		for(int i = 0; i < 6; ++ i) { // element (row i, column c) at i + 6 c
+			a[i + 6 * c] = (i == c) ? -1.0 : (c == i + 3) ? -dt : 0.0;
+			b[i + 6 * c] = (i == c) ? 1.0 : 0.0;
+		}
+}
+
+void rocv_range_linearize(spp_ctx *ctx, int64_t ne, const int64_t *d_recv_off, const int64_t *d_lm_off, const double *d_state,
+	const double *d_meas, double *d_J0, double *d_J1, double *d_r)
+{
+	launch_per_item(ctx, rocv_range_linearize_kernel, ne, d_recv_off, d_lm_off, d_state, d_meas, d_J0, d_J1, d_r);
+}
+
+void rocv_cv_linearize(spp_ctx *ctx, int64_t ne, const int64_t *d_off0, const int64_t *d_off1, const double *d_state,
+	const double *d_dt, double *d_J0, double *d_J1, double *d_r)
+{
+	launch_per_item(ctx, rocv_cv_linearize_kernel, ne, d_off0, d_off1, d_state, d_dt, d_J0, d_J1, d_r);
 }
 
 } // namespace spp

@@ -405,6 +405,10 @@ void se3_xyz_linearize(spp_ctx *ctx, int64_t ne, const int64_t *d_pose_off, cons
 	const double *d_meas, double *d_J0, double *d_J1, double *d_r);
 double slam3d_update(spp_ctx *ctx, int64_t n, double *d_state, const double *d_dx, int64_t n_poses,
 	const int64_t *d_pose_off, bool apply);
+void rocv_range_linearize(spp_ctx *ctx, int64_t ne, const int64_t *d_recv_off, const int64_t *d_lm_off, const double *d_state,
+	const double *d_meas, double *d_J0, double *d_J1, double *d_r);
+void rocv_cv_linearize(spp_ctx *ctx, int64_t ne, const int64_t *d_off0, const int64_t *d_off1, const double *d_state,
+	const double *d_dt, double *d_J0, double *d_J1, double *d_r);
 double edge_chi2(spp_ctx *ctx, int64_t ne, int rd, const double *d_r, const double *d_Om);
 void edge_robust_weights(spp_ctx *ctx, int64_t ne, int rd, int kind, double scale, double param, const double *d_r, double *d_w);
 double edge_hessian_maxdiag(spp_ctx *ctx, int64_t ne, int rd, int d0, int d1, const double *d_J0, const double *d_J1,
@@ -532,6 +536,7 @@ void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int n_groups
 	const int *g_rd, int64_t unary_vertex, const uint8_t *skip_vertex = nullptr); // skip_vertex[v]: v enters no vertex list
 int assemble_n_groups(const spp_ctx *ctx);
 int64_t assemble_group_edges(const spp_ctx *ctx, int group);
+bool assemble_group_is_unary(const spp_ctx *ctx, int group); // unary edges: no second vertex, J1 unused
 void assemble_run(spp_ctx *ctx, const double *J0, const double *J1, const double *Om, const double *r,
 	double damping, double *vals, double *eta); // plans of one group
 void assemble_groups_run(spp_ctx *ctx, const double *const *J0, const double *const *J1, const double *const *Om,

@@ -388,11 +388,16 @@ def problem_from_graph(path):
     BA files use the reference's VERTEX_CAM convention (camera-to-world in the file); a file with EDGE_PROJECT_P2SC /
     EDGE_P2SC lines goes to load_stereo_graph and comes back as one (6, 3, 3) group (stereo_linearize). A file with
     LANDMARK3:XYZ / EDGE_SE3_XYZ lines goes to load_slam3d_graph and comes back as the PAIR of its edge groups
-    (slam3d_linearize)."""
+    (slam3d_linearize); a file with ROCV: lines goes to load_rocv_graph and comes back as its THREE groups (rocv_linearize)."""
     from scipy.spatial.transform import Rotation
     with open(path) as f:
         toks = {ln.split()[0].upper() for ln in f if ln.split()}
     has_lm3 = bool(toks & _LM3_XYZ_EDGE)
+    if toks & _ROCV_TOKENS:  # range-only constant velocity: THREE edge groups, the last one unary (nonlinear.CRocv)
+        s = load_rocv_graph(path)
+        groups = rocv_linearize(s["dim"], s["state"], s["cv"], s["cv_info"], s["rng"], s["rng_info"], s["pri"], s["pri_info"])
+        return groups, "ROCV graph file (%d receivers, %d transmitters, %d constant-velocity edges, %d ranges, %d priors)" % (
+            int((s["dim"] == 6).sum()), int((s["dim"] == 3).sum()), s["cv"].shape[0], s["rng"].shape[0], s["pri"].size)
     if toks & _P2SC_EDGE:  # stereo BA: ONE (6, 3, 3) group, cameras CVertexSCam
         g = load_stereo_graph(path)
         prob = stereo_linearize(g["cams"], g["intr"], g["points"], g["obs"], g["cam_id"], g["pt_id"], g["info"])
@@ -1177,3 +1182,195 @@ def save_bai_graph(path, cams, intr, points, obs, info=None, cam_id=None, pt_id=
     first, as the parser wants), info (no, 2, 2) or None. Vertices are written in id order, in front of the edges."""
     with open(path, "w") as f:
         f.write("\n".join(bai_lines(cams, intr, points, obs, info, cam_id, pt_id, intr_id)) + "\n")
+
+
+# --------------------------------------------------------------------------------------------------
+# range-only constant-velocity SLAM (ROCV): receivers [p | v] (6) + transmitters (3); constant-velocity edges,
+# ranges, transmitter priors (include/slam/ROCV_Types.h, src/slam_app/SolveROCVImpl.cpp)
+# --------------------------------------------------------------------------------------------------
+_ROCV_TOKENS = {"ROCV:TRANSMITTER", "ROCV:TRANSMITTER_UF", "ROCV:RECEIVER", "ROCV:RECEIVER_GTFAKE", "ROCV:DELTA_TIME",
+                "ROCV:RANGE"}   # ParsePrimitives.h:1425, 1443, 1495, 1550, 1604, 1676
+
+
+def load_rocv_graph(path):
+    """A ROCV graph as the reference's parser and edge constructors would build it, line by line
+    (include/slam_app/ParsePrimitives.h:1414-1720). Returns
+      dim (nv,) 6 for a receiver / 3 for a transmitter, state (flat, laid out by dim), vertex ids 0 .. nv - 1,
+      cv (m, 3) i j dt + cv_info (m, 6, 6) + cv_seq (m,) position among all edges of the file,
+      rng (k, 3) receiver transmitter range + rng_info (k,) + rng_seq (k,),
+      pri (p,) transmitter + pri_info (p, 3, 3) + pri_seq (p,),
+      explicit (nv,) the vertex has a ROCV:TRANSMITTER / ROCV:RECEIVER line.
+    Lines: ROCV:TRANSMITTER id x y z (CVertexXYZParsePrimitive); ROCV:TRANSMITTER_UF id + the 6 upper-triangular values
+    of a 3x3 matrix row by row -- the parser calls them a covariance but hands them to TUnaryFactor3D::m_t_factor and on to
+    CEdgeLandmark3DPrior as the information AS GIVEN, nothing is inverted (:1460-1471, Parser.h:412-420, ROCV_Types.h:251-
+    252); ROCV:RECEIVER id x y z vx vy vz; ROCV:RECEIVER_GTfake: CIgnoreVertexType (ROCV_Types.h:683-687), skipped;
+    ROCV:DELTA_TIME i j dt + the 21 upper-triangular values of the 6x6 information: kept only when i < j, the parser
+    prints an error and DROPS a line in the other order (:1638-1656); ROCV:RANGE receiver transmitter range information.
+    A vertex an edge meets first is the null vertex (CInitializeNullVertex: zeros), except the second receiver of a
+    constant-velocity edge, which starts at (p0 + v0 dt, v0) (CConstVelocity_Initializer, ROCV_Types.h:365-371)."""
+    state, dimof, explicit = {}, {}, set()
+    cv, cv_info, cv_seq, rng, rng_info, rng_seq, pri, pri_info, pri_seq = [], [], [], [], [], [], [], [], []
+    n_edges = 0
+
+    def null(v, d):
+        if v not in state:
+            state[v], dimof[v] = np.zeros(d), d
+
+    with open(path) as f:
+        for ln in f:
+            t = ln.split()
+            if not t or t[0].startswith("#") or t[0].startswith("%"):
+                continue
+            tok, a = t[0].upper(), t[1:]
+            if tok == "ROCV:TRANSMITTER" and len(a) >= 4:
+                v = int(a[0])
+                state[v], dimof[v] = np.array([float(x) for x in a[1:4]]), 3
+                explicit.add(v)
+            elif tok == "ROCV:RECEIVER" and len(a) >= 7:
+                v = int(a[0])
+                state[v], dimof[v] = np.array([float(x) for x in a[1:7]]), 6
+                explicit.add(v)
+            elif tok == "ROCV:TRANSMITTER_UF" and len(a) >= 7:
+                v = int(a[0])
+                null(v, 3)
+                pri.append(v)
+                pri_info.append(_upper_to_full([float(x) for x in a[1:7]], 3))
+                pri_seq.append(n_edges)
+                n_edges += 1
+            elif tok == "ROCV:DELTA_TIME" and len(a) >= 24:
+                i, j, dt = int(a[0]), int(a[1]), float(a[2])
+                if not i < j:
+                    continue   # "edges are in switched order": the parser ignores the line
+                null(i, 6)
+                if j not in state:
+                    state[j], dimof[j] = np.concatenate([state[i][:3] + state[i][3:] * dt, state[i][3:]]), 6
+                cv.append([i, j, dt])
+                cv_info.append(_upper_to_full([float(x) for x in a[3:24]], 6))
+                cv_seq.append(n_edges)
+                n_edges += 1
+            elif tok == "ROCV:RANGE" and len(a) >= 4:
+                i, j = int(a[0]), int(a[1])
+                null(i, 6)
+                null(j, 3)
+                rng.append([i, j, float(a[2])])
+                rng_info.append(float(a[3]))
+                rng_seq.append(n_edges)
+                n_edges += 1
+    nv = max(state) + 1 if state else 0
+    if sorted(state) != list(range(nv)):
+        raise ValueError("vertex ids are not 0 .. n-1: %s" % path)
+    for grp, col, d in ((cv, 0, 6), (cv, 1, 6), (rng, 0, 6), (rng, 1, 3)):
+        if any(dimof[int(e[col])] != d for e in grp):
+            raise ValueError("an edge joins vertices of the wrong widths: %s" % path)
+    if any(dimof[v] != 3 for v in pri):
+        raise ValueError("a prior on a vertex that is not a transmitter: %s" % path)
+    dim = np.array([dimof[v] for v in range(nv)], dtype=np.int32)
+    return dict(dim=dim, state=np.concatenate([state[v] for v in range(nv)]) if nv else np.zeros(0),
+                cv=np.array(cv).reshape(-1, 3), cv_info=np.array(cv_info).reshape(-1, 6, 6),
+                cv_seq=np.array(cv_seq, dtype=np.int64), rng=np.array(rng).reshape(-1, 3),
+                rng_info=np.array(rng_info, dtype=np.float64), rng_seq=np.array(rng_seq, dtype=np.int64),
+                pri=np.array(pri, dtype=np.int64), pri_info=np.array(pri_info).reshape(-1, 3, 3),
+                pri_seq=np.array(pri_seq, dtype=np.int64),
+                explicit=np.isin(np.arange(nv), sorted(explicit)))
+
+
+def rocv_lines(dim, state, cv, cv_info, rng, rng_info, pri, pri_info, cv_seq=None, rng_seq=None, pri_seq=None, explicit=None,
+               ids=None):
+    """the lines of a ROCV graph file, everything with %.17g: the edges in the global order and, in front of the first edge
+    that touches it, the vertex line of every vertex listed in `explicit` (default: every vertex); the lines of listed
+    vertices that no edge touches come last. A receiver without a line must be met first as the second vertex of a
+    constant-velocity edge for the file to bring its state back (CConstVelocity_Initializer). ids: vertex id -> id
+    written (the application wants ids to appear in increasing order)."""
+    dim = np.asarray(dim)
+    base = slam2d_offsets(dim)
+    cv, rng, pri = np.asarray(cv, dtype=np.float64).reshape(-1, 3), np.asarray(rng, dtype=np.float64).reshape(-1, 3), np.asarray(pri)
+    m, k, p = len(cv), len(rng), len(pri)
+    cv_seq = np.arange(m) if cv_seq is None else np.asarray(cv_seq)
+    rng_seq = m + np.arange(k) if rng_seq is None else np.asarray(rng_seq)
+    pri_seq = m + k + np.arange(p) if pri_seq is None else np.asarray(pri_seq)
+    explicit = np.ones(dim.size, dtype=bool) if explicit is None else np.asarray(explicit, dtype=bool)
+    name = (lambda v: int(v)) if ids is None else (lambda v: ids[int(v)])
+    num = lambda xs: " ".join("%.17g" % x for x in xs)
+    edges = [None] * (m + k + p)
+    for e in range(m):
+        edges[cv_seq[e]] = (cv[e, :2], "ROCV:DELTA_TIME %d %d %s %s" % (
+            name(cv[e, 0]), name(cv[e, 1]), num(cv[e, 2:3]), num(np.asarray(cv_info[e])[np.triu_indices(6)])))
+    for e in range(k):
+        edges[rng_seq[e]] = (rng[e, :2], "ROCV:RANGE %d %d %s" % (name(rng[e, 0]), name(rng[e, 1]), num([rng[e, 2], rng_info[e]])))
+    for e in range(p):
+        edges[pri_seq[e]] = (pri[e:e + 1], "ROCV:TRANSMITTER_UF %d %s" % (name(pri[e]), num(np.asarray(pri_info[e])[np.triu_indices(3)])))
+    lines, done = [], np.zeros(dim.size, dtype=bool)
+
+    def vertex_line(u):
+        if explicit[u] and not done[u]:
+            lines.append("%s %d %s" % ("ROCV:TRANSMITTER" if dim[u] == 3 else "ROCV:RECEIVER", name(u), num(state[base[u]:base[u + 1]])))
+        done[u] = True
+
+    for vs, ln in edges:
+        for u in vs:
+            vertex_line(int(u))
+        lines.append(ln)
+    for u in range(dim.size):
+        vertex_line(u)
+    return lines
+
+
+def save_rocv_graph(path, dim, state, cv, cv_info, rng, rng_info, pri, pri_info, cv_seq=None, rng_seq=None, pri_seq=None,
+                    explicit=None):
+    """rocv_lines to a file: load_rocv_graph brings every array back bit for bit"""
+    with open(path, "w") as f:
+        f.write("\n".join(rocv_lines(dim, state, cv, cv_info, rng, rng_info, pri, pri_info, cv_seq, rng_seq, pri_seq,
+                                     explicit)) + "\n")
+
+
+def rocv_range_model(p, l, z):
+    """CEdgePosVel_Landmark3D<false> (ROCV_Types.h:163-205) for receiver positions p (k, 3), transmitters l (k, 3), ranges
+    z (k,): e = |p - l| from the differences (the reference's Jacobians divide by the square root of the expanded
+    polynomial, which cancels), r = z - e, J0 = [(p - l)^T / e | 0 0 0], J1 = -J0[0:3]; at e = 0 both Jacobians are exact
+    zeros and r = z (the reference divides 0 by 0). Returns J0 (k, 6), J1 (k, 3), r (k,)."""
+    d = p - l
+    e = np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2])
+    u = np.divide(d, e[:, None], out=np.zeros_like(d), where=e[:, None] > 0)
+    return np.concatenate([u, np.zeros_like(u)], axis=1), -u, z - e
+
+
+def rocv_cv_model(x0, x1, dt):
+    """CEdgeConstVelocity3D<false> (ROCV_Types.h:543-614) for receivers x0, x1 (m, 6) and time steps dt (m,): expectation
+    (p0 + v0 dt, v0), r = -(x1 - expectation), J0 = -[I, dt I; 0, I], J1 = I. Returns J0, J1 (m, 6, 6), r (m, 6)."""
+    m = dt.size
+    r = -(x1 - np.concatenate([x0[:, :3] + x0[:, 3:] * dt[:, None], x0[:, 3:]], axis=1))
+    J0 = np.tile(-np.eye(6), (m, 1, 1))
+    J0[:, np.arange(3), 3 + np.arange(3)] = -dt[:, None]
+    return J0, np.tile(np.eye(6), (m, 1, 1)), r
+
+
+def rocv_linearize(dim, state, cv, cv_info, rng, rng_info, pri, pri_info):
+    """The three edge groups of a ROCV graph at `state` (flat, laid out by dim), as synth.Problems over the SAME vertices:
+    constant velocity (6, 6, 6), ranges (6, 3, 1) and the transmitter priors, a UNARY group (d0, rd) = (3, 3) with v1 None,
+    d1 0 and an empty J1: J = I and r = 0 whatever the state (CEdgeLandmark3DPrior::Calculate_Jacobian_Expectation_Error,
+    ROCV_Types.h:302-310 -- the prior adds its information to the transmitter's diagonal block, nothing to eta, and its
+    chi2 is 0). No built-in unary factor: unary_vertex = -1 (CNullUnaryFactorFactory, SolveROCVImpl.cpp:42-43)."""
+    from .synth import Problem
+    dim = np.asarray(dim, dtype=np.int32)
+    x = np.asarray(state, dtype=np.float64)
+    base = slam2d_offsets(dim)
+    cv = np.asarray(cv, dtype=np.float64).reshape(-1, 3)
+    rng = np.asarray(rng, dtype=np.float64).reshape(-1, 3)
+    pri = np.asarray(pri, dtype=np.int64).ravel()
+    a, b = cv[:, 0].astype(np.int64), cv[:, 1].astype(np.int64)
+    J0, J1, r = rocv_cv_model(x[base[a][:, None] + np.arange(6)], x[base[b][:, None] + np.arange(6)], cv[:, 2])
+    m = a.size
+    g_cv = Problem(name="rocv_const_velocity", dim=dim, v0=a, v1=b, d0=6, d1=6, rd=6,
+                   J0=np.ascontiguousarray(J0.transpose(0, 2, 1)).reshape(m, 36),
+                   J1=np.ascontiguousarray(J1.transpose(0, 2, 1)).reshape(m, 36),
+                   Om=np.asarray(cv_info, dtype=np.float64).reshape(m, 36), r=r, unary_vertex=-1, damping=0.0)
+    vr, vt = rng[:, 0].astype(np.int64), rng[:, 1].astype(np.int64)
+    k = vr.size
+    H0, H1, rr = rocv_range_model(x[base[vr][:, None] + np.arange(3)], x[base[vt][:, None] + np.arange(3)], rng[:, 2])
+    g_rng = Problem(name="rocv_ranges", dim=dim, v0=vr, v1=vt, d0=6, d1=3, rd=1, J0=H0.reshape(k, 6), J1=H1.reshape(k, 3),
+                    Om=np.asarray(rng_info, dtype=np.float64).reshape(k, 1), r=rr.reshape(k, 1), unary_vertex=-1, damping=0.0)
+    p = pri.size
+    g_pri = Problem(name="rocv_priors", dim=dim, v0=pri, v1=None, d0=3, d1=0, rd=3, J0=np.tile(np.eye(3).ravel(), (p, 1)),
+                    J1=np.zeros((p, 0)), Om=np.asarray(pri_info, dtype=np.float64).reshape(p, 9), r=np.zeros((p, 3)),
+                    unary_vertex=-1, damping=0.0)
+    return g_cv, g_rng, g_pri

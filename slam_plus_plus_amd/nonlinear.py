@@ -20,7 +20,7 @@ import numpy as np
 from . import api
 from .formats import (se2_linearize, se3_linearize, se3_plus, ba_linearize, slam2d_linearize, slam2d_offsets,
                       slam3d_linearize, slam3d_offsets, slam3d_plus, stereo_linearize, bai_linearize, bai_intrinsics_plus,
-                      bai_ids, BAI_INTR_WIDTH)
+                      bai_ids, BAI_INTR_WIDTH, rocv_linearize)
 
 
 class CPoseGraph2D:
@@ -135,6 +135,49 @@ class CSlam3D(_CSlam):
 
     def plus(self, dx):
         self.state = slam3d_plus(self.dim, self.state, dx)  # poses composed, landmarks added (SE3_Types.h:44-47, :110-113)
+
+
+class CRocv:
+    """Range-only constant-velocity SLAM 'system' (src/slam_app/SolveROCVImpl.cpp), the interface of _CSlam: receivers
+    [p | v] (6) and transmitters (3) in one flat state laid out by `dim`; constant-velocity edges cv (m, 3) i j dt + cv_info
+    (m, 6, 6), ranges rng (k, 3) receiver transmitter range + rng_info (k,), priors on the transmitters pri (p,) + pri_info
+    (p, 3, 3) -- unary edges --, and the position of every edge in the graph's edge order (default: the three groups one
+    after the other). No built-in unary factor (CNullUnaryFactorFactory): the priors hold the graph."""
+    unary_vertex = -1
+
+    def __init__(self, dim, state, cv, cv_info, rng, rng_info, pri, pri_info, cv_seq=None, rng_seq=None, pri_seq=None):
+        self.dim = np.asarray(dim, dtype=np.int32)
+        self.state = np.array(state, dtype=np.float64)
+        self.cv, self.cv_info = np.asarray(cv, dtype=np.float64).reshape(-1, 3), np.asarray(cv_info, dtype=np.float64)
+        self.rng, self.rng_info = np.asarray(rng, dtype=np.float64).reshape(-1, 3), np.asarray(rng_info, dtype=np.float64)
+        self.pri, self.pri_info = np.asarray(pri, dtype=np.int64).ravel(), np.asarray(pri_info, dtype=np.float64)
+        m, k, p = self.cv.shape[0], self.rng.shape[0], self.pri.size
+        self.cv_seq = np.arange(m, dtype=np.int64) if cv_seq is None else np.asarray(cv_seq, dtype=np.int64)
+        self.rng_seq = m + np.arange(k, dtype=np.int64) if rng_seq is None else np.asarray(rng_seq, dtype=np.int64)
+        self.pri_seq = m + k + np.arange(p, dtype=np.int64) if pri_seq is None else np.asarray(pri_seq, dtype=np.int64)
+        self.base = slam2d_offsets(self.dim)
+
+    @classmethod
+    def from_problem(cls, p):
+        """from synth.rocv_problem or formats.load_rocv_graph"""
+        return cls(p["dim"], p["state"], p["cv"], p["cv_info"], p["rng"], p["rng_info"], p["pri"], p["pri_info"],
+                   p.get("cv_seq"), p.get("rng_seq"), p.get("pri_seq"))
+
+    def seqs(self):
+        return [self.cv_seq, self.rng_seq, self.pri_seq]
+
+    def linearize(self):
+        """the three edge groups (constant velocity, ranges, priors) as synth.Problems over the same vertices"""
+        return rocv_linearize(self.dim, self.state, self.cv, self.cv_info, self.rng, self.rng_info, self.pri, self.pri_info)
+
+    def groups(self):
+        return [(self.cv[:, 0], self.cv[:, 1], 6, 6, 6), (self.rng[:, 0], self.rng[:, 1], 6, 3, 1), (self.pri, None, 3, 0, 3)]
+
+    def chi2(self):
+        return float(sum(np.einsum("ei,eij,ej->", g.r, g.Om.reshape(-1, g.rd, g.rd), g.r) for g in self.linearize()))
+
+    def plus(self, dx):
+        self.state += dx   # both vertex types add plainly (ROCV_Types.h:60-63, CVertexLandmark3D)
 
 
 class _Path:
@@ -256,6 +299,76 @@ class _ResidentSlam3DPath(_ResidentSlamPath):
     kind = _SLAM3D
 
 
+class _ResidentROCVPath(_Path):
+    """the whole Gauss-Newton iteration of a CRocv in HBM: spp_rocv_cv_linearize_device and spp_rocv_range_linearize_device,
+    the priors' constants (J = I, r = 0, uploaded once), spp_assemble_groups_device over the three groups, analyze once,
+    spp_factor_solve_device, spp_slam2d_update_device without angles (the plain sum). Host traffic as in
+    _ResidentSlamPath. mode: MODE_AUTO takes the Schur mode (widths {6, 3}), which eliminates the handful of transmitters
+    and leaves a dense reduced system over ALL receivers; the sparse mode sees a chain with a few dense columns ordered
+    last and is the default."""
+
+    def __init__(self, device=0, mode=api.MODE_SPARSE):
+        super().__init__(device)
+        self.mode = mode
+
+    def _analyze_once(self):
+        if not self.analyzed:
+            self.ctx.analyze(self.st, self.mode)
+            self.analyzed = True
+
+    def begin(self, system):
+        ctx, s = self.ctx, system
+        up = lambda a: api.DeviceArray.from_host(ctx, np.ascontiguousarray(a).ravel())
+        self.m, self.k, self.p, self.n = s.cv.shape[0], s.rng.shape[0], s.pri.size, s.state.size
+        self.st = ctx.assemble_analyze_groups(s.dim, s.groups(), s.seqs(), s.unary_vertex)
+        off = lambda col: up(s.base[col.astype(np.int64)])
+        self.d_off = [off(s.cv[:, 0]), off(s.cv[:, 1]), off(s.rng[:, 0]), off(s.rng[:, 1])]
+        self.d_meas = [up(s.cv[:, 2]), up(s.rng[:, 2])]
+        self.d_state = up(s.state)
+        m, k, p = self.m, self.k, self.p
+        self.d_Om = [up(s.cv_info), up(s.rng_info), up(s.pri_info)]
+        self.d_J0 = [api.DeviceArray(ctx, 36 * m), api.DeviceArray(ctx, 6 * k), up(np.tile(np.eye(3).ravel(), (p, 1)))]
+        self.d_J1 = [api.DeviceArray(ctx, 36 * m), api.DeviceArray(ctx, 3 * k), None]
+        self.d_r = [api.DeviceArray(ctx, 6 * m), api.DeviceArray(ctx, k), up(np.zeros(3 * p))]
+        self.d_vals, self.d_eta = api.DeviceArray(ctx, self.st.nvals), api.DeviceArray(ctx, self.st.n)
+        self.analyzed = False
+
+    def linearize(self):
+        ctx = self.ctx
+        ctx.rocv_cv_linearize_device(self.m, self.d_off[0].ptr, self.d_off[1].ptr, self.d_state.ptr, self.d_meas[0].ptr,
+                                     self.d_J0[0].ptr, self.d_J1[0].ptr, self.d_r[0].ptr)
+        ctx.rocv_range_linearize_device(self.k, self.d_off[2].ptr, self.d_off[3].ptr, self.d_state.ptr, self.d_meas[1].ptr,
+                                        self.d_J0[1].ptr, self.d_J1[1].ptr, self.d_r[1].ptr)
+
+    def chi2(self):
+        """error at the current state (re-linearizes); the priors' chi2 is 0 (ROCV_Types.h:316-319)"""
+        self.linearize()
+        return (self.ctx.edge_chi2_device(self.m, 6, self.d_r[0].ptr, self.d_Om[0].ptr) +
+                self.ctx.edge_chi2_device(self.k, 1, self.d_r[1].ptr, self.d_Om[1].ptr))
+
+    def assemble(self):
+        ptrs = lambda arrs: [None if a is None else a.ptr for a in arrs]
+        self.ctx.assemble_groups_device(ptrs(self.d_J0), ptrs(self.d_J1), ptrs(self.d_Om), ptrs(self.d_r), 0.0,
+                                        self.d_vals.ptr, self.d_eta.ptr)
+
+    def step(self):
+        self.linearize()
+        self.assemble()
+        self._analyze_once()
+        if self.ctx.factor_solve_device(self.d_vals.ptr, self.d_eta.ptr) != 0:
+            return False, 0.0
+        return True, self._update(False)
+
+    def _update(self, apply):
+        return self.ctx.slam2d_update_device(self.n, self.d_state.ptr, self.d_eta.ptr, 0, None, apply=apply)
+
+    def apply(self):
+        self._update(True)
+
+    def finish(self, system):
+        system.state[:] = self.d_state.download()
+
+
 class _ResidentPath(_Path):
     """the whole Gauss-Newton iteration in HBM: linearization (spp_se2_linearize_device), assembly, solve,
     ||dx|| and the vertex update (spp_se2_update_device). Host traffic per iteration: 8 bytes (the norm)."""
@@ -303,7 +416,9 @@ class CNonlinearSolver_Lambda:
     def __init__(self, system, path=None, device=0, verbose=False, host_jacobians=False):
         self.system = system
         if path is None:  # the product paths need the GPU; host_jacobians keeps the linearization in numpy
-            if isinstance(system, _CSlam):
+            if isinstance(system, CRocv):
+                path = _DeviceGroupsPath(device, system.seqs()) if host_jacobians else _ResidentROCVPath(device)
+            elif isinstance(system, _CSlam):
                 resident = _ResidentSlam2DPath if isinstance(system, CSlam2D) else _ResidentSlam3DPath
                 path = _DeviceGroupsPath(device, [system.odo_seq, system.obs_seq]) if host_jacobians else resident(device)
             else:

@@ -493,6 +493,90 @@ def landmark3d_problem(n_poses=40, n_lm=60, seed=72, name="lm3d_small"):
 
 
 # ------------------------------------------------------------------------------------------------
+# range-only constant-velocity SLAM (ROCV): receivers [p | v] (6) + transmitters (3); constant-velocity edges (6, 6, 6),
+# ranges (6, 3, 1), transmitter priors: unary (3, 3)
+# ------------------------------------------------------------------------------------------------
+def rocv_problem(n_receivers=40, n_transmitters=5, seed=81, interleave=False, n_ranges=4, hub=0, name="rocv"):
+    """Range-only SLAM with a constant-velocity motion model (src/slam_app/SolveROCVImpl.cpp): a receiver flies a smooth
+    rising curve (about 2 m/s, a time step of about 1 s with jitter), its true velocity turning with the curve -- the
+    noise of the constant-velocity edges CEdgeConstVelocity3D --; every receiver ranges a random subset of n_ranges
+    transmitters (CEdgePosVel_Landmark3D, sigma 0.05); the transmitters stand around the curve at different heights, start
+    0.3 m off their true places and are held there by priors (CEdgeLandmark3DPrior; full 3x3 information matrices).
+    Vertex ids: half of the transmitters below the receivers' ids and half above, so that range blocks appear in both
+    orientations; interleave=True scatters the transmitters' ids among the receivers'. hub > 0: the middle receiver ranges EVERY transmitter `hub` times
+    (a 6-wide vertex beyond the sequential assembly kernel's 24 sources; a transmitter passes them once more than 24
+    receivers range it). Receivers start at the truth + noise (0.2 m, 0.1 m/s) and have a ROCV:RECEIVER line, except
+    every eighth, which starts where CConstVelocity_Initializer puts it: (p + v dt, v) of its predecessor. The edges are in
+    the order of an incremental run -- the first half of the priors, then per receiver its constant-velocity edge and its
+    ranges, then the other priors.
+    Returns Problem(dim, state (flat, laid out by dim), cv (m, 3) i j dt, cv_info, cv_seq, rng (k, 3) receiver transmitter
+    range, rng_info (k,), rng_seq, pri (p,), pri_info, pri_seq, explicit, recv_id, tx_id, truth, unary_vertex = -1)."""
+    rng = np.random.default_rng(seed)
+    R, T = n_receivers, n_transmitters
+    nv = R + T
+    if interleave:
+        ids = rng.permutation(nv)   # (receiver ids ascend along the chain: the parser drops a ROCV:DELTA_TIME line with i > j)
+        recv_id, tx_id = np.sort(ids[:R]), ids[R:]
+    else:
+        lo = T // 2
+        recv_id, tx_id = lo + np.arange(R), np.concatenate([np.arange(lo), lo + R + np.arange(T - lo)])
+    dt = 1.0 + rng.uniform(-0.05, 0.05, size=R - 1)
+    t = np.concatenate([[0.0], np.cumsum(dt)])
+    w = 0.2
+    pos = np.stack([10 * np.cos(w * t), 10 * np.sin(w * t), 0.3 * t], axis=1)
+    vel = np.stack([-10 * w * np.sin(w * t), 10 * w * np.cos(w * t), np.full(R, 0.3)], axis=1)
+    X = np.concatenate([pos, vel], axis=1)
+    ang = 2 * np.pi * (np.arange(T) + 0.3) / T
+    Tx = np.stack([18 * np.cos(ang), 18 * np.sin(ang), np.where(np.arange(T) % 2 == 0, -4.0, 12.0) + rng.uniform(-1, 1, size=T)], axis=1)
+    # constant-velocity edges along the chain: dp = 0.5 a dt^2 ~ 0.2, dv = a dt ~ 0.4 with a = 10 w^2
+    cv_info = np.tile(np.diag([1 / 0.2 ** 2] * 3 + [1 / 0.4 ** 2] * 3), (R - 1, 1, 1))
+    nr = min(n_ranges, T)
+    rr, rt = [], []
+    for i in range(R):
+        seen = np.sort(rng.choice(T, size=nr, replace=False))
+        rr.append(np.full(nr, i))
+        rt.append(seen)
+        if hub and i == R // 2:
+            rr.append(np.full(hub * T, i))
+            rt.append(np.tile(np.arange(T), hub))
+    rr, rt = np.concatenate(rr).astype(np.int64), np.concatenate(rt).astype(np.int64)
+    z = np.linalg.norm(pos[rr] - Tx[rt], axis=1) + rng.normal(0, 0.05, size=rr.size)
+    rng_info = np.full(rr.size, 1 / 0.05 ** 2)
+    A = rng.normal(size=(T, 3, 3)) * 0.3 + np.eye(3)
+    pri_info = A @ A.transpose(0, 2, 1) / 0.3 ** 2
+    # global edge order
+    first = np.arange(T) < (T + 1) // 2
+    t_cv, t_rng = 1.0 + np.arange(1, R), 1.0 + rr + 0.5
+    t_pri = np.where(first, 0.0, R + 2.0)
+    order = np.argsort(np.concatenate([t_cv, t_rng, t_pri]), kind="stable")
+    seq = np.empty(order.size, dtype=np.int64)
+    seq[order] = np.arange(order.size)
+    # initial estimate
+    est = X + np.concatenate([rng.normal(0, 0.2, size=(R, 3)), rng.normal(0, 0.1, size=(R, 3))], axis=1)
+    listed = np.arange(R) % 8 != 5
+    for i in np.flatnonzero(~listed):
+        est[i] = np.concatenate([est[i - 1, :3] + est[i - 1, 3:] * dt[i - 1], est[i - 1, 3:]])
+    d = rng.normal(size=(T, 3))
+    tx_est = Tx + 0.3 * d / np.linalg.norm(d, axis=1, keepdims=True)
+    dim = np.empty(nv, dtype=np.int32)
+    dim[recv_id], dim[tx_id] = 6, 3
+    base = np.zeros(nv + 1, dtype=np.int64)
+    np.cumsum(dim, out=base[1:])
+    state = np.empty(base[-1])
+    state[base[recv_id][:, None] + np.arange(6)] = est
+    state[base[tx_id][:, None] + np.arange(3)] = tx_est
+    explicit = np.ones(nv, dtype=bool)
+    explicit[recv_id[~listed]] = False
+    f = lambda a: a.astype(np.float64)
+    m = R - 1
+    return Problem(name=name, dim=dim, state=state, unary_vertex=-1, recv_id=recv_id, tx_id=tx_id, explicit=explicit,
+                   cv=np.stack([f(recv_id[:-1]), f(recv_id[1:]), dt], axis=1), cv_info=cv_info, cv_seq=seq[:m].copy(),
+                   rng=np.stack([f(recv_id[rr]), f(tx_id[rt]), z], axis=1), rng_info=rng_info, rng_seq=seq[m:m + rr.size].copy(),
+                   pri=tx_id.astype(np.int64), pri_info=pri_info, pri_seq=seq[m + rr.size:].copy(),
+                   truth=dict(receivers=X, transmitters=Tx))
+
+
+# ------------------------------------------------------------------------------------------------
 # stereo bundle adjustment: cameras CVertexSCam (6) + points (3), 3-d residuals (u, v, u_right), CEdgeP2SC3D
 # ------------------------------------------------------------------------------------------------
 def stereo_problem(nc=6, npts=40, seed=16, interleave=False, views=(2, 6), hubs=False, name="stereo"):
@@ -691,6 +775,8 @@ CONFIGS = {
     "slam3d_small": lambda: slam3d_problem(40, 60, 71, name="slam3d_small"),
     "slam3d_interleaved": lambda: slam3d_problem(150, 300, 73, interleave=True, name="slam3d_interleaved", hubs=26),
     "lm3d_small": lambda: landmark3d_problem(40, 60, 72),
+    "rocv_small": lambda: rocv_problem(40, 5, 81, name="rocv_small"),
+    "rocv_interleaved": lambda: rocv_problem(150, 8, 83, interleave=True, n_ranges=6, hub=3, name="rocv_interleaved"),
     "stereo_small": lambda: stereo_problem(6, 40, 16, name="stereo_small"),
     "stereo_interleaved": lambda: stereo_problem(30, 150, 17, interleave=True, hubs=True, name="stereo_interleaved"),
     "bai_tiny": lambda: bai_tiny(),
