@@ -74,8 +74,13 @@ int spp_last_error(const spp_ctx *ctx, char *buf, size_t buf_size);
  * that the host-pointer entry spp_factor_solve() copies to the device at the DMA rate of the link instead of through
  * the runtime's pageable bounce buffers: the reference's own workspace reuse, LinearSolver_UberBlock.h:332-348. */
 double *spp_host_staging(spp_ctx *ctx, int64_t n_doubles);
-/* run all work of this ctx on an externally owned hipStream_t (e.g. torch's current stream) */
+/* run all work of this ctx on an externally owned hipStream_t (e.g. torch's current stream). Drains the old stream and
+ * the ctx's side stream first. The results of spp_factor_solve_device and spp_schur_finish are ordered on this stream
+ * (see there): work the caller enqueues on it sees them complete; work on any OTHER stream needs spp_synchronize or an
+ * event of the caller's behind the call. */
 int spp_set_stream(spp_ctx *ctx, void *hip_stream);
+/* waits for everything enqueued on the ctx stream; reports (SPP_E_HIP) a backward substitution that timed out in a solve
+ * which had returned before it ended */
 int spp_synchronize(spp_ctx *ctx);
 
 /* ---- symbolic -----------------------------------------------------------------------------------
@@ -120,6 +125,7 @@ int spp_set_shard(spp_ctx *ctx, int rank, int world_size);
 #define SPP_INFO_S_CLEAR        20 /* what the last spp_schur_form / solve cleared of its S buffer: 0 all of it, 1 the tiles of the filled mask, 2 the right-hand side and padding columns (every block of S is written) */
 #define SPP_INFO_S_DEVICE_PTR   21 /* diagnostics, tests: device address of the S | rhs buffer spp_factor_solve owns (0: none yet) */
 #define SPP_INFO_ASM_HUB_CHUNK   22 /* assembly of ternary edges: edges one workgroup of the hub reduction sums (C); a constant, needs no analysis */
+#define SPP_INFO_SOLVE_ASYNC    23 /* what the last spp_factor_solve_device / spp_schur_finish did (SPP_SOLVE_ASYNC): 1 it returned when the factor's status was known, the solves and the back-substitution still running on the stream; 0 it drained the stream (profiling on, stream capture, sparse reduced system, sparse mode, the switch at 0) */
 int spp_get_info(const spp_ctx *ctx, int what, int64_t *out);
 /* elimination order chosen by the analysis: order[k] = source block column eliminated k-th */
 int spp_get_ordering(const spp_ctx *ctx, int64_t *h_order);
@@ -165,7 +171,14 @@ int spp_factor_solve(spp_ctx *ctx, const double *h_vals, double *h_rhs_inout);
 
 /* ---- numeric: device-resident entry points (Lambda lives in HBM across GN iterations) ------------
  * d_vals: nvals doubles in the layout given to spp_analyze; d_rhs: n doubles, in/out (contents unspecified after
- * SPP_NOT_POSDEF: the status is fetched once, after the solves have run). */
+ * SPP_NOT_POSDEF: the status is fetched once, after the solves have run).
+ * STREAM-ORDERED RESULT: with a dense reduced camera system (SPP_MODE_SCHUR; SPP_INFO_SOLVE_ASYNC tells) the call returns
+ * as soon as the factorization's status is known -- the return code is final -- while the triangular solves and the
+ * back-substitution may still be running on the ctx stream. d_rhs_inout is complete for any later work on the ctx
+ * stream (the next solve, spp_memcpy_d2d, the update kernels), for spp_memcpy_d2h and behind spp_synchronize; d_vals and
+ * d_rhs_inout must stay allocated until then (spp_device_free waits for the stream). Not so -- the call drains the stream
+ * as before -- with profiling on, under stream capture, for the sparse reduced system and the sparse mode, and with
+ * SPP_SOLVE_ASYNC=0. */
 int spp_factor_solve_device(spp_ctx *ctx, const double *d_vals, double *d_rhs_inout);
 
 /* split form for multi-GPU: (1) each rank forms its partial Schur complement and
@@ -174,6 +187,8 @@ int spp_factor_solve_device(spp_ctx *ctx, const double *d_vals, double *d_rhs_in
  * landmarks. With world_size == 1 step (2) is a no-op. rank 0 alone adds A and the pose rhs. */
 int spp_schur_buffer_size(const spp_ctx *ctx, int64_t *n_doubles);
 int spp_schur_form(spp_ctx *ctx, const double *d_vals, const double *d_rhs, double *d_S_rhs);
+/* spp_schur_finish returns like spp_factor_solve_device: with a dense S, once the status is known, d_rhs_inout ordered
+ * on the ctx stream (d_S_rhs is still being read until then). */
 int spp_schur_finish(spp_ctx *ctx, const double *d_vals, double *d_S_rhs, double *d_rhs_inout);
 /* Only the upper block-trapezoid of S carries data: pack it (128-column panels, rows 0 .. end of the
  * panel's diagonal block; 128^2 nblk (nblk + 1) / 2 doubles, about half of the square buffer) before

@@ -80,6 +80,17 @@ void dom_end(spp_ctx *ctx, double flops)
 
 } // namespace spp
 
+// Both streams of the ctx idle. Since a solve may return with its triangular solves and back-substitution still running
+// (SPP_SOLVE_ASYNC), everything that frees or reallocates what those kernels work on, swaps the stream or closes the
+// ctx comes through here first.
+static void ctx_drain(spp_ctx *ctx)
+{
+	(void)hipStreamSynchronize(ctx->stream);
+	if(ctx->side_stream)
+		(void)hipStreamSynchronize(ctx->side_stream);
+	ctx->status_pending = false;
+}
+
 #define SPP_TRY(ctx) try {
 #define SPP_CATCH(ctx) } catch(const spp::Error &e) { if(ctx) (ctx)->last_error = e.what(); return e.code; } \
 	catch(const std::bad_alloc &) { if(ctx) (ctx)->last_error = "host allocation failed"; return SPP_E_NOMEM; } \
@@ -135,7 +146,7 @@ int spp_free_memory(spp_ctx *ctx)
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
 	(void)hipSetDevice(ctx->device);
-	(void)hipStreamSynchronize(ctx->stream);
+	ctx_drain(ctx);
 	ctx->schur.release_all();
 	sparse_release(ctx);
 	assemble_release(ctx);
@@ -189,6 +200,11 @@ void spp_destroy(spp_ctx *ctx)
 		(void)hipEventDestroy(ctx->side_ev[0]);
 		(void)hipEventDestroy(ctx->side_ev[1]);
 	}
+	for(int i = 0; i < 2; ++ i)
+		if(ctx->status_ev[i])
+			(void)hipEventDestroy(ctx->status_ev[i]);
+	if(ctx->h_status)
+		(void)hipHostFree(ctx->h_status);
 	if(ctx->dense.h_chain_err)
 		(void)hipHostFree(ctx->dense.h_chain_err);
 	if(ctx->h_staging)
@@ -240,7 +256,7 @@ int spp_set_stream(spp_ctx *ctx, void *hip_stream)
 {
 	if(!ctx)
 		return SPP_E_BADARG;
-	(void)hipStreamSynchronize(ctx->stream);
+	ctx_drain(ctx);
 	if(ctx->own_stream && ctx->stream)
 		(void)hipStreamDestroy(ctx->stream);
 	ctx->stream = (hipStream_t)hip_stream;
@@ -289,6 +305,7 @@ int spp_analyze(spp_ctx *ctx, int64_t nb, const int64_t *col_ptr, const int64_t 
 	// sizes of the NEW structure beside the plan of the OLD one (the next solve would copy the wrong extents).
 	// The old plan is dropped first in any case -- after a failed analyze the ctx is "not analyzed".
 	ctx->mode = -1;
+	ctx_drain(ctx); // (the plan and the workspaces released below may still be at work for a solve that returned early)
 	VClock clk("spp_analyze");
 	Structure st;
 	st.nb = nb;
@@ -421,6 +438,7 @@ int spp_get_info(const spp_ctx *ctx, int what, int64_t *out)
 	case SPP_INFO_LM_STREAM: *out = (ctx->mode == SPP_MODE_SCHUR) ? ctx->schur.lm_stream_last : 0; break;
 	case SPP_INFO_BS_GROUPS: *out = (ctx->mode == SPP_MODE_SCHUR) ? ctx->schur.n_bs : 0; break;
 	case SPP_INFO_SCHUR_SIDE: *out = (ctx->mode == SPP_MODE_SCHUR) ? ctx->schur.side_last : 0; break;
+	case SPP_INFO_SOLVE_ASYNC: *out = (ctx->mode == SPP_MODE_SCHUR) ? ctx->schur.async_last : 0; break;
 	case SPP_INFO_S_CLEAR: *out = (ctx->mode == SPP_MODE_SCHUR) ? ctx->schur.clear_last : 0; break;
 	case SPP_INFO_S_DEVICE_PTR: *out = (ctx->mode == SPP_MODE_SCHUR) ? (int64_t)(uintptr_t)ctx->schur.S.p : 0; break;
 	case SPP_INFO_ASM_HUB_CHUNK: *out = ASM_HUB_CHUNK; break;
@@ -666,10 +684,14 @@ int spp_schur_finish(spp_ctx *ctx, const double *d_vals, double *d_S_rhs, double
 	SPP_TRY(ctx)
 	SPP_REQUIRE(ctx->mode == SPP_MODE_SCHUR, SPP_E_STATE, "spp_schur_finish: analyze in Schur mode first");
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
-	int ret = schur_finish(ctx, d_vals, d_S_rhs, d_rhs_inout); // synchronizes (status fetch)
+	// drains the stream for the status fetch, or -- dense S, SPP_SOLVE_ASYNC -- waits for the status alone and returns with the
+	// solves and the back-substitution still running: d_rhs_inout is then ordered on the ctx stream
+	int ret = schur_finish(ctx, d_vals, d_S_rhs, d_rhs_inout);
 	phase_end(ctx, SPP_PHASE_TOTAL);
 	phases_collect(ctx);
-	dense_chain_check(ctx); // a timed-out backward substitution is reported by the call that produced the result
+	// the chain kernels' timeout word is host memory, looked at after a synchronization: behind a drained stream it tells
+	// of this solve, behind an early return of the solves this one's status wait has synchronized with (the earlier ones)
+	dense_chain_check(ctx);
 	return ret;
 	SPP_CATCH(ctx)
 }
@@ -687,8 +709,10 @@ int spp_factor_solve_device(spp_ctx *ctx, const double *d_vals, double *d_rhs)
 	if(ctx->mode == SPP_MODE_SCHUR) {
 		SPP_REQUIRE(ctx->shard_world == 1, SPP_E_STATE,
 			"sharded ctx: use spp_schur_form / all-reduce / spp_schur_finish");
-		if(!ctx->schur.S.p || ctx->schur.S.cap < (size_t)schur_buffer_doubles(ctx))
+		if(!ctx->schur.S.p || ctx->schur.S.cap < (size_t)schur_buffer_doubles(ctx)) {
 			ctx->schur.unlisted_dirty = true; // a new allocation: nothing is known of its contents
+			ctx_drain(ctx); // (and the old one may be at work for a solve that returned early)
+		}
 		ctx->schur.S.reserve((size_t)schur_buffer_doubles(ctx));
 		schur_form(ctx, d_vals, d_rhs, ctx->schur.S.p, true);
 		ret = schur_finish(ctx, d_vals, ctx->schur.S.p, d_rhs);
@@ -696,8 +720,11 @@ int spp_factor_solve_device(spp_ctx *ctx, const double *d_vals, double *d_rhs)
 		ret = sparse_factor_solve(ctx, d_vals, d_rhs);
 	phase_end(ctx, SPP_PHASE_TOTAL);
 	phases_collect(ctx);
-	SPP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-	dense_chain_check(ctx);
+	// a dense Schur solve that returned on its status (SPP_SOLVE_ASYNC) leaves the stream running: the solution is ordered
+	// on it, for later work of this ctx, spp_memcpy_d2h and spp_synchronize
+	if(!(ctx->mode == SPP_MODE_SCHUR && ctx->schur.async_last))
+		SPP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+	dense_chain_check(ctx); // (see spp_schur_finish)
 	return ret;
 	SPP_CATCH(ctx)
 }
@@ -718,6 +745,7 @@ int spp_factor_solve(spp_ctx *ctx, const double *h_vals, double *h_rhs)
 		return ret; // the rhs is left untouched on failure, like the reference (LinearSolver_UberBlock.h:411-423)
 	SPP_HIP_CHECK(hipMemcpyAsync(h_rhs, ctx->d_rhs.p, ctx->st.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
 	SPP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+	dense_chain_check(ctx); // (the device entry may have returned with the backward substitution still running)
 	return SPP_OK;
 	SPP_CATCH(ctx)
 }
@@ -1087,6 +1115,7 @@ int spp_memcpy_d2h(spp_ctx *ctx, void *h_dst, const void *d_src, size_t bytes)
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	SPP_HIP_CHECK(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
 	SPP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+	dense_chain_check(ctx); // what is downloaded may be the result of a solve that returned with its chain kernel still running
 	return SPP_OK;
 	SPP_CATCH(ctx)
 }

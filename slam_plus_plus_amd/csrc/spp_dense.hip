@@ -640,6 +640,14 @@ void trsv_back_kernel(const double *__restrict__ R, int64_t ld, int64_t k0, int 
 }
 
 
+// The timeout word of the backward-substitution chains is page-locked host memory (DenseWork::h_chain_err): a workgroup that
+// gives up stores there itself, with a system-scope vector store, so no copy of the word sits on the stream behind every
+// solve. The host looks at it after a synchronization (dense_chain_check).
+__device__ __forceinline__ void chain_raise(int *err)
+{
+	__hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // Backward substitution as ONE launch: one workgroup per block row (128 rows), last block row first in dispatch
 // order; the workgroups run the dependent chain x_last -> ... -> x_0 through global memory instead of through 41
 // kernel launches. Workgroup b applies x_k to its rows for k = last .. b+1
@@ -694,7 +702,7 @@ void trsv_back_chain_kernel(const double *__restrict__ R, int64_t ld, int64_t n,
 		__syncthreads();
 		if(!ok) {
 			if(tid == 0)
-				*err = 1;
+				chain_raise(err);
 			return;
 		}
 		if(tid < NB)
@@ -880,7 +888,7 @@ void trsv_back_chain2_kernel(const double *__restrict__ R, int64_t ld, int64_t n
 			lds_barrier();
 			if(!ok[slot]) {
 				if(tid == 0)
-					*err = 1;
+					chain_raise(err);
 				alive = false;
 				return;
 			}
@@ -967,7 +975,7 @@ void trsv_back_chain2_kernel(const double *__restrict__ R, int64_t ld, int64_t n
 					++ spins;
 				}
 				if(spins >= SPIN_MAX)
-					*err = 1;
+					chain_raise(err);
 				const double xr = uv - part_sum(tid);
 				xs[b & 1][tid] = xr;
 				pay_store(xpay + (size_t)b * NB + tid, xr, K);
@@ -1036,7 +1044,7 @@ void trsv_back_chain2_kernel(const double *__restrict__ R, int64_t ld, int64_t n
 				++ spins;
 			}
 			if(spins >= SPIN_MAX)
-				*err = 1; // (the hop goes on with garbage: every workgroup still drains)
+				chain_raise(err); // (the hop goes on with garbage: every workgroup still drains)
 			zs[tid] = wv - part_sum(tid);
 		}
 		lds_barrier();
@@ -1146,7 +1154,8 @@ void dense_set_padding(spp_ctx *ctx, double *d_A, int64_t ld, int64_t n)
 // --------------------------------------------------------------------------------------------------
 // host drivers
 // --------------------------------------------------------------------------------------------------
-// info[0]: first failing pivot + 1, info[1]: timeout of the backward-substitution chain, info[2]: abort flag of
+// info[0]: first failing pivot + 1, info[1]: free (the backward-substitution chain's timeout word is host memory,
+// DenseWork::h_chain_err), info[2]: abort flag of
 // the device-flag hand-offs and the streamed launch (stays set until the host has seen it; TAIL_ABORT_TIMEOUT: a wait of
 // the streamed launch gave up), info[3]: abort flag of the sparse path's
 // dependency-driven launches -- zeroed once, when the buffer is created
@@ -1918,8 +1927,24 @@ void dense_chain_check(spp_ctx *ctx)
 int dense_info_fetch(spp_ctx *ctx, bool *dag_aborted)
 {
 	int h_info[4] = {0, 0, 0, 0};
-	SPP_HIP_CHECK(hipMemcpyAsync(h_info, ctx->dense.info.p, 4 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	dense_info_copy_on(ctx, ctx->stream, h_info);
 	SPP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+	return dense_info_eval(ctx, h_info, dag_aborted);
+}
+
+void dense_info_copy_on(spp_ctx *ctx, hipStream_t st, int *h_status4)
+{
+	SPP_HIP_CHECK(hipMemcpyAsync(h_status4, ctx->dense.info.p, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
+}
+
+int dense_info_eval(spp_ctx *ctx, const int *h_status4, bool *dag_aborted, bool drain_first)
+{
+	const int h_info[4] = {h_status4[0], h_status4[1], h_status4[2], h_status4[3]};
+	// Anything but four zeros is the rare case. The words were final when the factorization ended, but what the caller has
+	// enqueued behind it may still run: the ctx stream is drained first, so that the resets below (synchronous, as ever)
+	// and the switches to the fallback schedules meet an idle stream, and stay ordered in front of the next status reset.
+	if(drain_first && (h_info[0] | h_info[2] | h_info[3]))
+		SPP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
 	if(h_info[3]) { // a front of the dependency-driven sparse launches timed out waiting for a child / its parent
 		SPP_HIP_CHECK(hipMemset(ctx->dense.info.p + 3, 0, sizeof(int)));
 		sparse_dag_disable(ctx);
@@ -2024,6 +2049,17 @@ int dense_front_factor(spp_ctx *ctx, double *d_F, int64_t ld, int64_t w, int64_t
 	return info ? SPP_NOT_POSDEF : SPP_OK;
 }
 
+// the chain kernels' timeout word: page-locked host memory the device stores into (chain_raise); nothing travels on the
+// stream, dense_chain_check() looks at the word after a synchronization
+static void chain_err_ensure(DenseWork &dw)
+{
+	if(dw.h_chain_err)
+		return;
+	SPP_HIP_CHECK(hipHostMalloc((void**)&dw.h_chain_err, sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
+	*dw.h_chain_err = 0;
+	SPP_HIP_CHECK(hipHostGetDevicePointer((void**)&dw.d_chain_err, dw.h_chain_err, 0));
+}
+
 // back substitution R x = y with y in d_b (n entries); uses the block inverses of the last potrf.
 // d_b may be the rhs column of the factored matrix itself.
 void dense_potrs_upper(spp_ctx *ctx, const double *d_R, int64_t n, int64_t ld, double *d_b)
@@ -2044,10 +2080,7 @@ void dense_potrs_upper(spp_ctx *ctx, const double *d_R, int64_t n, int64_t ld, d
 			dw.trsv_pay.reserve(need);
 			SPP_HIP_CHECK(hipMemsetAsync(dw.trsv_pay.p, 0, dw.trsv_pay.cap * sizeof(double), s));
 		}
-		if(!dw.h_chain_err) {
-			SPP_HIP_CHECK(hipHostMalloc((void**)&dw.h_chain_err, sizeof(int), hipHostMallocDefault));
-			*dw.h_chain_err = 0;
-		}
+		chain_err_ensure(dw);
 		++ dw.epoch;
 		// the check constant of this solve: odd multiples of a 64-bit odd constant are distinct and non-zero modulo 2^64, so
 		// K repeats only after 2^63 solves (epoch is 64-bit)
@@ -2061,34 +2094,27 @@ void dense_potrs_upper(spp_ctx *ctx, const double *d_R, int64_t n, int64_t ld, d
 				SPP_HIP_CHECK(hipFuncSetAttribute((const void*)trsv_m_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TRSVM_LDS_DOUBLES * (int)sizeof(double)));
 			hipLaunchKernelGGL(trsv_m_kernel, dim3((unsigned)nblk - 1, 8), dim3(1024), TRSVM_LDS_DOUBLES * sizeof(double), s, d_R, ld, n, dw.tinv_all.p, dw.trsv_m.p);
 			hipLaunchKernelGGL((trsv_back_chain2_kernel<8, true>), dim3((unsigned)nblk + 1), dim3(512), 0, s,
-				d_R, ld, n, (int)nblk, dw.tinv_all.p, dw.trsv_m.p, d_b, xpay, wpay, K, dw.info.p + 1);
+				d_R, ld, n, (int)nblk, dw.tinv_all.p, dw.trsv_m.p, d_b, xpay, wpay, K, dw.d_chain_err);
 		} else
 			hipLaunchKernelGGL((trsv_back_chain2_kernel<8, false>), dim3((unsigned)nblk + 1), dim3(512), 0, s,
-				d_R, ld, n, (int)nblk, dw.tinv_all.p, (const double*)nullptr, d_b, xpay, wpay, K, dw.info.p + 1);
+				d_R, ld, n, (int)nblk, dw.tinv_all.p, (const double*)nullptr, d_b, xpay, wpay, K, dw.d_chain_err);
 		SPP_HIP_CHECK(hipGetLastError());
-		SPP_HIP_CHECK(hipMemcpyAsync(dw.h_chain_err, dw.info.p + 1, sizeof(int), hipMemcpyDeviceToHost, s));
 		return;
 	}
 	if(use_chain && nblk > 1 && nblk <= 1024) {
-		// one launch, the dependent chain runs through device flags (info[1] = timeout flag)
+		// one launch, the dependent chain runs through device flags
 		DenseWork &dw = ctx->dense;
 		if(dw.flags.cap < (size_t)nblk) {
 			dw.flags.reserve((size_t)nblk);
 			SPP_HIP_CHECK(hipMemsetAsync(dw.flags.p, 0, (size_t)nblk * sizeof(int), s));
 			dw.epoch = 0;
 		}
-		if(!dw.h_chain_err) {
-			SPP_HIP_CHECK(hipHostMalloc((void**)&dw.h_chain_err, sizeof(int), hipHostMallocDefault));
-			*dw.h_chain_err = 0;
-		}
+		chain_err_ensure(dw);
 		++ dw.epoch;
 		hipLaunchKernelGGL(trsv_back_chain_kernel, dim3((unsigned)nblk), dim3(256), 0, s, d_R, ld, n, (int)nblk,
-			dw.tinv_all.p, d_b, dw.xtmp.p, dw.flags.p, (int)dw.epoch, dw.info.p + 1);
+			dw.tinv_all.p, d_b, dw.xtmp.p, dw.flags.p, (int)dw.epoch, dw.d_chain_err);
 		SPP_HIP_CHECK(hipGetLastError());
 		SPP_HIP_CHECK(hipMemcpyAsync(d_b, dw.xtmp.p, n * sizeof(double), hipMemcpyDeviceToDevice, s));
-		// the timeout flag travels to pinned host memory; dense_chain_check() looks at it after the
-		// next synchronization of the stream (no extra round trip)
-		SPP_HIP_CHECK(hipMemcpyAsync(dw.h_chain_err, dw.info.p + 1, sizeof(int), hipMemcpyDeviceToHost, s));
 		return;
 	}
 	for(int64_t k = nblk; k > 0;) {

@@ -278,6 +278,7 @@ struct SchurPlan : SchurDims {
 	// reset of the coming factorization are already enqueued there
 	bool side_pending = false, side_padded = false;
 	int side_last = 0, clear_last = 0; // diagnostics of the last schur_form: SPP_INFO_SCHUR_SIDE, SPP_INFO_S_CLEAR
+	int async_last = 0;            // ... of the last schur_finish: 1 = it returned on the factor's status with the stream still running (SPP_SOLVE_ASYNC), 0 = it drained the stream (SPP_INFO_SOLVE_ASYNC)
 	void release_all();
 };
 
@@ -310,7 +311,8 @@ struct DenseWork {
 	DevBuf<double> trsv_m;         // M_b = Tinv_b R_{b, b+1} per block row (M form of the backward substitution)
 	DevBuf<double> trsv_pay;       // hand-over pairs {value, check word} of the one-workgroup chain: x (nblk x 128) and w (nblk x 128)
 	uint64_t epoch = 0;            // solves so far (backward-substitution chains tell one solve from the next by it)
-	int *h_chain_err = nullptr;
+	int *h_chain_err = nullptr;    // timeout word of the chain kernels: page-locked, mapped host memory they store into on their error path alone (dense_chain_check)
+	int *d_chain_err = nullptr;    // ... its device address
 	hipStream_t aux = nullptr;     // lookahead stream: potrf_diag + trsm of the next panel
 	hipEvent_t ev[2] = {nullptr, nullptr};
 	// device-flag hand-offs between the chain stream and the bulk stream (dense_factor_steps_enqueue):
@@ -362,6 +364,12 @@ struct spp_ctx {
 	// CU-masked and belongs to the per-step schedule of the dense factor.
 	hipStream_t side_stream = nullptr;
 	hipEvent_t side_ev[2] = {nullptr, nullptr};
+	// Solve stage (SPP_SOLVE_ASYNC): the factor's four status words travel to h_status (page-locked) on the side stream,
+	// forked from `stream` behind the factor by status_ev[0]; the host waits for status_ev[1], recorded behind the copy, and
+	// for nothing else. Both are re-recorded only after that wait.
+	hipEvent_t status_ev[2] = {nullptr, nullptr};
+	int *h_status = nullptr;
+	bool status_pending = false; // a copy was enqueued and the host has not waited for it (a call that failed in between)
 	std::string last_error;
 	int mode = -1; // -1: not analyzed
 	int shard_rank = 0, shard_world = 1;
@@ -501,6 +509,12 @@ int dense_potrf_upper(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, bool kee
 // leaves every tile outside the mask untouched); info_reset false: the caller has enqueued dense_info_reset_on() itself
 bool dense_potrf_upper_enqueue(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, bool info_reset = true);
 int dense_info_fetch(spp_ctx *ctx, bool *dag_aborted = nullptr); // dag_aborted given: a timed-out sparse launch is reported there instead of thrown
+// its two halves, for a caller that lets other work run between them: the copy of the four status words to h_status4
+// (page-locked) on a stream the caller orders behind the factorization, and -- once the host has waited for that copy --
+// what dense_info_fetch makes of them. drain_first: words that are not all zero (a failed pivot, a timed-out wait) are
+// acted on only after the ctx stream was synchronized, as in dense_info_fetch
+void dense_info_copy_on(spp_ctx *ctx, hipStream_t st, int *h_status4);
+int dense_info_eval(spp_ctx *ctx, const int *h_status4, bool *dag_aborted = nullptr, bool drain_first = false);
 void dense_potrs_upper(spp_ctx *ctx, const double *d_R, int64_t n, int64_t ld, double *d_b);
 void dense_aux_park(int device, hipStream_t s); // hands the bulk stream of a closing context to the next one
 void dense_factor_steps(spp_ctx *ctx, double *d_A, int64_t ld, int64_t n, int64_t rows, int64_t ncols,
@@ -510,7 +524,10 @@ void dense_info_ensure(spp_ctx *ctx); // the status words exist (created and zer
 void dense_info_reset_on(spp_ctx *ctx, hipStream_t st); // ... reset on a stream the caller orders against the ctx stream
 void dense_reserve(spp_ctx *ctx, int64_t nblk); // workspaces for nblk diagonal blocks (call at analyze time)
 
-void dense_chain_check(spp_ctx *ctx); // call after the stream was synchronized
+// call after the stream was synchronized. The chain kernels store their timeout word straight into page-locked host
+// memory (DenseWork::h_chain_err), so a timed-out chain is reported by the first call that synchronizes with its solve:
+// spp_synchronize, spp_memcpy_d2h, a draining entry point, or the next solve's status wait
+void dense_chain_check(spp_ctx *ctx);
 void dense_set_padding(spp_ctx *ctx, double *d_A, int64_t ld, int64_t n);
 void dense_set_padding_on(hipStream_t st, double *d_A, int64_t ld, int64_t n);
 struct TileMaskGuard { // hands a tile mask to the factorizations enqueued while it lives

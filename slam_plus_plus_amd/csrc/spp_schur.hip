@@ -1240,6 +1240,19 @@ static void side_stream_ensure(spp_ctx *ctx)
 	SPP_HIP_CHECK(hipEventCreateWithFlags(&ctx->side_ev[1], hipEventDisableTiming));
 }
 
+// what the early status of schur_finish needs beside the side stream: its two events and the page-locked words
+static void status_ensure(spp_ctx *ctx)
+{
+	side_stream_ensure(ctx);
+	if(ctx->h_status)
+		return;
+	if(!ctx->status_ev[0])
+		SPP_HIP_CHECK(hipEventCreateWithFlags(&ctx->status_ev[0], hipEventDisableTiming));
+	if(!ctx->status_ev[1])
+		SPP_HIP_CHECK(hipEventCreateWithFlags(&ctx->status_ev[1], hipEventDisableTiming));
+	SPP_HIP_CHECK(hipHostMalloc((void**)&ctx->h_status, 4 * sizeof(int), hipHostMallocDefault));
+}
+
 // the ctx stream waits for what schur_form put on the side stream (a no-op when there is nothing)
 static void side_stream_join(spp_ctx *ctx)
 {
@@ -1381,6 +1394,20 @@ static int schur_finish_t(spp_ctx *ctx, const double *d_vals, double *S, double 
 	const int64_t ld = sp.ld;
 	double *xcol;
 	side_stream_join(ctx); // the reduced rhs (and padding, status reset) of a one-call schur_form
+	// The status of the dense factor is final when the factor ends, ~230 us (Venice) before the back-substitution does. With
+	// SPP_SOLVE_ASYNC the four words leave on the side stream right behind the factor, the host waits for that copy alone, and
+	// the call returns with the triangular solves and the back-substitution still running: the caller's next launches reach
+	// the queue before it runs dry. The drained order stays with profiling on (phase_ms is read from a drained stream) and
+	// under stream capture (no fork inside a captured graph).
+	const bool early = !sp.sparse_S && switches().solve_async != 0 && !(ctx->flags & SPP_FLAG_PROFILE) && !stream_capturing(s);
+	sp.async_last = early ? 1 : 0;
+	if(early) {
+		status_ensure(ctx);
+		if(ctx->status_pending) { // (left behind by a call that failed between the copy and the wait)
+			SPP_HIP_CHECK(hipStreamSynchronize(ctx->side_stream));
+			ctx->status_pending = false;
+		}
+	}
 	if(sp.sparse_S) {
 		// supernodal multifrontal factorization + solves of the sparse reduced camera system (the
 		// reference's CLinearSolver_Schur with a sparse inner solver, LinearSolver_Schur.h:1844-1853)
@@ -1409,6 +1436,15 @@ static int schur_finish_t(spp_ctx *ctx, const double *d_vals, double *S, double 
 				sp.unlisted_dirty = false;
 		}
 		sp.side_padded = false;
+		if(early) {
+			// fork behind the factor: the side stream is in order, so the copy also comes behind the status reset this solve
+			// put there, and the next solve's reset behind the copy
+			SPP_HIP_CHECK(hipEventRecord(ctx->status_ev[0], s));
+			SPP_HIP_CHECK(hipStreamWaitEvent(ctx->side_stream, ctx->status_ev[0], 0));
+			dense_info_copy_on(ctx, ctx->side_stream, ctx->h_status);
+			SPP_HIP_CHECK(hipEventRecord(ctx->status_ev[1], ctx->side_stream));
+			ctx->status_pending = true;
+		}
 		phase_end(ctx, SPP_PHASE_FACTOR);
 		xcol = S + sp.n_red * ld;
 		phase_begin(ctx, SPP_PHASE_TRISOLVE);
@@ -1446,6 +1482,14 @@ static int schur_finish_t(spp_ctx *ctx, const double *d_vals, double *S, double 
 			sp.nc, sp.pose_rbase.p, xcol, d_rhs);
 	phase_end(ctx, SPP_PHASE_BACKSUBST);
 	SPP_HIP_CHECK(hipGetLastError());
+	if(early) {
+		// the one wait of the call: the copy behind the factor. Everything on the side stream (this solve's rhs, padding and
+		// reset included) and the factor itself are complete then, so all four events may be recorded again; the solution in
+		// d_rhs is ordered on the ctx stream. Words that are not all zero drain the ctx stream before they are acted on.
+		SPP_HIP_CHECK(hipEventSynchronize(ctx->status_ev[1]));
+		ctx->status_pending = false;
+		return dense_info_eval(ctx, ctx->h_status, nullptr, true) ? SPP_NOT_POSDEF : SPP_OK;
+	}
 	if(!sp.sparse_S && dense_info_fetch(ctx))
 		return SPP_NOT_POSDEF;
 	return SPP_OK;

@@ -60,6 +60,7 @@ struct Switches {
 	int schur_cam_order;      // SPP_SCHUR_CAM_ORDER (1): dense S with a tile mask: the cameras of a closed loop are ordered arc, arc, separators (tile-aligned dissection, schur_cam_order) when the cost model of the streamed factor gains 10 %; 0: the natural order always
 	int backsubst_fused;      // SPP_BACKSUBST_FUSED (1): 0: the products U^T dx through memory, two launches (rounds 1-3)
 	int schur_side;           // SPP_SCHUR_SIDE (1): the reduced right-hand side, the padding of S and the status reset run on a side stream beside the S accumulation, from SCHUR_SIDE_MIN_OBS observations on; 0: the serial order on the one stream; 2: the side stream whatever the size (tests)
+	int solve_async;          // SPP_SOLVE_ASYNC (1): dense reduced system: the factor's status travels to the host on the side stream while the triangular solves and the back-substitution run, and the solve returns once the status is known, its result ordered on the ctx stream (never under stream capture or with profiling on); 0: the status is fetched behind the back-substitution and the call drains the stream
 	int lm_stream;            // SPP_LM_STREAM (1): (factored form, 6 x 3 blocks) the landmark-side kernels fetch U cooperatively in 16-byte pieces, xw in observation order, the fused back-substitution with the next group's fetch in flight; 2: the same with xw camera-major in 16-byte pieces (measured slower: Venice step 2.675 against 2.618 ms); 0: one lane per block (rounds 3-7)
 
 	// ---- sparse path (spp_sparse.hip)
@@ -132,6 +133,7 @@ inline Switches parse_switches()
 	w.schur_cam_order = env_int("SPP_SCHUR_CAM_ORDER", 1);
 	w.backsubst_fused = env_int("SPP_BACKSUBST_FUSED", 1);
 	w.schur_side = env_int("SPP_SCHUR_SIDE", 1);
+	w.solve_async = env_int("SPP_SOLVE_ASYNC", 1);
 	w.lm_stream = env_int("SPP_LM_STREAM", 1);
 
 	w.mid_front_max = std::max(128, std::min(MID_FRONT_MAX, env_int("SPP_MID_FRONT_MAX", 320)));
