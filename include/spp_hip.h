@@ -48,7 +48,9 @@ extern "C" {
 /* spp_analyze modes */
 #define SPP_MODE_AUTO     0   /* Schur if two block widths with a block-diagonal landmark part, else sparse */
 #define SPP_MODE_SPARSE   1   /* ordering + supernodal block Cholesky on the whole Lambda */
-#define SPP_MODE_SCHUR    2   /* guided Schur complement (landmarks = smaller width) + dense reduced solve */
+#define SPP_MODE_SCHUR    2   /* guided Schur complement (landmarks = smaller width) + dense reduced solve; block widths
+                                   {6,3} (SE(3) cameras / poses + points), {3,2} (2D poses + landmarks), {7,3} (Sim(3)
+                                   cameras + points); anything else SPP_E_UNSUPPORTED */
 #define SPP_MODE_SCHUR_SPARSE 3 /* guided Schur complement, the reduced camera system kept sparse (block-CSC) and
                                    solved by the supernodal path: CLinearSolver_Schur with a sparse inner solver,
                                    include/slam/LinearSolver_Schur.h:1844-1853. AUTO picks it beyond 16384 reduced
@@ -206,8 +208,11 @@ int spp_schur_unpack(spp_ctx *ctx, const double *d_packed, double *d_S_rhs);
  * J0: ne x (rd x d0) col-major, J1: ne x (rd x d1), Omega: ne x (rd x rd), r: ne x rd.
  * Instantiated shapes (d0, d1, rd): (6,3,2) projections, (3,3,3) 2D odometry, (6,6,6) 3D odometry, (3,2,2) 2D landmark
  * observations, (6,3,3) 3D landmark (XYZ) observations, (6,3,1) ranges from a position-velocity vertex to a landmark
- * (CEdgePosVel_Landmark3D, include/slam/ROCV_Types.h:77-223: J0 ne x (1x6), J1 ne x (1x3), Omega ne x 1, r ne x 1); any other
- * is SPP_E_UNSUPPORTED.
+ * (CEdgePosVel_Landmark3D, include/slam/ROCV_Types.h:77-223: J0 ne x (1x6), J1 ne x (1x3), Omega ne x 1, r ne x 1), (7,3,2)
+ * projections into Sim(3) cameras (CEdgeP2C_XYZ_Sim3_G, include/slam/Sim3_Types.h:492-595: J0 ne x (2x7) belongs to the
+ * camera, J1 ne x (2x3) to the point -- the library's order is camera first, as for (6,3,2); the reference's typelist is
+ * (XYZ, CamSim3)); any other is SPP_E_UNSUPPORTED. (7,3,2) is the ONLY group of its plan: through this entry point, or as the
+ * one group of spp_assemble_analyze_groups (bit-equal); beside any other group, unary ones included, SPP_E_UNSUPPORTED.
  * The unary factor (identity, FlatSystem.h:441,467) is added to the diagonal block of vertex
  * `unary_vertex` (pass -1 for none). The reference's default build puts it on vertex 0 whatever its type
  * (__AUTO_UNARY_FACTOR_ON_VERTEX_ZERO, FlatSystem.h:331-337, _Lambda_Base.h:1903-1924; without that macro: on the
@@ -226,7 +231,8 @@ int spp_assemble_device(spp_ctx *ctx, const double *d_J0, const double *d_J1,
  * f_RobustWeight(r), evaluated by the caller -- and every following spp_assemble_device applies it exactly where the
  * reference does: H01 and H00 carry w once (T = J0^T Omega w), the first vertex's right-hand side w TWICE (T r w),
  * H11 and the second vertex's right-hand side once. The array is NOT copied (it must stay valid); NULL restores plain
- * edges; spp_assemble_analyze resets it. */
+ * edges; spp_assemble_analyze resets it. On a (7,3,2) plan a non-NULL array is SPP_E_UNSUPPORTED (and so from
+ * spp_assemble_set_group_edge_weights): the "first vertex twice" rule would attach to the landmark there. */
 int spp_assemble_set_edge_weights(spp_ctx *ctx, const double *d_w);
 /* Several edge groups in one Lambda: odometry (3,3,3) beside landmark observations (3,2,2), camera-camera constraints
  * (6,6,6) beside projections (6,3,2) -- the reference's AddEntriesInSparseSystem / Refresh_Lambda run over an edge pool of
@@ -253,7 +259,7 @@ int spp_assemble_set_edge_weights(spp_ctx *ctx, const double *d_w);
  * spp_assemble_groups_device (host arrays of n_groups device pointers) accepts any plan and gives the same bits on a
  * one-group plan.
  * Unary factor and damping as above; robust weights per group (NULL: plain), reset by either analyze call.
- * SPP_E_UNSUPPORTED: a shape not instantiated, two of (6,3,1) (6,3,2) (6,3,3) side by side, more than SPP_MAX_EDGE_GROUPS groups. SPP_E_BADARG: a vertex width that does
+ * SPP_E_UNSUPPORTED: a shape not instantiated, two of (6,3,1) (6,3,2) (6,3,3) side by side, a (7,3,2) group beside any other group, more than SPP_MAX_EDGE_GROUPS groups. SPP_E_BADARG: a vertex width that does
  * not match its group, a bad index, a self edge, h_seq not a permutation; the ctx then holds no assembly plan.
  * SPP_E_STATE: spp_assemble_device on a plan of several groups, spp_assemble_groups_device without a plan. */
 #define SPP_MAX_EDGE_GROUPS 4
@@ -398,6 +404,32 @@ int spp_ba_update_device(spp_ctx *ctx, int64_t n_cams, double *d_cams, const int
 	int64_t n_points, double *d_points, const int64_t *d_pt_dxoff, const double *d_dx, int64_t n_dx, int apply,
 	double *h_dx_norm2);
 
+/* ---- on-device geometry of Sim(3) bundle adjustment (CEdgeP2C_XYZ_Sim3_G, include/slam/Sim3_Types.h:492-595) ----
+ * Cameras: 7 doubles each, v = [t | w | s] in sim(3) (CVertexCamSim3, Sim3_Types.h:178-238), and 5 constant intrinsics
+ * each (fx fy cx cy d); points: XYZ. The camera is T = Exp(v) (CSim3Jacobians::t_Exp, include/slam/Sim3SolverBase.h:
+ * 3829-3905): rotation exp([w]x), scale e^s, translation tau = a t + b (w x t) + c w x (w x t), with a, b, c the
+ * coefficients of V there. spp_sim3_ba_linearize_device evaluates per observation CSim3Jacobians::Project_P2C_XYZ
+ * (:630-681): x = T^-1 X = e^-s R^T (X - tau), p - c = (fx x0/x2, fy x1/x2), k = d / (0.5 fx fy) -- the PRODUCT of the focal
+ * lengths, not the mono BA form --, uv = c + (1 + |p - c|^2 k)(p - c), residual z - uv; and its Jacobians w.r.t. the
+ * POST-multiplicative camera increment T Exp(delta) of Relative_to_Absolute (:435-452) and w.r.t. the point --
+ * analytically (d x / d delta = [-I | [x]x | -x], d x / d X = e^-s R^T), where the reference takes forward differences
+ * with delta = 1e-9 (:1043-1062). The scale column of J0 is identically zero (the projection does not see the scale of
+ * the camera frame) and is written as zeros; nothing is divided by |p - c|, a point on the optical axis gives finite
+ * Jacobians. a, b, c are evaluated by a Taylor series for s^2 + |w|^2 < 1 and in closed form beyond (the reference: four
+ * cells at 1e-6, whose truncated series approximate the same functions); both match the exact Exp to rounding.
+ * Output layout = input of spp_assemble_device for the (7,3,2) edge group: J0 no x (2x7) column-major, J1 no x (2x3),
+ * r no x 2. cam_of / pt_of: int32 indices into the camera / point arrays.
+ * spp_sim3_update_device has the signature of spp_ba_update_device: ||dx||^2 over the n_dx entries of dx -> *h_dx_norm2,
+ * and if `apply` camera i <- Log(Exp(camera i) Exp(dx[cam_dxoff[i] .. +7))) (CVertexCamSim3::Operator_Plus; v_Log
+ * :3740-3819, with V^-1 in closed form instead of the reference's QR; the composite rotation through unit quaternions,
+ * the composite scale as s1 + s2), point j += dx[pt_dxoff[j] .. +3). Synchronizes the stream. */
+int spp_sim3_ba_linearize_device(spp_ctx *ctx, int64_t n_obs, const int32_t *d_cam_of, const int32_t *d_pt_of,
+	const double *d_cams, const double *d_intrinsics, const double *d_points, const double *d_measurements,
+	double *d_J0, double *d_J1, double *d_r);
+int spp_sim3_update_device(spp_ctx *ctx, int64_t n_cams, double *d_cams, const int64_t *d_cam_dxoff,
+	int64_t n_points, double *d_points, const int64_t *d_pt_dxoff, const double *d_dx, int64_t n_dx, int apply,
+	double *h_dx_norm2);
+
 /* ---- on-device geometry of stereo bundle adjustment (CEdgeP2SC3D, include/slam/BA_Types.h:705-811) ----
  * Cameras: 6 doubles each [t | axis-angle], world -> left camera, and 6 constant intrinsics each (fx fy cx cy d b, b the
  * baseline: CVertexSCam, BA_Types.h:211-290); points: XYZ; measurements: 3 per observation (u v u_right).
@@ -442,7 +474,8 @@ int spp_ba_intrinsics_update_device(spp_ctx *ctx, int64_t n_intrinsics, double *
  * J_i^T Omega J_i over all edges (f_InitialDamping multiplies it by tau = 1e-3, :151-199); the denominator
  * dx . (alpha dx + eta) of the gain ratio (Aftermath, :204-222). Device inputs, host outputs, deterministic
  * reductions; each call synchronizes the stream. rd / (d0, d1): the edge group of spp_assemble_analyze (chi2: rd 1, 2, 3
- * or 6; max diagonal: (rd, d0, d1) = (2,6,3), (3,3,3), (6,6,6), (3,6,3), the XYZ observations, or (1,6,3), the ranges). */
+ * or 6; max diagonal: (rd, d0, d1) = (2,6,3), (3,3,3), (6,6,6), (3,6,3), the XYZ observations, (1,6,3), the ranges, or (2,7,3), the
+ * projections into Sim(3) cameras). */
 int spp_edge_chi2_device(spp_ctx *ctx, int64_t n_edges, int rd, const double *d_r, const double *d_Omega, double *h_chi2);
 int spp_edge_hessian_maxdiag_device(spp_ctx *ctx, int64_t n_edges, int rd, int d0, int d1, const double *d_J0,
 	const double *d_J1, const double *d_Omega, double *h_max);

@@ -39,7 +39,7 @@ EXPORTS = [
     "spp_se3_linearize_at_device", "spp_se3_xyz_linearize_device", "spp_slam3d_update_device", "spp_rocv_range_linearize_device",
     "spp_rocv_cv_linearize_device", "spp_device_malloc",
     "spp_device_free", "spp_memcpy_h2d", "spp_memcpy_d2h", "spp_memcpy_d2d", "spp_get_phase_ms", "spp_get_dominant_kernel",
-    "spp_microbench_copy", "spp_microbench_mfma_f64", "spp_microbench_ctile", "spp_microbench_update", "spp_block_ordering", "spp_schur_plan_host", "spp_set_profiling", "spp_se2_linearize_device", "spp_se2_update_device", "spp_ba_linearize_device", "spp_ba_stereo_linearize_device", "spp_ba_update_device", "spp_se3_linearize_device", "spp_se3_update_device", "spp_edge_chi2_device", "spp_edge_robust_weights_device", "spp_edge_hessian_maxdiag_device",
+    "spp_microbench_copy", "spp_microbench_mfma_f64", "spp_microbench_ctile", "spp_microbench_update", "spp_block_ordering", "spp_schur_plan_host", "spp_set_profiling", "spp_se2_linearize_device", "spp_se2_update_device", "spp_ba_linearize_device", "spp_ba_stereo_linearize_device", "spp_ba_update_device", "spp_sim3_ba_linearize_device", "spp_sim3_update_device", "spp_se3_linearize_device", "spp_se3_update_device", "spp_edge_chi2_device", "spp_edge_robust_weights_device", "spp_edge_hessian_maxdiag_device",
     "spp_lm_gain_denominator_device", "spp_dense_potrf_upper", "spp_dense_posv",
     "spp_dense_posv_masked", "spp_tile_mask_host", "spp_schur_tile_mask_host", "spp_tail_order_host", "spp_schur_cam_order_host",
     "spp_dense_gemm_tn_sub", "spp_dense_gemm_tn_sub_upper", "spp_dense_front_factor", "spp_version",
@@ -129,6 +129,8 @@ def load_library():
         "spp_ba_linearize_device": (cint, [vp, ctypes.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "spp_ba_stereo_linearize_device": (cint, [vp, ctypes.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "spp_ba_update_device": (cint, [vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, vp, vp, ctypes.c_int64, cint, _c_f64p]),
+        "spp_sim3_ba_linearize_device": (cint, [vp, ctypes.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "spp_sim3_update_device": (cint, [vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, vp, vp, ctypes.c_int64, cint, _c_f64p]),
         "spp_dense_potrf_upper": (cint, [vp, vp, i64, i64]),
         "spp_dense_posv": (cint, [vp, vp, i64, i64, vp]),
         "spp_dense_posv_masked": (cint, [vp, vp, i64, i64, vp, vp, i64]),
@@ -451,6 +453,18 @@ class Context:
         out = ctypes.c_double()
         self._check(self.lib.spp_ba_update_device(self.h, n_cams, d_cams, d_cam_dxoff, n_points, d_points, d_pt_dxoff,
                                                   d_dx, n_dx, 1 if apply else 0, ctypes.byref(out)))
+        return out.value ** 0.5
+
+    def sim3_ba_linearize_device(self, n_obs, d_cam_of, d_pt_of, d_cams, d_intr, d_points, d_meas, d_J0, d_J1, d_r):
+        """CEdgeP2C_XYZ_Sim3_G: cams 7 per camera [t | w | s] in sim(3), intr 5 per camera; J0 2x7, J1 2x3, r 2"""
+        return self._check(self.lib.spp_sim3_ba_linearize_device(self.h, n_obs, d_cam_of, d_pt_of, d_cams, d_intr, d_points,
+                                                                 d_meas, d_J0, d_J1, d_r))
+
+    def sim3_update_device(self, n_cams, d_cams, d_cam_dxoff, n_points, d_points, d_pt_dxoff, d_dx, n_dx, apply=True):
+        """cameras <- Log(Exp(cam) Exp(dx)), points += dx; returns ||dx||"""
+        out = ctypes.c_double()
+        self._check(self.lib.spp_sim3_update_device(self.h, n_cams, d_cams, d_cam_dxoff, n_points, d_points, d_pt_dxoff,
+                                                    d_dx, n_dx, 1 if apply else 0, ctypes.byref(out)))
         return out.value ** 0.5
 
     def ba_intrinsics_linearize_device(self, n_obs, d_cam_of, d_pt_of, d_intr_of, d_cams, d_intr, d_points, d_meas,

@@ -319,7 +319,8 @@ int spp_analyze(spp_ctx *ctx, int64_t nb, const int64_t *col_ptr, const int64_t 
 	st.base[0] = 0;
 	for(int64_t j = 0; j < nb; ++ j) {
 		// 7 = Sim(3) poses (include/slam/Sim3_Types.h); the sparse path works on scalar fronts and only needs a block to
-		// fit one wave in the assembly step (8 x 8 = 64 lanes); the Schur kernels are instantiated for {6,3}, {3,2}, 3, 6
+		// fit one wave in the assembly step (8 x 8 = 64 lanes); the Schur kernels are instantiated for {6,3}, {3,2}, {7,3}
+		// (Sim(3) cameras + XYZ landmarks), 3, 6
 		SPP_REQUIRE(dim[j] > 0 && dim[j] <= 8, SPP_E_BADARG, "block widths must be in 1..8");
 		st.base[j + 1] = st.base[j] + dim[j];
 	}
@@ -1001,6 +1002,26 @@ int spp_ba_update_device(spp_ctx *ctx, int64_t n_cams, double *d_cams, const int
 	   (n_points && (!d_points || !d_pt_dxoff)))
 		return SPP_E_BADARG;
 	return geometry_call(ctx, [&] { store_if(h_dx_norm2, ba_update(ctx, n_cams, d_cams, d_cam_dxoff, n_points, d_points, d_pt_dxoff, d_dx, n_dx, apply != 0)); });
+}
+
+int spp_sim3_ba_linearize_device(spp_ctx *ctx, int64_t n_obs, const int32_t *d_cam_of, const int32_t *d_pt_of,
+	const double *d_cams, const double *d_intrinsics, const double *d_points, const double *d_measurements,
+	double *d_J0, double *d_J1, double *d_r)
+{
+	if(!ctx || n_obs < 0 || !d_cam_of || !d_pt_of || !d_cams || !d_intrinsics || !d_points || !d_measurements ||
+	   !d_J0 || !d_J1 || !d_r)
+		return SPP_E_BADARG;
+	return geometry_call(ctx, [&] { sim3_ba_linearize(ctx, n_obs, d_cam_of, d_pt_of, d_cams, d_intrinsics, d_points, d_measurements, d_J0, d_J1, d_r); });
+}
+
+int spp_sim3_update_device(spp_ctx *ctx, int64_t n_cams, double *d_cams, const int64_t *d_cam_dxoff,
+	int64_t n_points, double *d_points, const int64_t *d_pt_dxoff, const double *d_dx, int64_t n_dx, int apply,
+	double *h_dx_norm2)
+{
+	if(!ctx || n_cams < 0 || n_points < 0 || n_dx < 0 || !d_dx || (n_cams && (!d_cams || !d_cam_dxoff)) ||
+	   (n_points && (!d_points || !d_pt_dxoff)))
+		return SPP_E_BADARG;
+	return geometry_call(ctx, [&] { store_if(h_dx_norm2, sim3_update(ctx, n_cams, d_cams, d_cam_dxoff, n_points, d_points, d_pt_dxoff, d_dx, n_dx, apply != 0)); });
 }
 
 int spp_edge_robust_weights_device(spp_ctx *ctx, int64_t n_edges, int rd, int kind, double scale, double param,

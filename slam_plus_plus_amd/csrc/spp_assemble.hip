@@ -46,6 +46,9 @@ void assemble_get_structure(const spp_ctx *ctx, int64_t *col_ptr, int64_t *row_i
 
 void assemble_set_edge_weights(spp_ctx *ctx, int group, const double *d_w)
 {
+	// (7,3,2): the reference's "first vertex carries the weight twice" rule (BaseTypes_Binary.h:768-848) would attach to the
+	// landmark there (its typelist is (XYZ, CamSim3), the library's order is camera first): refused rather than half right
+	SPP_REQUIRE(!d_w || ctx->assemble->d0[group] != 7, SPP_E_UNSUPPORTED, "robust weights on (7,3,2) edges");
 	ctx->assemble->edge_weights[group] = d_w;
 }
 
@@ -77,7 +80,8 @@ static bool same_shape(const AssemblePlan *ap, int ga, int gb)
 static bool shape_instantiated(int d0, int d1, int rd)
 {
 	return (d0 == 6 && d1 == 3 && rd == 2) || (d0 == 3 && d1 == 3 && rd == 3) || (d0 == 6 && d1 == 6 && rd == 6) ||
-		(d0 == 3 && d1 == 2 && rd == 2) || (d0 == 6 && d1 == 3 && rd == 3) || (d0 == 6 && d1 == 3 && rd == 1);
+		(d0 == 3 && d1 == 2 && rd == 2) || (d0 == 6 && d1 == 3 && rd == 3) || (d0 == 6 && d1 == 3 && rd == 1) ||
+		(d0 == 7 && d1 == 3 && rd == 2);
 }
 
 // a group of unary edges (d1 = 0, no second vertex array): (d0, rd) = (3,3) landmark / 2D pose prior, (6,6) pose prior
@@ -101,7 +105,9 @@ void assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *dim, int n_groups
 			any_unary = true;
 		} else {
 			SPP_REQUIRE(shape_instantiated(g_d0[g], g_d1[g], g_rd[g]), SPP_E_UNSUPPORTED,
-				"edge group (d0, d1, rd) not instantiated: (6,3,2) (3,3,3) (6,6,6) (3,2,2) (6,3,3) (6,3,1)");
+				"edge group (d0, d1, rd) not instantiated: (6,3,2) (3,3,3) (6,6,6) (3,2,2) (6,3,3) (6,3,1) (7,3,2)");
+			// (7,3,2) (Sim(3) cameras) has bodies in the one-group kernels only: it is the one group of its plan
+			SPP_REQUIRE(g_d0[g] != 7 || n_groups == 1, SPP_E_UNSUPPORTED, "a (7,3,2) edge group must be the only group of its plan");
 		}
 		ne += g_ne[g];
 	}
@@ -629,7 +635,8 @@ void vertex_wave_kernel(int64_t nlist, const int32_t *__restrict__ vlist, const 
 // ONE destination, its vertex: an entry of side 0 in that vertex's list at the edge's position, no off-diagonal block
 // (assemble_analyze files it under a column past the last), the body load_unary; its J1 pointer is never read.
 // --------------------------------------------------------------------------------------------------
-enum { SHAPE_632 = 0, SHAPE_333 = 1, SHAPE_666 = 2, SHAPE_322 = 3, SHAPE_633 = 4, SHAPE_631 = 5, SHAPE_U33 = 6, SHAPE_U66 = 7 };
+enum { SHAPE_632 = 0, SHAPE_333 = 1, SHAPE_666 = 2, SHAPE_322 = 3, SHAPE_633 = 4, SHAPE_631 = 5, SHAPE_U33 = 6, SHAPE_U66 = 7,
+	SHAPE_732 = 8 /* one-group plans only: no body in the groups kernels */ };
 
 struct GroupPtrs {
 	const double *J0, *J1, *Om, *r, *w;
@@ -851,6 +858,8 @@ static int shape_id(int d0, int d1, int rd)
 {
 	if(d1 == 0)
 		return d0 == 6 ? SHAPE_U66 : SHAPE_U33;
+	if(d0 == 7)
+		return SHAPE_732;
 	if(d0 == 6)
 		return d1 == 6 ? SHAPE_666 : (rd == 3 ? SHAPE_633 : rd == 1 ? SHAPE_631 : SHAPE_632);
 	return d1 == 3 ? SHAPE_333 : SHAPE_322;
@@ -960,6 +969,7 @@ void assemble_run(spp_ctx *ctx, const double *J0, const double *J1, const double
 	case SHAPE_666: assemble_t<6, 6, 6>(ctx, J0, J1, Om, r, damping, vals, eta); break;
 	case SHAPE_633: assemble_t<6, 3, 3>(ctx, J0, J1, Om, r, damping, vals, eta); break;
 	case SHAPE_631: assemble_t<6, 3, 1>(ctx, J0, J1, Om, r, damping, vals, eta); break;
+	case SHAPE_732: assemble_t<7, 3, 2>(ctx, J0, J1, Om, r, damping, vals, eta); break;
 	default: assemble_t<3, 2, 2>(ctx, J0, J1, Om, r, damping, vals, eta); break;
 	}
 }

@@ -11,7 +11,7 @@ namespace spp {
 // (group g holds the indices gstart[g] .. gstart[g + 1)), every list below holds such indices in ascending GLOBAL position
 // (h_seq of spp_assemble_analyze_groups; the concatenation itself without it). With one group and no h_seq that is the
 // edge index itself: the lists are then those the one-group kernels have always read.
-constexpr int MAX_WIDTH_CLASSES = 3; // distinct vertex widths of the instantiated shapes: 6, 3, 2
+constexpr int MAX_WIDTH_CLASSES = 3; // distinct vertex widths of one plan's shapes (6, 3, 2; a (7,3,2) plan holds 7 and 3 alone)
 
 // The border of a plan of ternary edges (camera, point, intrinsics; spp_assemble3.hip): every destination that touches an
 // intrinsics vertex. Destinations are numbered kind by kind -- H02 blocks (camera, intrinsics), H12 blocks (point,

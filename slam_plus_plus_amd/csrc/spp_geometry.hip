@@ -9,10 +9,11 @@
 //   BA projection            CEdgeP2C3D            ba_linearize_kernel
 //   BA, shared intrinsics    CEdgeP2CI3D (ternary) ba_intrinsics_linearize_kernel
 //   stereo BA projection     CEdgeP2SC3D           ba_stereo_linearize_kernel
+//   Sim(3) BA projection     CEdgeP2C_XYZ_Sim3_G   sim3_ba_linearize_kernel (7-wide cameras: Exp, Log and the update at the end)
 // The two addressings of an edge share one __device__ body (se2_linearize_edge, se3_linearize_edge), the two mono BA
 // edges share ba_p2c_edge. The kernels themselves stay named and non-templated: profiles are read by kernel name.
 // Vertex updates x <- x (+) dx, each returning ||dx||^2: se2_update, se3_update, ba_update (cameras as se3_plus, points),
-// ba_intrinsics_update, slam2d_update, slam3d_update (flat states addressed by scalar offsets).
+// ba_intrinsics_update, sim3_update (cameras as Log(Exp Exp)), slam2d_update, slam3d_update (flat states addressed by scalar offsets).
 // LM scalars: edge_chi2, edge_hessian_maxdiag, lm_gain_denominator; robust (Huber) edge weights.
 //
 // Every scalar is a deterministic two-stage reduction: block_reduce_256 inside each workgroup (one fixed LDS tree, sum or
@@ -784,7 +785,8 @@ double edge_hessian_maxdiag(spp_ctx *ctx, int64_t ne, int rd, int d0, int d1, co
 	else if(rd == 6 && d0 == 6 && d1 == 6) launch_per_item(ctx, edge_maxdiag_kernel<6, 6, 6>, ne, d_J0, d_J1, d_Om, part);
 	else if(rd == 3 && d0 == 6 && d1 == 3) launch_per_item(ctx, edge_maxdiag_kernel<3, 6, 3>, ne, d_J0, d_J1, d_Om, part);
 	else if(rd == 1 && d0 == 6 && d1 == 3) launch_per_item(ctx, edge_maxdiag_kernel<1, 6, 3>, ne, d_J0, d_J1, d_Om, part);
-	else throw Error(SPP_E_UNSUPPORTED, "max Hessian diagonal: edge group must be (2,6,3), (3,3,3), (6,6,6), (3,6,3) or (1,6,3)");
+	else if(rd == 2 && d0 == 7 && d1 == 3) launch_per_item(ctx, edge_maxdiag_kernel<2, 7, 3>, ne, d_J0, d_J1, d_Om, part);
+	else throw Error(SPP_E_UNSUPPORTED, "max Hessian diagonal: edge group must be (2,6,3), (3,3,3), (6,6,6), (3,6,3), (1,6,3) or (2,7,3)");
 	reduce_partials(ctx, ne, true);
 	return fetch_scalar(ctx);
 }
@@ -1140,6 +1142,203 @@ void rocv_cv_linearize(spp_ctx *ctx, int64_t ne, const int64_t *d_off0, const in
 	const double *d_dt, double *d_J0, double *d_J1, double *d_r)
 {
 	launch_per_item(ctx, rocv_cv_linearize_kernel, ne, d_off0, d_off1, d_state, d_dt, d_J0, d_J1, d_r);
+}
+
+// --------------------------------------------------------------------------------------------------
+// Sim(3) bundle adjustment: the edge CEdgeP2C_XYZ_Sim3_G (include/slam/Sim3_Types.h:492-595) between a point CVertexXYZ and
+// a camera CVertexCamSim3, a 7-vector v = [t | w | s] of sim(3) with 5 constant intrinsics. Reference (functional spec):
+//   CSim3Jacobians::t_Exp                include/slam/Sim3SolverBase.h:3829-3905   T = Exp(v) = (R, tau, sigma):
+//       R = exp([w]x), sigma = e^s, tau = V t, V = a I + b [w]x + c [w]x^2
+//   CSim3Jacobians::v_Log                :3740-3819 (the inverse; solves V t = tau by a Householder QR)
+//   CSim3Jacobians::Project_P2C_XYZ      :630-681   x = T^-1 X = e^-s R^T (X - tau), p - c = (fx x0/x2, fy x1/x2),
+//       k = intr[4] / (0.5 fx fy) -- the PRODUCT of the focal lengths --, uv = c + (1 + |p - c|^2 k)(p - c); r = z - uv
+//   its Jacobians                         :1043-1062 forward differences (delta = 1e-9) over Relative_to_Absolute (:435-452),
+//       the POST-multiplicative camera increment T Exp(d), and over an additive point increment
+// With theta = |w| and z = s + i theta the coefficients are a = phi(s), b = Im phi(z) / theta, c = (a - Re phi(z)) / theta^2,
+// phi(z) = (e^z - 1) / z. The reference evaluates them in four cells (|s|, theta against 1e-6), whose closed forms lose
+// digits to cancellation just above the thresholds; here (sim3_abc)
+//   |z|^2 < 1   the Taylor series b = sum p_n / (n + 1)!, c = sum q_n / (n + 1)! with p_n = Im z^n / theta,
+//               q_n = (s^n - Re z^n) / theta^2 by the recurrence p' = s p + s^n - theta^2 q, q' = s q + p (no division)
+//   otherwise   b = (s (E S - a) + E theta^2 C) / |z|^2, c = (a - E (S - s C)) / |z|^2 with E = e^s, S = sin(theta) / theta,
+//               C = (1 - cos(theta)) / theta^2 (S, C by two terms below theta = 1e-4): nothing is divided by theta
+// and a = expm1(s) / s. Jacobians analytic: x (T Exp(d)) = Exp(-d) x = x - dt - dw x x - ds x to first order, so
+//   d x / d d = [-I | [x]x | -x],  d x / d X = e^-s R^T,  J = P d x / d ., P = d uv / d x (2 x 3, as in ba_p2c_edge).
+// P x = 0 identically (the projection does not see the scale of the camera frame): the scale column of J0 is written as
+// exact zeros. Nothing is divided by |p - c|: a point on the optical axis gives finite Jacobians.
+// Log: V^-1 = (1 / a) I - (b / D) [w]x + ((b^2 - A c) / (a D)) [w]x^2, A = a - c theta^2, D = A^2 + theta^2 b^2 = |phi(z)|^2,
+// in closed form ([w]x^3 = -theta^2 [w]x) instead of the reference's QR.
+// One thread per observation: 12 + 3 gathered doubles + 16 B in, 176 B out (J0 2x7, J1 2x3 column-major, r).
+// --------------------------------------------------------------------------------------------------
+constexpr int SIM3_SERIES_TERMS = 24; // n |z|^(n-1) / (n + 1)! < 1e-19 from n = 21 on, |z| < 1
+
+// S = sin(theta) / theta, C = (1 - cos(theta)) / theta^2 and the half-angle pair (cos(theta / 2), sin(theta / 2) / theta)
+__device__ __forceinline__ void sim3_sinc(double th, double *S, double *C, double *ch, double *sh_over)
+{
+	if(th < 1e-4) {
+		const double th2 = th * th;
+		*S = 1.0 - th2 * (1.0 / 6.0);
+		*C = 0.5 - th2 * (1.0 / 24.0);
+		*ch = 1.0 - th2 * 0.125;
+		*sh_over = 0.5 - th2 * (1.0 / 48.0);
+	} else {
+		double sh, c;
+		sincos(0.5 * th, &sh, &c);
+		const double so = sh / th;
+		*S = 2.0 * so * c;
+		*C = 2.0 * so * so;
+		*ch = c;
+		*sh_over = so;
+	}
+}
+
+// a, b, c of V at (s, theta); E = e^s, S and C as above
+__device__ __forceinline__ void sim3_abc(double s, double th, double E, double S, double C, double *a, double *b, double *c)
+{
+	const double th2 = th * th, z2 = s * s + th2;
+	const double av = (s == 0.0) ? 1.0 : expm1(s) / s;
+	*a = av;
+	if(z2 < 1.0) {
+		double p = 0, q = 0, sn = 1, f = 1, bs = 0, cs = 0;
+		for(int n = 0; n < SIM3_SERIES_TERMS; ++ n) {
+			f /= (double)(n + 1);
+			bs += p * f;
+			cs += q * f;
+			const double pn = s * p + sn - th2 * q;
+			q = s * q + p;
+			p = pn;
+			sn *= s;
+		}
+		*b = bs;
+		*c = cs;
+	} else {
+		*b = (s * (E * S - av) + E * th2 * C) / z2;
+		*c = (av - E * (S - s * C)) / z2;
+	}
+}
+
+// T = Exp(v): R row-major, tau, E = e^s; q (may be null) <- the unit quaternion (w, x, y, z) of R with w >= 0
+__device__ __forceinline__ void sim3_exp(const double *v, double *R, double *tau, double *E_out, double *q)
+{
+	const double x = v[3], y = v[4], z = v[5], s = v[6];
+	const double th = sqrt(x * x + y * y + z * z), E = exp(s);
+	double S, C, ch, so, a, b, c;
+	sim3_sinc(th, &S, &C, &ch, &so);
+	sim3_abc(s, th, E, S, C, &a, &b, &c);
+	R[0] = 1 - C * (y * y + z * z); R[1] = C * x * y - S * z;       R[2] = C * x * z + S * y;
+	R[3] = C * x * y + S * z;       R[4] = 1 - C * (x * x + z * z); R[5] = C * y * z - S * x;
+	R[6] = C * x * z - S * y;       R[7] = C * y * z + S * x;       R[8] = 1 - C * (x * x + y * y);
+	const double t0 = v[0], t1 = v[1], t2 = v[2];
+	const double c0 = y * t2 - z * t1, c1 = z * t0 - x * t2, c2 = x * t1 - y * t0;       // w x t
+	const double d0 = y * c2 - z * c1, d1 = z * c0 - x * c2, d2 = x * c1 - y * c0;       // w x (w x t)
+	tau[0] = a * t0 + b * c0 + c * d0;
+	tau[1] = a * t1 + b * c1 + c * d1;
+	tau[2] = a * t2 + b * c2 + c * d2;
+	*E_out = E;
+	if(q) {
+		const double sg = (ch < 0) ? -1.0 : 1.0;
+		q[0] = sg * ch; q[1] = sg * so * x; q[2] = sg * so * y; q[3] = sg * so * z;
+	}
+}
+
+__global__ __launch_bounds__(256)
+void sim3_ba_linearize_kernel(int64_t no, const int32_t *__restrict__ cam_of, const int32_t *__restrict__ pt_of,
+	const double *__restrict__ cams, const double *__restrict__ intr, const double *__restrict__ pts,
+	const double *__restrict__ meas, double *__restrict__ J0, double *__restrict__ J1, double *__restrict__ r)
+{
+	const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if(e >= no)
+		return;
+	const double *cam = cams + 7 * (int64_t)cam_of[e], *in = intr + 5 * (int64_t)cam_of[e], *X = pts + 3 * (int64_t)pt_of[e];
+	double R[9], tau[3], E;
+	sim3_exp(cam, R, tau, &E, nullptr);
+	const double iE = 1.0 / E, y0 = X[0] - tau[0], y1 = X[1] - tau[1], y2 = X[2] - tau[2];
+	const double x0 = iE * (R[0] * y0 + R[3] * y1 + R[6] * y2); // e^-s R^T (X - tau)
+	const double x1 = iE * (R[1] * y0 + R[4] * y1 + R[7] * y2);
+	const double x2 = iE * (R[2] * y0 + R[5] * y1 + R[8] * y2);
+	const double fx = in[0], fy = in[1], k = in[4] / (0.5 * (fx * fy));
+	const double iz = 1.0 / x2, d0 = fx * x0 * iz, d1 = fy * x1 * iz, r2 = d0 * d0 + d1 * d1, g = 1.0 + r2 * k;
+	r[2 * e] = meas[2 * e] - (in[2] + g * d0);
+	r[2 * e + 1] = meas[2 * e + 1] - (in[3] + g * d1);
+	// P = d uv / d x (2 x 3) = ((g) I + 2 k d d^T) [fx/z 0 -fx x0/z^2; 0 fy/z -fy x1/z^2]
+	const double D00 = g + 2 * k * d0 * d0, D01 = 2 * k * d0 * d1, D11 = g + 2 * k * d1 * d1;
+	const double a0 = fx * iz, a2 = -fx * x0 * iz * iz, b1 = fy * iz, b2 = -fy * x1 * iz * iz;
+	const double P[6] = {D00 * a0, D01 * b1, D00 * a2 + D01 * b2,   // row 0
+	                     D01 * a0, D11 * b1, D01 * a2 + D11 * b2};  // row 1
+	double *a = J0 + 14 * e, *b = J1 + 6 * e;
+#pragma unroll
+	for(int i = 0; i < 2; ++ i) {
+		const double p0 = P[3 * i], p1 = P[3 * i + 1], p2 = P[3 * i + 2];
+		a[i] = -p0; a[2 + i] = -p1; a[4 + i] = -p2;                    // d / d dt = -P
+		a[6 + i] = p1 * x2 - p2 * x1;                                  // d / d dw = P [x]x
+		a[8 + i] = p2 * x0 - p0 * x2;
+		a[10 + i] = p0 * x1 - p1 * x0;
+		a[12 + i] = 0.0;                                               // d / d ds = -P x = 0
+#pragma unroll
+		for(int j = 0; j < 3; ++ j)                                    // d / d X = P e^-s R^T
+			b[2 * j + i] = iE * (p0 * R[3 * j] + p1 * R[3 * j + 1] + p2 * R[3 * j + 2]);
+	}
+}
+
+// camera <- Log(Exp(camera) Exp(d)) (CVertexCamSim3::Operator_Plus = Relative_to_Absolute, Sim3SolverBase.h:435-452):
+// (R1, tau1, E1)(R2, tau2, E2) = (R1 R2, tau1 + E1 R1 tau2, E1 E2), rotations composed as unit quaternions, s = s1 + s2
+__global__ __launch_bounds__(256)
+void sim3_update_cams_kernel(int64_t nc, double *__restrict__ cams, const int64_t *__restrict__ dxoff, const double *__restrict__ dx)
+{
+	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if(i >= nc)
+		return;
+	double *cam = cams + 7 * i;
+	const double *d = dx + dxoff[i];
+	double v1[7], v2[7];
+#pragma unroll
+	for(int j = 0; j < 7; ++ j) {
+		v1[j] = cam[j];
+		v2[j] = d[j];
+	}
+	double R1[9], R2[9], t1[3], t2[3], E1, E2, q1[4], q2[4], q[4], w[3];
+	sim3_exp(v1, R1, t1, &E1, q1);
+	sim3_exp(v2, R2, t2, &E2, q2);
+	const double tau0 = t1[0] + E1 * (R1[0] * t2[0] + R1[1] * t2[1] + R1[2] * t2[2]);
+	const double tau1 = t1[1] + E1 * (R1[3] * t2[0] + R1[4] * t2[1] + R1[5] * t2[2]);
+	const double tau2 = t1[2] + E1 * (R1[6] * t2[0] + R1[7] * t2[1] + R1[8] * t2[2]);
+	quat_mul(q1, q2, q);
+	quat_to_aa(q[0], q[1], q[2], q[3], w);
+	const double s = v1[6] + v2[6];
+	const double x = w[0], y = w[1], z = w[2], th2 = x * x + y * y + z * z, th = sqrt(th2);
+	double S, C, ch, so, a, b, c;
+	sim3_sinc(th, &S, &C, &ch, &so);
+	sim3_abc(s, th, exp(s), S, C, &a, &b, &c);
+	const double A = a - c * th2, D = A * A + th2 * b * b;
+	const double al = 1.0 / a, be = -b / D, ga = (b * b - A * c) / (a * D);
+	const double c0 = y * tau2 - z * tau1, c1 = z * tau0 - x * tau2, c2 = x * tau1 - y * tau0;   // w x tau
+	const double e0 = y * c2 - z * c1, e1 = z * c0 - x * c2, e2 = x * c1 - y * c0;               // w x (w x tau)
+	cam[0] = al * tau0 + be * c0 + ga * e0;
+	cam[1] = al * tau1 + be * c1 + ga * e1;
+	cam[2] = al * tau2 + be * c2 + ga * e2;
+	cam[3] = x; cam[4] = y; cam[5] = z;
+	cam[6] = s;
+}
+
+void sim3_ba_linearize(spp_ctx *ctx, int64_t no, const int32_t *d_cam_of, const int32_t *d_pt_of, const double *d_cams,
+	const double *d_intr, const double *d_pts, const double *d_meas, double *d_J0, double *d_J1, double *d_r)
+{
+	launch_per_item(ctx, sim3_ba_linearize_kernel, no, d_cam_of, d_pt_of, d_cams, d_intr, d_pts, d_meas, d_J0, d_J1, d_r);
+}
+
+// (the shape of ba_update: the norm over all of dx, cameras through Log(Exp Exp), points as plain sums)
+double sim3_update(spp_ctx *ctx, int64_t nc, double *d_cams, const int64_t *d_cam_dxoff, int64_t np, double *d_pts,
+	const int64_t *d_pt_dxoff, const double *d_dx, int64_t n_dx, bool apply)
+{
+	enqueue_norm2(ctx, n_dx, d_dx);
+	if(apply) {
+		launch_per_item(ctx, sim3_update_cams_kernel, nc, d_cams, d_cam_dxoff, d_dx);
+		launch_per_item(ctx, ba_update_points_kernel, np, d_pts, d_pt_dxoff, d_dx);
+	}
+	if(n_dx)
+		return fetch_scalar(ctx);
+	SPP_HIP_CHECK(hipGetLastError());
+	SPP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+	return 0;
 }
 
 } // namespace spp

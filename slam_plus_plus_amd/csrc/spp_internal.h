@@ -435,6 +435,10 @@ void ba_intrinsics_linearize(spp_ctx *ctx, int64_t no, const int32_t *d_cam_of, 
 double ba_intrinsics_update(spp_ctx *ctx, int64_t ni, double *d_intr, const int64_t *d_intr_dxoff, const double *d_dx, bool apply);
 double ba_update(spp_ctx *ctx, int64_t nc, double *d_cams, const int64_t *d_cam_dxoff, int64_t np, double *d_pts,
 	const int64_t *d_pt_dxoff, const double *d_dx, int64_t n_dx, bool apply);
+void sim3_ba_linearize(spp_ctx *ctx, int64_t no, const int32_t *d_cam_of, const int32_t *d_pt_of, const double *d_cams,
+	const double *d_intr, const double *d_pts, const double *d_meas, double *d_J0, double *d_J1, double *d_r);
+double sim3_update(spp_ctx *ctx, int64_t nc, double *d_cams, const int64_t *d_cam_dxoff, int64_t np, double *d_pts,
+	const int64_t *d_pt_dxoff, const double *d_dx, int64_t n_dx, bool apply);
 
 // ---- spp_symbolic.cpp ----
 void min_degree_order(int64_t nb, const int64_t *col_ptr, const int64_t *row_idx, std::vector<int64_t> &order);

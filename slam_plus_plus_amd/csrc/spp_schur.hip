@@ -1533,6 +1533,7 @@ void schur_form(spp_ctx *ctx, const double *d_vals, const double *d_rhs, double 
 	else if(dp == 3 && dl == 2) schur_form_t<3, 2>(ctx, d_vals, d_rhs, d_S_rhs, one_call);
 	else if(dp == 3 && dl == 3) schur_form_t<3, 3>(ctx, d_vals, d_rhs, d_S_rhs, one_call);
 	else if(dp == 6 && dl == 6) schur_form_t<6, 6>(ctx, d_vals, d_rhs, d_S_rhs, one_call);
+	else if(dp == 7 && dl == 3) schur_form_t<7, 3>(ctx, d_vals, d_rhs, d_S_rhs, one_call);
 	else throw Error(SPP_E_UNSUPPORTED, "Schur kernels: block widths not instantiated");
 }
 
@@ -1543,6 +1544,7 @@ int schur_finish(spp_ctx *ctx, const double *d_vals, double *d_S_rhs, double *d_
 	if(dp == 3 && dl == 2) return schur_finish_t<3, 2>(ctx, d_vals, d_S_rhs, d_rhs);
 	if(dp == 3 && dl == 3) return schur_finish_t<3, 3>(ctx, d_vals, d_S_rhs, d_rhs);
 	if(dp == 6 && dl == 6) return schur_finish_t<6, 6>(ctx, d_vals, d_S_rhs, d_rhs);
+	if(dp == 7 && dl == 3) return schur_finish_t<7, 3>(ctx, d_vals, d_S_rhs, d_rhs);
 	throw Error(SPP_E_UNSUPPORTED, "Schur kernels: block widths not instantiated");
 }
 

@@ -51,8 +51,8 @@ bool schur_applicable(const Structure &st, int *dp_out, int *dl_out)
 	if(d_a < 0 || d_b < 0)
 		return false;
 	int dp = std::max(d_a, d_b), dl = std::min(d_a, d_b);
-	if(!((dp == 6 && dl == 3) || (dp == 3 && dl == 2)))
-		return false; // kernel instantiations (BA: SE3 pose + XYZ; 2D SLAM: SE2 pose + XY)
+	if(!((dp == 6 && dl == 3) || (dp == 3 && dl == 2) || (dp == 7 && dl == 3)))
+		return false; // kernel instantiations (BA: SE3 pose + XYZ; 2D SLAM: SE2 pose + XY; Sim(3) BA: Sim3 camera + XYZ)
 	int64_t n_lm = 0;
 	for(int64_t j = 0; j < st.nb; ++ j) {
 		if(st.dim[j] == dl)

@@ -388,11 +388,18 @@ def problem_from_graph(path):
     BA files use the reference's VERTEX_CAM convention (camera-to-world in the file); a file with EDGE_PROJECT_P2SC /
     EDGE_P2SC lines goes to load_stereo_graph and comes back as one (6, 3, 3) group (stereo_linearize). A file with
     LANDMARK3:XYZ / EDGE_SE3_XYZ lines goes to load_slam3d_graph and comes back as the PAIR of its edge groups
-    (slam3d_linearize); a file with ROCV: lines goes to load_rocv_graph and comes back as its THREE groups (rocv_linearize)."""
+    (slam3d_linearize); a file with ROCV: lines goes to load_rocv_graph and comes back as its THREE groups (rocv_linearize);
+    a file with VERTEX_CAM:SIM3 lines goes to load_sim3_graph and comes back as one (7, 3, 2) group (sim3_ba_linearize)."""
     from scipy.spatial.transform import Rotation
     with open(path) as f:
         toks = {ln.split()[0].upper() for ln in f if ln.split()}
     has_lm3 = bool(toks & _LM3_XYZ_EDGE)
+    if _SIM3_CAM_TOKEN in toks:  # Sim(3) BA, told by its camera token (the edge token is the mono BA's): ONE (7, 3, 2) group
+        g = load_sim3_graph(path)
+        prob = sim3_ba_linearize(g["cams"], g["intr"], g["points"], g["obs"], g["cam_id"], g["pt_id"], g["info"])
+        prob["nc"], prob["npts"] = g["cam_id"].size, g["pt_id"].size
+        return prob, "Sim(3) BA graph file (%d cameras, %d points, %d observations)" % (
+            g["cam_id"].size, g["pt_id"].size, g["obs"].shape[0])
     if toks & _ROCV_TOKENS:  # range-only constant velocity: THREE edge groups, the last one unary (nonlinear.CRocv)
         s = load_rocv_graph(path)
         groups = rocv_linearize(s["dim"], s["state"], s["cv"], s["cv_info"], s["rng"], s["rng_info"], s["pri"], s["pri_info"])
@@ -1374,3 +1381,251 @@ def rocv_linearize(dim, state, cv, cv_info, rng, rng_info, pri, pri_info):
                     J1=np.zeros((p, 0)), Om=np.asarray(pri_info, dtype=np.float64).reshape(p, 9), r=np.zeros((p, 3)),
                     unary_vertex=-1, damping=0.0)
     return g_cv, g_rng, g_pri
+
+
+# --------------------------------------------------------------------------------------------------
+# Sim(3) bundle adjustment: cameras CVertexCamSim3 (7: v = [t | w | s] in sim(3)), points CVertexXYZ (3), one binary edge
+# CEdgeP2C_XYZ_Sim3_G per observation (include/slam/Sim3_Types.h:178-238, 492-595; CSim3Jacobians, Sim3SolverBase.h).
+# The float64 mirror of the device geometry (spp_geometry.hip, the Sim(3) part): the same cells, the same formulas.
+# --------------------------------------------------------------------------------------------------
+_SIM3_CAM_TOKEN = "VERTEX_CAM:SIM3"                      # include/ba_parameter_acra/Sim3_ParsePrimitives.h:146
+_SIM3_EDGE = {"EDGE_PROJECT_P2MC", "EDGE_P2MC"}          # what BAOptimizer.cpp:918-983 writes / ParsePrimitives.h
+SIM3_SERIES_TERMS = 24
+SIM3_SERIES_Z2 = 1.0      # s^2 + theta^2 below which a, b, c come from the Taylor series
+SIM3_SINC_THETA = 1e-4    # theta below which sin(theta) / theta and (1 - cos(theta)) / theta^2 come from two terms
+
+
+def _sim3_sinc(th):
+    """S = sin(th) / th, C = (1 - cos(th)) / th^2, cos(th / 2), sin(th / 2) / th"""
+    th = np.asarray(th, dtype=np.float64)
+    small = th < SIM3_SINC_THETA
+    t = np.where(small, 1.0, th)
+    sh, ch = np.sin(0.5 * t), np.cos(0.5 * t)
+    so = sh / t
+    th2 = th * th
+    return (np.where(small, 1.0 - th2 * (1.0 / 6.0), 2.0 * so * ch), np.where(small, 0.5 - th2 * (1.0 / 24.0), 2.0 * so * so),
+            np.where(small, 1.0 - th2 * 0.125, ch), np.where(small, 0.5 - th2 * (1.0 / 48.0), so))
+
+
+def sim3_abc(s, th):
+    """a, b, c of V = a I + b [w]x + c [w]x^2 (t_Exp, Sim3SolverBase.h:3867-3898) at scale logarithm s and angle th = |w|:
+    a = phi(s), b = Im phi(z) / th, c = (a - Re phi(z)) / th^2, phi(z) = (e^z - 1) / z, z = s + i th. Taylor series for
+    |z|^2 < 1 (no division), closed form beyond; returns (a, b, c, cell) with cell 0 = series, 1 = closed form."""
+    s, th = np.broadcast_arrays(np.asarray(s, dtype=np.float64), np.asarray(th, dtype=np.float64))
+    th2 = th * th
+    z2 = s * s + th2
+    a = np.where(s == 0.0, 1.0, np.expm1(s) / np.where(s == 0.0, 1.0, s))
+    p, q, sn, f = np.zeros_like(z2), np.zeros_like(z2), np.ones_like(z2), 1.0
+    bs, cs = np.zeros_like(z2), np.zeros_like(z2)
+    with np.errstate(over="ignore", invalid="ignore"):     # (the lanes of the other cell may overflow: not used)
+        for n in range(SIM3_SERIES_TERMS):
+            f = f / (n + 1)
+            bs = bs + p * f
+            cs = cs + q * f
+            p, q, sn = s * p + sn - th2 * q, s * q + p, sn * s
+        E = np.exp(s)
+        S, C, _, _ = _sim3_sinc(th)
+        zz = np.where(z2 == 0.0, 1.0, z2)
+        bc = (s * (E * S - a) + E * th2 * C) / zz
+        cc = (a - E * (S - s * C)) / zz
+    series = z2 < SIM3_SERIES_Z2
+    return a, np.where(series, bs, bc), np.where(series, cs, cc), np.where(series, 0, 1)
+
+
+def _cross(a, b):
+    return np.stack([a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2],
+                     a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], axis=1)
+
+
+def sim3_exp(v):
+    """T = Exp(v), v (n, 7) [t | w | s]: R (n, 3, 3), tau (n, 3), E = e^s (n,), q (n, 4) the unit quaternion (w, x, y, z)
+    of R with w >= 0 (CSim3Jacobians::t_Exp, Sim3SolverBase.h:3829-3905)"""
+    v = np.asarray(v, dtype=np.float64).reshape(-1, 7)
+    t, w, s = v[:, :3], v[:, 3:6], v[:, 6]
+    th = np.sqrt((w * w).sum(axis=1))
+    S, C, ch, so = _sim3_sinc(th)
+    a, b, c, _ = sim3_abc(s, th)
+    K = _hat(w)
+    R = np.eye(3)[None] + S[:, None, None] * K + C[:, None, None] * np.einsum("eij,ejk->eik", K, K)
+    wt = _cross(w, t)
+    tau = a[:, None] * t + b[:, None] * wt + c[:, None] * _cross(w, wt)
+    sg = np.where(ch < 0, -1.0, 1.0)
+    q = np.concatenate([(sg * ch)[:, None], (sg * so)[:, None] * w], axis=1)
+    return R, tau, np.exp(s), q
+
+
+def _quat_mul(p, q):
+    return np.stack([p[:, 0] * q[:, 0] - p[:, 1] * q[:, 1] - p[:, 2] * q[:, 2] - p[:, 3] * q[:, 3],
+                     p[:, 0] * q[:, 1] + p[:, 1] * q[:, 0] + p[:, 2] * q[:, 3] - p[:, 3] * q[:, 2],
+                     p[:, 0] * q[:, 2] - p[:, 1] * q[:, 3] + p[:, 2] * q[:, 0] + p[:, 3] * q[:, 1],
+                     p[:, 0] * q[:, 3] + p[:, 1] * q[:, 2] - p[:, 2] * q[:, 1] + p[:, 3] * q[:, 0]], axis=1)
+
+
+def _quat_to_aa(q):
+    q = np.where(q[:, :1] < 0, -q, q)
+    vn = np.sqrt((q[:, 1:] ** 2).sum(axis=1))
+    scale = np.where(vn < 1e-12, 2.0, 2.0 * np.arctan2(vn, q[:, 0]) / np.where(vn < 1e-12, 1.0, vn))
+    return q[:, 1:] * scale[:, None]
+
+
+def sim3_log(q, tau, s):
+    """the inverse of sim3_exp (v_Log, Sim3SolverBase.h:3740-3819): q (n, 4) unit quaternions (w, x, y, z), tau (n, 3), s (n,)
+    the LOGARITHM of the scale. V^-1 in closed form: (1 / a) I - (b / D) [w]x + ((b^2 - A c) / (a D)) [w]x^2, A = a - c th^2,
+    D = A^2 + th^2 b^2."""
+    w = _quat_to_aa(np.asarray(q, dtype=np.float64))
+    th2 = (w * w).sum(axis=1)
+    a, b, c, _ = sim3_abc(s, np.sqrt(th2))
+    A = a - c * th2
+    D = A * A + th2 * b * b
+    wt = _cross(w, tau)
+    t = (1.0 / a)[:, None] * tau + (-b / D)[:, None] * wt + ((b * b - A * c) / (a * D))[:, None] * _cross(w, wt)
+    return np.concatenate([t, w, np.asarray(s, dtype=np.float64)[:, None]], axis=1)
+
+
+def sim3_from_trs(trs):
+    """the parser's conversion (Sim3_ParsePrimitives.h:259-263): a file pose [translation | axis-angle | PLAIN scale]
+    (TSim3::from_tRs_vector) -> its logarithm, the 7-vector the vertex holds"""
+    trs = np.asarray(trs, dtype=np.float64).reshape(-1, 7)
+    w = trs[:, 3:6]
+    th = np.sqrt((w * w).sum(axis=1))
+    _, _, ch, so = _sim3_sinc(th)
+    sg = np.where(ch < 0, -1.0, 1.0)
+    q = np.concatenate([(sg * ch)[:, None], (sg * so)[:, None] * w], axis=1)
+    return sim3_log(q, trs[:, :3], np.log(trs[:, 6]))
+
+
+def sim3_to_trs(cams):
+    """a vertex state -> the file's pose [translation | axis-angle | plain scale] (Exp; the axis-angle is the state's own)"""
+    cams = np.asarray(cams, dtype=np.float64).reshape(-1, 7)
+    _, tau, E, _ = sim3_exp(cams)
+    return np.concatenate([tau, cams[:, 3:6], E[:, None]], axis=1)
+
+
+def sim3_expectation(cam, intr, X):
+    """CSim3Jacobians::Project_P2C_XYZ (Sim3SolverBase.h:630-681), one row per observation: x = e^-s R^T (X - tau),
+    k = intr[4] / (0.5 fx fy), uv = c + (1 + |p - c|^2 k)(p - c). Returns (uv, x, R, 1 / E)."""
+    R, tau, E, _ = sim3_exp(cam)
+    iE = 1.0 / E
+    x = iE[:, None] * np.einsum("eji,ej->ei", R, X - tau)
+    fx, fy = intr[:, 0], intr[:, 1]
+    iz = 1.0 / x[:, 2]
+    d = np.stack([fx * x[:, 0] * iz, fy * x[:, 1] * iz], axis=1)
+    g = 1.0 + (d ** 2).sum(axis=1) * (intr[:, 4] / (0.5 * (fx * fy)))
+    return intr[:, 2:4] + g[:, None] * d, x, R, iE
+
+
+def sim3_ba_linearize(cams, intr, points, obs, cam_id=None, pt_id=None, info=None):
+    """Hot-path inputs (synth.Problem, one (7, 3, 2) group, camera first) of a Sim(3) bundle adjustment: cams (nc, 7)
+    [t | w | s], intr (nc, 5) fx fy cx cy d (d the internal value), points (np, 3), obs (no, 4) camera index, point index,
+    u v. Jacobians analytic w.r.t. the post-multiplicative camera increment T Exp(delta) and the additive point increment:
+    d x / d delta = [-I | [x]x | -x] (the scale column of J0 is identically zero), d x / d X = e^-s R^T."""
+    from .synth import Problem
+    cams, intr, points, obs = (np.asarray(a, dtype=np.float64) for a in (cams, intr, points, obs))
+    nc, npts, no = cams.shape[0], points.shape[0], obs.shape[0]
+    co, po = obs[:, 0].astype(np.int64), obs[:, 1].astype(np.int64)
+    cam_id = np.arange(nc) if cam_id is None else np.asarray(cam_id)
+    pt_id = nc + np.arange(npts) if pt_id is None else np.asarray(pt_id)
+    itr = intr[co]
+    uv, x, R, iE = sim3_expectation(cams[co], itr, points[po])
+    fx, fy = itr[:, 0], itr[:, 1]
+    k = itr[:, 4] / (0.5 * (fx * fy))
+    iz = 1.0 / x[:, 2]
+    d = np.stack([fx * x[:, 0] * iz, fy * x[:, 1] * iz], axis=1)
+    g = 1.0 + (d ** 2).sum(axis=1) * k
+    Jd = np.zeros((no, 2, 3))
+    Jd[:, 0, 0], Jd[:, 0, 2] = fx * iz, -fx * x[:, 0] * iz * iz
+    Jd[:, 1, 1], Jd[:, 1, 2] = fy * iz, -fy * x[:, 1] * iz * iz
+    D = g[:, None, None] * np.eye(2)[None] + 2 * k[:, None, None] * np.einsum("ei,ej->eij", d, d)
+    P = np.einsum("eij,ejk->eik", D, Jd)
+    J0 = np.concatenate([-P, np.einsum("eij,ejk->eik", P, _hat(x)), np.zeros((no, 2, 1))], axis=2)
+    J1 = iE[:, None, None] * np.einsum("eij,ekj->eik", P, R)
+    dim = np.empty(nc + npts, dtype=np.int32)
+    dim[cam_id] = 7
+    dim[pt_id] = 3
+    Om = np.tile(np.eye(2).ravel(), (no, 1)) if info is None else np.ascontiguousarray(info, dtype=np.float64).reshape(no, 4)
+    return Problem(name="sim3_ba", dim=dim, v0=cam_id[co], v1=pt_id[po], d0=7, d1=3, rd=2,
+                   J0=np.ascontiguousarray(J0.transpose(0, 2, 1)).reshape(no, 14),
+                   J1=np.ascontiguousarray(J1.transpose(0, 2, 1)).reshape(no, 6),
+                   Om=Om, r=obs[:, 2:4] - uv, unary_vertex=-1, damping=0.0)
+
+
+def sim3_plus(cams, dx):
+    """camera (+) dx of CVertexCamSim3::Operator_Plus: Log(Exp(cam) Exp(dx)) (Relative_to_Absolute, Sim3SolverBase.h:435-452)"""
+    cams, dx = np.asarray(cams, dtype=np.float64).reshape(-1, 7), np.asarray(dx, dtype=np.float64).reshape(-1, 7)
+    R1, t1, E1, q1 = sim3_exp(cams)
+    _, t2, _, q2 = sim3_exp(dx)
+    tau = t1 + E1[:, None] * np.einsum("eij,ej->ei", R1, t2)
+    return sim3_log(_quat_mul(q1, q2), tau, cams[:, 6] + dx[:, 6])
+
+
+def load_sim3_graph(path):
+    """A Sim(3) BA graph as the reference's parser reads it (include/ba_parameter_acra/Sim3_ParsePrimitives.h:135-276):
+    `VERTEX_CAM:SIM3 id tx ty tz ax ay az s fx fy cx cy d` holds the pose as translation, axis-angle and PLAIN scale
+    (from_tRs_vector); the vertex stores its logarithm (sim3_from_trs) and d times 0.5 (fx + fy) (:125) -- the projection
+    later divides by 0.5 fx fy, as written there. `VERTEX_XYZ id x y z`; `EDGE_PROJECT_P2MC point-id cam-id u v` + the three
+    upper-triangular values of the information (BAOptimizer.cpp:918-983). Vertex lines may come after the edges that name
+    them. Returns dict(cams (nc, 7), cams_trs (nc, 7) the file's numbers, intr (nc, 5), points, obs (no, 4) camera INDEX,
+    point INDEX, u v, info (no, 2, 2), cam_id, pt_id: the vertex ids in file order)."""
+    cams, pts, edges, info = [], [], [], []
+    with open(path) as f:
+        for ln in f:
+            t = ln.split()
+            if not t or t[0].startswith("#") or t[0].startswith("%"):
+                continue
+            tok, a = t[0].upper(), t[1:]
+            if tok == _SIM3_CAM_TOKEN and len(a) >= 13:
+                cams.append([float(x) for x in a[:13]])
+            elif tok == "VERTEX_XYZ" and len(a) >= 4:
+                pts.append([float(x) for x in a[:4]])
+            elif tok in _SIM3_EDGE and len(a) >= 7:
+                edges.append([float(x) for x in a[:4]])
+                info.append(_upper_to_full([float(x) for x in a[4:7]], 2))
+    cams_f, pts_f, e = np.array(cams).reshape(-1, 13), np.array(pts).reshape(-1, 4), np.array(edges).reshape(-1, 4)
+    cam_id, pt_id = cams_f[:, 0].astype(np.int64), pts_f[:, 0].astype(np.int64)
+    nv = int(max(cam_id.max(initial=-1), pt_id.max(initial=-1), e[:, :2].max(initial=-1))) + 1
+    cam_index, pt_index = np.full(nv, -1, dtype=np.int64), np.full(nv, -1, dtype=np.int64)
+    cam_index[cam_id] = np.arange(cam_id.size)
+    pt_index[pt_id] = np.arange(pt_id.size)
+    ci, pi = cam_index[e[:, 1].astype(np.int64)], pt_index[e[:, 0].astype(np.int64)]
+    if (ci < 0).any() or (pi < 0).any():
+        raise ValueError("an EDGE_PROJECT_P2MC line names a vertex that is no VERTEX_CAM:SIM3 / VERTEX_XYZ: %s" % path)
+    intr = cams_f[:, 8:13].copy()
+    intr[:, 4] *= 0.5 * (intr[:, 0] + intr[:, 1])
+    return dict(cams=sim3_from_trs(cams_f[:, 1:8]), cams_trs=cams_f[:, 1:8].copy(), intr=intr, points=pts_f[:, 1:4].copy(),
+                obs=np.concatenate([ci[:, None].astype(np.float64), pi[:, None].astype(np.float64), e[:, 2:4]], axis=1),
+                info=np.array(info).reshape(-1, 2, 2), cam_id=cam_id, pt_id=pt_id)
+
+
+def sim3_lines(cams_trs, intr, points, obs, info=None, cam_id=None, pt_id=None):
+    """the lines of save_sim3_graph: every vertex line in front of the first edge that names it (else in id order behind
+    the edges), the edges as given, everything with %.17g"""
+    cams_trs, intr, points, obs = (np.asarray(a, dtype=np.float64) for a in (cams_trs, intr, points, obs))
+    nc, npts = cams_trs.shape[0], points.shape[0]
+    cam_id = np.arange(nc) if cam_id is None else np.asarray(cam_id)
+    pt_id = nc + np.arange(npts) if pt_id is None else np.asarray(pt_id)
+    intr_f = intr.copy()
+    intr_f[:, 4] /= 0.5 * (intr[:, 0] + intr[:, 1])   # the file holds d per pixel of radius, the reader scales it back
+    cam_line = lambda c: "VERTEX_CAM:SIM3 %d " % cam_id[c] + " ".join("%.17g" % x for x in (*cams_trs[c], *intr_f[c]))
+    pt_line = lambda p: "VERTEX_XYZ %d " % pt_id[p] + " ".join("%.17g" % x for x in points[p])
+    lines, cam_done, pt_done = [], np.zeros(nc, dtype=bool), np.zeros(npts, dtype=bool)
+    iu = np.triu_indices(2)
+    for k, o in enumerate(obs):
+        c, p = int(o[0]), int(o[1])
+        if not cam_done[c]:
+            lines.append(cam_line(c))
+            cam_done[c] = True
+        if not pt_done[p]:
+            lines.append(pt_line(p))
+            pt_done[p] = True
+        m = np.eye(2) if info is None else np.asarray(info[k])
+        lines.append("EDGE_PROJECT_P2MC %d %d " % (pt_id[p], cam_id[c]) + " ".join("%.17g" % x for x in (*o[2:4], *m[iu])))
+    rest = [(cam_id[c], cam_line(c)) for c in np.flatnonzero(~cam_done)] + [(pt_id[p], pt_line(p)) for p in np.flatnonzero(~pt_done)]
+    return lines + [ln for _, ln in sorted(rest)]
+
+
+def save_sim3_graph(path, cams_trs, intr, points, obs, info=None, cam_id=None, pt_id=None):
+    """Sim(3) BA graph in the reference's text format (tokens: load_sim3_graph). cams_trs (nc, 7): the poses as the FILE
+    holds them, [translation | axis-angle | plain scale] (sim3_to_trs of a vertex state); intr (nc, 5) with d the internal
+    value (the file gets d / (0.5 (fx + fy))); obs (no, 4) camera index, point index, u v (written point id first)."""
+    with open(path, "w") as f:
+        f.write("\n".join(sim3_lines(cams_trs, intr, points, obs, info, cam_id, pt_id)) + "\n")

@@ -20,7 +20,7 @@ import numpy as np
 from . import api
 from .formats import (se2_linearize, se3_linearize, se3_plus, ba_linearize, slam2d_linearize, slam2d_offsets,
                       slam3d_linearize, slam3d_offsets, slam3d_plus, stereo_linearize, bai_linearize, bai_intrinsics_plus,
-                      bai_ids, BAI_INTR_WIDTH, rocv_linearize)
+                      bai_ids, BAI_INTR_WIDTH, rocv_linearize, sim3_ba_linearize, sim3_plus)
 
 
 class CPoseGraph2D:
@@ -498,15 +498,17 @@ class _ResidentBAPath(_Path):
     spp_factor_solve_device, spp_ba_update_device, chi2 / alpha0 / gain-ratio reductions. A subclass overrides what its
     edge differs in: rd / n_ids, _analyze_structure, _dx_offsets, _begin_extra, linearize, _assemble, max_hessian_diag, and
     extends save / restore / apply / finish for a further vertex set."""
-    rd = 2                                  # residual dimension: the edge group is (6, 3, rd)
+    rd = 2                                  # residual dimension: the edge group is (cam_w, 3, rd)
+    cam_w = 6                               # width of a camera vertex (7: _ResidentSim3BAPath)
     n_ids = 2                               # obs starts with that many vertex ids (cam pt); the measurement follows
 
     def _analyze_structure(self, prob):
-        return self.ctx.assemble_analyze(prob.dim, prob.v0, prob.v1, 6, 3, self.rd, prob.unary_vertex)
+        return self.ctx.assemble_analyze(prob.dim, prob.v0, prob.v1, self.cam_w, 3, self.rd, prob.unary_vertex)
 
     def _dx_offsets(self, s):
         """scalar offsets of the cameras and of the points in the solution vector: cameras first"""
-        return 6 * np.arange(self.nc, dtype=np.int64), 6 * self.nc + 3 * np.arange(self.np, dtype=np.int64)
+        w = self.cam_w
+        return w * np.arange(self.nc, dtype=np.int64), w * self.nc + 3 * np.arange(self.np, dtype=np.int64)
 
     def _begin_extra(self, s, up):
         """device arrays of a further vertex set"""
@@ -523,11 +525,11 @@ class _ResidentBAPath(_Path):
         self.d_meas, self.d_Om = up(s.obs[:, self.n_ids:self.n_ids + rd]), up(prob.Om)
         cam_off, pt_off = self._dx_offsets(s)
         self.d_cam_off, self.d_pt_off = up(cam_off), up(pt_off)
-        self.d_J0, self.d_J1 = api.DeviceArray(ctx, 6 * rd * self.no), api.DeviceArray(ctx, 3 * rd * self.no)
+        self.d_J0, self.d_J1 = api.DeviceArray(ctx, self.cam_w * rd * self.no), api.DeviceArray(ctx, 3 * rd * self.no)
         self.d_r = api.DeviceArray(ctx, rd * self.no)
         self.d_vals, self.d_eta, self.d_dx = (api.DeviceArray(ctx, self.st.nvals), api.DeviceArray(ctx, self.st.n),
                                               api.DeviceArray(ctx, self.st.n))
-        self.s_cams, self.s_pts = api.DeviceArray(ctx, 6 * self.nc), api.DeviceArray(ctx, 3 * self.np)
+        self.s_cams, self.s_pts = api.DeviceArray(ctx, self.cam_w * self.nc), api.DeviceArray(ctx, 3 * self.np)
         self._begin_extra(s, up)
         self.analyzed = False
 
@@ -542,7 +544,7 @@ class _ResidentBAPath(_Path):
         return self.ctx.edge_chi2_device(self.no, self.rd, self.d_r.ptr, self.d_Om.ptr)
 
     def max_hessian_diag(self):
-        return self.ctx.edge_hessian_maxdiag_device(self.no, self.rd, 6, 3, self.d_J0.ptr, self.d_J1.ptr, self.d_Om.ptr)
+        return self.ctx.edge_hessian_maxdiag_device(self.no, self.rd, self.cam_w, 3, self.d_J0.ptr, self.d_J1.ptr, self.d_Om.ptr)
 
     def _assemble(self, alpha):
         self.ctx.assemble_device(self.d_J0.ptr, self.d_J1.ptr, self.d_Om.ptr, self.d_r.ptr, alpha, self.d_vals.ptr,
@@ -576,7 +578,7 @@ class _ResidentBAPath(_Path):
         self._update(True)
 
     def finish(self, system):
-        system.cams = self.d_cams.download().reshape(-1, 6)
+        system.cams = self.d_cams.download().reshape(-1, self.cam_w)
         system.points = self.d_pts.download().reshape(-1, 3)
 
 
@@ -638,6 +640,86 @@ class _ResidentStereoBAPath(_ResidentBAPath):
     def linearize(self):
         self.ctx.ba_stereo_linearize_device(self.no, self.d_cam_of.ptr, self.d_pt_of.ptr, self.d_cams.ptr, self.d_intr.ptr,
                                             self.d_pts.ptr, self.d_meas.ptr, self.d_J0.ptr, self.d_J1.ptr, self.d_r.ptr)
+
+
+class CBundleAdjustmentSim3:
+    """Sim(3) BA 'system' (CVertexCamSim3 + CVertexXYZ joined by CEdgeP2C_XYZ_Sim3_G, the observation of the reference's
+    ba_parameter_acra and incremental_ba_3dv), the interface of CStereoBundleAdjustment: cams (nc, 7) [t | w | s] in sim(3),
+    intr (nc, 5) fx fy cx cy d, points (np, 3), obs (no, 4) cam pt u v; info (no, 2, 2) or None (identity). Sim(3) BA has
+    seven gauge freedoms and a scale per camera that the projection does not see (the scale column of J0 is zero): the
+    damping of Levenberg-Marquardt is what makes Lambda definite, CNonlinearSolver_Lambda_LM is the loop to use."""
+
+    def __init__(self, cams, intr, points, obs, info=None, cam_id=None, pt_id=None):
+        self.cams = np.array(cams, dtype=np.float64)
+        self.intr = np.asarray(intr, dtype=np.float64)
+        self.points = np.array(points, dtype=np.float64)
+        self.obs = np.asarray(obs, dtype=np.float64)
+        self.info = None if info is None else np.asarray(info, dtype=np.float64)
+        nc, npts = self.cams.shape[0], self.points.shape[0]
+        self.cam_id = np.arange(nc) if cam_id is None else np.asarray(cam_id, dtype=np.int64)
+        self.pt_id = nc + np.arange(npts) if pt_id is None else np.asarray(pt_id, dtype=np.int64)
+        dim = np.empty(nc + npts, dtype=np.int64)
+        dim[self.cam_id], dim[self.pt_id] = 7, 3
+        base = slam3d_offsets(dim)
+        self.cam_off, self.pt_off = base[self.cam_id], base[self.pt_id]   # scalar offsets in the solution vector
+
+    @classmethod
+    def from_problem(cls, p):
+        """from synth.sim3_problem (its geometry) or formats.load_sim3_graph"""
+        g = p["geometry"] if "geometry" in p else p
+        return cls(g["cams"], g["intr"], g["points"], g["obs"], g["info"], g["cam_id"], g["pt_id"])
+
+    def linearize(self):
+        return sim3_ba_linearize(self.cams, self.intr, self.points, self.obs, self.cam_id, self.pt_id, self.info)
+
+    def chi2(self):
+        p = self.linearize()
+        return float(np.einsum("ei,eij,ej->", p.r, p.Om.reshape(-1, 2, 2), p.r))
+
+    def state(self):
+        return self.cams.copy(), self.points.copy()
+
+    def set_state(self, st):
+        self.cams, self.points = st[0].copy(), st[1].copy()
+
+    def plus(self, dx):
+        """CVertexCamSim3::Operator_Plus: Log(Exp(cam) Exp(d)); CVertexXYZ's the plain sum"""
+        self.cams = sim3_plus(self.cams, dx[self.cam_off[:, None] + np.arange(7)])
+        self.points = self.points + dx[self.pt_off[:, None] + np.arange(3)]
+
+
+class _ResidentSim3BAPath(_ResidentBAPath):
+    """the LM iteration pieces of a CBundleAdjustmentSim3 in HBM: _ResidentBAPath with the (7, 3, 2) group --
+    assemble_analyze(..., 7, 3, 2, ...), spp_sim3_ba_linearize_device, edge_hessian_maxdiag_device(no, 2, 7, 3, ...),
+    spp_sim3_update_device --, the vertices at the system's offsets. host_jacobians=True: J0, J1 and r come from the float64
+    mirror at the state downloaded from the device (formats.sim3_ba_linearize), everything else stays on the device."""
+    cam_w = 7
+
+    def __init__(self, device=0, host_jacobians=False):
+        super().__init__(device)
+        self.host_jacobians = host_jacobians
+
+    def begin(self, system):
+        super().begin(system)
+        self.system = system
+
+    def _dx_offsets(self, s):
+        return s.cam_off.astype(np.int64), s.pt_off.astype(np.int64)
+
+    def linearize(self):
+        if self.host_jacobians:
+            s = self.system
+            p = sim3_ba_linearize(self.d_cams.download().reshape(-1, 7), s.intr, self.d_pts.download().reshape(-1, 3), s.obs,
+                                  s.cam_id, s.pt_id, s.info)
+            for d, a in ((self.d_J0, p.J0), (self.d_J1, p.J1), (self.d_r, p.r)):
+                d.upload(np.ascontiguousarray(a).ravel())
+            return
+        self.ctx.sim3_ba_linearize_device(self.no, self.d_cam_of.ptr, self.d_pt_of.ptr, self.d_cams.ptr, self.d_intr.ptr,
+                                          self.d_pts.ptr, self.d_meas.ptr, self.d_J0.ptr, self.d_J1.ptr, self.d_r.ptr)
+
+    def _update(self, apply):
+        return self.ctx.sim3_update_device(self.nc, self.d_cams.ptr, self.d_cam_off.ptr, self.np, self.d_pts.ptr,
+                                           self.d_pt_off.ptr, self.d_dx.ptr, self.st.n, apply=apply)
 
 
 class CBundleAdjustmentIntrinsics:
@@ -746,7 +828,7 @@ class CNonlinearSolver_Lambda_LM:
               rho > 0: alpha *= max(1/3, 1 - (2 rho - 1)^3), nu = 2, last = err
               else   : alpha *= nu, nu *= 2, restore x, and the iteration budget grows by one (at most 10 times)
     `path`: _ResidentBAPath (default, GPU), _ResidentStereoBAPath for a CStereoBundleAdjustment, _ResidentBAIPath for a
-    CBundleAdjustmentIntrinsics, or any object with the
+    CBundleAdjustmentIntrinsics, _ResidentSim3BAPath for a CBundleAdjustmentSim3, or any object with the
     same methods (tests inject a host path)."""
 
     def __init__(self, system, path=None, device=0, verbose=False):

@@ -647,6 +647,76 @@ def stereo_states(prob):
 
 
 # ------------------------------------------------------------------------------------------------
+# Sim(3) bundle adjustment: cameras (7: [t | w | s] in sim(3)) + points (3), CEdgeP2C_XYZ_Sim3_G observations
+# ------------------------------------------------------------------------------------------------
+def sim3_problem(nc=6, npts=40, seed=26, interleave=False, views=(2, 6), hubs=False, name="sim3"):
+    """nc Sim(3) cameras on a ring of radius 10 around a point cloud, looking at the origin, with scales e^s, s uniform in
+    [-0.3, 0.3] (a camera is T = (R, centre, e^s), x = T^-1 X: its frame measures the scene in units of e^s); npts points in
+    a cube, each seen by views[0] .. views[1] distinct cameras; fx 500, fy 505, c = (320, 240), d = 0.1 on every odd camera
+    (divided by 0.5 fx fy in the projection). hubs: point 0 is seen by ALL cameras and camera 0 sees ALL points
+    (vertices of both widths beyond the 24 entries the sequential assembly kernel takes). interleave=True shuffles the
+    vertex ids. Measurements: the truth's projection + pixel noise (sigma 0.5, information its inverse square); the
+    estimate is the truth disturbed -- cameras by T Exp(d) with d ~ (0.03, 0.004 rad, 0.01), points by 0.05. Returns the
+    (7, 3, 2) group linearized at the estimate (formats.sim3_ba_linearize) with geometry = the states (sim3_states)."""
+    from scipy.spatial.transform import Rotation
+    from .formats import sim3_ba_linearize, sim3_expectation, sim3_from_trs, sim3_plus, sim3_to_trs
+    rng = np.random.default_rng(seed)
+    k = rng.integers(views[0], min(views[1], nc) + 1, size=npts)
+    cam_of = np.concatenate([np.sort(rng.choice(nc, size=kk, replace=False)) for kk in k])
+    pt_of = np.repeat(np.arange(npts, dtype=np.int64), k)
+    if hubs:
+        more_c = np.setdiff1d(np.arange(nc), cam_of[pt_of == 0])                         # point 0: every camera
+        more_p = np.array([j for j in range(1, npts) if 0 not in cam_of[pt_of == j]])    # camera 0: every point
+        cam_of = np.concatenate([cam_of, more_c, np.zeros(more_p.size, dtype=np.int64)])
+        pt_of = np.concatenate([pt_of, np.zeros(more_c.size, dtype=np.int64), more_p])
+    nobs = cam_of.size
+    th = 2 * np.pi * np.arange(nc) / nc
+    C = np.stack([10 * np.cos(th), 10 * np.sin(th), 0.5 * np.sin(3 * th)], axis=1)
+    z = -C / np.linalg.norm(C, axis=1, keepdims=True)
+    x = np.cross(np.array([0.0, 0.0, 1.0])[None, :], z)
+    x /= np.linalg.norm(x, axis=1, keepdims=True)
+    R = np.stack([x, np.cross(z, x), z], axis=1)  # rows = camera axes (world -> camera); the pose holds its transpose
+    scale = np.exp(rng.uniform(-0.3, 0.3, size=nc))
+    cams = sim3_from_trs(np.concatenate([C, Rotation.from_matrix(R.transpose(0, 2, 1)).as_rotvec(), scale[:, None]], axis=1))
+    intr = np.tile(np.array([500.0, 505.0, 320.0, 240.0, 0.0]), (nc, 1))
+    intr[1::2, 4] = 0.1
+    X = rng.uniform(-2, 2, size=(npts, 3))
+    sig = 0.5
+    meas = sim3_expectation(cams[cam_of], intr[cam_of], X[pt_of])[0] + rng.normal(0, sig, size=(nobs, 2))
+    info = np.tile(np.eye(2) / sig ** 2, (nobs, 1, 1))
+    est_c = sim3_plus(cams, rng.normal(0, 1, size=(nc, 7)) * np.array([0.03] * 3 + [0.004] * 3 + [0.01]))
+    est_p = X + rng.normal(0, 0.05, size=X.shape)
+    nv = nc + npts
+    if interleave:
+        perm = rng.permutation(nv)
+        cam_id, pt_id = perm[:nc], perm[nc:]
+    else:
+        cam_id, pt_id = np.arange(nc), nc + np.arange(npts)
+    f = lambda a: a.astype(np.float64)
+    obs = np.concatenate([f(cam_of)[:, None], f(pt_of)[:, None], meas], axis=1)
+    prob = sim3_ba_linearize(est_c, intr, est_p, obs, cam_id, pt_id, info)
+    J0, J1 = prob.J0.reshape(nobs, 7, 2), prob.J1.reshape(nobs, 3, 2)
+    h0 = np.einsum("eci,eij,ecj->ec", J0, info, J0).max()
+    h1 = np.einsum("eci,eij,ecj->ec", J1, info, J1).max()
+    prob.update(name=name, damping=1e-3 * float(max(h0, h1)), nc=nc, npts=npts,
+                geometry=dict(cams=est_c, cams_trs=sim3_to_trs(est_c), intr=intr, points=est_p, obs=obs, info=info, cam_of=cam_of,
+                              pt_of=pt_of, cam_id=cam_id, pt_id=pt_id, truth=dict(cams=cams, points=X)))
+    return prob
+
+
+def sim3_states(prob):
+    """The scene of a sim3_problem as input of spp_sim3_ba_linearize_device, like stereo_states: dict(cams (nc,7), intr
+    (nc,5), points (np,3), meas (no,2), cam_of, pt_of int32, cam_dxoff, pt_dxoff int64: scalar offset of every vertex in
+    the solution vector)."""
+    g = prob.geometry
+    base = np.zeros(prob.dim.size + 1, dtype=np.int64)
+    np.cumsum(prob.dim, out=base[1:])
+    return dict(cams=g["cams"].copy(), intr=g["intr"].copy(), points=g["points"].copy(), meas=g["obs"][:, 2:4].copy(),
+                cam_of=g["cam_of"].astype(np.int32), pt_of=g["pt_of"].astype(np.int32),
+                cam_dxoff=base[g["cam_id"]].copy(), pt_dxoff=base[g["pt_id"]].copy())
+
+
+# ------------------------------------------------------------------------------------------------
 # self-calibrating bundle adjustment: cameras (6) + points (3) + intrinsics vertices (5, stored 6 wide), ternary
 # CEdgeP2CI3D observations with 2-d residuals
 # ------------------------------------------------------------------------------------------------
@@ -779,6 +849,8 @@ CONFIGS = {
     "rocv_interleaved": lambda: rocv_problem(150, 8, 83, interleave=True, n_ranges=6, hub=3, name="rocv_interleaved"),
     "stereo_small": lambda: stereo_problem(6, 40, 16, name="stereo_small"),
     "stereo_interleaved": lambda: stereo_problem(30, 150, 17, interleave=True, hubs=True, name="stereo_interleaved"),
+    "sim3_small": lambda: sim3_problem(6, 40, 26, name="sim3_small"),
+    "sim3_interleaved": lambda: sim3_problem(30, 150, 27, interleave=True, hubs=True, name="sim3_interleaved"),
     "bai_tiny": lambda: bai_tiny(),
     "bai_small": lambda: bai_small(),
     "bai_hub": lambda: bai_hub(),
