@@ -15,7 +15,9 @@ block C stays well conditioned (cond <= 1e2, asserted) and the rounding of C^-1 
   edges63_long  the same plus a landmark with 257 observers: no fused back-substitution for this plan
   edges32       3-wide poses, 2-wide landmarks, 128 poses (n_red = 384), the same pair-count spread
   mis66, mis33  one width (MIS Schur cut): two hubs tied to 2100 leaves each (a split S block between the hubs once
-                the library eliminates the leaves), plus a chain of 40 vertices hanging off hub 1"""
+                the library eliminates the leaves), plus a chain of 40 vertices hanging off hub 1
+  ring()        closed loops and open chains of any widths (loop32 here, loop73 and chain73 in schur_fixtures_73.py)
+  tiny_shards   4 cameras, 2 landmarks: with 3 landmark shards one owns nothing"""
 import numpy as np
 
 from slam_plus_plus_amd.blockcsc import structure_from_pairs
@@ -154,13 +156,69 @@ def mis33():
     return _mis(3, 33)
 
 
+N_SPLIT = 2100   # landmarks of the designated pair of ring(): more than PAIR_CHUNK = 2048 products, a split S block
+
+
+def ring_a_edges(nc):
+    """the camera-camera blocks of ring(): (u, u + 5) for every 3rd camera u < nc - 5"""
+    u = np.arange(0, nc - 5, 3)
+    return u, u + 5
+
+
+def ring(nc, dp, dl, half, per=3, seed=0, split=None, wrap=True):
+    """a loop of nc cameras: for every camera c, `per` landmarks, each seen by c and by two distinct cameras c + o1, c + o2
+    with offsets drawn from 1..half (indices mod nc; with wrap=False an open chain: a landmark that would reach past the
+    last camera is not made); camera-camera blocks ring_a_edges(nc); N_SPLIT more landmarks seen by the two cameras of
+    `split` alone, which are tied by a camera-camera block as well"""
+    rng = np.random.default_rng(seed)
+    obs = []
+    lm = 0
+    for c in range(nc):
+        for _ in range(per):
+            o1, o2 = (int(o) for o in 1 + rng.choice(half, 2, replace=False))
+            if not wrap and c + max(o1, o2) >= nc:
+                continue
+            obs += [(c, lm), ((c + o1) % nc, lm), ((c + o2) % nc, lm)]
+            lm += 1
+    if split is not None:
+        for _ in range(N_SPLIT):
+            obs += [(split[0], lm), (split[1], lm)]
+            lm += 1
+    u, v = ring_a_edges(nc)
+    a_edges = list(zip(u.tolist(), v.tolist()))
+    if split is not None and tuple(split) not in a_edges:   # the split S block carries a camera-camera block too
+        a_edges.append(tuple(split))
+    return _guided(nc, lm, dp, dl, obs, a_edges, seed)
+
+
+LOOP32_SPLIT = (135, 140)
+
+
+def loop32():
+    """300 three-wide poses in a loop, 2-wide landmarks (n_red = 900, 8 tile rows; 128 poses per arc-length unit):
+    the camera order is accepted, camera-camera blocks in both senses, the split pair reversed
+    (tests/test_schur_fixtures_73_host.py asserts it)"""
+    return ring(300, 3, 2, half=10, seed=5, split=LOOP32_SPLIT)
+
+
+def _tiny_shards(dp, seed):
+    """4 cameras, 2 landmarks each seen by two cameras, one camera-camera block: with 3 landmark shards rank 2 owns
+    no landmark"""
+    return _guided(4, 2, dp, 3, [(0, 0), (1, 0), (2, 1), (3, 1)], [(1, 2)], seed)
+
+
+def tiny_shards():
+    return _tiny_shards(6, 46)
+
+
 GUIDED = {"edges63": edges63, "edges63_long": edges63_long, "edges32": edges32}
 MIS = {"mis66": mis66, "mis33": mis33}
 ALL = dict(GUIDED, **MIS)
+SHAPES = {"loop32": loop32, "tiny_shards": tiny_shards}   # (not edge fixtures: no pair-count spread)
 
 
 def make(name):
-    return ALL[name]()
+    return (ALL[name] if name in ALL else SHAPES[name])()
 
 
 def landmark_conds(lam, elim):

@@ -1,9 +1,10 @@
 """Child process of tests/test_gpu_schur_side.py and tests/test_gpu_schur_clear.py (the switches of the library are read
 once per process, so every variant runs in a process of its own). Prints one line "RESULT <json>".
 
-  side  <refs.pkl> <json options>   the edge fixtures of tests/schur_fixtures.py: S | rhs formed twice and solved twice in
+  side  <refs.pkl> <json options>   the edge fixtures of tests/schur_fixtures.py and edges73: S | rhs formed twice and solved twice in
                                     one context (bit-reproducible), checked against the longdouble reference, then two
-                                    landmark shards on one device through the split API; sha256 of everything
+                                    landmark shards on one device through the split API (edges63, edges73); sha256 of
+                                    everything
   clear <problem> <json options>    values A, B, A solved in ONE context, each compared with a fresh context's solve of the
                                     same values; then a failed pivot followed by a good solve; what schur_form cleared each
                                     time; which tiles of the solver's S buffer hold anything afterwards"""
@@ -22,10 +23,12 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from slam_plus_plus_amd import api, synth  # noqa: E402
 import schur_fixtures as fx  # noqa: E402
+import schur_fixtures_73 as fx73  # noqa: E402
 
 NB = 128
 SIDE_CASES = [("edges63", api.MODE_SCHUR), ("edges63_long", api.MODE_SCHUR), ("edges32", api.MODE_SCHUR),
-              ("mis66", api.MODE_SCHUR_MIS)]
+              ("mis66", api.MODE_SCHUR_MIS), ("edges73", api.MODE_SCHUR)]
+SHARD_CASES = ["edges63", "edges73"]   # two landmark shards each, reported as "<name>/2 shards"
 
 
 def chain90():
@@ -47,7 +50,7 @@ def problem(name):
     if name == "ba_ring300":   # the ring of tests/test_gpu_dense_tilemask.py: 15 tile rows
         from oracle import spp_oracle as orc
         return orc.assemble(synth.ba_problem(300, 20000, 100000, 300, heavy_tail=True, name=name))
-    return fx.make(name)
+    return fx73.make_any(name)   # (chain73: 6 tile rows, loop73: 19, 7-wide cameras that straddle the tile boundaries)
 
 
 def diagonal_entries(lam):
@@ -188,7 +191,7 @@ def run_side(refs_path, opt):
         return ctx
 
     for name, mode in SIDE_CASES:
-        lam, eta = fx.make(name)
+        lam, eta = fx73.make_any(name)
         R = refs[name]
         ctx = context()
         ctx.analyze(lam, mode)
@@ -216,7 +219,12 @@ def run_side(refs_path, opt):
         ctx.close()
 
     # split API: two landmark shards on one device, packed, summed on the host (the all-reduce), unpacked, finished
-    lam, eta = fx.make("edges63")
+    for name in SHARD_CASES:
+        out[name + "/2 shards"] = two_shards(context, *fx73.make_any(name))
+    return out
+
+
+def two_shards(context, lam, eta):
     ctxs, bufs, side = [], [], []
     hS, hx = hashlib.sha256(), hashlib.sha256()
     for r in range(2):
@@ -243,12 +251,11 @@ def run_side(refs_path, opt):
         assert c.schur_finish(dv.ptr, dS.ptr, dr.ptr) == 0
         c.synchronize()
         hx.update(dr.download().tobytes())
-    out["edges63/2 shards"] = dict(S=hS.hexdigest(), x=hx.hexdigest(), side=side)
     for c, b in zip(ctxs, bufs):
         for d in b:
             d.free()
         c.close()
-    return out
+    return dict(S=hS.hexdigest(), x=hx.hexdigest(), side=side)
 
 
 if __name__ == "__main__":

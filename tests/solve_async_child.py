@@ -6,6 +6,8 @@ SPP_SOLVE_ASYNC runs in a process of its own). Usage: solve_async_child.py <out.
                      twice in one context
   edges63, ba_small  the edge fixture of tests/schur_fixtures.py (15 tile rows, its pair-count spread) and the smoke problem
                      (two tile rows, the shortest chain): the same
+  edges73, loop73    7-wide cameras (tests/schur_fixtures_73.py): the edge fixture (17.5 tiles: the rhs column inside the
+                     last tile) and the 330-camera loop (19 tile rows, its camera order accepted): the same
   six in a row       on the loop's context: two different Lambda / eta pairs alternate, six solves enqueued with no
                      synchronization between them, each result parked by a stream-ordered copy, everything downloaded at
                      the end and compared with the same solve done alone
@@ -25,7 +27,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from slam_plus_plus_amd import api, synth  # noqa: E402
-import schur_fixtures as fx  # noqa: E402
+import schur_fixtures_73 as fx73  # noqa: E402
 import schur_side_child as side  # noqa: E402
 import test_gpu_cam_order as loop  # noqa: E402
 
@@ -38,7 +40,7 @@ def small_system(name):
     if name == "ba_small":
         from oracle import spp_oracle as orc
         return orc.assemble(synth.make("ba_small"))
-    return fx.make(name)
+    return fx73.make_any(name)
 
 
 def bad_values(lam, cam):
@@ -77,8 +79,8 @@ def run(out_path, opt):
         arrays[name.replace(" ", "_")] = xs[0]
         return ctx, dv, dr
 
-    for name in ("edges63", "ba_small"):
-        lam, eta = small_system(name)
+    for name in ("edges63", "ba_small", "edges73", "loop73"):
+        lam, eta = loop.system(name) if name == "loop73" else small_system(name)
         ctx, dv, dr = twice(name, lam, eta)
         dv.free()
         dr.free()
@@ -132,7 +134,7 @@ def run(out_path, opt):
     ctx.close()
 
     # ---- two landmark shards on one device: pack, sum on the host (the all-reduce), unpack, finish
-    lam, eta = fx.make("edges63")
+    lam, eta = fx73.make_any("edges63")
     ctxs, bufs, asy = [], [], []
     for r in range(2):
         c = context(lam, (r, 2))

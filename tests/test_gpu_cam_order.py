@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import schur_fixtures as fx
+import schur_fixtures_73 as fx73
 import schur_ref
 from slam_plus_plus_amd import api, synth
 
@@ -30,8 +31,12 @@ _CACHE = {}
 
 def system(kind):
     """'loop': the ring of synth.ba_problem plus camera-camera edges (c, c + 5) for every 7th camera; 'chain': the same
-    without the points whose window wraps around (no camera-camera edges)"""
+    without the points whose window wraps around (no camera-camera edges); a name of schur_fixtures_73.SHAPES or
+    schur_fixtures.SHAPES: that fixture (the loops of the other widths)"""
     if kind in _CACHE:
+        return _CACHE[kind]
+    if kind in fx73.SHAPES or kind in fx.SHAPES:   # the loops of other widths (tests/test_gpu_cam_order_73.py)
+        _CACHE[kind] = fx73.make_any(kind)
         return _CACHE[kind]
     prob = synth.ba_problem(NC, 4000, 16000, 5, heavy_tail=False, spread=0.06)
     cam, pt = prob.v0.astype(np.int64), prob.v1.astype(np.int64) - NC
@@ -68,11 +73,12 @@ def system(kind):
     return _CACHE[kind]
 
 
-def _ref_in_order(lam, eta, order_blocks):
-    """the reference of the whole system with the poses at the positions the library reports"""
-    if "ref" not in _CACHE:
-        _CACHE["ref"] = schur_ref.schur_ref(lam, eta, schur_ref.guided_elim(lam))
-    R = _CACHE["ref"]
+def _ref_in_order(lam, eta, order_blocks, kind="loop"):
+    """the reference of the whole system `kind` with the poses at the positions the library reports"""
+    key = "ref" if kind == "loop" else "ref " + kind
+    if key not in _CACHE:
+        _CACHE[key] = schur_ref.schur_ref(lam, eta, schur_ref.guided_elim(lam))
+    R = _CACHE[key]
     nat = np.searchsorted(R.poses, order_blocks)
     assert np.array_equal(R.poses[nat], order_blocks)
     dp, nc = R.dp, nat.size
@@ -142,7 +148,7 @@ for _ in range(2):
     assert c.factor_solve_device(dv.ptr, dr.ptr) == 0
     xs.append(dr.download())
 np.save(sys.argv[2], xs[0])
-print(json.dumps({"sha": [hashlib.sha256(x.tobytes()).hexdigest() for x in xs], "order": c.ordering(lam.nb)[:t.NC].tolist(),
+print(json.dumps({"sha": [hashlib.sha256(x.tobytes()).hexdigest() for x in xs], "order": c.ordering(lam.nb)[:c.info("N_POSES")].tolist(),
                   "streamed": c.info("DENSE_STREAMED")}))
 """
 

@@ -6,7 +6,8 @@ next item), SPP_SACC_TILE / SPP_SACC_TILE_COLS / SPP_SACC_XCD (the order of the 
 SPP_SACC_FACTORED / SPP_SACC_ULM (the operands: one packed block per observation, or W and U, landmark- or camera-major),
 SPP_BACKSUBST_FUSED (one launch, or the products U^T dx through memory).
 
-Each child forms S | rhs and solves the edge fixtures of tests/schur_fixtures.py twice (bit-reproducible), checks both
+Each child forms S | rhs and solves the edge fixtures of tests/schur_fixtures.py (6-, 3- and one-width cases) or of
+tests/schur_fixtures_73.py (7-wide cameras) twice (bit-reproducible), checks both
 against the reference itself and prints sha256 of S | rhs and of x. The parent demands the default's bits wherever the
 variant may change only the item order, the item-to-wave assignment or where an operand is stored: the sum of an item is
 fixed by its pair list."""
@@ -20,7 +21,7 @@ import tempfile
 import numpy as np
 import pytest
 
-import schur_fixtures as fx
+import schur_fixtures_73 as fx73
 import schur_ref
 from slam_plus_plus_amd import api
 
@@ -30,6 +31,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TESTS = os.path.join(ROOT, "tests")
 CASES = [("edges63", api.MODE_SCHUR), ("edges63_long", api.MODE_SCHUR), ("edges32", api.MODE_SCHUR),
          ("mis66", api.MODE_SCHUR_MIS)]
+# 7-wide cameras, 3-wide points (tests/schur_fixtures_73.py): the instantiations <7, 3> of every kernel the switches select --
+# the unfactored operands and the unfused back-substitution run nowhere else -- and the item pipeline at 21 doubles per
+# block. A child of their own per variant: each child keeps its time limit.
+CASES_73 = [("edges73", api.MODE_SCHUR), ("edges73_aligned", api.MODE_SCHUR)]
 
 CHILD = r"""
 import hashlib, json, pickle, sys
@@ -37,13 +42,13 @@ import numpy as np
 sys.path.insert(0, %r)
 sys.path.insert(0, %r)
 from slam_plus_plus_amd import api
-import schur_fixtures as fx
+import schur_fixtures_73 as fx73
 import schur_ref
 
 refs = pickle.load(open(sys.argv[1], "rb"))
 out = {}
 for name, mode in json.loads(sys.argv[2]):
-    lam, eta = fx.make(name)
+    lam, eta = fx73.make_any(name)
     R = refs[name]
     ctx = api.Context(0, 0)
     ctx.analyze(lam, mode)
@@ -91,11 +96,14 @@ SWITCHES = ["SPP_SACC_CHUNK", "SPP_SACC_TILE", "SPP_SACC_TILE_COLS", "SPP_SACC_X
 def _run(env_extra, refs_path):
     env = {k: v for k, v in os.environ.items() if k not in SWITCHES}
     env.update(env_extra)
-    r = subprocess.run([sys.executable, "-c", CHILD % (ROOT, TESTS), refs_path, json.dumps(CASES)], env=env,
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, "%s: exit %d\n%s%s" % (env_extra, r.returncode, r.stdout[-3000:], r.stderr[-3000:])
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1]
-    return json.loads(line[7:])
+    out = {}
+    for cases in (CASES, CASES_73):   # one child after the other; a non-zero exit ends the test
+        r = subprocess.run([sys.executable, "-c", CHILD % (ROOT, TESTS), refs_path, json.dumps(cases)], env=env,
+                           capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, "%s: exit %d\n%s%s" % (env_extra, r.returncode, r.stdout[-3000:], r.stderr[-3000:])
+        line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1]
+        out.update(json.loads(line[7:]))
+    return out
 
 
 def _references(ctx_modes):
@@ -104,7 +112,7 @@ def _references(ctx_modes):
     refs = {}
     c = api.Context(0)
     for name, mode in ctx_modes:
-        lam, eta = fx.make(name)
+        lam, eta = fx73.make_any(name)
         c.analyze(lam, mode)
         elim = np.sort(c.ordering(lam.nb)[lam.nb - c.info("N_LANDMARKS"):])
         R = schur_ref.schur_ref(lam, eta, elim).compact(dense=mode == api.MODE_SCHUR, sparse=mode != api.MODE_SCHUR)
@@ -118,19 +126,19 @@ def test_every_schur_switch():
     with tempfile.TemporaryDirectory() as tmp:
         path = os.path.join(tmp, "refs.pkl")
         with open(path, "wb") as f:
-            pickle.dump(_references(CASES), f)
+            pickle.dump(_references(CASES + CASES_73), f)
         base = _run({}, path)
         print("default", {k: "S %.3f xl %.3f xc %.3f" % (v["ratio_S"], v["ratio_xl"], v["ratio_xc"]) for k, v in base.items()})
         got = {}
         for tag, env, same_s, same_x in VARIANTS:   # one child at a time; the first failure ends the test
             got[tag] = g = _run(env, path)
             print(tag, {k: "S %.3f xl %.3f xc %.3f" % (v["ratio_S"], v["ratio_xl"], v["ratio_xc"]) for k, v in g.items()})
-            for name, _ in CASES:
+            for name, _ in CASES + CASES_73:
                 if same_s:
                     assert g[name]["S"] == base[name]["S"], (tag, name, "S | rhs differs from the default")
                 if same_x:
                     assert g[name]["x"] == base[name]["x"], (tag, name, "x differs from the default")
         # SPP_SACC_ULM moves only where U is stored: the same operations in the same order
-        for name, _ in CASES:
+        for name, _ in CASES + CASES_73:
             assert got["fact0"][name]["S"] == got["fact0ulm0"][name]["S"], name
             assert got["fact0"][name]["x"] == got["fact0ulm0"][name]["x"], name

@@ -3,7 +3,7 @@ of S and the status reset -- run beside the S accumulation, ordered against the 
 run with the same arguments, so S | rhs and x must have the bits of the serial order.
 
 The switch is read once per process: every variant is a child process (tests/schur_side_child.py), which forms and solves
-each edge fixture of tests/schur_fixtures.py twice in one context (bit-reproducible), checks both against the longdouble
+each edge fixture of tests/schur_fixtures.py and edges73 (7-wide cameras) twice in one context (bit-reproducible), checks both against the longdouble
 reference of tests/schur_ref.py, drives two landmark shards through the split API (form, pack without a synchronization
 in between, sum, unpack, finish) and prints sha256 of S | rhs and of x. The fixtures are far below SCHUR_SIDE_MIN_OBS
 observations, so the default (1) keeps the serial order on them and SPP_SCHUR_SIDE=2 forces the fork; the children report
@@ -23,7 +23,8 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD = os.path.join(ROOT, "tests", "schur_side_child.py")
-NAMES = [n for n, _ in child.SIDE_CASES] + ["edges63/2 shards"]
+SHARDS = [n + "/2 shards" for n in child.SHARD_CASES]
+NAMES = [n for n, _ in child.SIDE_CASES] + SHARDS
 
 
 @pytest.fixture(scope="module")
@@ -45,6 +46,8 @@ def runs(tmp_path_factory):
             assert r.returncode == 0, "%s: exit %d\n%s%s" % (key, r.returncode, r.stdout[-3000:], r.stderr[-3000:])
             cache[key] = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
             print(key, {k: v["side"] for k, v in cache[key].items()})
+            print(key, "largest error / bound", {k: "S %.3f xl %.3f xc %.3f" % (v["ratio_S"], v["ratio_xl"], v["ratio_xc"])
+                                                 for k, v in cache[key].items() if "ratio_S" in v})
         return cache[key]
     return run
 
@@ -86,6 +89,8 @@ def test_adopted_stream_gives_the_same_bits(runs):
 
 def test_split_api_gives_the_bits_of_the_serial_order(runs):
     forced, serial = runs(2), runs(0)
-    assert forced["edges63/2 shards"]["side"] == [1, 1] and serial["edges63/2 shards"]["side"] == [0, 0]
-    assert forced["edges63/2 shards"]["S"] == serial["edges63/2 shards"]["S"]
-    assert forced["edges63/2 shards"]["x"] == serial["edges63/2 shards"]["x"]
+    assert SHARDS == ["edges63/2 shards", "edges73/2 shards"]
+    for key in SHARDS:
+        assert forced[key]["side"] == [1, 1] and serial[key]["side"] == [0, 0]
+        assert forced[key]["S"] == serial[key]["S"]
+        assert forced[key]["x"] == serial[key]["x"]

@@ -22,7 +22,8 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD = os.path.join(ROOT, "tests", "solve_async_child.py")
-SMALL = ("edges63", "ba_small")
+SMALL = ("edges63", "ba_small", "edges73")
+LOOPS = ("loop300", "loop73")   # (name in the child's result; loop300 is loop.system("loop"))
 
 
 @pytest.fixture(scope="module")
@@ -58,7 +59,7 @@ def references():
 
 
 def _took(res, want):
-    for name in SMALL + ("loop300",):
+    for name in SMALL + LOOPS:
         assert res[name]["asy"] == [want, want], (name, res[name]["asy"])
     assert res["six in a row"]["asy"] == [want] * 6
     assert res["two shards"]["asy"] == [want, want]
@@ -67,7 +68,7 @@ def _took(res, want):
 
 
 def _same_bits(a, b, what):
-    for name in SMALL + ("loop300", "two shards"):
+    for name in SMALL + LOOPS + ("two shards",):
         assert a[name]["x"] == b[name]["x"], (what, name, "x differs")
 
 
@@ -78,6 +79,10 @@ def test_the_shapes_reach_the_code(runs):
     assert res["ba_small"]["tile_rows"] == 2, res["ba_small"]   # the smoke problem: the shortest chain there is
     # (edges63 is 320 cameras, 15 tile rows like the loop, with the pair-count spread of tests/schur_fixtures.py)
     assert res["edges63"]["tile_rows"] == 15, res["edges63"]
+    # 7-wide cameras: 17.5 tiles (the rhs column inside the last tile), and a loop of 19 tile rows in its camera order
+    assert res["edges73"]["tile_rows"] == 18 and res["edges73"]["streamed"] > 0, res["edges73"]
+    assert res["loop73"]["tile_rows"] == 19 and res["loop73"]["streamed"] > 0, "the streamed factor did not run on the 7-wide loop"
+    assert res["loop73"]["order"] != list(range(330)) and sorted(res["loop73"]["order"]) == list(range(330))
 
 
 def test_early_status_gives_the_bits_of_the_drained_order(runs):
@@ -88,7 +93,7 @@ def test_early_status_gives_the_bits_of_the_drained_order(runs):
     _same_bits(early, serial, "SPP_SOLVE_ASYNC=1 against =0")
     _same_bits(default, serial, "the default against SPP_SOLVE_ASYNC=0")
     for res in (serial, early):
-        for name in SMALL + ("loop300",):
+        for name in SMALL + LOOPS:
             assert res[name]["repro"], (name, "x not bit-reproducible")
 
 
@@ -102,6 +107,9 @@ def test_solutions_are_inside_the_bound_of_the_reference(runs, references, switc
     lam, eta = loop.system("loop")
     P = loop._ref_in_order(lam, eta, np.asarray(res["loop300"]["order"]))
     print("loop300 landmark / pose part, error / bound:", schur_ref.check_solution(P, lam, eta, xs["loop300"]))
+    lam, eta = loop.system("loop73")
+    P = loop._ref_in_order(lam, eta, np.asarray(res["loop73"]["order"]), "loop73")
+    print("loop73 landmark / pose part, error / bound:", schur_ref.check_solution(P, lam, eta, xs["loop73"]))
 
 
 @pytest.mark.parametrize("switch", [0, 1])

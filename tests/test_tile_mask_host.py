@@ -1,6 +1,7 @@
 """Host-only: the 128 x 128 tile mask of a dense reduced system and its symbolic fill (spp_tile_mask_host,
 spp_schur_tile_mask_host: what the streamed dense factor uses to skip structurally zero tiles of S) against a plain numpy
-elimination. Block sizes 6 and 3 do not divide 128, so blocks straddle tile edges in both directions. No GPU needed."""
+elimination. Block sizes 7, 6 and 3 do not divide 128, so blocks straddle tile edges in both directions (7-wide blocks at
+other places than 6-wide ones: only every 7th tile boundary is a block boundary). No GPU needed."""
 import numpy as np
 import pytest
 
@@ -59,7 +60,8 @@ def _patterns(nblk, rng):
     yield "random-lower", J[keep], I[keep]   # blocks given in the lower triangle mark the upper tile
 
 
-@pytest.mark.parametrize("bs,nblk", [(6, 43), (6, 64), (6, 150), (6, 871), (3, 300), (3, 1237), (2, 64), (6, 1365)])
+@pytest.mark.parametrize("bs,nblk", [(6, 43), (6, 64), (6, 150), (6, 871), (3, 300), (3, 1237), (2, 64), (6, 1365),
+                                     (7, 92), (7, 128), (7, 330)])
 @pytest.mark.parametrize("has_rhs", [True, False])
 def test_mask_and_fill_match_a_numpy_elimination(bs, nblk, has_rhs):
     n = bs * nblk
@@ -77,7 +79,7 @@ def test_mask_and_fill_match_a_numpy_elimination(bs, nblk, has_rhs):
 
 def test_n_not_a_multiple_of_the_block_size_and_tile_edges():
     # n = 128 k exactly: the right-hand side column opens a tile column of its own
-    for n, bs in [(256, 2), (384, 6), (130, 6), (127, 6), (129, 3)]:
+    for n, bs in [(256, 2), (384, 6), (130, 6), (127, 6), (129, 3), (644, 7), (896, 7), (130, 7)]:
         nblk = -(-n // bs)
         I, J = np.triu_indices(nblk)
         keep = (J - I) % 7 == 0
