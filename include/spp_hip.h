@@ -560,9 +560,30 @@ int spp_schur_cam_order_host(int64_t nb, const int32_t *dim, const int64_t *col_
  * the value of SPP_TAIL_EARLY to apply; beta: the order key i + beta j (SPP_TAIL_ORDER_BETA, 0 = row by row). With a mask,
  * early != 0 and the conditions of DESIGN section 11 met, the tiles of the trailing tile rows r* .. go first; otherwise
  * the table is the sorted one. info (may be NULL, 5 entries): tiles in front, r* (tile rows when none), whole rows
- * resident D, live demand of the other tiles, tiles of the widest row. Returns the number of entries or a negative error. */
+ * resident D, live demand of the other tiles, tiles of the widest row. Returns the number of entries or a negative error.
+ * Bit 1 of early (early = 3): the table the launch uses under a step order other than k ascending (SPP_TAIL_EARLY_LEAD,
+ * DESIGN section 25) -- a trailing run too large to go first whole has its leading rows r* .. r2 in front, then the rows
+ * < r* by the depth of their diagonal tile, then the rows > r2; info as above with the tiles and r* of those rows. */
 int spp_tail_order_host(int64_t n, int has_rhs, const uint64_t *words, int64_t nwords, int resident, int early, double beta,
 	int32_t *table, int32_t *info);
+/* spp_dense_posv_masked with the order in which a tile of the streamed factorization applies its steps given:
+ * step_order[0 .. nwords), a permutation of the tile rows 0 .. nwords - 1 (anything else: SPP_E_BADARG; nwords > 0). A tile
+ * applies the steps its mask selects in that order instead of k ascending -- a different summation order, the same
+ * factor up to rounding; the identity gives the bits of spp_dense_posv_masked. It takes effect where the whole
+ * factorization is one streamed launch (up to SPP_TAIL_ROWS tile rows) and is ignored elsewhere. */
+int spp_dense_posv_ordered(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, double *d_b, const uint64_t *words, int64_t nwords,
+	const int32_t *step_order);
+/* host only: the depth order of the steps for the tile mask words[0 .. nwords) (nwords = ceil(n / 128); closed under
+ * elimination by the call, right-hand side column included): steps sorted by the depth of their diagonal tile in the tile
+ * DAG -- depth(k) = 1 + max depth(j) over j < k with tile (j, k) listed, as in the cost model --, ties by k. Returns the
+ * number of entries or a negative error. (The Schur plan uses it under a dissected camera order only: DESIGN section 25.) */
+int spp_tail_step_order_host(int64_t n, const uint64_t *words, int64_t nwords, int32_t *step_order);
+/* host only: the step order the Schur plan of a block pattern hands to the streamed factor for landmark shard shard_rank
+ * of shard_world, read back from that plan (flags as spp_schur_cam_order_host): one entry per tile row of S (room for 64),
+ * the identity for every camera order but a dissected one and with SPP_TAIL_STEP_ORDER=0. Returns the number of entries
+ * (0 without a tile mask) or a negative error. */
+int spp_schur_step_order_host(int64_t nb, const int32_t *dim, const int64_t *col_ptr, const int64_t *row_idx, int shard_rank,
+	int shard_world, int flags, int32_t *step_order);
 /* C (m x n, ldc) -= A^T B with A: k x m (lda), B: k x n (ldb): the MFMA trailing-update kernel */
 int spp_dense_gemm_tn_sub(spp_ctx *ctx, int64_t m, int64_t n, int64_t k,
 	const double *d_A, int64_t lda, const double *d_B, int64_t ldb, double *d_C, int64_t ldc);

@@ -42,6 +42,7 @@ EXPORTS = [
     "spp_microbench_copy", "spp_microbench_mfma_f64", "spp_microbench_ctile", "spp_microbench_update", "spp_block_ordering", "spp_schur_plan_host", "spp_set_profiling", "spp_se2_linearize_device", "spp_se2_update_device", "spp_ba_linearize_device", "spp_ba_stereo_linearize_device", "spp_ba_update_device", "spp_sim3_ba_linearize_device", "spp_sim3_update_device", "spp_se3_linearize_device", "spp_se3_update_device", "spp_edge_chi2_device", "spp_edge_robust_weights_device", "spp_edge_hessian_maxdiag_device",
     "spp_lm_gain_denominator_device", "spp_dense_potrf_upper", "spp_dense_posv",
     "spp_dense_posv_masked", "spp_tile_mask_host", "spp_schur_tile_mask_host", "spp_tail_order_host", "spp_schur_cam_order_host",
+    "spp_dense_posv_ordered", "spp_tail_step_order_host", "spp_schur_step_order_host",
     "spp_dense_gemm_tn_sub", "spp_dense_gemm_tn_sub_upper", "spp_dense_front_factor", "spp_version",
 ]
 
@@ -138,6 +139,9 @@ def load_library():
         "spp_schur_tile_mask_host": (cint, [i64, vp, vp, vp, cint, cint, vp]),
         "spp_tail_order_host": (cint, [i64, cint, vp, i64, cint, cint, dbl, vp, vp]),
         "spp_schur_cam_order_host": (cint, [i64, vp, vp, vp, cint, cint, cint, vp, vp, vp]),
+        "spp_dense_posv_ordered": (cint, [vp, vp, i64, i64, vp, vp, i64, vp]),
+        "spp_tail_step_order_host": (cint, [i64, vp, i64, vp]),
+        "spp_schur_step_order_host": (cint, [i64, vp, vp, vp, cint, cint, cint, vp]),
         "spp_dense_gemm_tn_sub": (cint, [vp, i64, i64, i64, vp, i64, vp, i64, vp, i64]),
         "spp_dense_gemm_tn_sub_upper": (cint, [vp, i64, i64, i64, vp, i64, vp, i64, vp, i64]),
         "spp_dense_front_factor": (cint, [vp, vp, i64, i64, i64, vp]),
@@ -255,17 +259,47 @@ def tail_order_host(n, words, has_rhs=True, resident=256, early=True, beta=0.0):
     `words` (empty / None: no mask) on a device that holds `resident` workgroups (spp_tail_order_host). Returns
     (tiles, info): tiles is a list of (i, j) in workgroup order, info a dict with n_early (tiles seated in front),
     r_star (their first tile row; the number of tile rows when there are none), rows_resident (D), live_demand, widest.
-    No GPU needed."""
+    early=3: the table with the leading rows of a trailing run that is too large to be seated whole (what the launch uses
+    under a step order, SPP_TAIL_EARLY_LEAD). No GPU needed."""
     lib = load_library()
     words = np.ascontiguousarray(words if words is not None else [], dtype=np.uint64)
     table = np.zeros(64 * 65 // 2 + 64, dtype=np.int32)
     info = np.zeros(5, dtype=np.int32)
     code = lib.spp_tail_order_host(int(n), 1 if has_rhs else 0, _ptr(words) if words.size else None, words.size, int(resident),
-                                   1 if early else 0, float(beta), _ptr(table), _ptr(info))
+                                   int(early), float(beta), _ptr(table), _ptr(info))
     if code < 0:
         raise SppError("spp_tail_order_host failed: %d" % code)
     tiles = [(int(t) >> 16, int(t) & 0xffff) for t in table[:code]]
     return tiles, dict(zip(("n_early", "r_star", "rows_resident", "live_demand", "widest"), (int(v) for v in info)))
+
+
+def tail_step_order_host(n, words):
+    """Host-only: the depth order of the steps of the streamed dense factor for an n x n matrix with the tile mask `words`
+    (one uint64 per tile row; closed under elimination by the call, right-hand side column included): the steps sorted by
+    the depth of their diagonal tile in the tile DAG, ties by k (spp_tail_step_order_host). No GPU needed."""
+    lib = load_library()
+    words = np.ascontiguousarray(words, dtype=np.uint64)
+    out = np.zeros(64, dtype=np.int32)
+    code = lib.spp_tail_step_order_host(int(n), _ptr(words), words.size, _ptr(out))
+    if code < 0:
+        raise SppError("spp_tail_step_order_host failed: %d" % code)
+    return out[:code].copy()
+
+
+def schur_step_order_host(lam, sparse_S=False, mis=False, shard_rank=0, shard_world=1):
+    """Host-only: the step order the dense Schur plan of a BlockCSC pattern hands to the streamed factor, read back from
+    the host plan of landmark shard shard_rank of shard_world (spp_schur_step_order_host): one entry per tile row of S,
+    the identity unless the camera order is a dissected one; empty without a tile mask. No GPU needed."""
+    lib = load_library()
+    col_ptr = np.ascontiguousarray(lam.col_ptr, dtype=np.int64)
+    row_idx = np.ascontiguousarray(lam.row_idx, dtype=np.int64)
+    dim = np.ascontiguousarray(lam.dim, dtype=np.int32)
+    out = np.zeros(64, dtype=np.int32)
+    code = lib.spp_schur_step_order_host(lam.nb, _ptr(dim), _ptr(col_ptr), _ptr(row_idx), shard_rank, shard_world,
+                                         (1 if sparse_S else 0) | (2 if mis else 0), _ptr(out))
+    if code < 0:
+        raise SppError("spp_schur_step_order_host failed: %d" % code)
+    return out[:code].copy()
 
 
 class DeviceArray:

@@ -607,6 +607,21 @@ int spp_schur_cam_order_host(int64_t nb, const int32_t *dim, const int64_t *col_
 	});
 }
 
+// host only: the step order the Schur plan of a structure and landmark shard hands to the streamed factor, read back from that
+// plan (flags as above): step_order[p] = the p-th step a tile applies, one entry per tile row of S (room for 64), the identity
+// where the plan carries none (every order but a dissected one). Returns the number of entries.
+int spp_schur_step_order_host(int64_t nb, const int32_t *dim, const int64_t *col_ptr, const int64_t *row_idx, int shard_rank,
+	int shard_world, int flags, int32_t *step_order)
+{
+	return schur_host_entry(nb, dim, col_ptr, row_idx, shard_rank, shard_world, step_order, [&](const Structure &st) {
+		std::vector<int32_t> order;
+		schur_step_order_host_probe(st, shard_rank, shard_world, (flags & 1) != 0, (flags & 2) != 0, order);
+		for(size_t q = 0; q < order.size(); ++ q)
+			step_order[q] = order[q];
+		return (int)order.size();
+	});
+}
+
 int spp_schur_buffer_size(const spp_ctx *ctx, int64_t *n_doubles)
 {
 	if(!ctx || !n_doubles)
@@ -1286,7 +1301,7 @@ int spp_tail_order_host(int64_t n, int has_rhs, const uint64_t *words, int64_t n
 		std::vector<int> order;
 		int oinfo[5];
 		const bool use = nwords && early; // (as the launch: only with a mask in force)
-		tail_order_table(bits, (int)Tr, (int)Tc, false, beta, use ? resident : 0, use, order, oinfo);
+		tail_order_table(bits, (int)Tr, (int)Tc, false, beta, use ? resident : 0, use, order, oinfo, use && (early & 2) != 0);
 		for(size_t q = 0; q < order.size(); ++ q)
 			table[q] = order[q];
 		if(info)
@@ -1298,18 +1313,48 @@ int spp_tail_order_host(int64_t n, int has_rhs, const uint64_t *words, int64_t n
 	}
 }
 
-int spp_dense_posv_masked(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, double *d_b, const uint64_t *words, int64_t nwords)
+int spp_tail_step_order_host(int64_t n, const uint64_t *words, int64_t nwords, int32_t *step_order)
+{
+	const int64_t Tr = (n + DENSE_NB - 1) / DENSE_NB;
+	if(n <= 0 || n / DENSE_NB + 1 > 64 || !words || nwords != Tr || !step_order)
+		return SPP_E_BADARG;
+	try {
+		std::vector<uint64_t> mask(words, words + nwords);
+		tile_mask_close(n, true, true, mask); // (a filled mask stays what it is)
+		std::vector<int32_t> order;
+		tail_step_order(mask, order);
+		for(size_t q = 0; q < order.size(); ++ q)
+			step_order[q] = order[q];
+		return (int)order.size();
+	} catch(...) {
+		return SPP_E_NOMEM;
+	}
+}
+
+// the masked solve, with the order in which the tiles of the streamed launch apply their steps (nullptr: ascending)
+static int dense_posv_entry(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, double *d_b, const uint64_t *words, int64_t nwords,
+	const int32_t *step_order)
 {
 	if(!ctx || !d_A || !d_b || n <= 0 || ld < n || nwords < 0 || (nwords && !words))
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	std::vector<uint64_t> mask(words, words + nwords);
+	std::vector<int32_t> order;
 	if(nwords) {
 		SPP_REQUIRE(nwords == (n + DENSE_NB - 1) / DENSE_NB, SPP_E_BADARG, "posv: one mask word per tile row of 128");
 		tile_mask_close(n, true, true, mask);
 	}
-	TileMaskGuard guard(ctx->dense, &mask);
+	if(step_order) {
+		std::vector<char> seen((size_t)nwords, 0);
+		for(int64_t q = 0; q < nwords; ++ q) {
+			SPP_REQUIRE(step_order[q] >= 0 && step_order[q] < nwords && !seen[(size_t)step_order[q]], SPP_E_BADARG,
+				"posv: the step order must be a permutation of the tile rows 0 .. nwords - 1");
+			seen[(size_t)step_order[q]] = 1;
+		}
+		order.assign(step_order, step_order + nwords);
+	}
+	TileMaskGuard guard(ctx->dense, &mask, &order);
 	const int64_t ldp = ((n + 1 + DENSE_NB - 1) / DENSE_NB) * DENSE_NB;
 	DevBuf<double> tmp;
 	tmp.reserve((size_t)ldp * ldp);
@@ -1329,6 +1374,19 @@ int spp_dense_posv_masked(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, doub
 	dense_chain_check(ctx);
 	return ret;
 	SPP_CATCH(ctx)
+}
+
+int spp_dense_posv_masked(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, double *d_b, const uint64_t *words, int64_t nwords)
+{
+	return dense_posv_entry(ctx, d_A, n, ld, d_b, words, nwords, nullptr);
+}
+
+int spp_dense_posv_ordered(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, double *d_b, const uint64_t *words, int64_t nwords,
+	const int32_t *step_order)
+{
+	if(!step_order || nwords <= 0)
+		return SPP_E_BADARG;
+	return dense_posv_entry(ctx, d_A, n, ld, d_b, words, nwords, step_order);
 }
 
 int spp_dense_gemm_tn_sub(spp_ctx *ctx, int64_t m, int64_t n, int64_t k, const double *d_A, int64_t lda,

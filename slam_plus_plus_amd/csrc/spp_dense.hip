@@ -1577,13 +1577,20 @@ static bool launch_dense_tail(spp_ctx *ctx, double *d_A, int64_t ld, int64_t row
 			dw.tail_resident = 0; // (unknown: nothing goes in front)
 		}
 	}
+	// (a trailing run too large to be seated whole: its leading rows, where a step order lets a seated tile keep level with
+	// the chains that feed it -- tail_order_table's lead)
+	const bool ordered = k < 0 && dw.step_order && (int64_t)dw.step_order->size() == nsteps;
+	bool ascending = true;
+	for(int q = 0; ordered && q < Tr; ++ q)
+		ascending = ascending && (*dw.step_order)[(size_t)q] == q;
+	const bool lead = early && ordered && !ascending && sw.tail_early_lead != 0;
 	if(dw.tail_order_tr != Tr || dw.tail_order_tc != Tc || dw.tail_order_bits != bits || dw.tail_order_pre != (k >= 0) ||
-	   dw.tail_order_masked != early) {
+	   dw.tail_order_masked != early || dw.tail_order_lead != lead) {
 		if(!dw.tail_order_host.empty())
 			SPP_HIP_CHECK(hipStreamSynchronize(s)); // (an upload of the table's former host image may still be reading it)
 		std::vector<int> &order = dw.tail_order_host; // (the asynchronous upload reads it after this call returns)
 		int oinfo[5];
-		tail_order_table(bits, Tr, Tc, k >= 0, sw.tail_order_beta, early ? dw.tail_resident : 0, early, order, oinfo);
+		tail_order_table(bits, Tr, Tc, k >= 0, sw.tail_order_beta, early ? dw.tail_resident : 0, early, order, oinfo, lead);
 		if(sw.verbose)
 			fprintf(stderr, "[spp] streamed tail: %d x %d tiles, %d listed, %d resident; %d tiles of rows %d.. seated first (whole rows resident %d, live demand %d)\n",
 				Tr, Tc, (int)order.size(), early ? dw.tail_resident : 0, oinfo[0], oinfo[1], oinfo[2], oinfo[3]);
@@ -1593,6 +1600,7 @@ static bool launch_dense_tail(spp_ctx *ctx, double *d_A, int64_t ld, int64_t row
 		dw.tail_order_bits = bits;
 		dw.tail_order_pre = k >= 0;
 		dw.tail_order_masked = early;
+		dw.tail_order_lead = lead;
 	}
 	const int ntile = (int)dw.tail_order_host.size();
 	TailArgs a;
@@ -1600,6 +1608,33 @@ static bool launch_dense_tail(spp_ctx *ctx, double *d_A, int64_t ld, int64_t row
 	memset(a.rowbits, 0, sizeof(a.rowbits));
 	for(size_t q = 0; q < bits.size(); ++ q)
 		a.rowbits[q] = bits[q];
+	// The step list: k ascending (the row panel in front of the region first), or the caller's step order where this
+	// launch is the whole factorization -- with or without its mask in force (SPP_TAIL_MASK changes scheduling, never bits).
+	{
+		const std::vector<int32_t> *so = ordered ? dw.step_order : nullptr;
+		if(so) { // (the kernel indexes its step words with these)
+			uint64_t seen = 0;
+			for(int q = 0; q < Tr; ++ q) {
+				const int32_t v = (*so)[(size_t)q];
+				SPP_REQUIRE(v >= 0 && v < Tr && !((seen >> v) & 1), SPP_E_BADARG, "streamed tail: the step order is not a permutation of the tile rows");
+				seen |= 1ull << v;
+			}
+		}
+		unsigned char list[sizeof(a.sorder)];
+		memset(list, TAIL_NO_STEP, sizeof(list));
+		int p = 0;
+		if(k >= 0)
+			list[p ++] = (unsigned char)(signed char)-1;
+		for(int q = 0; q < Tr; ++ q)
+			list[p ++] = (unsigned char)(so ? (*so)[(size_t)q] : q);
+		for(size_t w = 0; w < sizeof(a.sorder) / 8; ++ w) {
+			a.sorder[w] = 0;
+			for(int b = 0; b < 8; ++ b)
+				a.sorder[w] |= (unsigned long long)list[8 * w + b] << (8 * b);
+		}
+		if(sw.verbose && so)
+			fprintf(stderr, "[spp] streamed tail: %d steps in the caller's step order\n", Tr);
+	}
 	a.A = d_A;
 	a.ld = ld;
 	a.rows = rows;

@@ -24,7 +24,13 @@
 // set E of trailing tile rows may be numbered in front of all others (tail_order_table, spp_tile_plan.cpp): no tile outside
 // E waits for one of E, and the host uses E only when E and the live tiles outside it are resident together. Every wait
 // is bounded (abort word).
-// Summation order per tile: steps ascending, row tiles ascending -- fixed, bit-reproducible.
+// Summation order per tile: its steps in the order of the launch's step list, row tiles ascending -- fixed, bit-
+// reproducible. The list is k ascending, except where the caller of a whole factorization hands over a step order
+// (TailArgs::sorder, tail_step_order in spp_tile_plan.cpp: by the depth of the step's diagonal tile): two chains of steps
+// that do not see each other emit their row tiles side by side, and a tile both update -- a separator tile of a
+// dissected order -- would, k ascending, leave the second chain's row tiles lying until the first chain has ended and
+// then have that whole backlog in front of it. The order changes neither counters nor waits nor the workgroup numbering:
+// whichever step a tile waits for, its row tiles come from workgroups with smaller indices.
 // Structure: the launch takes one 64-bit word per step (bit j of word k = tile (k, j) of the FILLED pattern is nonzero,
 // spp_tile_plan.cpp: tile_mask_close). Only tiles with their bit set have a workgroup; tile (i, j) applies step k only if
 // bits i and j of word k are both set, and neither waits for nor fetches a row tile of a step it skips -- such an update
@@ -57,7 +63,17 @@ struct TailArgs {
 	// rowbits[k + 1], bit j: tile (k, j) of the region is nonzero after symbolic fill (region tile indices); rowbits[0]
 	// is the row panel in front of the region (have_pre)
 	unsigned long long rowbits[TAIL_MAX_ROWS + 1];
+	// the order in which a tile applies its steps, one byte per step, eight to a word (entry p in byte p & 7 of
+	// sorder[p >> 3]): the step as a signed byte -- -1: the row panel in front of the region --, TAIL_NO_STEP behind the
+	// last one. Ascending unless the caller hands a step order to a whole factorization (launch_dense_tail).
+	unsigned long long sorder[TAIL_MAX_ROWS / 8 + 1];
 };
+constexpr int TAIL_NO_STEP = 127; // (no tile row: a tile applies the steps below its own row only)
+
+__host__ __device__ inline int tail_sorder_at(const unsigned long long *sorder, const int p)
+{
+	return (int)(signed char)(unsigned char)(sorder[p >> 3] >> (8 * (p & 7)));
+}
 
 // the value a timed-out wait of the streamed launch leaves in the abort word (the host tells it from the other raisers:
 // a non-positive pivot, a cross-stream flag wait of the per-step schedule in front of it, both store 1)
@@ -213,13 +229,26 @@ void dense_tail_kernel(const TailArgs a)
 		const int ek = tid & 15, ec = tid >> 4; // this thread's elements: (ek, ec) and (ek, ec + 64) of a row tile
 		constexpr int PS = 18;                  // column stride of a row tile's LDS image (even: 16-byte aligned columns)
 		const int ekp = 4 * (ek & 3) + (ek >> 2);
-		const int kfirst = a.have_pre ? -1 : 0;
-		// the steps this tile applies (bit k - kfirst): both row tiles (k, ti) and (k, tj) nonzero
-		unsigned long long steps = 0;
-		for(int k = kfirst; k < ti; ++ k) {
+		// the steps this tile applies, as positions in the step list a.sorder (bit p = its entry p): a step k below the
+		// tile's own row with both row tiles (k, ti) and (k, tj) nonzero. The tile takes them in the order of the list
+		// (ascending k unless the host handed a step order over: then the steps of chains that run side by side, interleaved
+		// as they are emitted). Whatever the order, the producers are tiles of rows < ti: smaller workgroup indices.
+		// (First by step -- bit k + 1, the step words fetched one after the other as they lie --, then moved to the positions
+		// of the list: no fetch there depends on another.)
+		unsigned long long ksteps = 0;
+		for(int k = a.have_pre ? -1 : 0; k < ti; ++ k) {
 			const unsigned long long w = a.rowbits[k + 1];
-			if(((w >> ti) & (w >> tj) & 1) != 0)
-				steps |= 1ull << (k - kfirst);
+			ksteps |= ((w >> ti) & (w >> tj) & 1) << (k + 1);
+		}
+		unsigned long long steps = 0;
+		for(int q = 0; 8 * q < a.Tr + a.have_pre; ++ q) {
+			const unsigned long long word = a.sorder[q];
+#pragma unroll
+			for(int b = 0; b < 8; ++ b) {
+				const int k = (int)(signed char)(unsigned char)(word >> (8 * b));
+				if(k < ti && ((ksteps >> (k + 1)) & 1) != 0)
+					steps |= 1ull << (8 * q + b);
+			}
 		}
 		const int nst = 8 * __builtin_popcountll(steps);
 		double va[2], vb[2];
@@ -237,12 +266,15 @@ void dense_tail_kernel(const TailArgs a)
 		int avail = a.have_pre ? 8 : 0; // row tiles of the current step known to be out
 		pre_first = diag && nst > 0 && (nst & 1) == 0 && a.rows - i0 >= 16; // (the last round's images are the second pair; the right-hand side column is not in the first tile)
 		bool inflight = false;
-		int k = kfirst;
+		int k = a.have_pre ? -1 : 0;
+		int knext = steps ? tail_sorder_at(a.sorder, __builtin_ctzll(steps)) : k; // (looked up one step ahead: a fetch from the argument block)
 		for(int sidx = 0; sidx < nst; ++ sidx) {
 			const int J = sidx & 7;
 			if(J == 0) { // the next step this tile applies
-				k = kfirst + __builtin_ctzll(steps);
+				k = knext;
 				steps &= steps - 1;
+				if(steps)
+					knext = tail_sorder_at(a.sorder, __builtin_ctzll(steps));
 			}
 			if(J == 0 && k >= 0)
 				avail = 0;

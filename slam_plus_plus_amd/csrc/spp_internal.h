@@ -239,6 +239,7 @@ struct SchurPlan : SchurDims {
 	std::vector<int64_t> lm_block;   // owned landmark index -> original block column
 	std::vector<uint8_t> is_lm;      // per block column: eliminated by the Schur complement (any shard)
 	std::vector<uint64_t> tile_mask; // dense S: its filled 128 x 128 tile pattern over ALL shards (tile_mask_close); empty: every tile
+	std::vector<int32_t> step_order; // dense S in a dissected camera order: the step order of the streamed factor (tail_step_order of tile_mask); empty: ascending
 	// device arrays
 	DevBuf<int32_t> lm_ptr;        // [nl+1] first obs of landmark
 	DevBuf<int32_t> bs_ptr;        // [n_bs+1] landmark ranges of the fused back-substitution (at most 256 observations each); n_bs = 0: two launches
@@ -299,12 +300,17 @@ struct DenseWork {
 	std::vector<int> tail_order_host; // its host image (the upload is asynchronous: it lives as long as the table)
 	int tail_order_tr = 0, tail_order_tc = 0;
 	std::vector<uint64_t> tail_order_bits; // ... and for these step words (the table is keyed by the tile mask as well)
+	bool tail_order_lead = false;  // ... with / without the leading rows of a trailing run that is too large (tail_order_table's lead)
 	bool tail_order_pre = false, tail_order_masked = false; // ... with / without a row panel in front, with / without a caller's mask
 	int tail_resident = -1;        // workgroups of the streamed launch the device holds at once (occupancy x CUs); -1: not asked yet
 	// Tile structure of the matrix the next factorization gets (set by the caller for that one call, TileMaskGuard): one
 	// word per tile row of 128, bit j = tile (i, j) is nonzero after symbolic fill (tile_mask_close). nullptr or a size
 	// that does not match the factorization's tile rows: every tile is nonzero.
 	const std::vector<uint64_t> *tile_mask = nullptr;
+	// The order in which the tiles of the next factorization apply their steps, when the whole of it is ONE streamed launch
+	// (set with the mask, TileMaskGuard): a permutation of its tile rows. nullptr or another size: ascending. It changes
+	// the summation order, so -- unlike the mask -- it holds whatever SPP_TAIL_MASK says.
+	const std::vector<int32_t> *step_order = nullptr;
 	bool tail_masked_whole = false; // the last factorization was ONE streamed launch (no per-step front) under the caller's tile mask
 	int tail_rows_last = 0;        // tile rows the last factorization streamed (diagnostics: SPP_INFO_DENSE_STREAMED)
 	bool tail_disabled = false;    // a streamed launch timed out on this ctx: later factorizations take the per-step schedule
@@ -470,8 +476,12 @@ struct TileDagCost {
 TileDagCost tile_dag_cost(int64_t n, const std::vector<uint64_t> &filled, int resident); // (filled: tile_mask_close(n, true, true))
 // workgroup -> tile (i << 16 | j) of the streamed launch for the step words bits[0 .. Tr] of a region (host only; the rule
 // and the progress condition are stated at its definition)
+// lead: where the trailing run is too large to be seated whole, its leading rows are (used together with a step order)
 void tail_order_table(const std::vector<uint64_t> &bits, int Tr, int Tc, bool have_pre, double beta, int resident, bool early,
-	std::vector<int> &order, int *info);
+	std::vector<int> &order, int *info, bool lead = false);
+// the order in which a tile of the streamed launch applies its steps: by the depth of the step's diagonal tile in the
+// tile DAG of the filled mask (one word per tile row), ties by k (host only; stated at its definition)
+void tail_step_order(const std::vector<uint64_t> &filled, std::vector<int32_t> &order);
 
 // ---- spp_schur_plan.cpp ----
 void build_schur_plan(spp_ctx *ctx, bool sparse_S, bool mis = false);
@@ -484,6 +494,10 @@ void schur_tile_mask_host_probe(const Structure &st, std::vector<uint64_t> &word
 // nothing is chosen. Returns whether cam_order differs from the identity.
 bool schur_cam_order_host_probe(const Structure &st, int shard_rank, int shard_world, bool sparse_S, bool mis, const int64_t *order_in,
 	std::vector<int32_t> &cam_order, TileDagCost cost[2]);
+// host only: the step order the Schur plan of a structure and shard hands to the streamed factor, read back from that plan
+// (one entry per tile row of S, the identity where the plan carries none; empty without a tile mask). Returns whether
+// the plan carries one.
+bool schur_step_order_host_probe(const Structure &st, int shard_rank, int shard_world, bool sparse_S, bool mis, std::vector<int32_t> &step_order);
 
 // ---- spp_sparse (symbolic on host + numeric on device) ----
 void sparse_analyze(spp_ctx *ctx, const Structure &st); // plan for `st` (Lambda, or the sparse reduced system)
@@ -534,10 +548,14 @@ void dense_reserve(spp_ctx *ctx, int64_t nblk); // workspaces for nblk diagonal 
 void dense_chain_check(spp_ctx *ctx);
 void dense_set_padding(spp_ctx *ctx, double *d_A, int64_t ld, int64_t n);
 void dense_set_padding_on(hipStream_t st, double *d_A, int64_t ld, int64_t n);
-struct TileMaskGuard { // hands a tile mask to the factorizations enqueued while it lives
+struct TileMaskGuard { // hands a tile mask (and a step order) to the factorizations enqueued while it lives
 	DenseWork &d;
-	TileMaskGuard(DenseWork &dw, const std::vector<uint64_t> *m) : d(dw) { d.tile_mask = (m && !m->empty()) ? m : nullptr; }
-	~TileMaskGuard() { d.tile_mask = nullptr; }
+	TileMaskGuard(DenseWork &dw, const std::vector<uint64_t> *m, const std::vector<int32_t> *so = nullptr) : d(dw)
+	{
+		d.tile_mask = (m && !m->empty()) ? m : nullptr;
+		d.step_order = (so && !so->empty()) ? so : nullptr;
+	}
+	~TileMaskGuard() { d.tile_mask = nullptr; d.step_order = nullptr; }
 };
 // unit tests: the partial factorization of a big sparse front, laid out (identity padding after the w pivots) and
 // factored as the sparse path does; d_F (h x h, ld) <- the result in the unpadded layout, d_image (optional, ldp x hp with

@@ -1423,8 +1423,9 @@ static int schur_finish_t(spp_ctx *ctx, const double *d_vals, double *S, double 
 		// idle for ~40 us before the solves (after a failure they run on garbage and the result is discarded)
 		{
 			// S is a band plus what elimination fills: the streamed launch skips the tiles that stay zero. The mask covers the
-			// landmarks of every shard, so it also holds for an S summed over the ranks.
-			TileMaskGuard guard(ctx->dense, &sp.tile_mask);
+			// landmarks of every shard, so it also holds for an S summed over the ranks. (Under a dissected camera order the
+			// plan adds the order in which the tiles take the two arcs' steps.)
+			TileMaskGuard guard(ctx->dense, &sp.tile_mask, &sp.step_order);
 			// any schedule but the fully masked streamed launch (per-step, unmasked, a row panel in front of the streamed
 			// launch) writes tiles outside the mask: the next schur_form on this buffer then clears all of it. (Set first: a
 			// call that fails halfway leaves the buffer marked.)

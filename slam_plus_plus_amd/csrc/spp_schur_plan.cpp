@@ -32,7 +32,7 @@ void SchurPlan::release_all()
 	sblk_voff.release(); s_st = Structure(); sparse_S = false; mis = false;
 	pair_a.release(); pair_b.release(); multi_blk.release(); multi_ptr.release(); cinv.release(); lfac.release();
 	W.release(); Up.release(); xw.release(); partial.release(); S.release();
-	pose_block.clear(); lm_block.clear(); is_lm.clear(); tile_mask.clear();
+	pose_block.clear(); lm_block.clear(); is_lm.clear(); tile_mask.clear(); step_order.clear();
 }
 
 // Guided ordering is possible when there are exactly two block widths and the blocks of the
@@ -515,6 +515,8 @@ struct SchurPlanHost : SchurDims {
 	Structure s_st;
 	std::vector<uint64_t> tile_mask; // dense S: filled tile pattern (schur_tile_mask); empty: every tile
 	TileDagCost cam_cost[2];               // the model's figures of the natural order / of the order used
+	bool cam_dissected = false;            // the camera order is a dissection (arc, arc, separators), not the natural one
+	std::vector<int32_t> step_order;       // ... then the step order of the streamed factor on tile_mask (tail_step_order); empty: ascending
 };
 
 struct Obs { int32_t lm, pose; int64_t off; };
@@ -587,6 +589,7 @@ static void apply_cam_order(const Structure &st, bool sparse_S, bool mis, SchurP
 	std::vector<int32_t> &pose_of = w.pose_of;
 	std::vector<int32_t> cam_order;
 	if(schur_cam_order(st, is_lm, pose_of, nc, dp, sparse_S, mis, nullptr, cam_order, h.cam_cost)) {
+		h.cam_dissected = true;
 		const std::vector<int64_t> natural(h.pose_block);
 		for(int64_t q = 0; q < nc; ++ q) {
 			h.pose_block[q] = natural[cam_order[q]];
@@ -1271,6 +1274,17 @@ static void schur_plan_host(const Structure &st, int shard_rank, int shard_world
 		"reduced camera system too large for the dense path (use SPP_MODE_SCHUR_SPARSE)");
 	if(!sparse_S)
 		schur_tile_mask(st, h.is_lm, w.pose_of, h.dp, h.n_red, h.tile_mask);
+	// The step order of the streamed factor: only under a dissected camera order, whose arcs emit their row tiles side by
+	// side (every other order keeps its steps ascending, bit for bit as before). From the mask over ALL shards and from
+	// nothing a run-time switch of the factor's scheduling changes: every rank, and SPP_TAIL_MASK = 0 / 1, get the same one.
+	if(h.cam_dissected && !h.tile_mask.empty() && switches().tail_step_order) {
+		tail_step_order(h.tile_mask, h.step_order);
+		bool identity = true;
+		for(size_t q = 0; q < h.step_order.size(); ++ q)
+			identity = identity && h.step_order[q] == (int32_t)q;
+		if(identity)
+			h.step_order.clear();
+	}
 	scan_columns(st, h, w);
 	clk.lap("partition + observation scan");
 	// Sharded + sparse reduced system: every rank must hold the SAME block structure of S (the union
@@ -1316,6 +1330,7 @@ void build_schur_plan(spp_ctx *ctx, bool sparse_S, bool mis)
 	sp.is_lm.swap(h.is_lm);
 	sp.add_A = (ctx->shard_rank == 0);
 	sp.tile_mask.swap(h.tile_mask);
+	sp.step_order.swap(h.step_order);
 	if(sparse_S) {
 		sp.s_st = h.s_st;
 		sp.sblk_voff.upload(h.sblk_voff, s);
@@ -1450,6 +1465,20 @@ void schur_tile_mask_host_probe(const Structure &st, std::vector<uint64_t> &word
 	PlanScratch w;
 	schur_partition(st, 0, 1, false, h, w);
 	schur_tile_mask(st, h.is_lm, w.pose_of, h.dp, h.nc * h.dp, words);
+}
+
+bool schur_step_order_host_probe(const Structure &st, int shard_rank, int shard_world, bool sparse_S, bool mis, std::vector<int32_t> &step_order)
+{
+	SchurPlanHost h;
+	schur_plan_host(st, shard_rank, shard_world, sparse_S || mis, mis, h);
+	const bool carried = !h.step_order.empty();
+	step_order = h.step_order;
+	if(!carried) {
+		step_order.resize(h.tile_mask.size());
+		for(size_t q = 0; q < step_order.size(); ++ q)
+			step_order[q] = (int32_t)q;
+	}
+	return carried;
 }
 
 bool schur_cam_order_host_probe(const Structure &st, int shard_rank, int shard_world, bool sparse_S, bool mis, const int64_t *order_in,

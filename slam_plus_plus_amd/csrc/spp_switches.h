@@ -45,6 +45,8 @@ struct Switches {
 	int tail_mask;            // SPP_TAIL_MASK (1): 0: every tile, whatever structure the caller knows (A/B timing, tests)
 	double tail_order_beta;   // SPP_TAIL_ORDER_BETA (0): the streamed launch's workgroup order key i + beta j (0 = row by row)
 	int tail_early;           // SPP_TAIL_EARLY (1): with a tile mask, the trailing tile rows whose every tile lags go to the front of the streamed launch's workgroup order (tail_order_table); 0: the sorted order alone
+	int tail_step_order;      // SPP_TAIL_STEP_ORDER (1): under a dissected camera order the tiles of the streamed launch apply their steps by the depth of the step's diagonal tile (the arcs' steps interleaved as they are emitted, tail_step_order); 0: ascending
+	int tail_early_lead;      // SPP_TAIL_EARLY_LEAD (1): under a step order, a trailing run of lagging tile rows that is too large to be seated whole has its leading rows seated first (tail_order_table); 0: nothing of it. The table alone changes: same bits either way
 	long long tail_timeout_ticks; // SPP_TAIL_TIMEOUT_TICKS (5e7 = 0.5 s): bound of a wait of the streamed launch (tests: a tiny value forces the timeout and the per-step fallback)
 	int tail_trace;           // SPP_TAIL_TRACE (off): n: the n-th launch prints per tile row when its diagonal tile had all updates, was factored, and when the first panel tile started / ended
 	int trsv_chain;           // SPP_TRSV_CHAIN (2): 2: the chain inside one workgroup, 1: a workgroup per hop (round 2), 0: a launch per hop (round 1)
@@ -119,6 +121,8 @@ inline Switches parse_switches()
 	w.tail_mask = env_int("SPP_TAIL_MASK", 1);
 	w.tail_order_beta = env_double("SPP_TAIL_ORDER_BETA", 0.0);
 	w.tail_early = env_int("SPP_TAIL_EARLY", 1);
+	w.tail_step_order = env_int("SPP_TAIL_STEP_ORDER", 1);
+	w.tail_early_lead = env_int("SPP_TAIL_EARLY_LEAD", 1);
 	w.tail_timeout_ticks = env_i64("SPP_TAIL_TIMEOUT_TICKS", WAIT_TICKS_DEFAULT);
 	w.tail_trace = env_int("SPP_TAIL_TRACE", 0);
 	w.trsv_chain = env_int("SPP_TRSV_CHAIN", 2);

@@ -1,6 +1,7 @@
 // spp_tile_plan.cpp -- host-side tile planning of the dense factor (integer work on 128 x 128 tile masks): which tiles
 // of a reduced system are structurally nonzero (tile_mask_mark, tile_mask_close), which workgroup of the streamed launch
-// takes which tile (tail_order_table), and the cost model of that launch on a filled mask (tile_dag_cost).
+// takes which tile (tail_order_table), in which order a tile applies its steps (tail_step_order), and the cost model of
+// that launch on a filled mask (tile_dag_cost).
 
 #include "spp_internal.h"
 #include <algorithm>
@@ -78,8 +79,26 @@ int64_t tile_mask_close(int64_t n, bool has_rhs, bool fill, std::vector<uint64_t
 //   |E| <= resident / 2   and   resident - |E| >= max over r of #{(i, j) outside E : first(i, j) <= r <= i}
 // (the live demand: tiles that have something to do while the chain is at row r), otherwise the table is the base
 // order, entry for entry. info (may be null): {|E|, r*, D, live demand, widest row} -- r* = Tr, |E| = 0 when E is not used.
+// lead (the caller sets it only together with a step order other than k ascending, tail_step_order below): a run that
+// fails these conditions -- the 20 separator rows of a dissected Venice order, 210 tiles against 128 -- is not given up.
+// E becomes its LEADING rows r* .. r2, the largest r2 with
+//   |E| <= resident / 2   and   resident - |E| >= the live demand of the tiles of rows < r*   (as above),
+// and the table is E, then the rows < r*, then the rows > r2. The rows < r* are numbered by the depth of their diagonal
+// tile (ties: the base order) and not row by row: they are the chains that run side by side, each of which needs its
+// next rows resident, and row by row the workgroups E leaves them all go to the first chain (measured, DESIGN section
+// 25). Progress:
+//   a tile of a row < r* waits for tiles of rows above its own alone -- never for E, never for a row > r2 --, a listed tile
+//   (k, i), k < i, makes depth(k) < depth(i), so depth then base order is topological among them: with E seated they
+//   complete one after the other on the resident - |E| >= 1 workgroups that are left;
+//   a tile of E waits for tiles of rows < r* and for tiles of E in rows above its own, numbered before it inside E: E
+//   completes row by row once the rows < r* have;
+//   a tile of a row > r2 waits for smaller indices only.
+// (Unlike the whole run the leading rows are not closed under "consumer of": the rows > r2 consume E, from behind it in
+// the numbering.) The step order is what makes the seats pay: a tile of E, resident from the start, takes the steps of
+// all chains as they come out and is level with them when the longest one ends; k ascending it would sit on its
+// workgroup through the whole first chain with the others' row tiles piling up. With lead off the table is as before.
 void tail_order_table(const std::vector<uint64_t> &bits, int Tr, int Tc, bool have_pre, double beta, int resident, bool early,
-	std::vector<int> &order, int *info)
+	std::vector<int> &order, int *info, bool lead)
 {
 	std::vector<std::pair<double, int> > key;
 	for(int i = 0; i < Tr; ++ i)
@@ -139,13 +158,62 @@ void tail_order_table(const std::vector<uint64_t> &bits, int Tr, int Tc, bool ha
 	}
 	if(info)
 		info[3] = demand;
-	if(n_early == 0 || n_early > resident / 2 || resident - n_early < demand)
+	if(n_early == 0)
 		return;
+	if(n_early > resident / 2 || resident - n_early < demand) {
+		if(!lead)
+			return;
+		// the leading rows r* .. r2 of the run (see above)
+		const int room = std::min(resident / 2, resident - demand);
+		int r2 = r_star - 1, n_lead = 0;
+		for(int i = r_star; i < Tr; ++ i) {
+			const int row = (int)__builtin_popcountll(bits[(size_t)i + 1] & ~((1ull << i) - 1) & (Tc == 64 ? ~0ull : (1ull << Tc) - 1));
+			if(n_lead + row > room)
+				break;
+			n_lead += row;
+			r2 = i;
+		}
+		if(n_lead == 0)
+			return;
+		std::vector<int> depth((size_t)Tr, 1); // (of the diagonal tiles: tile_dag_cost's definition)
+		for(int k = 0; k < Tr; ++ k)
+			for(int j = 0; j < k; ++ j)
+				if((bits[(size_t)j + 1] >> k) & 1)
+					depth[k] = std::max(depth[k], depth[j] + 1);
+		auto key = [&](const int t) { const int i = t >> 16; return i < r_star ? 1 + depth[i] : (i <= r2 ? 0 : 2 + Tr); };
+		std::stable_sort(order.begin(), order.end(), [&key](const int x, const int y) { return key(x) < key(y); });
+		if(info) {
+			info[0] = n_lead;
+			info[1] = r_star;
+		}
+		return;
+	}
 	std::stable_partition(order.begin(), order.end(), [r_star](const int t) { return (t >> 16) >= r_star; });
 	if(info) {
 		info[0] = n_early;
 		info[1] = r_star;
 	}
+}
+
+// The order in which a tile of the streamed launch applies its steps (spp_dense_tail.h): the steps sorted by the depth of
+// their diagonal tile in the tile DAG -- depth(k) = 1 + max depth(j) over j < k with tile (j, k) listed, 1 without such a
+// j: the definition of tile_dag_cost below --, ties by k. Two chains that do not see each other (the arcs of a dissected
+// camera order) emit their row tiles side by side, step m of either at about m chain steps into the launch, and that
+// is the order of their depths: a tile that both update takes the steps as they come out instead of waiting for the whole
+// first chain with the second one's row tiles long in memory. Along every dependency path the depth grows, so a chain
+// (a band, a bordered band) keeps k ascending: the identity. A function of the filled mask alone.
+void tail_step_order(const std::vector<uint64_t> &filled, std::vector<int32_t> &order)
+{
+	const int Tr = (int)std::min<size_t>(filled.size(), 64);
+	std::vector<int> depth((size_t)Tr, 1);
+	for(int k = 0; k < Tr; ++ k)
+		for(int j = 0; j < k; ++ j)
+			if((filled[(size_t)j] >> k) & 1)
+				depth[k] = std::max(depth[k], depth[j] + 1);
+	order.resize((size_t)Tr);
+	for(int k = 0; k < Tr; ++ k)
+		order[k] = k;
+	std::stable_sort(order.begin(), order.end(), [&depth](const int32_t x, const int32_t y) { return depth[x] < depth[y]; });
 }
 
 TileDagCost tile_dag_cost(int64_t n, const std::vector<uint64_t> &filled, int resident)
