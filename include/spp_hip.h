@@ -128,6 +128,7 @@ int spp_set_shard(spp_ctx *ctx, int rank, int world_size);
 #define SPP_INFO_S_DEVICE_PTR   21 /* diagnostics, tests: device address of the S | rhs buffer spp_factor_solve owns (0: none yet) */
 #define SPP_INFO_ASM_HUB_CHUNK   22 /* assembly of ternary edges: edges one workgroup of the hub reduction sums (C); a constant, needs no analysis */
 #define SPP_INFO_SOLVE_ASYNC    23 /* what the last spp_factor_solve_device / spp_schur_finish did (SPP_SOLVE_ASYNC): 1 it returned when the factor's status was known, the solves and the back-substitution still running on the stream; 0 it drained the stream (profiling on, stream capture, sparse reduced system, sparse mode, the switch at 0) */
+#define SPP_INFO_FACTOR_KEPT    24 /* 1: the ctx holds a factor spp_solve_device / spp_marginals_device may use: the last spp_factor_solve_device returned SPP_OK in SPP_MODE_SCHUR with a dense reduced system, unsharded, and nothing has rewritten it since; 0 otherwise (needs no analysis) */
 int spp_get_info(const spp_ctx *ctx, int what, int64_t *out);
 /* elimination order chosen by the analysis: order[k] = source block column eliminated k-th */
 int spp_get_ordering(const spp_ctx *ctx, int64_t *h_order);
@@ -182,6 +183,32 @@ int spp_factor_solve(spp_ctx *ctx, const double *h_vals, double *h_rhs_inout);
  * as before -- with profiling on, under stream capture, for the sparse reduced system and the sparse mode, and with
  * SPP_SOLVE_ASYNC=0. */
 int spp_factor_solve_device(spp_ctx *ctx, const double *d_vals, double *d_rhs_inout);
+
+/* ---- solve again on the kept factor -----------------------------------------
+ * Lambda X = B for nrhs further right-hand sides against the factor the last successful spp_factor_solve_device of this
+ * ctx left behind (SPP_INFO_FACTOR_KEPT): no S accumulation, no factorization. d_B: n x nrhs, column-major, leading
+ * dimension ldb >= n, rows in Lambda's numbering, overwritten by X; nothing outside its n rows and nrhs columns is touched.
+ * CONTRACT: d_vals must hold the values that call factored, unchanged -- the landmark side reads U and C from them, and the
+ * library cannot tell whether they are the same. Column j of the result has the same bits whatever the other columns hold
+ * and wherever it stands; two runs give the same bits.
+ * STREAM-ORDERED: the call enqueues on the ctx stream and returns; d_B is complete for later work on that stream, for
+ * spp_memcpy_d2h and behind spp_synchronize -- also behind a solve that returned early (SPP_SOLVE_ASYNC). d_vals and d_B
+ * must stay allocated until then.
+ * The factor is kept by SPP_OK of spp_factor_solve_device in SPP_MODE_SCHUR (dense reduced system, unsharded) and dropped
+ * on entry of every call that rewrites S, the dense workspaces or the plan: any factor / solve, spp_schur_form /
+ * spp_schur_finish (whatever their buffer: the block inverses are the ctx's), spp_dense_*, spp_analyze and the
+ * spp_assemble_analyze* calls, spp_set_shard, spp_free_memory. The two calls below keep it.
+ * SPP_E_STATE: no kept factor. SPP_E_UNSUPPORTED: a sparse reduced system (SPP_MODE_SCHUR_SPARSE, SPP_MODE_SCHUR_MIS), the
+ * sparse mode, a sharded ctx. SPP_E_BADARG: a null pointer, nrhs < 1, ldb < n. */
+int spp_solve_device(spp_ctx *ctx, const double *d_vals, double *d_B, int64_t ldb, int64_t nrhs);
+/* Joint covariance of chosen vertices: d_cov (m x m, column-major, m = sum of their widths) <- E^T Lambda^-1 E, E the unit
+ * block columns of the n_sel vertices h_vertices (block columns of Lambda: cameras and landmarks in any mix and order, each
+ * at most once) -- one solve with m columns on the kept factor, as the reference's Schur_Marginals solves against the
+ * factor of S block column by block column (include/slam/BAMarginals.h). Rows and columns follow h_vertices. The upper
+ * triangle is computed and mirrored: exactly symmetric. Workspace: n x m doubles. Contract, ordering and errors as above;
+ * SPP_E_BADARG also for n_sel < 1, a vertex out of range or listed twice. Which damping Lambda carries is the caller's
+ * choice (a bundle adjustment without a scale prior has a gauge direction only damping makes definite). */
+int spp_marginals_device(spp_ctx *ctx, const double *d_vals, int64_t n_sel, const int64_t *h_vertices, double *d_cov);
 
 /* split form for multi-GPU: (1) each rank forms its partial Schur complement and
  * reduced rhs into d_S_rhs = [S (ld x ld, column-major, upper blocks) | rhs (ld)] ; (2) the caller
@@ -528,6 +555,10 @@ int spp_microbench_update(spp_ctx *ctx, int64_t m, int iters, double *ms_per_lau
 int spp_dense_potrf_upper(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld);
 /* A x = b by the dense path (upper triangle of A read; A <- R, b <- x) */
 int spp_dense_posv(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, double *d_b);
+/* A X = B for nrhs columns: A is factored as by spp_dense_potrf_upper (no right-hand side rides along; A <- R with the
+ * same bits), then B (n x nrhs, column-major, ldb >= n) <- X by the multi-column solves of the kept-factor path
+ * (spp_solve_device); returns the factor's status (B untouched after SPP_NOT_POSDEF) */
+int spp_dense_posv_multi(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, double *d_B, int64_t ldb, int64_t nrhs);
 /* the same with the tile structure of A given: words[i], bit j set = the 128 x 128 tile (i, j), i <= j, of A may be nonzero
  * (nwords = ceil(n / 128); nwords = 0: every tile). The call adds the diagonal tiles and the right-hand side's tile column
  * and closes the pattern under elimination; the streamed factorization then skips the tiles that stay zero. A tile

@@ -22,14 +22,14 @@ MODE_AUTO, MODE_SPARSE, MODE_SCHUR, MODE_SCHUR_SPARSE, MODE_SCHUR_MIS = 0, 1, 2,
 FLAG_PROFILE = 1
 INFO = dict(MODE=0, N=1, NNZB=2, NVALS=3, FACTOR_NNZ=4, FACTOR_FLOPS=5, N_REDUCED=6, N_POSES=7,
             N_LANDMARKS=8, SCHUR_PAIRS=9, N_OBS=10, SOLVE_BYTES=11, N_SUPERNODES=12, N_LEVELS=13, S_LD=14, S_NNZB=15, DENSE_STREAMED=16,
-            LM_STREAM=17, BS_GROUPS=18, SCHUR_SIDE=19, S_CLEAR=20, S_DEVICE_PTR=21, ASM_HUB_CHUNK=22, SOLVE_ASYNC=23)
+            LM_STREAM=17, BS_GROUPS=18, SCHUR_SIDE=19, S_CLEAR=20, S_DEVICE_PTR=21, ASM_HUB_CHUNK=22, SOLVE_ASYNC=23, FACTOR_KEPT=24)
 PHASES = ["permute", "schur_inv", "schur_gemm", "schur_rhs", "factor", "trisolve", "backsubst", "assemble", "total"]
 
 # every symbol include/spp_hip.h declares (tests/test_abi.py checks the .so exports them all)
 EXPORTS = [
     "spp_create", "spp_destroy", "spp_free_memory", "spp_last_error", "spp_host_staging", "spp_set_stream", "spp_synchronize",
     "spp_analyze", "spp_set_shard", "spp_get_info", "spp_get_ordering", "spp_sparse_fronts", "spp_factor_solve",
-    "spp_factor_solve_device", "spp_schur_buffer_size", "spp_schur_form", "spp_schur_finish",
+    "spp_factor_solve_device", "spp_solve_device", "spp_marginals_device", "spp_schur_buffer_size", "spp_schur_form", "spp_schur_finish",
     "spp_schur_packed_size", "spp_schur_pack", "spp_schur_unpack",
     "spp_assemble_analyze", "spp_assemble_get_structure", "spp_assemble_device", "spp_assemble_set_edge_weights",
     "spp_assemble_analyze_groups", "spp_assemble_groups_device", "spp_assemble_set_group_edge_weights",
@@ -40,7 +40,7 @@ EXPORTS = [
     "spp_rocv_cv_linearize_device", "spp_device_malloc",
     "spp_device_free", "spp_memcpy_h2d", "spp_memcpy_d2h", "spp_memcpy_d2d", "spp_get_phase_ms", "spp_get_dominant_kernel",
     "spp_microbench_copy", "spp_microbench_mfma_f64", "spp_microbench_ctile", "spp_microbench_update", "spp_block_ordering", "spp_schur_plan_host", "spp_set_profiling", "spp_se2_linearize_device", "spp_se2_update_device", "spp_ba_linearize_device", "spp_ba_stereo_linearize_device", "spp_ba_update_device", "spp_sim3_ba_linearize_device", "spp_sim3_update_device", "spp_se3_linearize_device", "spp_se3_update_device", "spp_edge_chi2_device", "spp_edge_robust_weights_device", "spp_edge_hessian_maxdiag_device",
-    "spp_lm_gain_denominator_device", "spp_dense_potrf_upper", "spp_dense_posv",
+    "spp_lm_gain_denominator_device", "spp_dense_potrf_upper", "spp_dense_posv", "spp_dense_posv_multi",
     "spp_dense_posv_masked", "spp_tile_mask_host", "spp_schur_tile_mask_host", "spp_tail_order_host", "spp_schur_cam_order_host",
     "spp_dense_posv_ordered", "spp_tail_step_order_host", "spp_schur_step_order_host",
     "spp_dense_gemm_tn_sub", "spp_dense_gemm_tn_sub_upper", "spp_dense_front_factor", "spp_version",
@@ -80,6 +80,8 @@ def load_library():
         "spp_sparse_fronts": (i64, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
         "spp_factor_solve": (cint, [vp, vp, vp]),
         "spp_factor_solve_device": (cint, [vp, vp, vp]),
+        "spp_solve_device": (cint, [vp, vp, vp, i64, i64]),
+        "spp_marginals_device": (cint, [vp, vp, i64, vp, vp]),
         "spp_schur_buffer_size": (cint, [vp, _c_i64p]),
         "spp_schur_form": (cint, [vp, vp, vp, vp]),
         "spp_schur_finish": (cint, [vp, vp, vp, vp]),
@@ -134,6 +136,7 @@ def load_library():
         "spp_sim3_update_device": (cint, [vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, vp, vp, ctypes.c_int64, cint, _c_f64p]),
         "spp_dense_potrf_upper": (cint, [vp, vp, i64, i64]),
         "spp_dense_posv": (cint, [vp, vp, i64, i64, vp]),
+        "spp_dense_posv_multi": (cint, [vp, vp, i64, i64, vp, i64, i64]),
         "spp_dense_posv_masked": (cint, [vp, vp, i64, i64, vp, vp, i64]),
         "spp_tile_mask_host": (cint, [i64, cint, i64, vp, vp, cint, cint, vp, vp]),
         "spp_schur_tile_mask_host": (cint, [i64, vp, vp, vp, cint, cint, vp]),
@@ -541,6 +544,35 @@ class Context:
 
     def factor_solve_device(self, d_vals, d_rhs):
         return self._check(self.lib.spp_factor_solve_device(self.h, d_vals, d_rhs))
+
+    def solve_device(self, d_vals, d_B, nrhs, ldb=None):
+        """Lambda X = B for nrhs columns (device pointer d_B, column-major, leading dimension ldb, default n) against the
+        factor the last successful factor_solve_device left (info("FACTOR_KEPT")); d_vals must be the values that call
+        factored. Stream-ordered: B is complete behind synchronize() / a download."""
+        if ldb is None:
+            ldb = self.info("N")
+        return self._check(self.lib.spp_solve_device(self.h, d_vals, d_B, int(ldb), int(nrhs)))
+
+    def marginals(self, d_vals, vertices):
+        """joint covariance E^T Lambda^-1 E of the given vertices (block columns of Lambda, each at most once, any mix of
+        cameras and landmarks) as an (m, m) numpy array, rows and columns in the order of `vertices`; exactly symmetric"""
+        vertices = np.ascontiguousarray(vertices, dtype=np.int64)
+        keep = getattr(self, "_keep", None)
+        dim = np.asarray(keep.dim) if keep is not None else np.zeros(0, dtype=np.int32)
+        if vertices.size == 0 or vertices.min() < 0 or vertices.max() >= dim.size:
+            m = 1   # (the library rejects the list; the buffer only has to exist)
+        else:
+            m = max(1, int(dim[vertices].sum()))
+        d_cov = DeviceArray(self, m * m)
+        try:
+            self._check(self.lib.spp_marginals_device(self.h, d_vals, vertices.size, _ptr(vertices), d_cov.ptr))
+            return d_cov.download().reshape((m, m), order="F")
+        finally:
+            d_cov.free()
+
+    def dense_posv_multi(self, d_A, n, ld, d_B, ldb, nrhs):
+        """A X = B for nrhs columns by the dense factor and the multi-column solves (unit tests); returns the status"""
+        return self._check(self.lib.spp_dense_posv_multi(self.h, d_A, int(n), int(ld), d_B, int(ldb), int(nrhs)))
 
     def schur_buffer_size(self):
         out = ctypes.c_int64()

@@ -147,9 +147,14 @@ int spp_free_memory(spp_ctx *ctx)
 	SPP_TRY(ctx)
 	(void)hipSetDevice(ctx->device);
 	ctx_drain(ctx);
+	ctx->schur.factor_kept = false;
 	ctx->schur.release_all();
 	sparse_release(ctx);
 	assemble_release(ctx);
+	ctx->dense.trsm_w.release();
+	ctx->again_panel.release();
+	ctx->again_cols.release();
+	ctx->again_rows.release();
 	ctx->dense.tinv.release();
 	ctx->dense.tinv_all.release();
 	ctx->dense.xtmp.release();
@@ -287,6 +292,7 @@ int spp_set_shard(spp_ctx *ctx, int rank, int world_size)
 {
 	if(!ctx || world_size < 1 || rank < 0 || rank >= world_size)
 		return SPP_E_BADARG;
+	ctx->schur.factor_kept = false; // (the plan no longer matches the ctx)
 	ctx->shard_rank = rank;
 	ctx->shard_world = world_size;
 	return SPP_OK;
@@ -305,6 +311,7 @@ int spp_analyze(spp_ctx *ctx, int64_t nb, const int64_t *col_ptr, const int64_t 
 	// sizes of the NEW structure beside the plan of the OLD one (the next solve would copy the wrong extents).
 	// The old plan is dropped first in any case -- after a failed analyze the ctx is "not analyzed".
 	ctx->mode = -1;
+	ctx->schur.factor_kept = false;
 	ctx_drain(ctx); // (the plan and the workspaces released below may still be at work for a solve that returned early)
 	VClock clk("spp_analyze");
 	Structure st;
@@ -415,7 +422,7 @@ int spp_get_info(const spp_ctx *ctx, int what, int64_t *out)
 	if(!ctx || !out)
 		return SPP_E_BADARG;
 	if(ctx->mode < 0 && what != SPP_INFO_NNZB && what != SPP_INFO_NVALS && what != SPP_INFO_N && what != SPP_INFO_DENSE_STREAMED &&
-	   what != SPP_INFO_ASM_HUB_CHUNK)
+	   what != SPP_INFO_ASM_HUB_CHUNK && what != SPP_INFO_FACTOR_KEPT)
 		return SPP_E_STATE;
 	switch(what) {
 	case SPP_INFO_MODE: *out = (ctx->mode != SPP_MODE_SCHUR) ? ctx->mode : ctx->schur.mis ? SPP_MODE_SCHUR_MIS :
@@ -443,6 +450,7 @@ int spp_get_info(const spp_ctx *ctx, int what, int64_t *out)
 	case SPP_INFO_S_CLEAR: *out = (ctx->mode == SPP_MODE_SCHUR) ? ctx->schur.clear_last : 0; break;
 	case SPP_INFO_S_DEVICE_PTR: *out = (ctx->mode == SPP_MODE_SCHUR) ? (int64_t)(uintptr_t)ctx->schur.S.p : 0; break;
 	case SPP_INFO_ASM_HUB_CHUNK: *out = ASM_HUB_CHUNK; break;
+	case SPP_INFO_FACTOR_KEPT: *out = (ctx->mode == SPP_MODE_SCHUR && ctx->schur.factor_kept) ? 1 : 0; break;
 	default: return SPP_E_BADARG;
 	}
 	return SPP_OK;
@@ -637,6 +645,7 @@ int spp_schur_form(spp_ctx *ctx, const double *d_vals, const double *d_rhs, doub
 	if(!ctx || !d_vals || !d_rhs || !d_S_rhs)
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
+	ctx->schur.factor_kept = false; // (the packed operand, and with the own buffer S, are rewritten)
 	SPP_REQUIRE(ctx->mode == SPP_MODE_SCHUR, SPP_E_STATE, "spp_schur_form: analyze in Schur mode first");
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	phases_reset(ctx);
@@ -698,6 +707,7 @@ int spp_schur_finish(spp_ctx *ctx, const double *d_vals, double *d_S_rhs, double
 	if(!ctx || !d_vals || !d_rhs_inout || !d_S_rhs)
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
+	ctx->schur.factor_kept = false; // (whatever the buffer: the block inverses of the ctx are rewritten)
 	SPP_REQUIRE(ctx->mode == SPP_MODE_SCHUR, SPP_E_STATE, "spp_schur_finish: analyze in Schur mode first");
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	// drains the stream for the status fetch, or -- dense S, SPP_SOLVE_ASYNC -- waits for the status alone and returns with the
@@ -717,6 +727,7 @@ int spp_factor_solve_device(spp_ctx *ctx, const double *d_vals, double *d_rhs)
 	if(!ctx || !d_vals || !d_rhs)
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
+	ctx->schur.factor_kept = false;
 	SPP_REQUIRE(ctx->mode >= 0, SPP_E_STATE, "spp_factor_solve: call spp_analyze first");
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	phases_reset(ctx);
@@ -741,7 +752,44 @@ int spp_factor_solve_device(spp_ctx *ctx, const double *d_vals, double *d_rhs)
 	if(!(ctx->mode == SPP_MODE_SCHUR && ctx->schur.async_last))
 		SPP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
 	dense_chain_check(ctx); // (see spp_schur_finish)
+	// R in the own S buffer and the whole block inverses stay valid until a call that rewrites them: spp_solve_device
+	ctx->schur.factor_kept = ret == SPP_OK && ctx->mode == SPP_MODE_SCHUR && !ctx->schur.sparse_S && !ctx->schur.mis &&
+		ctx->shard_world == 1;
 	return ret;
+	SPP_CATCH(ctx)
+}
+
+// what spp_solve_device and spp_marginals_device check before they touch anything (the ctx stays as it was)
+static void require_kept_factor(const spp_ctx *ctx, const char *who)
+{
+	SPP_REQUIRE(ctx->mode >= 0, SPP_E_STATE, std::string(who) + ": no kept factor (call spp_analyze and spp_factor_solve_device first)");
+	SPP_REQUIRE(ctx->mode == SPP_MODE_SCHUR && !ctx->schur.sparse_S && !ctx->schur.mis && ctx->shard_world == 1, SPP_E_UNSUPPORTED,
+		std::string(who) + ": only the dense reduced system of SPP_MODE_SCHUR, unsharded, keeps its factor");
+	SPP_REQUIRE(ctx->schur.factor_kept, SPP_E_STATE, std::string(who) + ": no kept factor (the last spp_factor_solve_device failed, or a later call rewrote it)");
+}
+
+int spp_solve_device(spp_ctx *ctx, const double *d_vals, double *d_B, int64_t ldb, int64_t nrhs)
+{
+	if(!ctx || !d_vals || !d_B || nrhs < 1)
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	require_kept_factor(ctx, "spp_solve_device");
+	SPP_REQUIRE(ldb >= ctx->st.n, SPP_E_BADARG, "spp_solve_device: ldb < n");
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	schur_solve_again(ctx, d_vals, d_B, ldb, nrhs);
+	return SPP_OK;
+	SPP_CATCH(ctx)
+}
+
+int spp_marginals_device(spp_ctx *ctx, const double *d_vals, int64_t n_sel, const int64_t *h_vertices, double *d_cov)
+{
+	if(!ctx || !d_vals || !h_vertices || !d_cov || n_sel < 1)
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	require_kept_factor(ctx, "spp_marginals_device");
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	schur_marginals(ctx, d_vals, n_sel, h_vertices, d_cov);
+	return SPP_OK;
 	SPP_CATCH(ctx)
 }
 
@@ -775,6 +823,7 @@ int spp_assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *h_dim, int64_t
 	if(!h_dim || !h_v0 || !h_v1 || nv <= 0 || ne <= 0)
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
+	ctx->schur.factor_kept = false;
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	assemble_analyze(ctx, nv, h_dim, 1, &ne, &h_v0, &h_v1, nullptr, &d0, &d1, &rd, unary_vertex);
 	return SPP_OK;
@@ -791,6 +840,7 @@ int spp_assemble_analyze_groups(spp_ctx *ctx, int64_t nv, const int32_t *h_dim, 
 	if(!h_dim || nv <= 0 || n_groups <= 0 || !h_ne || !h_v0 || !h_v1 || !h_d0 || !h_d1 || !h_rd)
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
+	ctx->schur.factor_kept = false;
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	SPP_REQUIRE(n_groups <= SPP_MAX_EDGE_GROUPS, SPP_E_UNSUPPORTED, "more than SPP_MAX_EDGE_GROUPS edge groups");
 	int64_t total = 0;
@@ -862,6 +912,7 @@ int spp_assemble_analyze_ternary(spp_ctx *ctx, int64_t nv, const int32_t *h_dim,
 	if(!h_dim || !h_v0 || !h_v1 || !h_v2 || nv <= 0 || ne <= 0)
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
+	ctx->schur.factor_kept = false;
 	SPP_REQUIRE(d0 == 6 && d1 == 3 && d2 == 6 && live2 == 5 && rd == 2, SPP_E_UNSUPPORTED,
 		"ternary edge shape (d0, d1, d2, rd) / live2 not instantiated: (6,3,6,2) / 5");
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
@@ -1245,6 +1296,7 @@ int spp_dense_potrf_upper(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld)
 	if(!ctx || !d_A || n <= 0 || ld < n)
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
+	ctx->schur.factor_kept = false;
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	const int64_t ldp = ((n + 1 + DENSE_NB - 1) / DENSE_NB) * DENSE_NB;
 	DevBuf<double> tmp;
@@ -1254,6 +1306,32 @@ int spp_dense_potrf_upper(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld)
 		hipMemcpyDeviceToDevice, ctx->stream));
 	dense_set_padding(ctx, tmp.p, ldp, n);
 	int ret = dense_potrf_upper(ctx, tmp.p, n, ldp, true);
+	SPP_HIP_CHECK(hipMemcpy2DAsync(d_A, ld * sizeof(double), tmp.p, ldp * sizeof(double), n * sizeof(double), n,
+		hipMemcpyDeviceToDevice, ctx->stream));
+	SPP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+	return ret;
+	SPP_CATCH(ctx)
+}
+
+// the factorization of spp_dense_potrf_upper (no right-hand side rides along), then the multi-column solves of the
+// kept-factor path on B; A <- R with the bits spp_dense_potrf_upper leaves
+int spp_dense_posv_multi(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, double *d_B, int64_t ldb, int64_t nrhs)
+{
+	if(!ctx || !d_A || !d_B || n <= 0 || ld < n || ldb < n || nrhs < 1)
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	ctx->schur.factor_kept = false;
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	const int64_t ldp = ((n + 1 + DENSE_NB - 1) / DENSE_NB) * DENSE_NB;
+	DevBuf<double> tmp;
+	tmp.reserve((size_t)ldp * ldp);
+	SPP_HIP_CHECK(hipMemsetAsync(tmp.p, 0, (size_t)ldp * ldp * sizeof(double), ctx->stream));
+	SPP_HIP_CHECK(hipMemcpy2DAsync(tmp.p, ldp * sizeof(double), d_A, ld * sizeof(double), n * sizeof(double), n,
+		hipMemcpyDeviceToDevice, ctx->stream));
+	dense_set_padding(ctx, tmp.p, ldp, n);
+	int ret = dense_potrf_upper(ctx, tmp.p, n, ldp, true);
+	if(ret == SPP_OK)
+		dense_potrs_multi(ctx, tmp.p, n, ldp, d_B, ldb, nrhs);
 	SPP_HIP_CHECK(hipMemcpy2DAsync(d_A, ld * sizeof(double), tmp.p, ldp * sizeof(double), n * sizeof(double), n,
 		hipMemcpyDeviceToDevice, ctx->stream));
 	SPP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
@@ -1338,6 +1416,7 @@ static int dense_posv_entry(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, do
 	if(!ctx || !d_A || !d_b || n <= 0 || ld < n || nwords < 0 || (nwords && !words))
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
+	ctx->schur.factor_kept = false;
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	std::vector<uint64_t> mask(words, words + nwords);
 	std::vector<int32_t> order;
@@ -1395,6 +1474,7 @@ int spp_dense_gemm_tn_sub(spp_ctx *ctx, int64_t m, int64_t n, int64_t k, const d
 	if(!ctx || !d_A || !d_B || !d_C)
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
+	ctx->schur.factor_kept = false;
 	SPP_REQUIRE((lda % 2) == 0 && (ldb % 2) == 0, SPP_E_BADARG, "gemm_tn_sub: lda/ldb must be even (16-byte loads)");
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	dense_gemm_tn_sub(ctx, m, n, k, d_A, lda, d_B, ldb, d_C, ldc, false);
@@ -1409,6 +1489,7 @@ int spp_dense_gemm_tn_sub_upper(spp_ctx *ctx, int64_t m, int64_t n, int64_t k, c
 	if(!ctx || !d_A || !d_B || !d_C)
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
+	ctx->schur.factor_kept = false;
 	SPP_REQUIRE((lda % 2) == 0 && (ldb % 2) == 0, SPP_E_BADARG, "gemm_tn_sub: lda/ldb must be even (16-byte loads)");
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	dense_gemm_tn_sub(ctx, m, n, k, d_A, lda, d_B, ldb, d_C, ldc, true);
@@ -1422,6 +1503,7 @@ int spp_dense_front_factor(spp_ctx *ctx, double *d_F, int64_t ld, int64_t w, int
 	if(!ctx || !d_F)
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
+	ctx->schur.factor_kept = false;
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	return dense_front_factor(ctx, d_F, ld, w, h, d_image);
 	SPP_CATCH(ctx)

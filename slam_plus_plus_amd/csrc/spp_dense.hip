@@ -2333,3 +2333,4 @@ double microbench_update(spp_ctx *ctx, int64_t m, int iters)
 }
 
 } // namespace spp
+#include "spp_dense_trsm.h" // k right-hand sides against the kept factor: a launch per block row and direction

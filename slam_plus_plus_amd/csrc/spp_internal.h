@@ -279,6 +279,9 @@ struct SchurPlan : SchurDims {
 	// reset of the coming factorization are already enqueued there
 	bool side_pending = false, side_padded = false;
 	int side_last = 0, clear_last = 0; // diagnostics of the last schur_form: SPP_INFO_SCHUR_SIDE, SPP_INFO_S_CLEAR
+	// the last spp_factor_solve_device left a factor a further solve may use (dense S in the own buffer, unsharded, SPP_OK):
+	// R in S, the whole block inverses in dense.tinv_all. Cleared on entry of every call that rewrites any of it (SPP_INFO_FACTOR_KEPT)
+	bool factor_kept = false;
 	int async_last = 0;            // ... of the last schur_finish: 1 = it returned on the factor's status with the stream still running (SPP_SOLVE_ASYNC), 0 = it drained the stream (SPP_INFO_SOLVE_ASYNC)
 	void release_all();
 };
@@ -316,6 +319,7 @@ struct DenseWork {
 	bool tail_disabled = false;    // a streamed launch timed out on this ctx: later factorizations take the per-step schedule
 	DevBuf<double> trsv_m;         // M_b = Tinv_b R_{b, b+1} per block row (M form of the backward substitution)
 	DevBuf<double> trsv_pay;       // hand-over pairs {value, check word} of the one-workgroup chain: x (nblk x 128) and w (nblk x 128)
+	DevBuf<double> trsm_w;         // multi-column solves (spp_dense_trsm.h): the panel of finished blocks, nblk * 128 rows x 128 columns
 	uint64_t epoch = 0;            // solves so far (backward-substitution chains tell one solve from the next by it)
 	int *h_chain_err = nullptr;    // timeout word of the chain kernels: page-locked, mapped host memory they store into on their error path alone (dense_chain_check)
 	int *d_chain_err = nullptr;    // ... its device address
@@ -390,6 +394,11 @@ struct spp_ctx {
 	spp::DevBuf<double> d_vals, d_rhs;
 	double *h_staging = nullptr; // page-locked host buffer handed out by spp_host_staging()
 	size_t h_staging_cap = 0;    // doubles
+	// spp_solve_device / spp_marginals_device (spp_solve_again.hip): the camera panel of a pass (ld x 128), the unit block
+	// columns and the selected rows of a covariance (the host image lives as long as its asynchronous upload may run)
+	spp::DevBuf<double> again_panel, again_cols;
+	spp::DevBuf<int64_t> again_rows;
+	std::vector<int64_t> again_rows_host;
 	spp::DevBuf<double> geom_partial; // partial sums of ||dx||^2 (spp_geometry.hip)
 	// profiling
 	spp::PhaseTimer timer;
@@ -520,6 +529,12 @@ void schur_form(spp_ctx *ctx, const double *d_vals, const double *d_rhs, double 
 int schur_finish(spp_ctx *ctx, const double *d_vals, double *d_S_rhs, double *d_rhs);
 void schur_pack(spp_ctx *ctx, double *S, double *packed, bool pack);
 
+// ---- spp_solve_again.hip ----
+// Lambda X = B in place for nrhs columns (n rows in Lambda's numbering, leading dimension ldb) against the kept factor
+void schur_solve_again(spp_ctx *ctx, const double *d_vals, double *d_B, int64_t ldb, int64_t nrhs);
+// E^T Lambda^-1 E of the selected vertices (block columns of Lambda), m x m, exactly symmetric
+void schur_marginals(spp_ctx *ctx, const double *d_vals, int64_t n_sel, const int64_t *h_vertices, double *d_cov);
+
 // ---- spp_dense.hip ----
 constexpr int DENSE_NB = 128;
 int dense_potrf_upper(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, bool keep_inverses);
@@ -534,6 +549,9 @@ int dense_info_fetch(spp_ctx *ctx, bool *dag_aborted = nullptr); // dag_aborted 
 void dense_info_copy_on(spp_ctx *ctx, hipStream_t st, int *h_status4);
 int dense_info_eval(spp_ctx *ctx, const int *h_status4, bool *dag_aborted = nullptr, bool drain_first = false);
 void dense_potrs_upper(spp_ctx *ctx, const double *d_R, int64_t n, int64_t ld, double *d_b);
+// R^T R X = B in place for nrhs columns against the factor and the block inverses of the last factorization (spp_dense_trsm.h)
+void dense_potrs_multi(spp_ctx *ctx, const double *d_R, int64_t n, int64_t ld, double *d_B, int64_t ldb, int64_t nrhs);
+void dense_tinv_complete(spp_ctx *ctx); // the stored block inverses in their whole form (no-op when they are)
 void dense_aux_park(int device, hipStream_t s); // hands the bulk stream of a closing context to the next one
 void dense_factor_steps(spp_ctx *ctx, double *d_A, int64_t ld, int64_t n, int64_t rows, int64_t ncols,
 	int64_t nsteps, bool has_rhs);
