@@ -129,6 +129,7 @@ int spp_set_shard(spp_ctx *ctx, int rank, int world_size);
 #define SPP_INFO_ASM_HUB_CHUNK   22 /* assembly of ternary edges: edges one workgroup of the hub reduction sums (C); a constant, needs no analysis */
 #define SPP_INFO_SOLVE_ASYNC    23 /* what the last spp_factor_solve_device / spp_schur_finish did (SPP_SOLVE_ASYNC): 1 it returned when the factor's status was known, the solves and the back-substitution still running on the stream; 0 it drained the stream (profiling on, stream capture, sparse reduced system, sparse mode, the switch at 0) */
 #define SPP_INFO_FACTOR_KEPT    24 /* 1: the ctx holds a factor spp_solve_device / spp_marginals_device may use: the last spp_factor_solve_device returned SPP_OK in SPP_MODE_SCHUR with a dense reduced system, unsharded, and nothing has rewritten it since; 0 otherwise (needs no analysis) */
+#define SPP_INFO_SPARSE_FACTOR_KEPT 25 /* 1: the ctx holds a sparse factor spp_sparse_solve_device / spp_sparse_marginals_device may use: the last spp_factor_solve_device returned SPP_OK in SPP_MODE_SPARSE, unsharded, and no call that drops it has been entered since; 0 otherwise (needs no analysis). SPP_INFO_FACTOR_KEPT stays 0 in the sparse mode */
 int spp_get_info(const spp_ctx *ctx, int what, int64_t *out);
 /* elimination order chosen by the analysis: order[k] = source block column eliminated k-th */
 int spp_get_ordering(const spp_ctx *ctx, int64_t *h_order);
@@ -209,6 +210,36 @@ int spp_solve_device(spp_ctx *ctx, const double *d_vals, double *d_B, int64_t ld
  * SPP_E_BADARG also for n_sel < 1, a vertex out of range or listed twice. Which damping Lambda carries is the caller's
  * choice (a bundle adjustment without a scale prior has a gauge direction only damping makes definite). */
 int spp_marginals_device(spp_ctx *ctx, const double *d_vals, int64_t n_sel, const int64_t *h_vertices, double *d_cov);
+
+/* ---- solve again on the kept SPARSE factor: pose graphs ------------------------
+ * Lambda X = B for nrhs further right-hand sides against the multifrontal factor the last successful
+ * spp_factor_solve_device / spp_factor_solve of this ctx left in the fronts of its sparse plan
+ * (SPP_INFO_SPARSE_FACTOR_KEPT): a forward and a backward multifrontal substitution, no factorization. d_B: n x nrhs,
+ * column-major, leading dimension ldb >= n, rows in Lambda's numbering, overwritten by X; nothing outside its n rows and
+ * nrhs columns is written. There is no d_vals: the fronts hold all of R, so nothing is asked of Lambda's values.
+ * Column j of the result has the same bits whatever the other columns hold, wherever it stands and however many columns
+ * the call carries; two runs give the same bits. (They are not the bits of spp_factor_solve_device on that column: its
+ * forward substitution rides inside the factorization and sums in another order.)
+ * STREAM-ORDERED: the call enqueues on the ctx stream and returns; d_B is complete for later work on that stream, for
+ * spp_memcpy_d2h and behind spp_synchronize. d_B must stay allocated until then.
+ * The factor is kept by SPP_OK of spp_factor_solve_device / spp_factor_solve when the ctx's mode is SPP_MODE_SPARSE (also
+ * SPP_MODE_AUTO resolving to it, and the repeated enqueue after a timed-out dependency-driven launch), unsharded. It is
+ * dropped on entry of every call that drops the dense Schur factor above: any factor / solve, spp_schur_form /
+ * spp_schur_finish, spp_dense_*, spp_analyze and the spp_assemble_analyze* calls, spp_set_shard, spp_free_memory. The two
+ * calls below keep it, and so do spp_solve_device / spp_marginals_device (which answer SPP_E_UNSUPPORTED in this mode).
+ * Refusals, each checked before anything is touched (the ctx stays usable):
+ * SPP_E_STATE: no kept factor -- never solved, the last solve returned SPP_NOT_POSDEF, or a later call dropped it.
+ * SPP_E_UNSUPPORTED: SPP_MODE_SCHUR, SPP_MODE_SCHUR_SPARSE, SPP_MODE_SCHUR_MIS, a sharded ctx.
+ * SPP_E_BADARG: a null pointer, nrhs < 1, ldb < n. */
+int spp_sparse_solve_device(spp_ctx *ctx, double *d_B, int64_t ldb, int64_t nrhs);
+/* Joint covariance of chosen vertices of a pose graph, the job of the reference's CMarginals (include/slam/Marginals.h):
+ * d_cov (m x m, column-major, m = sum of their widths) <- E^T Lambda^-1 E, E the unit block columns of the n_sel vertices
+ * h_vertices (block columns of Lambda of any widths, in any order, each at most once). Rows and columns follow h_vertices.
+ * One m-column spp_sparse_solve_device of unit columns built on the device; the upper triangle is computed and mirrored:
+ * exactly symmetric. Workspace: n x m doubles in the ctx. Ordering, keeping and refusals as above; SPP_E_BADARG also for
+ * n_sel < 1, a vertex out of range or listed twice. NOT FOR STREAM CAPTURE: the call waits for the ctx stream once on entry
+ * (the list of rows is staged in host memory of the ctx) and may reallocate its n x m workspace when m grows. */
+int spp_sparse_marginals_device(spp_ctx *ctx, int64_t n_sel, const int64_t *h_vertices, double *d_cov);
 
 /* split form for multi-GPU: (1) each rank forms its partial Schur complement and
  * reduced rhs into d_S_rhs = [S (ld x ld, column-major, upper blocks) | rhs (ld)] ; (2) the caller

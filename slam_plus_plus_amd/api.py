@@ -22,14 +22,16 @@ MODE_AUTO, MODE_SPARSE, MODE_SCHUR, MODE_SCHUR_SPARSE, MODE_SCHUR_MIS = 0, 1, 2,
 FLAG_PROFILE = 1
 INFO = dict(MODE=0, N=1, NNZB=2, NVALS=3, FACTOR_NNZ=4, FACTOR_FLOPS=5, N_REDUCED=6, N_POSES=7,
             N_LANDMARKS=8, SCHUR_PAIRS=9, N_OBS=10, SOLVE_BYTES=11, N_SUPERNODES=12, N_LEVELS=13, S_LD=14, S_NNZB=15, DENSE_STREAMED=16,
-            LM_STREAM=17, BS_GROUPS=18, SCHUR_SIDE=19, S_CLEAR=20, S_DEVICE_PTR=21, ASM_HUB_CHUNK=22, SOLVE_ASYNC=23, FACTOR_KEPT=24)
+            LM_STREAM=17, BS_GROUPS=18, SCHUR_SIDE=19, S_CLEAR=20, S_DEVICE_PTR=21, ASM_HUB_CHUNK=22, SOLVE_ASYNC=23, FACTOR_KEPT=24,
+            SPARSE_FACTOR_KEPT=25)
 PHASES = ["permute", "schur_inv", "schur_gemm", "schur_rhs", "factor", "trisolve", "backsubst", "assemble", "total"]
 
 # every symbol include/spp_hip.h declares (tests/test_abi.py checks the .so exports them all)
 EXPORTS = [
     "spp_create", "spp_destroy", "spp_free_memory", "spp_last_error", "spp_host_staging", "spp_set_stream", "spp_synchronize",
     "spp_analyze", "spp_set_shard", "spp_get_info", "spp_get_ordering", "spp_sparse_fronts", "spp_factor_solve",
-    "spp_factor_solve_device", "spp_solve_device", "spp_marginals_device", "spp_schur_buffer_size", "spp_schur_form", "spp_schur_finish",
+    "spp_factor_solve_device", "spp_solve_device", "spp_marginals_device", "spp_sparse_solve_device", "spp_sparse_marginals_device",
+    "spp_schur_buffer_size", "spp_schur_form", "spp_schur_finish",
     "spp_schur_packed_size", "spp_schur_pack", "spp_schur_unpack",
     "spp_assemble_analyze", "spp_assemble_get_structure", "spp_assemble_device", "spp_assemble_set_edge_weights",
     "spp_assemble_analyze_groups", "spp_assemble_groups_device", "spp_assemble_set_group_edge_weights",
@@ -82,6 +84,8 @@ def load_library():
         "spp_factor_solve_device": (cint, [vp, vp, vp]),
         "spp_solve_device": (cint, [vp, vp, vp, i64, i64]),
         "spp_marginals_device": (cint, [vp, vp, i64, vp, vp]),
+        "spp_sparse_solve_device": (cint, [vp, vp, i64, i64]),
+        "spp_sparse_marginals_device": (cint, [vp, i64, vp, vp]),
         "spp_schur_buffer_size": (cint, [vp, _c_i64p]),
         "spp_schur_form": (cint, [vp, vp, vp, vp]),
         "spp_schur_finish": (cint, [vp, vp, vp, vp]),
@@ -566,6 +570,31 @@ class Context:
         d_cov = DeviceArray(self, m * m)
         try:
             self._check(self.lib.spp_marginals_device(self.h, d_vals, vertices.size, _ptr(vertices), d_cov.ptr))
+            return d_cov.download().reshape((m, m), order="F")
+        finally:
+            d_cov.free()
+
+    def sparse_solve_device(self, d_B, nrhs, ldb=None):
+        """Lambda X = B for nrhs columns (device pointer d_B, column-major, leading dimension ldb, default n) against the
+        sparse factor the last successful factor_solve_device left in MODE_SPARSE (info("SPARSE_FACTOR_KEPT")).
+        Stream-ordered: B is complete behind synchronize() / a download."""
+        if ldb is None:
+            ldb = self.info("N")
+        return self._check(self.lib.spp_sparse_solve_device(self.h, d_B, int(ldb), int(nrhs)))
+
+    def sparse_marginals(self, vertices):
+        """joint covariance E^T Lambda^-1 E of the given vertices of a pose graph (block columns of Lambda, each at most
+        once, any widths and order) from the kept sparse factor, as an (m, m) numpy array; exactly symmetric"""
+        vertices = np.ascontiguousarray(vertices, dtype=np.int64)
+        keep = getattr(self, "_keep", None)
+        dim = np.asarray(keep.dim) if keep is not None else np.zeros(0, dtype=np.int32)
+        if vertices.size == 0 or vertices.min() < 0 or vertices.max() >= dim.size:
+            m = 1   # (the library rejects the list; the buffer only has to exist)
+        else:
+            m = max(1, int(dim[vertices].sum()))
+        d_cov = DeviceArray(self, m * m)
+        try:
+            self._check(self.lib.spp_sparse_marginals_device(self.h, vertices.size, _ptr(vertices), d_cov.ptr))
             return d_cov.download().reshape((m, m), order="F")
         finally:
             d_cov.free()

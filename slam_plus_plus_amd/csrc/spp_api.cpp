@@ -80,6 +80,13 @@ void dom_end(spp_ctx *ctx, double flops)
 
 } // namespace spp
 
+// every call that rewrites what a kept factor consists of -- or the plan it belongs to -- starts with this
+static inline void drop_kept_factors(spp_ctx *ctx)
+{
+	ctx->schur.factor_kept = false;
+	ctx->sparse_factor_kept = false;
+}
+
 // Both streams of the ctx idle. Since a solve may return with its triangular solves and back-substitution still running
 // (SPP_SOLVE_ASYNC), everything that frees or reallocates what those kernels work on, swaps the stream or closes the
 // ctx comes through here first.
@@ -147,7 +154,7 @@ int spp_free_memory(spp_ctx *ctx)
 	SPP_TRY(ctx)
 	(void)hipSetDevice(ctx->device);
 	ctx_drain(ctx);
-	ctx->schur.factor_kept = false;
+	drop_kept_factors(ctx);
 	ctx->schur.release_all();
 	sparse_release(ctx);
 	assemble_release(ctx);
@@ -292,7 +299,7 @@ int spp_set_shard(spp_ctx *ctx, int rank, int world_size)
 {
 	if(!ctx || world_size < 1 || rank < 0 || rank >= world_size)
 		return SPP_E_BADARG;
-	ctx->schur.factor_kept = false; // (the plan no longer matches the ctx)
+	drop_kept_factors(ctx); // (the plan no longer matches the ctx)
 	ctx->shard_rank = rank;
 	ctx->shard_world = world_size;
 	return SPP_OK;
@@ -311,7 +318,7 @@ int spp_analyze(spp_ctx *ctx, int64_t nb, const int64_t *col_ptr, const int64_t 
 	// sizes of the NEW structure beside the plan of the OLD one (the next solve would copy the wrong extents).
 	// The old plan is dropped first in any case -- after a failed analyze the ctx is "not analyzed".
 	ctx->mode = -1;
-	ctx->schur.factor_kept = false;
+	drop_kept_factors(ctx);
 	ctx_drain(ctx); // (the plan and the workspaces released below may still be at work for a solve that returned early)
 	VClock clk("spp_analyze");
 	Structure st;
@@ -422,7 +429,7 @@ int spp_get_info(const spp_ctx *ctx, int what, int64_t *out)
 	if(!ctx || !out)
 		return SPP_E_BADARG;
 	if(ctx->mode < 0 && what != SPP_INFO_NNZB && what != SPP_INFO_NVALS && what != SPP_INFO_N && what != SPP_INFO_DENSE_STREAMED &&
-	   what != SPP_INFO_ASM_HUB_CHUNK && what != SPP_INFO_FACTOR_KEPT)
+	   what != SPP_INFO_ASM_HUB_CHUNK && what != SPP_INFO_FACTOR_KEPT && what != SPP_INFO_SPARSE_FACTOR_KEPT)
 		return SPP_E_STATE;
 	switch(what) {
 	case SPP_INFO_MODE: *out = (ctx->mode != SPP_MODE_SCHUR) ? ctx->mode : ctx->schur.mis ? SPP_MODE_SCHUR_MIS :
@@ -451,6 +458,7 @@ int spp_get_info(const spp_ctx *ctx, int what, int64_t *out)
 	case SPP_INFO_S_DEVICE_PTR: *out = (ctx->mode == SPP_MODE_SCHUR) ? (int64_t)(uintptr_t)ctx->schur.S.p : 0; break;
 	case SPP_INFO_ASM_HUB_CHUNK: *out = ASM_HUB_CHUNK; break;
 	case SPP_INFO_FACTOR_KEPT: *out = (ctx->mode == SPP_MODE_SCHUR && ctx->schur.factor_kept) ? 1 : 0; break;
+	case SPP_INFO_SPARSE_FACTOR_KEPT: *out = (ctx->mode == SPP_MODE_SPARSE && ctx->sparse_factor_kept) ? 1 : 0; break;
 	default: return SPP_E_BADARG;
 	}
 	return SPP_OK;
@@ -645,7 +653,7 @@ int spp_schur_form(spp_ctx *ctx, const double *d_vals, const double *d_rhs, doub
 	if(!ctx || !d_vals || !d_rhs || !d_S_rhs)
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
-	ctx->schur.factor_kept = false; // (the packed operand, and with the own buffer S, are rewritten)
+	drop_kept_factors(ctx); // (the packed operand, and with the own buffer S, are rewritten)
 	SPP_REQUIRE(ctx->mode == SPP_MODE_SCHUR, SPP_E_STATE, "spp_schur_form: analyze in Schur mode first");
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	phases_reset(ctx);
@@ -707,7 +715,7 @@ int spp_schur_finish(spp_ctx *ctx, const double *d_vals, double *d_S_rhs, double
 	if(!ctx || !d_vals || !d_rhs_inout || !d_S_rhs)
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
-	ctx->schur.factor_kept = false; // (whatever the buffer: the block inverses of the ctx are rewritten)
+	drop_kept_factors(ctx); // (whatever the buffer: the block inverses of the ctx are rewritten)
 	SPP_REQUIRE(ctx->mode == SPP_MODE_SCHUR, SPP_E_STATE, "spp_schur_finish: analyze in Schur mode first");
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	// drains the stream for the status fetch, or -- dense S, SPP_SOLVE_ASYNC -- waits for the status alone and returns with the
@@ -727,7 +735,7 @@ int spp_factor_solve_device(spp_ctx *ctx, const double *d_vals, double *d_rhs)
 	if(!ctx || !d_vals || !d_rhs)
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
-	ctx->schur.factor_kept = false;
+	drop_kept_factors(ctx);
 	SPP_REQUIRE(ctx->mode >= 0, SPP_E_STATE, "spp_factor_solve: call spp_analyze first");
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	phases_reset(ctx);
@@ -755,6 +763,8 @@ int spp_factor_solve_device(spp_ctx *ctx, const double *d_vals, double *d_rhs)
 	// R in the own S buffer and the whole block inverses stay valid until a call that rewrites them: spp_solve_device
 	ctx->schur.factor_kept = ret == SPP_OK && ctx->mode == SPP_MODE_SCHUR && !ctx->schur.sparse_S && !ctx->schur.mis &&
 		ctx->shard_world == 1;
+	// the sparse mode: every supernode's pivot rows of R stay in the plan's fronts until the next factorization
+	ctx->sparse_factor_kept = ret == SPP_OK && ctx->mode == SPP_MODE_SPARSE && ctx->shard_world == 1;
 	return ret;
 	SPP_CATCH(ctx)
 }
@@ -793,6 +803,40 @@ int spp_marginals_device(spp_ctx *ctx, const double *d_vals, int64_t n_sel, cons
 	SPP_CATCH(ctx)
 }
 
+// what spp_sparse_solve_device and spp_sparse_marginals_device check before they touch anything
+static void require_kept_sparse_factor(const spp_ctx *ctx, const char *who)
+{
+	SPP_REQUIRE(ctx->mode >= 0, SPP_E_STATE, std::string(who) + ": no kept factor (call spp_analyze and spp_factor_solve_device first)");
+	SPP_REQUIRE(ctx->mode == SPP_MODE_SPARSE && ctx->shard_world == 1, SPP_E_UNSUPPORTED,
+		std::string(who) + ": only SPP_MODE_SPARSE, unsharded, keeps a sparse factor (the dense Schur mode: spp_solve_device)");
+	SPP_REQUIRE(ctx->sparse_factor_kept, SPP_E_STATE, std::string(who) + ": no kept factor (the last spp_factor_solve_device failed, or a later call dropped it)");
+}
+
+int spp_sparse_solve_device(spp_ctx *ctx, double *d_B, int64_t ldb, int64_t nrhs)
+{
+	if(!ctx || !d_B || nrhs < 1)
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	require_kept_sparse_factor(ctx, "spp_sparse_solve_device");
+	SPP_REQUIRE(ldb >= ctx->st.n, SPP_E_BADARG, "spp_sparse_solve_device: ldb < n");
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	sparse_solve_again(ctx, d_B, ldb, nrhs);
+	return SPP_OK;
+	SPP_CATCH(ctx)
+}
+
+int spp_sparse_marginals_device(spp_ctx *ctx, int64_t n_sel, const int64_t *h_vertices, double *d_cov)
+{
+	if(!ctx || !h_vertices || !d_cov || n_sel < 1)
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	require_kept_sparse_factor(ctx, "spp_sparse_marginals_device");
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	sparse_marginals(ctx, n_sel, h_vertices, d_cov);
+	return SPP_OK;
+	SPP_CATCH(ctx)
+}
+
 int spp_factor_solve(spp_ctx *ctx, const double *h_vals, double *h_rhs)
 {
 	if(!ctx || !h_vals || !h_rhs)
@@ -823,7 +867,7 @@ int spp_assemble_analyze(spp_ctx *ctx, int64_t nv, const int32_t *h_dim, int64_t
 	if(!h_dim || !h_v0 || !h_v1 || nv <= 0 || ne <= 0)
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
-	ctx->schur.factor_kept = false;
+	drop_kept_factors(ctx);
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	assemble_analyze(ctx, nv, h_dim, 1, &ne, &h_v0, &h_v1, nullptr, &d0, &d1, &rd, unary_vertex);
 	return SPP_OK;
@@ -840,7 +884,7 @@ int spp_assemble_analyze_groups(spp_ctx *ctx, int64_t nv, const int32_t *h_dim, 
 	if(!h_dim || nv <= 0 || n_groups <= 0 || !h_ne || !h_v0 || !h_v1 || !h_d0 || !h_d1 || !h_rd)
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
-	ctx->schur.factor_kept = false;
+	drop_kept_factors(ctx);
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	SPP_REQUIRE(n_groups <= SPP_MAX_EDGE_GROUPS, SPP_E_UNSUPPORTED, "more than SPP_MAX_EDGE_GROUPS edge groups");
 	int64_t total = 0;
@@ -912,7 +956,7 @@ int spp_assemble_analyze_ternary(spp_ctx *ctx, int64_t nv, const int32_t *h_dim,
 	if(!h_dim || !h_v0 || !h_v1 || !h_v2 || nv <= 0 || ne <= 0)
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
-	ctx->schur.factor_kept = false;
+	drop_kept_factors(ctx);
 	SPP_REQUIRE(d0 == 6 && d1 == 3 && d2 == 6 && live2 == 5 && rd == 2, SPP_E_UNSUPPORTED,
 		"ternary edge shape (d0, d1, d2, rd) / live2 not instantiated: (6,3,6,2) / 5");
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
@@ -1296,7 +1340,7 @@ int spp_dense_potrf_upper(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld)
 	if(!ctx || !d_A || n <= 0 || ld < n)
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
-	ctx->schur.factor_kept = false;
+	drop_kept_factors(ctx);
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	const int64_t ldp = ((n + 1 + DENSE_NB - 1) / DENSE_NB) * DENSE_NB;
 	DevBuf<double> tmp;
@@ -1320,7 +1364,7 @@ int spp_dense_posv_multi(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, doubl
 	if(!ctx || !d_A || !d_B || n <= 0 || ld < n || ldb < n || nrhs < 1)
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
-	ctx->schur.factor_kept = false;
+	drop_kept_factors(ctx);
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	const int64_t ldp = ((n + 1 + DENSE_NB - 1) / DENSE_NB) * DENSE_NB;
 	DevBuf<double> tmp;
@@ -1416,7 +1460,7 @@ static int dense_posv_entry(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, do
 	if(!ctx || !d_A || !d_b || n <= 0 || ld < n || nwords < 0 || (nwords && !words))
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
-	ctx->schur.factor_kept = false;
+	drop_kept_factors(ctx);
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	std::vector<uint64_t> mask(words, words + nwords);
 	std::vector<int32_t> order;
@@ -1474,7 +1518,7 @@ int spp_dense_gemm_tn_sub(spp_ctx *ctx, int64_t m, int64_t n, int64_t k, const d
 	if(!ctx || !d_A || !d_B || !d_C)
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
-	ctx->schur.factor_kept = false;
+	drop_kept_factors(ctx);
 	SPP_REQUIRE((lda % 2) == 0 && (ldb % 2) == 0, SPP_E_BADARG, "gemm_tn_sub: lda/ldb must be even (16-byte loads)");
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	dense_gemm_tn_sub(ctx, m, n, k, d_A, lda, d_B, ldb, d_C, ldc, false);
@@ -1489,7 +1533,7 @@ int spp_dense_gemm_tn_sub_upper(spp_ctx *ctx, int64_t m, int64_t n, int64_t k, c
 	if(!ctx || !d_A || !d_B || !d_C)
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
-	ctx->schur.factor_kept = false;
+	drop_kept_factors(ctx);
 	SPP_REQUIRE((lda % 2) == 0 && (ldb % 2) == 0, SPP_E_BADARG, "gemm_tn_sub: lda/ldb must be even (16-byte loads)");
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	dense_gemm_tn_sub(ctx, m, n, k, d_A, lda, d_B, ldb, d_C, ldc, true);
@@ -1503,7 +1547,7 @@ int spp_dense_front_factor(spp_ctx *ctx, double *d_F, int64_t ld, int64_t w, int
 	if(!ctx || !d_F)
 		return SPP_E_BADARG;
 	SPP_TRY(ctx)
-	ctx->schur.factor_kept = false;
+	drop_kept_factors(ctx);
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	return dense_front_factor(ctx, d_F, ld, w, h, d_image);
 	SPP_CATCH(ctx)

@@ -399,6 +399,9 @@ struct spp_ctx {
 	spp::DevBuf<double> again_panel, again_cols;
 	spp::DevBuf<int64_t> again_rows;
 	std::vector<int64_t> again_rows_host;
+	// spp_sparse_solve_device / spp_sparse_marginals_device (spp_sparse_solve.hip): the fronts of the sparse plan hold the
+	// factor of the last spp_factor_solve_device (SPP_MODE_SPARSE, SPP_OK) and nothing has rewritten them since
+	bool sparse_factor_kept = false;
 	spp::DevBuf<double> geom_partial; // partial sums of ||dx||^2 (spp_geometry.hip)
 	// profiling
 	spp::PhaseTimer timer;
@@ -534,6 +537,13 @@ void schur_pack(spp_ctx *ctx, double *S, double *packed, bool pack);
 void schur_solve_again(spp_ctx *ctx, const double *d_vals, double *d_B, int64_t ldb, int64_t nrhs);
 // E^T Lambda^-1 E of the selected vertices (block columns of Lambda), m x m, exactly symmetric
 void schur_marginals(spp_ctx *ctx, const double *d_vals, int64_t n_sel, const int64_t *h_vertices, double *d_cov);
+
+// ---- spp_sparse_solve.hip ----
+// Lambda X = B in place for nrhs columns (n rows in Lambda's numbering, leading dimension ldb) against the fronts the last
+// sparse factorization left in the plan
+void sparse_solve_again(spp_ctx *ctx, double *d_B, int64_t ldb, int64_t nrhs);
+// E^T Lambda^-1 E of the selected vertices (block columns of Lambda), m x m, exactly symmetric
+void sparse_marginals(spp_ctx *ctx, int64_t n_sel, const int64_t *h_vertices, double *d_cov);
 
 // ---- spp_dense.hip ----
 constexpr int DENSE_NB = 128;
