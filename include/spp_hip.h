@@ -623,11 +623,24 @@ int spp_schur_cam_order_host(int64_t nb, const int32_t *dim, const int64_t *col_
  * early != 0 and the conditions of DESIGN section 11 met, the tiles of the trailing tile rows r* .. go first; otherwise
  * the table is the sorted one. info (may be NULL, 5 entries): tiles in front, r* (tile rows when none), whole rows
  * resident D, live demand of the other tiles, tiles of the widest row. Returns the number of entries or a negative error.
- * Bit 1 of early (early = 3): the table the launch uses under a step order other than k ascending (SPP_TAIL_EARLY_LEAD,
- * DESIGN section 25) -- a trailing run too large to go first whole has its leading rows r* .. r2 in front, then the rows
- * < r* by the depth of their diagonal tile, then the rows > r2; info as above with the tiles and r* of those rows. */
+ * Bit 1 of early (early = 3): the table the launch uses under the depth order of the mask (spp_tail_step_order_host) where
+ * that is not k ascending (SPP_TAIL_EARLY_LEAD) -- a trailing run too large to go first whole has its
+ * leading rows r* .. r2 in front, then the rows < r* by the depth of their diagonal tile, then the rows > r2; info as above
+ * with the tiles and r* of those rows. The call is spp_tail_plan_host with nothing in front and no limit on the tile rows. */
 int spp_tail_order_host(int64_t n, int has_rhs, const uint64_t *words, int64_t nwords, int resident, int early, double beta,
 	int32_t *table, int32_t *info);
+/* host only: everything the host decides for the streamed launch that takes the region behind the
+ * first `front` tile rows (0: the whole factorization) of an n x n matrix (+ right-hand side column with has_rhs), computed
+ * by the function the launch itself calls. words[0 .. nwords): the FILLED tile mask of the whole matrix (nwords =
+ * ceil(n / 128), or 0: no mask); step_order[0 .. norder) (norder = 0: none): the caller's step order, used where it has one
+ * entry per tile row and front = 0; tail_rows: SPP_TAIL_ROWS; resident, beta: as above; early: bit 0 SPP_TAIL_EARLY, bit 1
+ * SPP_TAIL_EARLY_LEAD, bit 2 set = SPP_TAIL_MASK off. Out (each may be NULL but table): rowbits (65 words) -- word i + 1 the
+ * listed tiles of the region's tile row i in region indices, word 0 the row panel in front of the region --, steps (72
+ * entries): the launch's step list as the kernel unpacks it, -1 = the row panel in front, 127 behind the last step,
+ * table and info as above. Returns the number of table entries, 0 where the region is not one streamed launch (nothing
+ * is written), SPP_E_BADARG for a step order that is no permutation, or another negative error. */
+int spp_tail_plan_host(int64_t n, int has_rhs, const uint64_t *words, int64_t nwords, const int32_t *step_order, int64_t norder,
+	int front, int tail_rows, int resident, int early, double beta, uint64_t *rowbits, int32_t *steps, int32_t *table, int32_t *info);
 /* spp_dense_posv_masked with the order in which a tile of the streamed factorization applies its steps given:
  * step_order[0 .. nwords), a permutation of the tile rows 0 .. nwords - 1 (anything else: SPP_E_BADARG; nwords > 0). A tile
  * applies the steps its mask selects in that order instead of k ascending -- a different summation order, the same

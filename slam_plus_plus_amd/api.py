@@ -43,7 +43,7 @@ EXPORTS = [
     "spp_device_free", "spp_memcpy_h2d", "spp_memcpy_d2h", "spp_memcpy_d2d", "spp_get_phase_ms", "spp_get_dominant_kernel",
     "spp_microbench_copy", "spp_microbench_mfma_f64", "spp_microbench_ctile", "spp_microbench_update", "spp_block_ordering", "spp_schur_plan_host", "spp_set_profiling", "spp_se2_linearize_device", "spp_se2_update_device", "spp_ba_linearize_device", "spp_ba_stereo_linearize_device", "spp_ba_update_device", "spp_sim3_ba_linearize_device", "spp_sim3_update_device", "spp_se3_linearize_device", "spp_se3_update_device", "spp_edge_chi2_device", "spp_edge_robust_weights_device", "spp_edge_hessian_maxdiag_device",
     "spp_lm_gain_denominator_device", "spp_dense_potrf_upper", "spp_dense_posv", "spp_dense_posv_multi",
-    "spp_dense_posv_masked", "spp_tile_mask_host", "spp_schur_tile_mask_host", "spp_tail_order_host", "spp_schur_cam_order_host",
+    "spp_dense_posv_masked", "spp_tile_mask_host", "spp_schur_tile_mask_host", "spp_tail_order_host", "spp_tail_plan_host", "spp_schur_cam_order_host",
     "spp_dense_posv_ordered", "spp_tail_step_order_host", "spp_schur_step_order_host",
     "spp_dense_gemm_tn_sub", "spp_dense_gemm_tn_sub_upper", "spp_dense_front_factor", "spp_version",
 ]
@@ -145,6 +145,7 @@ def load_library():
         "spp_tile_mask_host": (cint, [i64, cint, i64, vp, vp, cint, cint, vp, vp]),
         "spp_schur_tile_mask_host": (cint, [i64, vp, vp, vp, cint, cint, vp]),
         "spp_tail_order_host": (cint, [i64, cint, vp, i64, cint, cint, dbl, vp, vp]),
+        "spp_tail_plan_host": (cint, [i64, cint, vp, i64, vp, i64, cint, cint, cint, cint, dbl, vp, vp, vp, vp]),
         "spp_schur_cam_order_host": (cint, [i64, vp, vp, vp, cint, cint, cint, vp, vp, vp]),
         "spp_dense_posv_ordered": (cint, [vp, vp, i64, i64, vp, vp, i64, vp]),
         "spp_tail_step_order_host": (cint, [i64, vp, i64, vp]),
@@ -278,6 +279,40 @@ def tail_order_host(n, words, has_rhs=True, resident=256, early=True, beta=0.0):
         raise SppError("spp_tail_order_host failed: %d" % code)
     tiles = [(int(t) >> 16, int(t) & 0xffff) for t in table[:code]]
     return tiles, dict(zip(("n_early", "r_star", "rows_resident", "live_demand", "widest"), (int(v) for v in info)))
+
+
+TAIL_NO_STEP = 127   # the step list's entry behind the last step
+SPP_E_BADARG = -1
+
+
+def tail_plan_host(n, words, step_order=None, front=0, has_rhs=True, tail_rows=44, resident=256, early=3, beta=0.0, tail_mask=True):
+    """Host-only: what the host decides for the streamed launch behind the first `front` tile rows (0: the whole
+    factorization) of an n x n matrix with the filled tile mask `words` (None: no mask) and the caller's step order
+    `step_order` (None: none), from the function the launch calls (spp_tail_plan_host). tail_rows, early (bit 0
+    SPP_TAIL_EARLY, bit 1 SPP_TAIL_EARLY_LEAD), beta and tail_mask are the switches' values. Returns None where the region
+    is not one streamed launch, else a dict: rowbits (Tr + 1 ints, [0] the row panel in front), steps (the 72 unpacked
+    entries of the step list), tiles (list of (i, j) in workgroup order), info (as tail_order_host). A step order that is
+    no permutation raises SppError with code SPP_E_BADARG. No GPU needed."""
+    lib = load_library()
+    words = np.ascontiguousarray(words if words is not None else [], dtype=np.uint64)
+    so = np.ascontiguousarray(step_order if step_order is not None else [], dtype=np.int32)
+    rowbits = np.zeros(65, dtype=np.uint64)
+    steps = np.zeros(72, dtype=np.int32)
+    table = np.zeros(64 * 65 // 2 + 64, dtype=np.int32)
+    info = np.zeros(5, dtype=np.int32)
+    code = lib.spp_tail_plan_host(int(n), 1 if has_rhs else 0, _ptr(words) if words.size else None, words.size,
+                                  _ptr(so) if so.size else None, so.size, int(front), int(tail_rows), int(resident),
+                                  int(early) | (0 if tail_mask else 4), float(beta), _ptr(rowbits), _ptr(steps), _ptr(table), _ptr(info))
+    if code < 0:
+        err = SppError("spp_tail_plan_host failed: %d" % code)
+        err.code = code
+        raise err
+    if code == 0:
+        return None
+    tr = -(-int(n) // 128) - int(front)
+    return {"rowbits": [int(w) for w in rowbits[:tr + 1]], "steps": steps.tolist(),
+            "tiles": [(int(t) >> 16, int(t) & 0xffff) for t in table[:code]],
+            "info": dict(zip(("n_early", "r_star", "rows_resident", "live_demand", "widest"), (int(v) for v in info)))}
 
 
 def tail_step_order_host(n, words):

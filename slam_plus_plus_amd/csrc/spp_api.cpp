@@ -173,8 +173,7 @@ int spp_free_memory(spp_ctx *ctx)
 	ctx->dense.trsv_m.release();
 	ctx->dense.tail_pub.release();
 	ctx->dense.tail_order.release();
-	ctx->dense.tail_order_tr = ctx->dense.tail_order_tc = 0;
-	ctx->dense.tail_order_bits.clear();
+	ctx->dense.tail_plan.key = TailPlan::Key(); // (matches no launch: the next one makes and uploads its table)
 	ctx->dense.tail_dinv.release();
 	ctx->dense.tail_epoch = 0;
 	ctx->dense.epoch = 0;
@@ -1407,29 +1406,49 @@ int spp_tile_mask_host(int64_t n, int bs, int64_t nblk, const int32_t *i1, const
 	}
 }
 
+int spp_tail_plan_host(int64_t n, int has_rhs, const uint64_t *words, int64_t nwords, const int32_t *step_order, int64_t norder,
+	int front, int tail_rows, int resident, int early, double beta, uint64_t *rowbits, int32_t *steps, int32_t *table, int32_t *info)
+{
+	const int64_t nsteps = (n + DENSE_NB - 1) / DENSE_NB;
+	if(n <= 0 || nwords < 0 || nwords > TAIL_MAX_ROWS || (nwords && (!words || nwords != nsteps)) || norder < 0 || (norder && !step_order) ||
+	   front < 0 || !table || !(beta >= 0))
+		return SPP_E_BADARG;
+	try {
+		const std::vector<uint64_t> mask(words, words + nwords);
+		const std::vector<int32_t> order(step_order, step_order + norder);
+		const TailSwitches sw = {tail_rows, (early & 4) ? 0 : 1, early & 1, (early >> 1) & 1, beta};
+		const TailPlan p = tail_plan(nwords ? &mask : nullptr, norder ? &order : nullptr, nsteps, n, has_rhs ? n + 1 : n, (int64_t)front - 1,
+			resident, sw);
+		if(!p.applies)
+			return 0;
+		if(rowbits)
+			std::copy(p.key.rowbits.begin(), p.key.rowbits.end(), rowbits);
+		for(int q = 0; steps && q < 8 * TAIL_SORDER_WORDS; ++ q)
+			steps[q] = tail_sorder_at(p.sorder, q);
+		std::copy(p.table.begin(), p.table.end(), table);
+		if(info)
+			std::copy(p.info, p.info + 5, info);
+		return (int)p.table.size();
+	} catch(const Error &e) {
+		return e.code;
+	} catch(...) {
+		return SPP_E_NOMEM;
+	}
+}
+
 int spp_tail_order_host(int64_t n, int has_rhs, const uint64_t *words, int64_t nwords, int resident, int early, double beta,
 	int32_t *table, int32_t *info)
 {
 	const int64_t Tr = (n + DENSE_NB - 1) / DENSE_NB, Tc = has_rhs ? n / DENSE_NB + 1 : Tr;
-	if(n <= 0 || Tr > 64 || Tc > 64 || nwords < 0 || (nwords && (!words || nwords != Tr)) || !table || !(beta >= 0))
+	if(n <= 0 || Tr > 64 || Tc > 64)
 		return SPP_E_BADARG;
 	try {
-		// the step words as the streamed launch of a whole factorization forms them (launch_dense_tail, k = -1)
-		std::vector<uint64_t> bits((size_t)Tr + 1);
-		const uint64_t all_cols = Tc == 64 ? ~0ull : (1ull << Tc) - 1;
-		bits[0] = all_cols;
-		for(int64_t i = 0; i < Tr; ++ i)
-			bits[(size_t)i + 1] = (((nwords ? words[i] : all_cols) | (1ull << i)) & ~((1ull << i) - 1)) & all_cols;
-		std::vector<int> order;
-		int oinfo[5];
-		const bool use = nwords && early; // (as the launch: only with a mask in force)
-		tail_order_table(bits, (int)Tr, (int)Tc, false, beta, use ? resident : 0, use, order, oinfo, use && (early & 2) != 0);
-		for(size_t q = 0; q < order.size(); ++ q)
-			table[q] = order[q];
-		if(info)
-			for(int q = 0; q < 5; ++ q)
-				info[q] = oinfo[q];
-		return (int)order.size();
+		// (bit 1 of early: the launch seats leading rows only under a step order other than k ascending -- the mask's depth order)
+		std::vector<int32_t> order;
+		if(nwords == Tr && words && (early & 2))
+			tail_step_order(std::vector<uint64_t>(words, words + nwords), order);
+		return spp_tail_plan_host(n, has_rhs, words, nwords, order.data(), (int64_t)order.size(), 0, TAIL_MAX_ROWS, resident, (early ? 1 : 0) | (early & 2), beta,
+			nullptr, nullptr, table, info);
 	} catch(...) {
 		return SPP_E_NOMEM;
 	}
@@ -1469,12 +1488,7 @@ static int dense_posv_entry(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, do
 		tile_mask_close(n, true, true, mask);
 	}
 	if(step_order) {
-		std::vector<char> seen((size_t)nwords, 0);
-		for(int64_t q = 0; q < nwords; ++ q) {
-			SPP_REQUIRE(step_order[q] >= 0 && step_order[q] < nwords && !seen[(size_t)step_order[q]], SPP_E_BADARG,
-				"posv: the step order must be a permutation of the tile rows 0 .. nwords - 1");
-			seen[(size_t)step_order[q]] = 1;
-		}
+		SPP_REQUIRE(is_permutation(step_order, nwords), SPP_E_BADARG, "posv: the step order must be a permutation of the tile rows 0 .. nwords - 1");
 		order.assign(step_order, step_order + nwords);
 	}
 	TileMaskGuard guard(ctx->dense, &mask, &order);

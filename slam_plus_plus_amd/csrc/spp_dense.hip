@@ -1523,29 +1523,33 @@ static bool launch_dense_tail(spp_ctx *ctx, double *d_A, int64_t ld, int64_t row
 	const int64_t c1 = (k + 1) * NB; // (k = -1: the whole factorization, no row panel in front of it)
 	if(!dense_tail_applies(ctx, rows, nsteps))
 		return false;
-	const int Tr = (int)(nsteps - (k + 1)), Tc = (int)((ncols - c1 + NB - 1) / NB);
-	if(Tr < 1 || Tr > sw.tail_rows || Tc < Tr || Tc > Tr + 1 || Tc > TAIL_MAX_ROWS) // (tail_rows is 0 with the streamed tail switched off)
-		return false;
-	// (more tiles than CUs are fine: workgroups are dispatched row by row and leave after their own step, a workgroup that
-	// starts late finds the row tiles of the steps it missed in memory and catches up at the speed of its matrix cores)
-	// The step words of the region: bit j of bits[i + 1] = tile (i, j) of the region is nonzero, bits[0] = the row panel
-	// in front of it. From the caller's filled mask of the whole matrix (global tile indices, one word per tile row) --
-	// a sub-pattern of a filled pattern that starts at a later step is filled too --, or every tile.
-	const std::vector<uint64_t> *mask = (sw.tail_mask && dw.tile_mask && (int64_t)dw.tile_mask->size() == nsteps) ? dw.tile_mask : nullptr;
-	std::vector<uint64_t> bits((size_t)Tr + 1);
-	const uint64_t all_cols = Tc == 64 ? ~0ull : (1ull << Tc) - 1;
-	for(int i = -1; i < Tr; ++ i) {
-		const int64_t g = k + 1 + i; // global tile row
-		uint64_t w = (mask && g >= 0) ? ((*mask)[(size_t)g] >> (k + 1)) : all_cols;
-		if(i >= 0)
-			w = (w | (1ull << i)) & ~((1ull << i) - 1); // the diagonal tile always, nothing below it
-		bits[(size_t)i + 1] = w & all_cols;
-	}
 	hipStream_t s = ctx->stream;
 	static uint64_t attr_seen = 0;
 	if(first_on_this_device(attr_seen))
 		SPP_HIP_CHECK(hipFuncSetAttribute((const void*)dense_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
 			TAIL_LDS_DOUBLES * (int)sizeof(double)));
+	if(dw.tail_resident < 0) { // workgroups the device holds at once: the table's rule for seating tiles early depends on it
+		int per_cu = 0;
+		hipDeviceProp_t prop;
+		if(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)dense_tail_kernel, POTRF_THREADS,
+		   TAIL_LDS_DOUBLES * sizeof(double)) == hipSuccess && hipGetDeviceProperties(&prop, ctx->device) == hipSuccess)
+			dw.tail_resident = std::max(per_cu, 0) * prop.multiProcessorCount;
+		else {
+			(void)hipGetLastError();
+			dw.tail_resident = 0; // (unknown: nothing goes in front)
+		}
+	}
+	// Step words, step list and workgroup table: tail_plan() in spp_tile_plan.cpp has the rules. The table is kept from launch
+	// to launch, made and uploaded again only when its key changes.
+	TailPlan plan = tail_plan(dw.tile_mask, dw.step_order, nsteps, rows, ncols, k, dw.tail_resident, TailSwitches::of(sw), &dw.tail_plan);
+	if(!plan.applies)
+		return false;
+	if(plan.table_fresh && !dw.tail_plan.table.empty())
+		SPP_HIP_CHECK(hipStreamSynchronize(s)); // (an upload of the table's former host image may still be reading it)
+	dw.tail_plan = std::move(plan);
+	const TailPlan &p = dw.tail_plan; // (the asynchronous upload reads its table after this call returns)
+	const int Tr = p.key.Tr, Tc = p.key.Tc, ntile = (int)p.table.size();
+	// buffers and epoch of the hand-over counters; the table, where it is a new one
 	if(dw.tail_pub.cap < (size_t)Tr * Tc) {
 		dw.tail_pub.reserve(std::max<size_t>((size_t)Tr * Tc, 24 * 25));
 		SPP_HIP_CHECK(hipMemsetAsync(dw.tail_pub.p, 0, dw.tail_pub.cap * sizeof(int), s));
@@ -1557,90 +1561,26 @@ static bool launch_dense_tail(spp_ctx *ctx, double *d_A, int64_t ld, int64_t row
 		SPP_HIP_CHECK(hipMemsetAsync(dw.tail_pub.p, 0, dw.tail_pub.cap * sizeof(int), s));
 		dw.tail_epoch = 1;
 	}
-	// Workgroup -> tile. Tile (i, j) needs row tiles of (k, i) and (k, j), k < i, so any key alpha i + beta j with alpha > 0,
-	// beta >= 0 sorts the tiles topologically (producers before consumers: progress whatever is resident). Row by row
-	// (beta = 0) the 256 CUs start on the first ~6 rows, far tiles included, and the near-diagonal tiles of the rows
-	// behind them start late; beta > 0 holds the far columns back a little in favour of those.
-	// With a tile mask in force the tiles that every early step updates but that row by row get a CU many steps late (the
-	// trailing triangle of a bordered band) are seated first: tail_order_table() in spp_tile_plan.cpp has the rule and the
-	// condition under which progress still holds -- it depends on how many workgroups the device holds at once. Without
-	// a mask the table is the sorted one.
-	const bool early = mask != nullptr && sw.tail_early != 0;
-	if(early && dw.tail_resident < 0) {
-		int per_cu = 0;
-		hipDeviceProp_t prop;
-		if(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)dense_tail_kernel, POTRF_THREADS,
-		   TAIL_LDS_DOUBLES * sizeof(double)) == hipSuccess && hipGetDeviceProperties(&prop, ctx->device) == hipSuccess)
-			dw.tail_resident = std::max(per_cu, 0) * prop.multiProcessorCount;
-		else {
-			(void)hipGetLastError();
-			dw.tail_resident = 0; // (unknown: nothing goes in front)
-		}
-	}
-	// (a trailing run too large to be seated whole: its leading rows, where a step order lets a seated tile keep level with
-	// the chains that feed it -- tail_order_table's lead)
-	const bool ordered = k < 0 && dw.step_order && (int64_t)dw.step_order->size() == nsteps;
-	bool ascending = true;
-	for(int q = 0; ordered && q < Tr; ++ q)
-		ascending = ascending && (*dw.step_order)[(size_t)q] == q;
-	const bool lead = early && ordered && !ascending && sw.tail_early_lead != 0;
-	if(dw.tail_order_tr != Tr || dw.tail_order_tc != Tc || dw.tail_order_bits != bits || dw.tail_order_pre != (k >= 0) ||
-	   dw.tail_order_masked != early || dw.tail_order_lead != lead) {
-		if(!dw.tail_order_host.empty())
-			SPP_HIP_CHECK(hipStreamSynchronize(s)); // (an upload of the table's former host image may still be reading it)
-		std::vector<int> &order = dw.tail_order_host; // (the asynchronous upload reads it after this call returns)
-		int oinfo[5];
-		tail_order_table(bits, Tr, Tc, k >= 0, sw.tail_order_beta, early ? dw.tail_resident : 0, early, order, oinfo, lead);
+	if(p.table_fresh) {
 		if(sw.verbose)
 			fprintf(stderr, "[spp] streamed tail: %d x %d tiles, %d listed, %d resident; %d tiles of rows %d.. seated first (whole rows resident %d, live demand %d)\n",
-				Tr, Tc, (int)order.size(), early ? dw.tail_resident : 0, oinfo[0], oinfo[1], oinfo[2], oinfo[3]);
-		dw.tail_order.upload(order, s);
-		dw.tail_order_tr = Tr;
-		dw.tail_order_tc = Tc;
-		dw.tail_order_bits = bits;
-		dw.tail_order_pre = k >= 0;
-		dw.tail_order_masked = early;
-		dw.tail_order_lead = lead;
+				Tr, Tc, ntile, p.resident, p.info[0], p.info[1], p.info[2], p.info[3]);
+		dw.tail_order.upload(p.table, s);
 	}
-	const int ntile = (int)dw.tail_order_host.size();
+	if(sw.verbose && p.ordered)
+		fprintf(stderr, "[spp] streamed tail: %d steps in the caller's step order\n", Tr);
 	TailArgs a;
 	a.order = dw.tail_order.p;
 	memset(a.rowbits, 0, sizeof(a.rowbits));
-	for(size_t q = 0; q < bits.size(); ++ q)
-		a.rowbits[q] = bits[q];
-	// The step list: k ascending (the row panel in front of the region first), or the caller's step order where this
-	// launch is the whole factorization -- with or without its mask in force (SPP_TAIL_MASK changes scheduling, never bits).
-	{
-		const std::vector<int32_t> *so = ordered ? dw.step_order : nullptr;
-		if(so) { // (the kernel indexes its step words with these)
-			uint64_t seen = 0;
-			for(int q = 0; q < Tr; ++ q) {
-				const int32_t v = (*so)[(size_t)q];
-				SPP_REQUIRE(v >= 0 && v < Tr && !((seen >> v) & 1), SPP_E_BADARG, "streamed tail: the step order is not a permutation of the tile rows");
-				seen |= 1ull << v;
-			}
-		}
-		unsigned char list[sizeof(a.sorder)];
-		memset(list, TAIL_NO_STEP, sizeof(list));
-		int p = 0;
-		if(k >= 0)
-			list[p ++] = (unsigned char)(signed char)-1;
-		for(int q = 0; q < Tr; ++ q)
-			list[p ++] = (unsigned char)(so ? (*so)[(size_t)q] : q);
-		for(size_t w = 0; w < sizeof(a.sorder) / 8; ++ w) {
-			a.sorder[w] = 0;
-			for(int b = 0; b < 8; ++ b)
-				a.sorder[w] |= (unsigned long long)list[8 * w + b] << (8 * b);
-		}
-		if(sw.verbose && so)
-			fprintf(stderr, "[spp] streamed tail: %d steps in the caller's step order\n", Tr);
-	}
+	std::copy(p.key.rowbits.begin(), p.key.rowbits.end(), a.rowbits);
+	static_assert(sizeof(a.sorder) == sizeof(p.sorder), "one layout of the step list");
+	memcpy(a.sorder, p.sorder, sizeof(a.sorder));
 	a.A = d_A;
 	a.ld = ld;
 	a.rows = rows;
 	a.ncols = ncols;
 	a.c0 = c1;
-	a.have_pre = (k >= 0) ? 1 : 0;
+	a.have_pre = p.key.have_pre ? 1 : 0;
 	a.Tr = Tr;
 	a.Tc = Tc;
 	a.has_rhs = has_rhs ? 1 : 0;
@@ -1668,7 +1608,7 @@ static bool launch_dense_tail(spp_ctx *ctx, double *d_A, int64_t ld, int64_t row
 		dom_end(ctx, m * m * m / 3.0 + (a.have_pre ? (double)NB * m * (m + 1.0) : 0.0) + 2.0 * m * m);
 	}
 	dw.tail_rows_last = Tr;
-	dw.tail_masked_whole = k < 0 && mask != nullptr;
+	dw.tail_masked_whole = p.masked && !p.key.have_pre;
 	SPP_HIP_CHECK(hipGetLastError());
 	if(a.trace) {
 		std::vector<long long> h((size_t)Tr * 8);
@@ -1683,6 +1623,127 @@ static bool launch_dense_tail(spp_ctx *ctx, double *d_A, int64_t ld, int64_t row
 	return true;
 }
 
+// Hand-offs between the chain stream (ctx stream) and the bulk stream of the per-step schedule below, one verb per event
+// of the protocol. Two carriers:
+//   events -- evA = "the latest row panel is complete", evB = "the latest bulk update is complete" (two barrier packets
+//     per direction, ~6 us each on the critical chain). Every verb is its event call, nothing is deferred;
+//   flags (use_flags) -- words in device memory with the epoch of this factorization as their value: sync[2 k] = "row
+//     panel k is complete" (signalled behind the panel solve on the chain stream, awaited in front of the bulk update),
+//     sync[2 k + 1] = "bulk update k is complete" (signalled behind it on the bulk stream, awaited in front of the chain's
+//     next tile-row kernel). A one-wave kernel costs 5-6 us of queue time, so a signal is not enqueued when its event
+//     happens but held back until the next wait on ITS stream and enqueued with it as one launch
+//     (flag_signal_wait_kernel), on the bulk stream between two updates that otherwise run back to back.
+// What holds for the flags:
+//   1. a held-back signal is never left behind a wait on its stream: whatever enqueues a wait takes the signal along or
+//      sends it first (else each stream could wait for a signal queued behind the other's wait);
+//   2. before the chain stream enqueues the wait for bulk update k, that update's signal is in the bulk stream's queue;
+//   3. the join is an event -- the ctx stream's successors need the whole bulk stream drained --, and the last bulk
+//      update's signal is dropped: nobody waits for that flag;
+//   4. the bulk stream starts behind everything enqueued on the ctx stream so far (the matrix itself): one event per
+//      factorization.
+class StepHandOffs {
+	spp_ctx *ctx;
+	DenseWork &dw;
+	const hipStream_t s, s2;   // chain, bulk
+	const hipEvent_t evA, evB;
+	const bool use_flags;
+	int ep = 0;                // flags: the epoch
+	int64_t panel = -1, bulk = -1;   // the latest row panel / bulk update reported complete
+	int64_t held_panel = -1;   // flags: "row panel held_panel is complete" not yet enqueued on the chain stream
+	int64_t held_bulk = -1;    // flags: "bulk update held_bulk is complete" not yet enqueued on the bulk stream
+	int64_t chain_owes = -1;   // flags: the chain's next tile-row kernel has to wait for bulk update chain_owes
+
+	int *panel_flag(int64_t k) const { return dw.sync.p + 2 * k; }
+	int *bulk_flag(int64_t k) const { return dw.sync.p + 2 * k + 1; }
+	void send_held_bulk()
+	{
+		if(held_bulk >= 0)
+			flag_signal(s2, bulk_flag(held_bulk), ep);
+		held_bulk = -1;
+	}
+
+public:
+	StepHandOffs(spp_ctx *c, int64_t nsteps, bool flags) : ctx(c), dw(c->dense), s(c->stream), s2(c->dense.aux), evA(c->dense.ev[0]),
+		evB(c->dense.ev[1]), use_flags(flags)
+	{
+		if(!use_flags)
+			return;
+		if(dw.sync.cap < (size_t)(2 * nsteps + 16)) {
+			dw.sync.reserve((size_t)(2 * nsteps + 16));
+			SPP_HIP_CHECK(hipMemsetAsync(dw.sync.p, 0, dw.sync.cap * sizeof(int), s));
+			dw.sync_epoch = 1; // the self-test used the value 1
+		}
+		ep = ++ dw.sync_epoch;
+		SPP_HIP_CHECK(hipEventRecord(evA, s)); // (4.)
+		SPP_HIP_CHECK(hipStreamWaitEvent(s2, evA, 0));
+	}
+	void panel_complete(int64_t k) // on the chain stream
+	{
+		panel = k;
+		if(use_flags)
+			held_panel = k;
+		else
+			SPP_HIP_CHECK(hipEventRecord(evA, s));
+	}
+	void bulk_takes_panel() // the bulk stream waits for the latest row panel
+	{
+		if(use_flags && held_bulk >= 0) {
+			hipLaunchKernelGGL(flag_signal_wait_kernel, dim3(1), dim3(64), 0, s2, bulk_flag(held_bulk), ep, make_flag_wait(ctx, panel_flag(panel), ep));
+			held_bulk = -1;
+		} else if(use_flags)
+			flag_wait(ctx, s2, panel_flag(panel), ep);
+		else
+			SPP_HIP_CHECK(hipStreamWaitEvent(s2, evA, 0));
+	}
+	void bulk_complete(int64_t k) // on the bulk stream
+	{
+		bulk = k;
+		if(use_flags)
+			held_bulk = k;
+		else
+			SPP_HIP_CHECK(hipEventRecord(evB, s2));
+	}
+	void chain_waits_now() // the chain stream waits for the latest bulk update: a wait of its own (event or one-wave kernel)
+	{
+		if(!use_flags) {
+			SPP_HIP_CHECK(hipStreamWaitEvent(s, evB, 0));
+			return;
+		}
+		if(held_bulk == bulk)
+			send_held_bulk(); // (2.: no further hand-over to the bulk stream took the signal along)
+		if(held_panel >= 0) // (1.)
+			flag_signal(s, panel_flag(held_panel), ep);
+		held_panel = -1;
+		flag_wait(ctx, s, bulk_flag(bulk), ep);
+	}
+	void chain_waits_before_tile_row() // ... in front of its next tile-row kernel (flags: with flush()), or an event wait now
+	{
+		if(use_flags)
+			chain_owes = bulk;
+		else
+			SPP_HIP_CHECK(hipStreamWaitEvent(s, evB, 0));
+	}
+	void flush() // everything held back on the chain stream: the panel signal, the wait for a bulk update, or both in one launch
+	{
+		if(chain_owes >= 0 && held_bulk == chain_owes)
+			send_held_bulk(); // (2.)
+		if(chain_owes >= 0 && held_panel >= 0)
+			hipLaunchKernelGGL(flag_signal_wait_kernel, dim3(1), dim3(64), 0, s, panel_flag(held_panel), ep, make_flag_wait(ctx, bulk_flag(chain_owes), ep));
+		else if(chain_owes >= 0)
+			flag_wait(ctx, s, bulk_flag(chain_owes), ep);
+		else if(held_panel >= 0)
+			flag_signal(s, panel_flag(held_panel), ep);
+		chain_owes = held_panel = -1;
+	}
+	void join() // the chain stream waits for the whole bulk stream (3.)
+	{
+		held_bulk = -1;
+		if(use_flags)
+			SPP_HIP_CHECK(hipEventRecord(evB, s2));
+		SPP_HIP_CHECK(hipStreamWaitEvent(s, evB, 0));
+	}
+};
+
 // The two-stream schedule. Chain (ctx stream): fused [tile row k+1 <- panel k, potrf_diag(k+1)], panel solve k+1.
 // Bulk (CU-masked second stream): everything below the tile row, handed over right after the panel solve; once the
 // trailing matrix is at most 2560 rows the whole step runs on the chain stream (one fused launch updates every
@@ -1695,94 +1756,11 @@ static void dense_factor_steps_enqueue(spp_ctx *ctx, double *d_A, int64_t ld, in
 	int64_t nsteps, bool has_rhs, bool use_flags, bool allow_fused)
 {
 	hipStream_t s = ctx->stream, s2 = ctx->dense.aux;
-	hipEvent_t evA = ctx->dense.ev[0], evB = ctx->dense.ev[1];
-	// Hand-offs between the chain stream and the bulk stream: events (two barrier packets per direction, ~6 us
-	// each on the critical chain) or, with use_flags, words in device memory: flag[2 k] = "row panel k is
-	// complete" (signal kernel behind the panel solve on s, wait kernel in front of the bulk update on s2),
-	// flag[2 k + 1] = "bulk update k is complete" (signal kernel behind it on s2; a wait kernel in front of the chain's
-	// next tile-row kernel). Values are the epoch of this factorization.
 	DenseWork &dw = ctx->dense;
 	// pivots [n_id, n) are exact identity padding (big fronts of the sparse path pad their pivot block to a multiple of
 	// 128): the diagonal-block kernel skips the 16-wide panels that consist of padding only
 	const int64_t n_id = (dw.ident_from >= 0 && dw.ident_from < n) ? dw.ident_from : n;
-	int ep = 0;
-	int64_t step_a = -1, step_b = -1; // steps whose hand-over / bulk update the "events" currently name
-	int64_t need_wait_b = -1;         // flags only: the next chain kernel has to wait for bulk update need_wait_b
-	if(use_flags) {
-		if(dw.sync.cap < (size_t)(2 * nsteps + 16)) {
-			dw.sync.reserve((size_t)(2 * nsteps + 16));
-			SPP_HIP_CHECK(hipMemsetAsync(dw.sync.p, 0, dw.sync.cap * sizeof(int), s));
-			dw.sync_epoch = 1; // the self-test used the value 1
-		}
-		ep = ++ dw.sync_epoch;
-		// the bulk stream must start after everything enqueued on the ctx stream so far (the matrix itself): one event per factorization
-		SPP_HIP_CHECK(hipEventRecord(evA, s));
-		SPP_HIP_CHECK(hipStreamWaitEvent(s2, evA, 0));
-	}
-	int64_t pend_sig = -1; // flags only: "row panel pend_sig is complete" not yet enqueued (merged with the next wait on s)
-	auto record_a = [&](int64_t k) { // row panel k is complete on s
-		step_a = k;
-		if(use_flags)
-			pend_sig = k; // enqueued by flush_wait_b(), together with the wait that follows it on the chain stream
-		else
-			SPP_HIP_CHECK(hipEventRecord(evA, s));
-	};
-	// (flags) the bulk stream's "bulk update k is complete" is not enqueued on its own either: the wait for the next row
-	// panel follows it directly on that stream, and the two are one launch -- a one-wave kernel costs 5-6 us of queue time
-	// each, between two bulk updates that otherwise run back to back
-	int64_t pend_sig_b = -1;
-	auto wait_a_on_bulk = [&]() {
-		if(use_flags && pend_sig_b >= 0) {
-			hipLaunchKernelGGL(flag_signal_wait_kernel, dim3(1), dim3(64), 0, s2, dw.sync.p + 2 * pend_sig_b + 1, ep,
-				make_flag_wait(ctx, dw.sync.p + 2 * step_a, ep));
-			pend_sig_b = -1;
-		} else if(use_flags)
-			flag_wait(ctx, s2, dw.sync.p + 2 * step_a, ep);
-		else
-			SPP_HIP_CHECK(hipStreamWaitEvent(s2, evA, 0));
-	};
-	auto flush_sig_b = [&]() {
-		if(pend_sig_b >= 0)
-			flag_signal(s2, dw.sync.p + 2 * pend_sig_b + 1, ep);
-		pend_sig_b = -1;
-	};
-	auto record_b = [&](int64_t k) { // bulk update k is complete on s2
-		step_b = k;
-		if(use_flags)
-			pend_sig_b = k; // enqueued with the wait for row panel k + 1 (wait_a_on_bulk), or by flush_sig_b()
-		else
-			SPP_HIP_CHECK(hipEventRecord(evB, s2));
-	};
-	auto wait_b_now = [&]() { // a wait of its own on the chain stream (event or one-wave kernel)
-		if(use_flags && pend_sig_b == step_b)
-			flush_sig_b(); // (no further hand-over to the bulk stream took the signal along)
-		if(use_flags && pend_sig >= 0) { // a deferred panel signal goes first (never left behind a wait)
-			flag_signal(s, dw.sync.p + 2 * pend_sig, ep);
-			pend_sig = -1;
-		}
-		if(use_flags)
-			flag_wait(ctx, s, dw.sync.p + 2 * step_b + 1, ep);
-		else
-			SPP_HIP_CHECK(hipStreamWaitEvent(s, evB, 0));
-	};
-	auto wait_b_deferred = [&]() { // in front of the chain's next tile-row kernel (flags), or an event wait now
-		if(use_flags)
-			need_wait_b = step_b;
-		else
-			SPP_HIP_CHECK(hipStreamWaitEvent(s, evB, 0));
-	};
-	auto flush_wait_b = [&]() { // everything deferred on the chain stream: the panel signal, the wait for a bulk update, or both in one launch
-		if(need_wait_b >= 0 && pend_sig_b == need_wait_b)
-			flush_sig_b(); // the signal this wait is for must be in the bulk stream's queue
-		if(need_wait_b >= 0 && pend_sig >= 0)
-			hipLaunchKernelGGL(flag_signal_wait_kernel, dim3(1), dim3(64), 0, s, dw.sync.p + 2 * pend_sig, ep,
-				make_flag_wait(ctx, dw.sync.p + 2 * need_wait_b + 1, ep));
-		else if(need_wait_b >= 0)
-			flag_wait(ctx, s, dw.sync.p + 2 * need_wait_b + 1, ep);
-		else if(pend_sig >= 0)
-			flag_signal(s, dw.sync.p + 2 * pend_sig, ep);
-		need_wait_b = pend_sig = -1;
-	};
+	StepHandOffs hand(ctx, nsteps, use_flags);
 	bool bulk_pending = false;
 	// Fused chain kernel (update_potrf_kernel): the update of a row region from panel kp and the factorization of the
 	// region's first diagonal block (step kn) in one launch; the panel solve of step kn follows as its own launch.
@@ -1841,7 +1819,7 @@ static void dense_factor_steps_enqueue(spp_ctx *ctx, double *d_A, int64_t ld, in
 		if(m <= 0 || r0 >= ncols)
 			return;
 		const double *P = d_A + kp0 + r0 * ld;
-		flush_wait_b();
+		hand.flush();
 		launch_gemm_staged<32, 32, 16, 16, 0>(s, m, ncols - r0, NB, P, ld, P, ld, d_A + r0 + r0 * ld, ld, true);
 	};
 	if(allow_fused && nsteps >= 2 && switches().tail_rows * NB >= rows && dense_tail_applies(ctx, rows, nsteps) &&
@@ -1859,7 +1837,7 @@ static void dense_factor_steps_enqueue(spp_ctx *ctx, double *d_A, int64_t ld, in
 		if(rows - c1 <= single_below || (allow_fused && switches().tail_rows * NB >= rows - c1 && dense_tail_applies(ctx, rows, nsteps))) {
 			// small trailing matrix: the whole update is shorter than a cross-stream hand-off plus the tile row
 			if(bulk_pending) {
-				wait_b_now();
+				hand.chain_waits_now();
 				bulk_pending = false;
 			}
 			const double *P = d_A + k0 + c1 * ld;
@@ -1888,15 +1866,15 @@ static void dense_factor_steps_enqueue(spp_ctx *ctx, double *d_A, int64_t ld, in
 		// The bulk update needs only row panel k (complete at this point of the chain stream) and writes rows >= c2,
 		// disjoint from the tile row the chain touches next: it is handed to the bulk stream BEFORE the tile row, so
 		// that consecutive bulk updates run back to back.
-		record_a(k);
+		hand.panel_complete(k);
 		if(bulk_pending) { // the previous bulk update touched every row >= c1
-			wait_b_deferred();
+			hand.chain_waits_before_tile_row();
 			bulk_pending = false;
 		}
 		const bool have_bulk = rows - c2 > 0 && c2 < ncols;
 		bool fused_done = false; // potrf of step k+1 already done by the fused kernel
 		if(have_bulk) {
-			wait_a_on_bulk();
+			hand.bulk_takes_panel();
 			const double *P = d_A + k0 + c2 * ld;
 			hipStream_t keep = ctx->stream;
 			ctx->stream = s2; // dom events + gemm launch on the bulk stream
@@ -1908,25 +1886,21 @@ static void dense_factor_steps_enqueue(spp_ctx *ctx, double *d_A, int64_t ld, in
 			if(big)
 				dom_end(ctx, 2.0 * NB * (0.5 * mr * (mr + 1.0) + mr * (double)(ncols - rows)));
 			ctx->stream = keep;
-			record_b(k);
+			hand.bulk_complete(k);
 			bulk_pending = true;
 		}
 		if(fused && k + 1 < nsteps && rows - c1 >= NB) {
-			flush_wait_b();
+			hand.flush();
 			fused_update_potrf(c1, NB, k0, k + 1); // tile row k+1 <- panel k, potrf(k+1) inside
 			fused_done = true;
 		} else
 			tile_row(c1, k0);
-		flush_wait_b();
+		hand.flush();
 		if(k + 1 < nsteps)
 			potrf_and_panel(k + 1, fused_done);
 	}
-	if(bulk_pending) { // the join is an event: the ctx stream's successors need the whole bulk stream drained
-		pend_sig_b = -1; // (nobody waits for that flag)
-		if(use_flags)
-			SPP_HIP_CHECK(hipEventRecord(evB, s2));
-		SPP_HIP_CHECK(hipStreamWaitEvent(s, evB, 0));
-	}
+	if(bulk_pending)
+		hand.join();
 	SPP_HIP_CHECK(hipGetLastError());
 }
 

@@ -41,8 +41,6 @@
 
 namespace spp {
 
-constexpr int TAIL_MAX_ROWS = 64; // tile columns of a region: one bit each in a step's word
-
 struct TailArgs {
 	double *A;           // the matrix (column-major, leading dimension ld)
 	int64_t ld;
@@ -65,15 +63,10 @@ struct TailArgs {
 	unsigned long long rowbits[TAIL_MAX_ROWS + 1];
 	// the order in which a tile applies its steps, one byte per step, eight to a word (entry p in byte p & 7 of
 	// sorder[p >> 3]): the step as a signed byte -- -1: the row panel in front of the region --, TAIL_NO_STEP behind the
-	// last one. Ascending unless the caller hands a step order to a whole factorization (launch_dense_tail).
+	// last one (tail_sorder_at / tail_sorder_pack in spp_internal.h). Ascending unless the caller hands a step order to a
+	// whole factorization (tail_plan).
 	unsigned long long sorder[TAIL_MAX_ROWS / 8 + 1];
 };
-constexpr int TAIL_NO_STEP = 127; // (no tile row: a tile applies the steps below its own row only)
-
-__host__ __device__ inline int tail_sorder_at(const unsigned long long *sorder, const int p)
-{
-	return (int)(signed char)(unsigned char)(sorder[p >> 3] >> (8 * (p & 7)));
-}
 
 // the value a timed-out wait of the streamed launch leaves in the abort word (the host tells it from the other raisers:
 // a non-positive pivot, a cross-stream flag wait of the per-step schedule in front of it, both store 1)

@@ -287,6 +287,59 @@ struct SchurPlan : SchurDims {
 };
 
 // ------------------------------------------------------------------------------------------------
+// the streamed launch of the dense factor (spp_dense_tail.h): what the host decides for it (tail_plan, spp_tile_plan.cpp)
+// ------------------------------------------------------------------------------------------------
+constexpr int TAIL_MAX_ROWS = 64; // tile columns of a region: one bit each in a step's word
+constexpr int TAIL_NO_STEP = 127; // (no tile row: a tile applies the steps below its own row only)
+constexpr int TAIL_SORDER_WORDS = TAIL_MAX_ROWS / 8 + 1;
+
+// The step list of a launch, one byte per step, eight to a word (entry p in byte p & 7 of sorder[p >> 3]): the step as a
+// signed byte -- -1: the row panel in front of the region --, TAIL_NO_STEP behind the last one.
+__host__ __device__ inline int tail_sorder_at(const unsigned long long *sorder, const int p)
+{
+	return (int)(signed char)(unsigned char)(sorder[p >> 3] >> (8 * (p & 7)));
+}
+
+inline void tail_sorder_pack(unsigned long long *sorder, const int *list, const int n) // (entries behind list[n - 1]: TAIL_NO_STEP)
+{
+	for(int p = 0; p < 8 * TAIL_SORDER_WORDS; ++ p) {
+		if(!(p & 7))
+			sorder[p >> 3] = 0;
+		sorder[p >> 3] |= (unsigned long long)(unsigned char)(signed char)(p < n ? list[p] : TAIL_NO_STEP) << (8 * (p & 7));
+	}
+}
+
+struct TailSwitches { // the run-time switches a plan depends on, as values (the host probes vary them within one process)
+	int tail_rows, tail_mask, tail_early, tail_early_lead;
+	double tail_order_beta;
+	static TailSwitches of(const Switches &sw) { return TailSwitches{sw.tail_rows, sw.tail_mask, sw.tail_early, sw.tail_early_lead, sw.tail_order_beta}; }
+};
+
+struct TailPlan {
+	bool applies = false;  // false: the region is not one streamed launch (the per-step schedule goes on); nothing below is set
+	// what the workgroup table is a function of (beside the order key's beta and the resident count, fixed for a device)
+	struct Key {
+		int Tr = 0, Tc = 0;            // tile rows / tile columns of the region
+		bool have_pre = false;         // a row panel in front of the region (step -1)
+		bool early = false;            // the caller's mask in force and SPP_TAIL_EARLY: lagging trailing rows may go first
+		bool lead = false;             // ... the leading rows of a run that is too large (tail_order_table's lead)
+		// the step words: bit j of rowbits[i + 1] = tile (i, j) of the region is nonzero, rowbits[0] = the row panel in front
+		std::vector<uint64_t> rowbits;
+		bool operator ==(const Key &o) const
+		{
+			return Tr == o.Tr && Tc == o.Tc && have_pre == o.have_pre && early == o.early && lead == o.lead && rowbits == o.rowbits;
+		}
+	} key;
+	bool masked = false;   // the caller's tile mask is in force (else every tile is listed)
+	bool ordered = false;  // the step list is the caller's step order (else ascending)
+	unsigned long long sorder[TAIL_SORDER_WORDS]; // the step list (-1 first with have_pre), packed
+	int resident = 0;      // resident workgroups the table was made for (0 unless early)
+	bool table_fresh = false; // the table was computed by this call (false: taken over from a former plan with the same key)
+	std::vector<int> table; // workgroup -> tile (i << 16 | j)
+	int info[5] = {0, 0, 0, 0, 0}; // tail_order_table's figures of that table
+};
+
+// ------------------------------------------------------------------------------------------------
 // dense Cholesky workspace
 // ------------------------------------------------------------------------------------------------
 struct DenseWork {
@@ -299,13 +352,9 @@ struct DenseWork {
 	DevBuf<int> tail_pub;          // streamed tail of the dense factor: per tile, (epoch << 4) | row tiles published
 	DevBuf<double> tail_dinv;      // ... and the inverse 16 x 16 diagonal tiles it publishes
 	int tail_epoch = 0;
-	DevBuf<int> tail_order;        // workgroup -> tile of the streamed launch, for tail_order_tr x tail_order_tc tiles
-	std::vector<int> tail_order_host; // its host image (the upload is asynchronous: it lives as long as the table)
-	int tail_order_tr = 0, tail_order_tc = 0;
-	std::vector<uint64_t> tail_order_bits; // ... and for these step words (the table is keyed by the tile mask as well)
-	bool tail_order_lead = false;  // ... with / without the leading rows of a trailing run that is too large (tail_order_table's lead)
-	bool tail_order_pre = false, tail_order_masked = false; // ... with / without a row panel in front, with / without a caller's mask
-	int tail_resident = -1;        // workgroups of the streamed launch the device holds at once (occupancy x CUs); -1: not asked yet
+	DevBuf<int> tail_order;        // workgroup -> tile of the streamed launch: tail_plan.table on the device
+	TailPlan tail_plan;            // the plan of the last streamed launch; its table is the host image of tail_order (the upload is asynchronous: it lives as long as the table)
+	int tail_resident = -1;       // workgroups of the streamed launch the device holds at once (occupancy x CUs); -1: not asked yet
 	// Tile structure of the matrix the next factorization gets (set by the caller for that one call, TileMaskGuard): one
 	// word per tile row of 128, bit j = tile (i, j) is nonzero after symbolic fill (tile_mask_close). nullptr or a size
 	// that does not match the factorization's tile rows: every tile is nonzero.
@@ -491,6 +540,15 @@ TileDagCost tile_dag_cost(int64_t n, const std::vector<uint64_t> &filled, int re
 // lead: where the trailing run is too large to be seated whole, its leading rows are (used together with a step order)
 void tail_order_table(const std::vector<uint64_t> &bits, int Tr, int Tc, bool have_pre, double beta, int resident, bool early,
 	std::vector<int> &order, int *info, bool lead = false);
+// Everything the host decides for a streamed launch (host only, no device call; stated at its definition): the region behind
+// step k (-1: the whole factorization) of a factorization of nsteps tile rows, `rows` pivot rows and ncols columns; mask
+// (may be null): the caller's filled mask, one word per tile row; step_order (may be null): the caller's step order;
+// resident: workgroups the device holds at once. former (may be null): a plan whose table is taken over -- moved, its
+// storage stays where it is -- when the key is the same; no table is computed then. Throws SPP_E_BADARG for a step order
+// that is no permutation.
+TailPlan tail_plan(const std::vector<uint64_t> *mask, const std::vector<int32_t> *step_order, int64_t nsteps, int64_t rows,
+	int64_t ncols, int64_t k, int resident, const TailSwitches &sw, TailPlan *former = nullptr);
+bool is_permutation(const int32_t *v, int64_t n); // v[0 .. n) holds every value 0 .. n - 1 once
 // the order in which a tile of the streamed launch applies its steps: by the depth of the step's diagonal tile in the
 // tile DAG of the filled mask (one word per tile row), ties by k (host only; stated at its definition)
 void tail_step_order(const std::vector<uint64_t> &filled, std::vector<int32_t> &order);

@@ -303,15 +303,10 @@ static void cam_graph_mask(const CamGraph &g, const std::vector<int32_t> &pos, i
 // whether the streamed launch keeps its progress margin on this mask: the live-demand condition of tail_order_table
 static bool cam_order_live_ok(const std::vector<uint64_t> &filled, int64_t n_red)
 {
-	const int Tr = (int)filled.size(), Tc = (int)(n_red / DENSE_NB + 1);
-	std::vector<uint64_t> bits((size_t)Tr + 1);
-	bits[0] = Tc == 64 ? ~0ull : (1ull << Tc) - 1;
-	for(int i = 0; i < Tr; ++ i)
-		bits[(size_t)i + 1] = filled[i];
-	std::vector<int> order;
-	int info[5];
-	tail_order_table(bits, Tr, Tc, false, 0.0, TAIL_MODEL_RESIDENT, true, order, info);
-	return info[0] > 0 || info[3] <= TAIL_MODEL_RESIDENT; // the trailing rows are seated early, or everything live fits
+	// (the whole factorization as one launch under the mask, k ascending, on the model's device)
+	const TailSwitches sw = {TAIL_MAX_ROWS, 1, 1, 0, 0.0};
+	const TailPlan p = tail_plan(&filled, nullptr, (int64_t)filled.size(), n_red, n_red + 1, -1, TAIL_MODEL_RESIDENT, sw);
+	return p.applies && (p.info[0] > 0 || p.info[3] <= TAIL_MODEL_RESIDENT); // the trailing rows are seated early, or everything live fits
 }
 
 // The rule. A LOOP is cut only: the first and the last camera of the natural order are co-visible (the natural order is

@@ -1,7 +1,7 @@
 // spp_tile_plan.cpp -- host-side tile planning of the dense factor (integer work on 128 x 128 tile masks): which tiles
 // of a reduced system are structurally nonzero (tile_mask_mark, tile_mask_close), which workgroup of the streamed launch
-// takes which tile (tail_order_table), in which order a tile applies its steps (tail_step_order), and the cost model of
-// that launch on a filled mask (tile_dag_cost).
+// takes which tile (tail_order_table), everything else the host decides for that launch (tail_plan), in which order a tile
+// applies its steps (tail_step_order), and the cost model of that launch on a filled mask (tile_dag_cost).
 
 #include "spp_internal.h"
 #include <algorithm>
@@ -193,6 +193,78 @@ void tail_order_table(const std::vector<uint64_t> &bits, int Tr, int Tc, bool ha
 		info[0] = n_early;
 		info[1] = r_star;
 	}
+}
+
+bool is_permutation(const int32_t *v, int64_t n)
+{
+	std::vector<char> seen((size_t)n, 0);
+	for(int64_t q = 0; q < n; ++ q) {
+		if(v[q] < 0 || v[q] >= n || seen[(size_t)v[q]])
+			return false;
+		seen[(size_t)v[q]] = 1;
+	}
+	return true;
+}
+
+// The streamed launch (spp_dense_tail.h) takes everything behind row panel k -- the update of step k, then steps k + 1 .. --
+// when that trailing matrix is a full factorization (every tile row a pivot block) of at most tail_rows tile rows (0: the
+// launch is switched off) and TAIL_MAX_ROWS tile columns, the right-hand side's included. More tiles than CUs are fine:
+// workgroups are dispatched in table order and leave after their own step, a workgroup that starts late finds the row
+// tiles of the steps it missed in memory and catches up at the speed of its matrix cores.
+//   Step words: from the caller's filled mask of the whole matrix (global tile indices; a sub-pattern of a filled pattern
+// that starts at a later step is filled too) with tail_mask, else every tile; the diagonal tile always, nothing below it.
+//   Step list: the row panel in front of the region first, then k ascending, or the caller's step order where the launch is
+// the whole factorization -- with or without its mask in force (tail_mask changes scheduling, never bits).
+//   Table: tail_order_table above. Lagging trailing rows go first (early) only with a mask in force; the leading rows of a
+// run too large to be seated whole (lead) only under a step order other than k ascending, where a seated tile keeps level
+// with the chains that feed it.
+TailPlan tail_plan(const std::vector<uint64_t> *mask, const std::vector<int32_t> *step_order, int64_t nsteps, int64_t rows,
+	int64_t ncols, int64_t k, int resident, const TailSwitches &sw, TailPlan *former)
+{
+	TailPlan p;
+	const int64_t f = k + 1; // tile rows eliminated in front of the region
+	const int64_t Tr = nsteps - f, Tc = (ncols - f * DENSE_NB + DENSE_NB - 1) / DENSE_NB;
+	if(nsteps * DENSE_NB < rows || Tr < 1 || Tr > sw.tail_rows || Tc < Tr || Tc > Tr + 1 || Tc > TAIL_MAX_ROWS)
+		return p;
+	p.applies = true;
+	TailPlan::Key &key = p.key;
+	key.Tr = (int)Tr;
+	key.Tc = (int)Tc;
+	key.have_pre = f > 0;
+	if(!sw.tail_mask || (mask && (int64_t)mask->size() != nsteps))
+		mask = nullptr;
+	p.masked = mask != nullptr;
+	const uint64_t all_cols = Tc == 64 ? ~0ull : (1ull << Tc) - 1;
+	key.rowbits.resize((size_t)Tr + 1);
+	for(int64_t i = -1; i < Tr; ++ i) {
+		uint64_t w = (mask && f + i >= 0) ? ((*mask)[(size_t)(f + i)] >> f) : all_cols;
+		if(i >= 0)
+			w = (w | (1ull << i)) & ~((1ull << i) - 1);
+		key.rowbits[(size_t)i + 1] = w & all_cols;
+	}
+	p.ordered = f == 0 && step_order && (int64_t)step_order->size() == nsteps;
+	bool ascending = true;
+	int list[TAIL_MAX_ROWS + 1], n = 0;
+	if(p.ordered) // (the kernel indexes its step words with these)
+		SPP_REQUIRE(is_permutation(step_order->data(), Tr), SPP_E_BADARG, "streamed tail: the step order is not a permutation of the tile rows");
+	if(key.have_pre)
+		list[n ++] = -1;
+	for(int q = 0; q < (int)Tr; ++ q) {
+		list[n ++] = p.ordered ? (*step_order)[(size_t)q] : q;
+		ascending = ascending && list[n - 1] == q;
+	}
+	tail_sorder_pack(p.sorder, list, n);
+	key.early = p.masked && sw.tail_early != 0;
+	key.lead = key.early && !ascending && sw.tail_early_lead != 0;
+	p.resident = key.early ? resident : 0;
+	if(former && former->key == key) {
+		p.table.swap(former->table);
+		std::copy(former->info, former->info + 5, p.info);
+		return p;
+	}
+	p.table_fresh = true;
+	tail_order_table(key.rowbits, key.Tr, key.Tc, key.have_pre, sw.tail_order_beta, p.resident, key.early, p.table, p.info, key.lead);
+	return p;
 }
 
 // The order in which a tile of the streamed launch applies its steps (spp_dense_tail.h): the steps sorted by the depth of

@@ -53,6 +53,11 @@ def _check(tag, n, words, has_rhs, resident, beta=0.0):
     base = _sorted_table(rows, beta)
     tiles, info = api.tail_order_host(n, words, has_rhs, resident, True, beta)
     what = (tag, n, has_rhs, resident, info)
+    # it is the plan of the launch that takes the whole factorization (spp_tail_plan_host, tests/test_tail_plan_host.py), and
+    # the rows above are that plan's step words
+    plan = api.tail_plan_host(n, words, has_rhs=has_rhs, tail_rows=64, resident=resident, early=1, beta=beta)
+    assert plan["tiles"] == tiles and plan["info"] == info, what
+    assert plan["rowbits"] == [(1 << Tc) - 1] + [sum(1 << j for j in r) for r in rows], what
     # a permutation of the listed tiles
     assert len(tiles) == len(base) and sorted(tiles) == sorted(base), what
     widest = max(len(r) for r in rows)
