@@ -240,6 +240,17 @@ int spp_sparse_solve_device(spp_ctx *ctx, double *d_B, int64_t ldb, int64_t nrhs
  * n_sel < 1, a vertex out of range or listed twice. NOT FOR STREAM CAPTURE: the call waits for the ctx stream once on entry
  * (the list of rows is staged in host memory of the ctx) and may reallocate its n x m workspace when m grows. */
 int spp_sparse_marginals_device(spp_ctx *ctx, int64_t n_sel, const int64_t *h_vertices, double *d_cov);
+/* Blocks of Sigma = Lambda^-1 on the stored pattern of Lambda, from the kept sparse factor
+ * (SPP_INFO_SPARSE_FACTOR_KEPT), the job of the reference's CMarginals::Calculate_DenseMarginals_Recurrent_FBS.
+ * d_sigma: SPP_INFO_NVALS doubles in the layout of vals: the block of Sigma at (i, j) stands where Lambda's stored
+ * block (i, j) stands (upper incl. diagonal, each block column-major). Diagonal blocks exactly symmetric.
+ * Selected inversion down the assembly tree on the kept fronts: work of the order of the factorization's, no solve per
+ * column. It takes no d_vals (the fronts hold all of R), keeps the factor and writes nothing into it.
+ * STREAM-ORDERED on the ctx stream; no host synchronisation after the first call, which allocates the workspace (as many
+ * doubles as the fronts hold; spp_free_memory frees it). Keeping and refusals as for spp_sparse_solve_device, each checked
+ * before anything is touched: SPP_E_STATE without a kept factor, SPP_E_UNSUPPORTED in the three Schur modes and on a
+ * sharded ctx, SPP_E_BADARG for a null pointer. */
+int spp_sparse_sigma_device(spp_ctx *ctx, double *d_sigma);
 
 /* split form for multi-GPU: (1) each rank forms its partial Schur complement and
  * reduced rhs into d_S_rhs = [S (ld x ld, column-major, upper blocks) | rhs (ld)] ; (2) the caller

@@ -802,7 +802,7 @@ int spp_marginals_device(spp_ctx *ctx, const double *d_vals, int64_t n_sel, cons
 	SPP_CATCH(ctx)
 }
 
-// what spp_sparse_solve_device and spp_sparse_marginals_device check before they touch anything
+// what spp_sparse_solve_device, spp_sparse_marginals_device and spp_sparse_sigma_device check before they touch anything
 static void require_kept_sparse_factor(const spp_ctx *ctx, const char *who)
 {
 	SPP_REQUIRE(ctx->mode >= 0, SPP_E_STATE, std::string(who) + ": no kept factor (call spp_analyze and spp_factor_solve_device first)");
@@ -832,6 +832,18 @@ int spp_sparse_marginals_device(spp_ctx *ctx, int64_t n_sel, const int64_t *h_ve
 	require_kept_sparse_factor(ctx, "spp_sparse_marginals_device");
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	sparse_marginals(ctx, n_sel, h_vertices, d_cov);
+	return SPP_OK;
+	SPP_CATCH(ctx)
+}
+
+int spp_sparse_sigma_device(spp_ctx *ctx, double *d_sigma)
+{
+	if(!ctx || !d_sigma)
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	require_kept_sparse_factor(ctx, "spp_sparse_sigma_device");
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	sparse_sigma(ctx, d_sigma);
 	return SPP_OK;
 	SPP_CATCH(ctx)
 }

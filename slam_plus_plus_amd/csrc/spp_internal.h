@@ -603,6 +603,11 @@ void sparse_solve_again(spp_ctx *ctx, double *d_B, int64_t ldb, int64_t nrhs);
 // E^T Lambda^-1 E of the selected vertices (block columns of Lambda), m x m, exactly symmetric
 void sparse_marginals(spp_ctx *ctx, int64_t n_sel, const int64_t *h_vertices, double *d_cov);
 
+// ---- spp_sparse_sigma.hip ----
+// the blocks of Lambda^-1 on the stored pattern of Lambda (the layout of vals) from the fronts the last sparse
+// factorization left in the plan
+void sparse_sigma(spp_ctx *ctx, double *d_sigma);
+
 // ---- spp_dense.hip ----
 constexpr int DENSE_NB = 128;
 int dense_potrf_upper(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, bool keep_inverses);

@@ -1,5 +1,6 @@
 // spp_sparse_plan.h -- the plan of the sparse path and the argument block of its frontal kernels, shared by the
-// factorization (spp_sparse.hip) and the solves on the kept factor (spp_sparse_solve.hip). Device units only.
+// factorization (spp_sparse.hip), the solves on the kept factor (spp_sparse_solve.hip) and the selected inversion on it
+// (spp_sparse_sigma.hip). Device units only.
 #pragma once
 
 #include "spp_internal.h"
@@ -12,6 +13,14 @@ struct AgainFront {
 	int32_t h, w, ld, pad;
 	int32_t row0, rowsp;      // permuted row of the first pivot, offset of the front's rows in `rows`
 	int32_t cb, ce;           // its children in child_list
+};
+
+// what a workgroup of the selected inversion needs of its front and of the front's parent (spp_sparse_sigma.hip)
+struct SigmaFront {
+	int64_t off, poff;        // offset of the front / of its parent in `fronts` and in `sigma_z`
+	int32_t h, w, ld, pad;
+	int32_t pw, ppad, pld;    // the parent's pivots, padding and leading dimension (a root: 0, never read)
+	int32_t relp;             // offset of the front's entries in `rel`
 };
 
 constexpr int NCLS = 5; // size classes of a front (sparse_analyze); h_cls_ptr is indexed by level * NCLS + class
@@ -75,6 +84,11 @@ struct SparsePlan {
 	std::vector<AgainFront> h_again_desc;      // [ns] in the order of level_fronts
 	DevBuf<AgainFront> again_desc;
 	DevBuf<double> again_xp, again_upd;        // permuted panel (n x 128) and update panels (again_urows x 128); a pass uses 16 * NCT doubles per row
+	// selected inversion on the kept factor (spp_sparse_sigma.hip): built on the first such call
+	std::vector<SigmaFront> h_sigma_desc;      // [ns] in the order of level_fronts
+	std::vector<int32_t> h_sigma_level;        // [n_levels * 5]: LDS doubles of the class 0 - 2 launches, their tiles of 16 update / pivot columns, the same two of classes 3 - 4
+	DevBuf<SigmaFront> sigma_desc;
+	DevBuf<double> sigma_z;                    // Sigma on every front's indices: front_doubles, the layout of `fronts`
 };
 
 // local (unpadded) front index -> index in a padded image: `pad` entries are inserted after the w pivots
