@@ -593,9 +593,8 @@ class Context:
             ldb = self.info("N")
         return self._check(self.lib.spp_solve_device(self.h, d_vals, d_B, int(ldb), int(nrhs)))
 
-    def marginals(self, d_vals, vertices):
-        """joint covariance E^T Lambda^-1 E of the given vertices (block columns of Lambda, each at most once, any mix of
-        cameras and landmarks) as an (m, m) numpy array, rows and columns in the order of `vertices`; exactly symmetric"""
+    def _marginals(self, vertices, call):
+        """the (m, m) covariance of `vertices`: call(count, vertex pointer, device pointer of the m x m result)"""
         vertices = np.ascontiguousarray(vertices, dtype=np.int64)
         keep = getattr(self, "_keep", None)
         dim = np.asarray(keep.dim) if keep is not None else np.zeros(0, dtype=np.int32)
@@ -605,10 +604,15 @@ class Context:
             m = max(1, int(dim[vertices].sum()))
         d_cov = DeviceArray(self, m * m)
         try:
-            self._check(self.lib.spp_marginals_device(self.h, d_vals, vertices.size, _ptr(vertices), d_cov.ptr))
+            self._check(call(vertices.size, _ptr(vertices), d_cov.ptr))
             return d_cov.download().reshape((m, m), order="F")
         finally:
             d_cov.free()
+
+    def marginals(self, d_vals, vertices):
+        """joint covariance E^T Lambda^-1 E of the given vertices (block columns of Lambda, each at most once, any mix of
+        cameras and landmarks) as an (m, m) numpy array, rows and columns in the order of `vertices`; exactly symmetric"""
+        return self._marginals(vertices, lambda k, v, cov: self.lib.spp_marginals_device(self.h, d_vals, k, v, cov))
 
     def sparse_solve_device(self, d_B, nrhs, ldb=None):
         """Lambda X = B for nrhs columns (device pointer d_B, column-major, leading dimension ldb, default n) against the
@@ -621,19 +625,7 @@ class Context:
     def sparse_marginals(self, vertices):
         """joint covariance E^T Lambda^-1 E of the given vertices of a pose graph (block columns of Lambda, each at most
         once, any widths and order) from the kept sparse factor, as an (m, m) numpy array; exactly symmetric"""
-        vertices = np.ascontiguousarray(vertices, dtype=np.int64)
-        keep = getattr(self, "_keep", None)
-        dim = np.asarray(keep.dim) if keep is not None else np.zeros(0, dtype=np.int32)
-        if vertices.size == 0 or vertices.min() < 0 or vertices.max() >= dim.size:
-            m = 1   # (the library rejects the list; the buffer only has to exist)
-        else:
-            m = max(1, int(dim[vertices].sum()))
-        d_cov = DeviceArray(self, m * m)
-        try:
-            self._check(self.lib.spp_sparse_marginals_device(self.h, vertices.size, _ptr(vertices), d_cov.ptr))
-            return d_cov.download().reshape((m, m), order="F")
-        finally:
-            d_cov.free()
+        return self._marginals(vertices, lambda k, v, cov: self.lib.spp_sparse_marginals_device(self.h, k, v, cov))
 
     def sparse_sigma_device(self, d_sigma):
         """the blocks of Sigma = Lambda^-1 on the stored pattern of Lambda into d_sigma (device pointer, NVALS doubles in the

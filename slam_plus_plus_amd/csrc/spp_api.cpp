@@ -797,7 +797,8 @@ int spp_marginals_device(spp_ctx *ctx, const double *d_vals, int64_t n_sel, cons
 	SPP_TRY(ctx)
 	require_kept_factor(ctx, "spp_marginals_device");
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
-	schur_marginals(ctx, d_vals, n_sel, h_vertices, d_cov);
+	kept_marginals(ctx, "spp_marginals_device", n_sel, h_vertices, d_cov,
+		[&](double *d_B, int64_t ldb, int64_t nrhs) { schur_solve_again(ctx, d_vals, d_B, ldb, nrhs); });
 	return SPP_OK;
 	SPP_CATCH(ctx)
 }
@@ -831,7 +832,8 @@ int spp_sparse_marginals_device(spp_ctx *ctx, int64_t n_sel, const int64_t *h_ve
 	SPP_TRY(ctx)
 	require_kept_sparse_factor(ctx, "spp_sparse_marginals_device");
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
-	sparse_marginals(ctx, n_sel, h_vertices, d_cov);
+	kept_marginals(ctx, "spp_sparse_marginals_device", n_sel, h_vertices, d_cov,
+		[&](double *d_B, int64_t ldb, int64_t nrhs) { sparse_solve_again(ctx, d_B, ldb, nrhs); });
 	return SPP_OK;
 	SPP_CATCH(ctx)
 }

@@ -8,6 +8,7 @@
 #include <vector>
 #include <sys/mman.h>
 #include <utility>
+#include <functional>
 #include <new>
 #include <exception>
 #include <thread>
@@ -443,12 +444,12 @@ struct spp_ctx {
 	spp::DevBuf<double> d_vals, d_rhs;
 	double *h_staging = nullptr; // page-locked host buffer handed out by spp_host_staging()
 	size_t h_staging_cap = 0;    // doubles
-	// spp_solve_device / spp_marginals_device (spp_solve_again.hip): the camera panel of a pass (ld x 128), the unit block
-	// columns and the selected rows of a covariance (the host image lives as long as its asynchronous upload may run)
+	// spp_solve_device (spp_solve_again.hip): the camera panel of a pass (ld x 128); kept_marginals (either kept factor): the
+	// unit block columns and the selected rows of a covariance (the host image lives as long as its asynchronous upload may run)
 	spp::DevBuf<double> again_panel, again_cols;
 	spp::DevBuf<int64_t> again_rows;
 	std::vector<int64_t> again_rows_host;
-	// spp_sparse_solve_device / spp_sparse_marginals_device (spp_sparse_solve.hip): the fronts of the sparse plan hold the
+	// spp_sparse_solve_device / spp_sparse_marginals_device / spp_sparse_sigma_device: the fronts of the sparse plan hold the
 	// factor of the last spp_factor_solve_device (SPP_MODE_SPARSE, SPP_OK) and nothing has rewritten them since
 	bool sparse_factor_kept = false;
 	spp::DevBuf<double> geom_partial; // partial sums of ||dx||^2 (spp_geometry.hip)
@@ -593,15 +594,16 @@ void schur_pack(spp_ctx *ctx, double *S, double *packed, bool pack);
 // ---- spp_solve_again.hip ----
 // Lambda X = B in place for nrhs columns (n rows in Lambda's numbering, leading dimension ldb) against the kept factor
 void schur_solve_again(spp_ctx *ctx, const double *d_vals, double *d_B, int64_t ldb, int64_t nrhs);
-// E^T Lambda^-1 E of the selected vertices (block columns of Lambda), m x m, exactly symmetric
-void schur_marginals(spp_ctx *ctx, const double *d_vals, int64_t n_sel, const int64_t *h_vertices, double *d_cov);
+// E^T Lambda^-1 E of the selected vertices (block columns of Lambda), m x m, exactly symmetric, on whichever kept factor
+// `solve` works: solve(d_B, ldb, nrhs) is Lambda X = B in place on the ctx's stream. `who` names the entry point in the
+// error texts.
+typedef std::function<void(double *d_B, int64_t ldb, int64_t nrhs)> KeptSolve;
+void kept_marginals(spp_ctx *ctx, const char *who, int64_t n_sel, const int64_t *h_vertices, double *d_cov, const KeptSolve &solve);
 
 // ---- spp_sparse_solve.hip ----
 // Lambda X = B in place for nrhs columns (n rows in Lambda's numbering, leading dimension ldb) against the fronts the last
 // sparse factorization left in the plan
 void sparse_solve_again(spp_ctx *ctx, double *d_B, int64_t ldb, int64_t nrhs);
-// E^T Lambda^-1 E of the selected vertices (block columns of Lambda), m x m, exactly symmetric
-void sparse_marginals(spp_ctx *ctx, int64_t n_sel, const int64_t *h_vertices, double *d_cov);
 
 // ---- spp_sparse_sigma.hip ----
 // the blocks of Lambda^-1 on the stored pattern of Lambda (the layout of vals) from the fronts the last sparse

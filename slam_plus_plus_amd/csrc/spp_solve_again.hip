@@ -252,29 +252,32 @@ void sa_gather_cov_kernel(int64_t m, const int64_t *__restrict__ rows, const dou
 	cov[e] = (a <= b) ? X[rows[a] + b * n] : X[rows[b] + a * n];
 }
 
-void schur_marginals(spp_ctx *ctx, const double *d_vals, int64_t n_sel, const int64_t *h_vertices, double *d_cov)
+// E^T Lambda^-1 E on either kept factor: the unit columns of the selected rows, `solve` on them, the symmetric gather.
+// The whole list is validated first, then the stream is drained, then the host image is rewritten: a refused call
+// neither waits nor touches anything.
+void kept_marginals(spp_ctx *ctx, const char *who, int64_t n_sel, const int64_t *h_vertices, double *d_cov, const KeptSolve &solve)
 {
 	const Structure &st = ctx->st;
 	hipStream_t s = ctx->stream;
 	std::vector<char> seen((size_t)st.nb, 0);
-	// (an earlier call's upload of the host image may still be in flight: the stream is drained before it is rewritten)
-	SPP_HIP_CHECK(hipStreamSynchronize(s));
-	std::vector<int64_t> &rows = ctx->again_rows_host;
-	rows.clear();
+	std::vector<int64_t> rows;
 	for(int64_t q = 0; q < n_sel; ++ q) {
 		const int64_t v = h_vertices[q];
-		SPP_REQUIRE(v >= 0 && v < st.nb, SPP_E_BADARG, "spp_marginals_device: vertex out of range");
-		SPP_REQUIRE(!seen[(size_t)v], SPP_E_BADARG, "spp_marginals_device: a vertex is selected twice");
+		SPP_REQUIRE(v >= 0 && v < st.nb, SPP_E_BADARG, std::string(who) + ": vertex out of range");
+		SPP_REQUIRE(!seen[(size_t)v], SPP_E_BADARG, std::string(who) + ": a vertex is selected twice");
 		seen[(size_t)v] = 1;
 		for(int r = 0; r < st.dim[v]; ++ r)
 			rows.push_back(st.base[v] + r);
 	}
-	const int64_t m = (int64_t)rows.size(), n = st.n;
-	ctx->again_rows.upload(rows, s);
+	// (an earlier call's upload of the host image may still be in flight: the stream is drained before it is rewritten)
+	SPP_HIP_CHECK(hipStreamSynchronize(s));
+	ctx->again_rows_host.swap(rows);
+	const int64_t m = (int64_t)ctx->again_rows_host.size(), n = st.n;
+	ctx->again_rows.upload(ctx->again_rows_host, s);
 	ctx->again_cols.reserve((size_t)n * m);
 	SPP_HIP_CHECK(hipMemsetAsync(ctx->again_cols.p, 0, (size_t)n * m * sizeof(double), s));
 	hipLaunchKernelGGL(sa_unit_cols_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, m, ctx->again_rows.p, ctx->again_cols.p, n);
-	schur_solve_again(ctx, d_vals, ctx->again_cols.p, n, m);
+	solve(ctx->again_cols.p, n, m);
 	hipLaunchKernelGGL(sa_gather_cov_kernel, dim3((unsigned)((m * m + 255) / 256)), dim3(256), 0, s, m, ctx->again_rows.p,
 		ctx->again_cols.p, n, d_cov);
 	SPP_HIP_CHECK(hipGetLastError());

@@ -15,65 +15,27 @@
 // Z22 it owns; classes 3 - 4: step 1 is a launch of its own, sg_fetch_kernel), step 3 in the next, each once for the
 // fronts of classes 0 - 2 and once for those of classes 3 - 4 -- the body is chosen by the front's size class alone.
 //   classes 0 - 2  sg_cols_kernel: the pivot rows of R and the 16 work columns in LDS, every entry one chain of explicit
-//                  fused multiply-adds in a fixed order (the bodies of ss_fwd_kernel / ss_bwd_kernel, spp_sparse_solve.hip);
+//                  fused multiply-adds in a fixed order (fs_lds_fwd / fs_lds_bwd of spp_front_subst.h, the bodies of
+//                  ss_fwd_kernel / ss_bwd_kernel too);
 //   classes 3 - 4  sg_cols_mfma_kernel: sixteen waves, the work columns are the columns of Z themselves, the products are
 //                  chains of v_mfma_f64_16x16x4_f64 split over the waves by the front's shape alone and summed in wave
-//                  order (the bodies of ss_fwd_mfma_kernel / ss_bwd_mfma_kernel); Z21 and the lower triangle of Z11 are
-//                  mirrored by launches of their own (sg_mirror_kernel): a column under work is nobody else's to write.
+//                  order (fs_mfma_fwd / fs_mfma_bwd, the bodies of ss_fwd_mfma_kernel / ss_bwd_mfma_kernel too); Z21 and
+//                  the lower triangle of Z11 are mirrored by launches of their own (sg_mirror_kernel): a column under
+//                  work is nobody else's to write.
 // The parent is finished by the launch boundary; inside a launch a workgroup reads R, its parent's Z and its own columns
 // of Z and writes its own columns (classes 0 - 2: also their mirror rows, which nobody reads before the next launch). No
 // flags, no waits. A column of Z meets the same instruction sequence wherever it lands in a tile.
 
-#include "spp_internal.h"
-#include "spp_sparse_plan.h"
-#include "spp_tiles.h"
+#include "spp_front_subst.h"
 #include <algorithm>
 
 namespace spp {
 
-constexpr int SG_NT = 256;          // threads of a workgroup of the LDS body
+constexpr int SG_NT = FS_NT;        // threads of a workgroup of the LDS body
 constexpr int SG_CW = 16;           // columns of Z a workgroup owns
-constexpr int SG_PB = 16;           // pivots of a block of the triangular solves
-constexpr int SG_MT = 1024;         // threads of a workgroup of the MFMA body
-constexpr int SG_MW = SG_MT / 64;   // its waves
+constexpr int SG_MT = FS_MT;        // threads of a workgroup of the MFMA body
 // the largest front of class 2 (w = 112, h - 1 = 127): its pivot rows at column stride w | 1 beside 16 work columns
 constexpr size_t SG_LDS_MAX = (size_t)(113 * 127 + 127 * SG_CW) * sizeof(double);
-
-__device__ const double sg_zero_word = 0.0;
-
-// the 16 x 16 diagonal tile at pivot j0 into LDS (R[i, k] at tri[i + k * 17], upper triangle); beyond the nb valid pivots
-// the identity. Masked by address select in front of the load: every lane loads, none outside the front.
-__device__ __forceinline__ void sg_stage_tri(const double *F, int ld, int j0, int nb, double *tri)
-{
-	if(threadIdx.x < SG_PB * SG_PB) {
-		const int e = threadIdx.x, i = e & 15, k = e >> 4;
-		const bool in = i <= k && k < nb;
-		const double v = *(in ? F + (j0 + i) + (int64_t)(j0 + k) * ld : F);
-		tri[i + k * 17] = in ? v : (i == k ? 1.0 : 0.0);
-	}
-}
-
-// forward sweep of the staged tile over the 16 entries of one column held by 16 lanes (R^T y = t)
-__device__ __forceinline__ double sg_sweep_fwd(double t, const double *tri, int r, int lane)
-{
-#pragma unroll
-	for(int i = 0; i < SG_PB; ++ i) {
-		const double yi = __shfl(t, (lane & 48) + i) / tri[i + i * 17];
-		t = (r == i) ? yi : ((r > i) ? __builtin_fma(-tri[i + r * 17], yi, t) : t);
-	}
-	return t;
-}
-
-// backward sweep (R x = t), from the last pivot up
-__device__ __forceinline__ double sg_sweep_bwd(double t, const double *tri, int r, int lane)
-{
-#pragma unroll
-	for(int i = SG_PB - 1; i >= 0; -- i) {
-		const double xi = __shfl(t, (lane & 48) + i) / tri[i + i * 17];
-		t = (r == i) ? xi : ((r < i) ? __builtin_fma(-tri[r + i * 17], xi, t) : t);
-	}
-	return t;
-}
 
 // ---- classes 0 - 2 ---------------------------------------------------------------------------------------------------
 // PIV = false: the columns w .. h - 2 of Z (steps 1 and 2), PIV = true: the pivot columns (step 3). Dynamic LDS:
@@ -82,10 +44,10 @@ template <bool PIV>
 __global__ __launch_bounds__(SG_NT)
 void sg_cols_kernel(const SigmaFront *__restrict__ desc, const double *__restrict__ fronts, double *zs, const int32_t *__restrict__ rel)
 {
-	constexpr int CW = SG_CW, NR = SG_NT / CW;
+	constexpr int CW = SG_CW;
 	extern __shared__ double sg_sm[];
-	__shared__ double tri[SG_PB * 17];
-	__shared__ double ts[SG_PB * CW];
+	__shared__ double tri[FS_PB * 17];
+	__shared__ double ts[FS_PB * CW];
 	const SigmaFront fd = desc[blockIdx.x];
 	const int h = fd.h, w = fd.w, ld = fd.ld, pad = fd.pad;
 	const int hc = h - 1, ws = w | 1, m = hc - w;
@@ -96,11 +58,8 @@ void sg_cols_kernel(const SigmaFront *__restrict__ desc, const double *__restric
 	double *Rs = sg_sm, *T = sg_sm + ws * hc; // R[i, c] at Rs[i + c * ws]; entry r of column col at T[r * CW + col]
 	const double *F = fronts + fd.off;
 	double *Z = zs + fd.off;
-	const int tid = threadIdx.x, lane = tid & 63, col = tid % CW, q = tid / CW;
-	for(int e = tid; e < w * hc; e += SG_NT) {
-		const int i = e % w, c = e / w;
-		Rs[i + c * ws] = F[i + (int64_t)padded(c, w, pad) * ld];
-	}
+	const int tid = threadIdx.x;
+	fs_stage_rows(F, ld, w, pad, hc, ws, Rs);
 	// the work columns: e_c over Z21[:, c] (PIV), 0 over Z22[:, c] fetched from the parent and kept (otherwise); a column
 	// beyond the front's last is solved on zeros and never stored
 	for(int e = tid; e < hc * CW; e += SG_NT) {
@@ -118,55 +77,9 @@ void sg_cols_kernel(const SigmaFront *__restrict__ desc, const double *__restric
 		T[r * CW + cl] = v;
 	}
 	__syncthreads();
-	if(PIV) {
-		// ---- y = R11^-T e_c, 16 pivots per block from the tile's first column on (the rows above it stay zero): the
-		// products with the blocks above, then the diagonal tile
-		for(int j0 = c0; j0 < w; j0 += SG_PB) {
-			const int nb = (w - j0 < SG_PB) ? w - j0 : SG_PB;
-			sg_stage_tri(Rs, ws, j0, nb, tri);
-			if(q < SG_PB) {
-				double acc = 0.0;
-				if(q < nb) {
-					const double *Rc = Rs + (j0 + q) * ws;
-					acc = T[(j0 + q) * CW + col];
-					for(int p = c0; p < j0; ++ p)
-						acc = __builtin_fma(-Rc[p], T[p * CW + col], acc);
-				}
-				ts[q * CW + col] = acc;
-			}
-			__syncthreads();
-			{ // lane group of 16 = the 16 entries of one column
-				const int r = tid & 15, cc = tid >> 4;
-				const double t = sg_sweep_fwd(ts[r * CW + cc], tri, r, lane);
-				if(r < nb)
-					T[(j0 + r) * CW + cc] = t;
-			}
-			__syncthreads();
-		}
-	}
-	// ---- x = R11^-1 (y - R12 t), 16 pivots per block from the last one up: everything right of the block, then the tile
-	for(int j0 = ((w - 1) / SG_PB) * SG_PB; j0 >= 0; j0 -= SG_PB) {
-		const int nb = (w - j0 < SG_PB) ? w - j0 : SG_PB;
-		sg_stage_tri(Rs, ws, j0, nb, tri);
-		if(q < SG_PB) {
-			double acc = 0.0;
-			if(q < nb) {
-				const double *Rr = Rs + j0 + q;
-				acc = T[(j0 + q) * CW + col];
-				for(int c = j0 + nb; c < hc; ++ c)
-					acc = __builtin_fma(-Rr[c * ws], T[c * CW + col], acc);
-			}
-			ts[q * CW + col] = acc;
-		}
-		__syncthreads();
-		{
-			const int r = tid & 15, cc = tid >> 4;
-			const double t = sg_sweep_bwd(ts[r * CW + cc], tri, r, lane);
-			if(r < nb)
-				T[(j0 + r) * CW + cc] = t;
-		}
-		__syncthreads();
-	}
+	if(PIV)
+		fs_lds_fwd<CW>(Rs, ws, w, c0, T, tri, ts); // y = R11^-T e_c from the tile's first column on: the rows above stay zero
+	fs_lds_bwd<CW>(Rs, ws, w, hc, T, tri, ts);     // x = R11^-1 (y - R12 t)
 	// the column and its mirror row; of a pivot column the rows up to the diagonal
 	for(int e = tid; e < w * CW; e += SG_NT) {
 		const int r = e % w, cl = e / w, c = c0 + cl;
@@ -180,35 +93,28 @@ void sg_cols_kernel(const SigmaFront *__restrict__ desc, const double *__restric
 }
 
 // ---- classes 3 - 4 ---------------------------------------------------------------------------------------------------
-// D[i][j] += sum over 16 inner indices of A[k][i] B[k][j]; the lane holds A[4 kk + l4][l15], B[4 kk + l4][l15] and
-// D[l4 + 4 r][l15] (the layout of tile_atb, spp_tiles.h)
-__device__ __forceinline__ v4f64 sg_mfma16(const double *const pa[4], const double *const pb[4], v4f64 acc)
-{
-	double fa[4], fb[4];
-#pragma unroll
-	for(int kk = 0; kk < 4; ++ kk) {
-		fa[kk] = *pa[kk];
-		fb[kk] = *pb[kk];
-	}
-#pragma unroll
-	for(int kk = 0; kk < 4; ++ kk)
-		acc = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[kk], fb[kk], acc, 0, 0, 0);
-	return acc;
-}
+// where the 16 work columns of a workgroup live: the tile's own columns of Z in the arena (row stride 1, column stride ld,
+// first one cbase in the padded image). A tile column beyond the front's last works on a copy of the last one and is never
+// stored: no lane reads outside the front.
+struct SigmaCols {
+	double *Z;
+	int ld, pad, cbase, last;
+	__device__ double *piv(int p, int j) const { return Z + (int64_t)(cbase + (j < last ? j : last)) * ld + p; }
+	__device__ const double *upd(int c, int j) const { return piv(c + pad, j); }
+	__device__ double start(int p, int j) const { return *piv(p, j); }
+	__device__ bool may_store(int j) const { return j <= last; }
+};
 
-// The work columns are the tile's own columns of Z in the arena (row stride 1, column stride ld): step 2 finds Z22 in
-// their rows w .. h - 2 (sg_fetch_kernel, the launch before) and clears the pivot rows, step 3 finds Z21 there and sets
-// e_c. The products in front of a 16-pivot block are split over the waves by 16-blocks of the inner index, each wave ONE
-// chain of MFMAs over its blocks ascending, the partial tiles summed in wave order. Operands are masked by an address
-// select in front of the load (a masked lane reads sg_zero_word): rows and columns beyond the front's are never touched.
+// Step 2 finds Z22 in the columns' rows w .. h - 2 (sg_fetch_kernel, the launch before) and clears the pivot rows, step 3
+// finds Z21 there and sets e_c.
 template <bool PIV>
 __global__ __launch_bounds__(SG_MT)
 void sg_cols_mfma_kernel(const SigmaFront *__restrict__ desc, const double *__restrict__ fronts, double *zs)
 {
 	constexpr int CW = SG_CW;
-	__shared__ double tri[SG_PB * 17];
-	__shared__ double ts[SG_PB * CW];
-	__shared__ double part[SG_MW][SG_PB * CW];
+	__shared__ double tri[FS_PB * 17];
+	__shared__ double ts[FS_PB * CW];
+	__shared__ double part[FS_MW][FS_PB * CW];
 	const SigmaFront fd = desc[blockIdx.x];
 	const int h = fd.h, w = fd.w, ld = fd.ld, pad = fd.pad;
 	const int hc = h - 1, m = hc - w;
@@ -218,13 +124,8 @@ void sg_cols_mfma_kernel(const SigmaFront *__restrict__ desc, const double *__re
 		return;
 	const double *F = fronts + fd.off;
 	double *Z = zs + fd.off;
-	const int tid = threadIdx.x, col = tid % CW, q = tid / CW;
-	const int lane = tid & 63, wave = tid >> 6, l15 = lane & 15, l4 = lane >> 4;
-	// a tile column beyond the front's last works on a copy of the last one and is never stored: no mask to carry
-	const int last = ncols - 1 - c0;
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	const int cbase = PIV ? c0 : w + pad + c0;     // first column of the tile in the padded image
-	const double *Zc = Z + (int64_t)(cbase + (col < last ? col : last)) * ld; // column `col` of the tile
-	const double *Zb = Z + (int64_t)(cbase + (l15 < last ? l15 : last)) * ld; // B operand: entry p of column l15 of the tile
 	// (sixteen waves, sixteen columns: wave v fills column v of the tile)
 	if(c0 + wave < ncols) {
 		double *Zw = Z + (int64_t)(cbase + wave) * ld;
@@ -237,97 +138,10 @@ void sg_cols_mfma_kernel(const SigmaFront *__restrict__ desc, const double *__re
 		}
 	}
 	__syncthreads();
-	if(PIV) {
-		// ---- y = R11^-T e_c from the tile's first column on
-		for(int j0 = c0; j0 < w; j0 += SG_PB) {
-			const int nb = (w - j0 < SG_PB) ? w - j0 : SG_PB;
-			sg_stage_tri(F, ld, j0, nb, tri);
-			{
-				v4f64 acc = (v4f64){0, 0, 0, 0};
-				const bool ci = l15 < nb; // column j0 + l15 of R is a pivot column
-				for(int p0 = c0 + wave * SG_PB; p0 < j0; p0 += SG_MW * SG_PB) { // (p0 + 15 < j0 <= w: rows in range)
-					const double *pa[4], *pb[4];
-#pragma unroll
-					for(int kk = 0; kk < 4; ++ kk) {
-						const int p = p0 + 4 * kk + l4;
-						pa[kk] = ci ? F + p + (int64_t)(j0 + l15) * ld : &sg_zero_word;
-						pb[kk] = Zb + p;
-					}
-					acc = sg_mfma16(pa, pb, acc);
-				}
-#pragma unroll
-				for(int r = 0; r < 4; ++ r)
-					part[wave][(l4 + 4 * r) * CW + l15] = acc[r];
-			}
-			__syncthreads();
-			if(q < SG_PB) {
-				double t = q < nb ? Zc[j0 + q] : 0.0;
-#pragma unroll
-				for(int v = 0; v < SG_MW; ++ v)
-					t -= part[v][q * CW + col];
-				ts[q * CW + col] = q < nb ? t : 0.0;
-			}
-			__syncthreads();
-			if(tid < SG_PB * CW) { // waves 0 - 3: lane group of 16 = the 16 entries of one column
-				const int r = tid & 15, cc = tid >> 4;
-				const double t = sg_sweep_fwd(ts[r * CW + cc], tri, r, lane);
-				if(r < nb && c0 + cc < ncols)
-					Z[(j0 + r) + (int64_t)(cbase + cc) * ld] = t;
-			}
-			__syncthreads();
-		}
-	}
-	// ---- x = R11^-1 (y - R12 t)
-	for(int j0 = ((w - 1) / SG_PB) * SG_PB; j0 >= 0; j0 -= SG_PB) {
-		const int nb = (w - j0 < SG_PB) ? w - j0 : SG_PB;
-		sg_stage_tri(F, ld, j0, nb, tri);
-		{
-			v4f64 acc = (v4f64){0, 0, 0, 0};
-			const bool ri = l15 < nb; // row j0 + l15 of R is a pivot row
-			const double *Fr = F + j0 + l15;
-			// the 16-blocks right of the block: n1 inside the pivot columns (from j0 + 16), then n2 beyond (from w)
-			const int n1 = (w - (j0 + nb) + SG_PB - 1) / SG_PB, n2 = (m + SG_PB - 1) / SG_PB;
-			for(int b = wave; b < n1 + n2; b += SG_MW) {
-				const double *pa[4], *pb[4];
-				if(b < n1) {
-#pragma unroll
-					for(int kk = 0; kk < 4; ++ kk) {
-						const int c = j0 + nb + b * SG_PB + 4 * kk + l4;
-						pa[kk] = (ri && c < w) ? Fr + (int64_t)c * ld : &sg_zero_word;
-						pb[kk] = c < w ? Zb + c : &sg_zero_word;
-					}
-				} else {
-#pragma unroll
-					for(int kk = 0; kk < 4; ++ kk) {
-						const int c = w + (b - n1) * SG_PB + 4 * kk + l4;
-						const bool in = c < hc;
-						pa[kk] = (ri && in) ? Fr + (int64_t)(c + pad) * ld : &sg_zero_word;
-						pb[kk] = in ? Zb + c + pad : &sg_zero_word;
-					}
-				}
-				acc = sg_mfma16(pa, pb, acc);
-			}
-#pragma unroll
-			for(int r = 0; r < 4; ++ r)
-				part[wave][(l4 + 4 * r) * CW + l15] = acc[r];
-		}
-		__syncthreads();
-		if(q < SG_PB) {
-			double t = q < nb ? Zc[j0 + q] : 0.0;
-#pragma unroll
-			for(int v = 0; v < SG_MW; ++ v)
-				t -= part[v][q * CW + col];
-			ts[q * CW + col] = q < nb ? t : 0.0;
-		}
-		__syncthreads();
-		if(tid < SG_PB * CW) {
-			const int r = tid & 15, cc = tid >> 4;
-			const double t = sg_sweep_bwd(ts[r * CW + cc], tri, r, lane);
-			if(r < nb && c0 + cc < ncols)
-				Z[(j0 + r) + (int64_t)(cbase + cc) * ld] = t;
-		}
-		__syncthreads();
-	}
+	const SigmaCols cols{Z, ld, pad, cbase, ncols - 1 - c0};
+	if(PIV)
+		fs_mfma_fwd(F, ld, w, c0, cols, tri, ts, part); // y = R11^-T e_c from the tile's first column on
+	fs_mfma_bwd(F, ld, w, pad, hc, cols, tri, ts, part); // x = R11^-1 (y - R12 t)
 }
 
 // step 1 of the fronts of classes 3 - 4: Z22 from the parent, a workgroup per (front, 16 columns), a wave per column

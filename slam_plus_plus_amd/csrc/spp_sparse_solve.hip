@@ -1,5 +1,5 @@
-// spp_sparse_solve.hip -- Lambda X = B for k right-hand sides against the multifrontal factor a sparse solve left behind,
-// and the joint covariance of chosen vertices on top of it.
+// spp_sparse_solve.hip -- Lambda X = B for k right-hand sides against the multifrontal factor a sparse solve left behind
+// (DESIGN.md section 27); the joint covariance of chosen vertices is kept_marginals (spp_solve_again.hip) on top of it.
 //
 // After spp_factor_solve_device in the sparse mode every supernode's pivot rows of R (R^T R = P Lambda P^T) sit in the
 // plan's `fronts`: R[i, c] = F[i + padded(c, w, pad) * ld], i < w, c < h - 1 (column h - 1 is the right-hand-side slot of
@@ -26,55 +26,34 @@
 // Children are added in list order and no sum meets another column's values: column j of a k-column solve has the bits
 // of that column solved alone, whatever k, tile and lane.
 
-#include "spp_internal.h"
-#include "spp_sparse_plan.h"
-#include "spp_tiles.h"
+// The triangular part of both bodies -- the staging, the block loops, the sweep of the diagonal tile -- is
+// spp_front_subst.h's, shared with spp_sparse_sigma.hip; here is what is the solve's own: the permutation, the extend-add
+// of the children's panels and the update panel.
+
+#include "spp_front_subst.h"
 #include <algorithm>
 
 namespace spp {
 
-constexpr int SS_NT = 256;    // threads of a workgroup: CW columns x 256 / CW rows
+constexpr int SS_NT = FS_NT;  // threads of a workgroup: CW columns x 256 / CW rows
 constexpr int SS_PASS = 128;  // columns of a pass
-constexpr int SS_PB = 16;     // pivots of a block of the triangular solves
+constexpr int SS_PB = FS_PB;  // pivots of a block of the triangular solves
 
 struct SolveArgs {
-	const int64_t *front_off;
-	const int32_t *front_h, *front_w, *front_ld, *front_pad;
-	const int32_t *child_ptr, *child_list, *rel_ptr, *rel, *rows_ptr, *rows;
+	const int32_t *front_h, *front_w;
+	const int32_t *child_list, *rel_ptr, *rel, *rows;
 	const int64_t *uoff;   // first row of a front's update panel
 	const double *fronts;
 	double *xp, *upd;      // xs doubles per row
 	int xs, kc;            // row stride of xp / upd, columns of the pass
 };
 
-// the 16 x 16 diagonal tile at pivot j0 into LDS (R[i, k] at tri[i + k * 17], upper triangle); beyond the nb valid pivots
-// the identity. Masked by address select in front of the load: every lane loads, none outside the front.
-__device__ __forceinline__ void ss_stage_tri(const double *F, int ld, int j0, int nb, double *tri)
-{
-	for(int e = threadIdx.x; e < SS_PB * SS_PB; e += SS_NT) {
-		const int i = e & 15, k = e >> 4;
-		const bool in = i <= k && k < nb;
-		const double v = *(in ? F + (j0 + i) + (int64_t)(j0 + k) * ld : F);
-		tri[i + k * 17] = in ? v : (i == k ? 1.0 : 0.0);
-	}
-}
-
 // ---- classes 0 - 2: the front's pivot rows staged in LDS --------------------------------------------------------------
 // A workgroup owns (front, CW columns). It stages the w x (h - 1) pivot rows of R once (column stride w | 1) and keeps
 // the front's whole work vector t (h - 1 entries per column) beside them: every product chain runs from LDS. Dynamic
 // LDS: (ws (h - 1) + (h - 1) CW) doubles, at most 131 KB (w = 112, h - 1 = 127); a launch asks for its largest front's.
-// The 16 x 16 diagonal tile is solved by a sweep across 16 lanes per column: the solved pivot goes round by __shfl, every
-// later entry takes its product -- entry r still meets its products in the order of the pivots.
 constexpr int SS_CH = 32; // children whose descriptors a workgroup caches
 constexpr size_t SS_LDS_MAX = (size_t)(113 * 127 + 127 * 16) * sizeof(double);
-
-__device__ __forceinline__ void ss_stage_rows(const double *F, int ld, int w, int pad, int hc, int ws, double *Rs)
-{
-	for(int e = threadIdx.x; e < w * hc; e += SS_NT) {
-		const int i = e % w, c = e / w;
-		Rs[i + c * ws] = F[i + (int64_t)padded(c, w, pad) * ld];
-	}
-}
 
 template <int CW>
 __global__ __launch_bounds__(SS_NT)
@@ -89,8 +68,7 @@ void ss_fwd_kernel(const AgainFront *__restrict__ desc, SolveArgs a)
 	const int hc = h - 1, ws = w | 1;
 	double *Rs = ss_sm, *T = ss_sm + ws * hc; // R[i, c] at Rs[i + c * ws]; t[r] of column col at T[r * CW + col]
 	const double *F = a.fronts + fd.off;
-	const int32_t *rw = a.rows + fd.rowsp;
-	const int tid = threadIdx.x, lane = tid & 63, col = tid % CW, q = tid / CW;
+	const int tid = threadIdx.x, col = tid % CW, q = tid / CW;
 	const int c0 = (int)blockIdx.y * CW;
 	const bool act = c0 + col < a.kc;
 	const int64_t xs = a.xs;
@@ -108,7 +86,7 @@ void ss_fwd_kernel(const AgainFront *__restrict__ desc, SolveArgs a)
 		ch_rel[tid] = a.rel_ptr[c];
 		ch_u[tid] = a.uoff[c];
 	}
-	ss_stage_rows(F, ld, w, pad, hc, ws, Rs);
+	fs_stage_rows(F, ld, w, pad, hc, ws, Rs);
 	for(int r = q; r < hc; r += NR)
 		T[r * CW + col] = (act && r < w) ? X[r * xs] : 0.0; // (a column beyond k is solved on zeros and never stored)
 	__syncthreads();
@@ -129,34 +107,7 @@ void ss_fwd_kernel(const AgainFront *__restrict__ desc, SolveArgs a)
 				T[rl[i] * CW + col] += Uc[i * xs];
 		__syncthreads();
 	}
-	// ---- y = R11^-T t, 16 pivots per block: the products with the blocks above, then the diagonal tile
-	for(int j0 = 0; j0 < w; j0 += SS_PB) {
-		const int nb = (w - j0 < SS_PB) ? w - j0 : SS_PB;
-		ss_stage_tri(Rs, ws, j0, nb, tri);
-		if(q < SS_PB) {
-			double acc = 0.0;
-			if(q < nb) {
-				const double *Rc = Rs + (j0 + q) * ws;
-				acc = T[(j0 + q) * CW + col];
-				for(int p = 0; p < j0; ++ p)
-					acc = __builtin_fma(-Rc[p], T[p * CW + col], acc);
-			}
-			ts[q * CW + col] = acc;
-		}
-		__syncthreads();
-		if(tid < SS_PB * CW) { // lane group of 16 = the 16 entries of one column
-			const int r = tid & 15, cc = tid >> 4;
-			double t = ts[r * CW + cc];
-#pragma unroll
-			for(int i = 0; i < SS_PB; ++ i) {
-				const double yi = __shfl(t, (lane & 48) + i) / tri[i + i * 17];
-				t = (r == i) ? yi : ((r > i) ? __builtin_fma(-tri[i + r * 17], yi, t) : t);
-			}
-			if(r < nb)
-				T[(j0 + r) * CW + cc] = t;
-		}
-		__syncthreads();
-	}
+	fs_lds_fwd<CW>(Rs, ws, w, 0, T, tri, ts); // y = R11^-T t
 	// ---- update panel of the front: t[w:h-1] - R12^T y, one chain per entry over all pivots
 	for(int r = w + q; r < hc; r += NR) {
 		const double *Rc = Rs + r * ws;
@@ -189,78 +140,43 @@ void ss_bwd_kernel(const AgainFront *__restrict__ desc, SolveArgs a)
 	double *Rs = ss_sm, *T = ss_sm + ws * hc;
 	const double *F = a.fronts + fd.off;
 	const int32_t *rw = a.rows + fd.rowsp;
-	const int tid = threadIdx.x, lane = tid & 63, col = tid % CW, q = tid / CW;
+	const int tid = threadIdx.x, col = tid % CW, q = tid / CW;
 	const int c0 = (int)blockIdx.y * CW;
 	const bool act = c0 + col < a.kc;
 	const int64_t xs = a.xs;
 	const double *Xg = a.xp + c0 + col;        // by global permuted row: the ancestors' final x
 	double *X = a.xp + (int64_t)fd.row0 * xs + c0 + col;
-	ss_stage_rows(F, ld, w, pad, hc, ws, Rs);
+	fs_stage_rows(F, ld, w, pad, hc, ws, Rs);
 	for(int r = q; r < hc; r += NR)
 		T[r * CW + col] = act ? (r < w ? X[r * xs] : Xg[(int64_t)rw[r] * xs]) : 0.0;
 	__syncthreads();
-	// ---- x = R11^-1 (y - R12 t), 16 pivots per block from the last one up: everything right of the block, then the tile
-	for(int j0 = ((w - 1) / SS_PB) * SS_PB; j0 >= 0; j0 -= SS_PB) {
-		const int nb = (w - j0 < SS_PB) ? w - j0 : SS_PB;
-		ss_stage_tri(Rs, ws, j0, nb, tri);
-		if(q < SS_PB) {
-			double acc = 0.0;
-			if(q < nb) {
-				const double *Rr = Rs + j0 + q;
-				acc = T[(j0 + q) * CW + col];
-				for(int c = j0 + nb; c < hc; ++ c)
-					acc = __builtin_fma(-Rr[c * ws], T[c * CW + col], acc);
-			}
-			ts[q * CW + col] = acc;
-		}
-		__syncthreads();
-		if(tid < SS_PB * CW) {
-			const int r = tid & 15, cc = tid >> 4;
-			double t = ts[r * CW + cc];
-#pragma unroll
-			for(int i = SS_PB - 1; i >= 0; -- i) {
-				const double xi = __shfl(t, (lane & 48) + i) / tri[i + i * 17];
-				t = (r == i) ? xi : ((r < i) ? __builtin_fma(-tri[r + i * 17], xi, t) : t);
-			}
-			if(r < nb)
-				T[(j0 + r) * CW + cc] = t;
-		}
-		__syncthreads();
-	}
+	fs_lds_bwd<CW>(Rs, ws, w, hc, T, tri, ts); // x = R11^-1 (y - R12 t)
 	if(act)
 		for(int r = q; r < w; r += NR)
 			X[r * xs] = T[r * CW + col];
 }
 
 // ---- classes 3 - 4: the products on v_mfma_f64_16x16x4_f64 -----------------------------------------------------------
-// A workgroup (sixteen waves) owns (front, 16 columns). The products in front of a 16-pivot block -- R[0:j0, block]^T y
-// forward, R[block, right of it] x backward -- are split over the waves by 16-blocks of the inner index (block b goes to
-// wave b % 16): each wave runs ONE chain of MFMAs over its blocks ascending, the partial tiles are summed in wave order, the
-// diagonal tile is solved by a column sweep across 16 lanes per column (entry r takes its products in the order of the
-// solved pivots). The update panel goes by 16-row tiles, a wave per
-// tile, one chain over all pivots. Which wave sums what depends on the front alone: a column meets the same instruction
-// sequence whatever k, tile and lane, and an MFMA column never meets another column's values.
-// Operands are masked by an address select in front of the load (a masked lane reads ss_zero_word): rows and columns
-// beyond w / h - 1 are the next front's, or nobody's.
-__device__ const double ss_zero_word = 0.0;
-constexpr int SS_MT = 1024;      // threads of a workgroup of the MFMA body
-constexpr int SS_MW = SS_MT / 64; // its waves
+// A workgroup (sixteen waves) owns (front, 16 columns); the work columns are the rows of xp themselves. The update panel
+// goes by 16-row tiles, a wave per tile, one chain over all pivots. Rows and columns beyond w / h - 1 are the next
+// front's, or nobody's: masked as in spp_front_subst.h.
+constexpr int SS_MT = FS_MT;      // threads of a workgroup of the MFMA body
+constexpr int SS_MW = FS_MW;      // its waves
 
-// D[i][j] += sum over 16 inner indices of A[k][i] B[k][j]; the lane holds A[4 kk + l4][l15], B[4 kk + l4][l15] and
-// D[l4 + 4 r][l15] (the layout of tile_atb, spp_tiles.h)
-__device__ __forceinline__ v4f64 ss_mfma16(const double *const pa[4], const double *const pb[4], v4f64 acc)
-{
-	double fa[4], fb[4];
-#pragma unroll
-	for(int kk = 0; kk < 4; ++ kk) {
-		fa[kk] = *pa[kk];
-		fb[kk] = *pb[kk];
-	}
-#pragma unroll
-	for(int kk = 0; kk < 4; ++ kk)
-		acc = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[kk], fb[kk], acc, 0, 0, 0);
-	return acc;
-}
+// where the 16 work columns of a workgroup live: rows of xp (stride xs), the tile's columns side by side; the update rows
+// through the front's row list. Columns beyond kc are allocated (xs is a multiple of 16) and hold nothing.
+struct SolveCols {
+	double *xg;          // row 0 of xp, the tile's first column: rows by their global permuted number
+	int row0;            // the front's first pivot row
+	const int32_t *rw;   // the front's rows
+	int xs, kc0;         // row stride, columns of the pass from the tile's first on
+	__device__ SolveCols(const SolveArgs &a, const AgainFront &fd, int c0)
+		: xg(a.xp + c0), row0(fd.row0), rw(a.rows + fd.rowsp), xs(a.xs), kc0(a.kc - c0) {}
+	__device__ double *piv(int p, int j) const { return xg + (int64_t)(row0 + p) * xs + j; }
+	__device__ const double *upd(int c, int j) const { return xg + (int64_t)rw[c] * xs + j; }
+	__device__ double start(int p, int j) const { return may_store(j) ? *piv(p, j) : 0.0; }
+	__device__ bool may_store(int j) const { return j < kc0; }
+};
 
 __global__ __launch_bounds__(SS_MT)
 void ss_fwd_mfma_kernel(const AgainFront *__restrict__ desc, SolveArgs a)
@@ -273,7 +189,6 @@ void ss_fwd_mfma_kernel(const AgainFront *__restrict__ desc, SolveArgs a)
 	const int h = fd.h, w = fd.w, ld = fd.ld, pad = fd.pad;
 	const int m = h - 1 - w;
 	const double *F = a.fronts + fd.off;
-	const int32_t *rw = a.rows + fd.rowsp;
 	const int tid = threadIdx.x, col = tid % CW, q = tid / CW;
 	const int lane = tid & 63, wave = tid >> 6, l15 = lane & 15, l4 = lane >> 4;
 	const int c0 = (int)blockIdx.y * CW;
@@ -302,48 +217,7 @@ void ss_fwd_mfma_kernel(const AgainFront *__restrict__ desc, SolveArgs a)
 			}
 		__syncthreads();
 	}
-	for(int j0 = 0; j0 < w; j0 += SS_PB) {
-		const int nb = (w - j0 < SS_PB) ? w - j0 : SS_PB;
-		ss_stage_tri(F, ld, j0, nb, tri);
-		{
-			v4f64 acc = (v4f64){0, 0, 0, 0};
-			const bool ci = l15 < nb; // column j0 + l15 of R is a pivot column
-			for(int p0 = wave * SS_PB; p0 < j0; p0 += SS_MW * SS_PB) { // (p0 + 15 < j0 <= w: rows in range)
-				const double *pa[4], *pb[4];
-#pragma unroll
-				for(int kk = 0; kk < 4; ++ kk) {
-					const int p = p0 + 4 * kk + l4;
-					pa[kk] = ci ? F + p + (int64_t)(j0 + l15) * ld : &ss_zero_word;
-					pb[kk] = Xb + p * xs;
-				}
-				acc = ss_mfma16(pa, pb, acc);
-			}
-#pragma unroll
-			for(int r = 0; r < 4; ++ r)
-				part[wave][(l4 + 4 * r) * CW + l15] = acc[r];
-		}
-		__syncthreads();
-		if(q < SS_PB) {
-			double t = (act && q < nb) ? X[(j0 + q) * xs] : 0.0;
-#pragma unroll
-			for(int v = 0; v < SS_MW; ++ v)
-				t -= part[v][q * CW + col];
-			ts[q * CW + col] = (act && q < nb) ? t : 0.0;
-		}
-		__syncthreads();
-		if(tid < SS_PB * CW) { // waves 0 - 3: lane group of 16 = the 16 entries of one column; pivot i solved, then swept into the rest
-			const int r = tid & 15, cc = tid >> 4;
-			double t = ts[r * CW + cc];
-#pragma unroll
-			for(int i = 0; i < SS_PB; ++ i) {
-				const double yi = __shfl(t, (lane & 48) + i) / tri[i + i * 17];
-				t = (r == i) ? yi : ((r > i) ? __builtin_fma(-tri[i + r * 17], yi, t) : t);
-			}
-			if(r < nb && c0 + cc < a.kc)
-				a.xp[((int64_t)fd.row0 + j0 + r) * xs + c0 + cc] = t;
-		}
-		__syncthreads();
-	}
+	fs_mfma_fwd(F, ld, w, 0, SolveCols(a, fd, c0), tri, ts, part); // y = R11^-T t
 	// ---- update panel -= R12^T y, a wave per tile of 16 rows
 	for(int i0 = wave * SS_PB; i0 < m; i0 += SS_MW * SS_PB) {
 		v4f64 acc = (v4f64){0, 0, 0, 0};
@@ -353,10 +227,10 @@ void ss_fwd_mfma_kernel(const AgainFront *__restrict__ desc, SolveArgs a)
 #pragma unroll
 			for(int kk = 0; kk < 4; ++ kk) {
 				const int p = p0 + 4 * kk + l4;
-				pa[kk] = (ci && p < w) ? F + p + (int64_t)(w + pad + i0 + l15) * ld : &ss_zero_word;
-				pb[kk] = p < w ? Xb + p * xs : &ss_zero_word;
+				pa[kk] = (ci && p < w) ? F + p + (int64_t)(w + pad + i0 + l15) * ld : &fs_zero_word;
+				pb[kk] = p < w ? Xb + p * xs : &fs_zero_word;
 			}
-			acc = ss_mfma16(pa, pb, acc);
+			acc = fs_mfma16(pa, pb, acc);
 		}
 		if(c0 + l15 < a.kc) {
 			double *Ul = a.upd + fd.uoff * xs + c0 + l15;
@@ -378,73 +252,8 @@ void ss_bwd_mfma_kernel(const AgainFront *__restrict__ desc, SolveArgs a)
 	__shared__ double ts[SS_PB * CW];
 	__shared__ double part[SS_MW][SS_PB * CW];
 	const AgainFront fd = desc[blockIdx.x]; // (one scalar fetch: no walk list -> front -> rows)
-	const int h = fd.h, w = fd.w, ld = fd.ld, pad = fd.pad;
-	const double *F = a.fronts + fd.off;
-	const int32_t *rw = a.rows + fd.rowsp;
-	const int tid = threadIdx.x, col = tid % CW, q = tid / CW;
-	const int lane = tid & 63, wave = tid >> 6, l15 = lane & 15, l4 = lane >> 4;
-	const int c0 = (int)blockIdx.y * CW;
-	const bool act = c0 + col < a.kc;
-	const int64_t xs = a.xs;
-	double *X = a.xp + (int64_t)fd.row0 * xs + c0 + col;
-	const double *Xb = a.xp + (int64_t)fd.row0 * xs + c0 + l15; // own pivots, column l15 of the tile
-	const double *Xgb = a.xp + c0 + l15;                       // by global permuted row: the ancestors' x
-	for(int j0 = ((w - 1) / SS_PB) * SS_PB; j0 >= 0; j0 -= SS_PB) {
-		const int nb = (w - j0 < SS_PB) ? w - j0 : SS_PB;
-		ss_stage_tri(F, ld, j0, nb, tri);
-		{
-			v4f64 acc = (v4f64){0, 0, 0, 0};
-			const bool ri = l15 < nb; // row j0 + l15 of R is a pivot row
-			const double *Fr = F + j0 + l15;
-			// the 16-blocks right of the block: n1 inside the pivot columns (from j0 + 16), then n2 beyond (from w)
-			const int n1 = (w - (j0 + nb) + SS_PB - 1) / SS_PB, n2 = (h - 1 - w + SS_PB - 1) / SS_PB;
-			for(int b = wave; b < n1 + n2; b += SS_MW) {
-				const double *pa[4], *pb[4];
-				if(b < n1) {
-#pragma unroll
-					for(int kk = 0; kk < 4; ++ kk) {
-						const int c = j0 + nb + b * SS_PB + 4 * kk + l4;
-						pa[kk] = (ri && c < w) ? Fr + (int64_t)c * ld : &ss_zero_word;
-						pb[kk] = c < w ? Xb + c * xs : &ss_zero_word;
-					}
-				} else {
-#pragma unroll
-					for(int kk = 0; kk < 4; ++ kk) {
-						const int c = w + (b - n1) * SS_PB + 4 * kk + l4;
-						const bool in = c < h - 1;
-						const int g = rw[in ? c : 0];
-						pa[kk] = (ri && in) ? Fr + (int64_t)(c + pad) * ld : &ss_zero_word;
-						pb[kk] = in ? Xgb + (int64_t)g * xs : &ss_zero_word;
-					}
-				}
-				acc = ss_mfma16(pa, pb, acc);
-			}
-#pragma unroll
-			for(int r = 0; r < 4; ++ r)
-				part[wave][(l4 + 4 * r) * CW + l15] = acc[r];
-		}
-		__syncthreads();
-		if(q < SS_PB) {
-			double t = (act && q < nb) ? X[(j0 + q) * xs] : 0.0;
-#pragma unroll
-			for(int v = 0; v < SS_MW; ++ v)
-				t -= part[v][q * CW + col];
-			ts[q * CW + col] = (act && q < nb) ? t : 0.0;
-		}
-		__syncthreads();
-		if(tid < SS_PB * CW) { // as forward, from the last pivot up
-			const int r = tid & 15, cc = tid >> 4;
-			double t = ts[r * CW + cc];
-#pragma unroll
-			for(int i = SS_PB - 1; i >= 0; -- i) {
-				const double xi = __shfl(t, (lane & 48) + i) / tri[i + i * 17];
-				t = (r == i) ? xi : ((r < i) ? __builtin_fma(-tri[r + i * 17], xi, t) : t);
-			}
-			if(r < nb && c0 + cc < a.kc)
-				a.xp[((int64_t)fd.row0 + j0 + r) * xs + c0 + cc] = t;
-		}
-		__syncthreads();
-	}
+	// x = R11^-1 (y - R12 x of the ancestors, by global permuted row)
+	fs_mfma_bwd(a.fronts + fd.off, fd.ld, fd.w, fd.pad, fd.h - 1, SolveCols(a, fd, (int)blockIdx.y * CW), tri, ts, part);
 }
 
 // Xp[i, j] = B[perm[i], j], a thread per (row, column of the pass)
@@ -557,10 +366,8 @@ void sparse_solve_again(spp_ctx *ctx, double *d_B, int64_t ldb, int64_t nrhs)
 		const int xs = 16 * nct; // (the MFMA body reads whole tiles of 16 columns)
 		const unsigned tiles16 = (unsigned)((kc + 15) / 16);
 		SolveArgs a;
-		a.front_off = sp->front_off.p;
-		a.front_h = sp->front_h.p; a.front_w = sp->front_w.p; a.front_ld = sp->front_ld.p; a.front_pad = sp->front_pad.p;
-		a.child_ptr = sp->child_ptr.p; a.child_list = sp->child_list.p; a.rel_ptr = sp->rel_ptr.p; a.rel = sp->rel.p;
-		a.rows_ptr = sp->rows_ptr.p; a.rows = sp->rows.p;
+		a.front_h = sp->front_h.p; a.front_w = sp->front_w.p;
+		a.child_list = sp->child_list.p; a.rel_ptr = sp->rel_ptr.p; a.rel = sp->rel.p; a.rows = sp->rows.p;
 		a.uoff = sp->again_uoff.p;
 		a.fronts = sp->fronts.p;
 		a.xp = sp->again_xp.p; a.upd = sp->again_upd.p;
@@ -577,55 +384,6 @@ void sparse_solve_again(spp_ctx *ctx, double *d_B, int64_t ldb, int64_t nrhs)
 		}
 		hipLaunchKernelGGL(ss_scatter_kernel, dim3(gn), dim3(SS_NT), 0, s, n, kc, xs, sp->perm_scalar.p, sp->again_xp.p, B, ldb);
 	}
-	SPP_HIP_CHECK(hipGetLastError());
-}
-
-// ---- covariances ---------------------------------------------------------------------------------------------------
-// column j of E is the unit vector of row rows[j]
-__global__ __launch_bounds__(256)
-void ss_unit_cols_kernel(int64_t m, const int64_t *__restrict__ rows, double *__restrict__ E, int64_t n)
-{
-	const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if(j < m)
-		E[rows[j] + j * n] = 1.0;
-}
-
-// cov(a, b) = X(rows[a], b) for a <= b, mirrored below: exactly symmetric
-__global__ __launch_bounds__(256)
-void ss_gather_cov_kernel(int64_t m, const int64_t *__restrict__ rows, const double *__restrict__ X, int64_t n, double *__restrict__ cov)
-{
-	const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if(e >= m * m)
-		return;
-	const int64_t a = e % m, b = e / m;
-	cov[e] = (a <= b) ? X[rows[a] + b * n] : X[rows[b] + a * n];
-}
-
-void sparse_marginals(spp_ctx *ctx, int64_t n_sel, const int64_t *h_vertices, double *d_cov)
-{
-	const Structure &st = ctx->st;
-	hipStream_t s = ctx->stream;
-	std::vector<char> seen((size_t)st.nb, 0);
-	std::vector<int64_t> rows;
-	for(int64_t q = 0; q < n_sel; ++ q) {
-		const int64_t v = h_vertices[q];
-		SPP_REQUIRE(v >= 0 && v < st.nb, SPP_E_BADARG, "spp_sparse_marginals_device: vertex out of range");
-		SPP_REQUIRE(!seen[(size_t)v], SPP_E_BADARG, "spp_sparse_marginals_device: a vertex is selected twice");
-		seen[(size_t)v] = 1;
-		for(int r = 0; r < st.dim[v]; ++ r)
-			rows.push_back(st.base[v] + r);
-	}
-	// (an earlier call's upload of the host image may still be in flight: the stream is drained before it is rewritten)
-	SPP_HIP_CHECK(hipStreamSynchronize(s));
-	ctx->again_rows_host.swap(rows);
-	const int64_t m = (int64_t)ctx->again_rows_host.size(), n = st.n;
-	ctx->again_rows.upload(ctx->again_rows_host, s);
-	ctx->again_cols.reserve((size_t)n * m);
-	SPP_HIP_CHECK(hipMemsetAsync(ctx->again_cols.p, 0, (size_t)n * m * sizeof(double), s));
-	hipLaunchKernelGGL(ss_unit_cols_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, m, ctx->again_rows.p, ctx->again_cols.p, n);
-	sparse_solve_again(ctx, ctx->again_cols.p, n, m);
-	hipLaunchKernelGGL(ss_gather_cov_kernel, dim3((unsigned)((m * m + 255) / 256)), dim3(256), 0, s, m, ctx->again_rows.p,
-		ctx->again_cols.p, n, d_cov);
 	SPP_HIP_CHECK(hipGetLastError());
 }
 
