@@ -16,7 +16,7 @@ block C stays well conditioned (cond <= 1e2, asserted) and the rounding of C^-1 
   edges32       3-wide poses, 2-wide landmarks, 128 poses (n_red = 384), the same pair-count spread
   mis66, mis33  one width (MIS Schur cut): two hubs tied to 2100 leaves each (a split S block between the hubs once
                 the library eliminates the leaves), plus a chain of 40 vertices hanging off hub 1
-  ring()        closed loops and open chains of any widths (loop32 here, loop73 and chain73 in schur_fixtures_73.py)
+  ring()        closed loops and open chains of any widths (loop32 and loop63 here, loop73 and chain73 in schur_fixtures_73.py)
   tiny_shards   4 cameras, 2 landmarks: with 3 landmark shards one owns nothing"""
 import numpy as np
 
@@ -201,6 +201,17 @@ def loop32():
     return ring(300, 3, 2, half=10, seed=5, split=LOOP32_SPLIT)
 
 
+LOOP63_SPLIT = (135, 140)
+
+
+def loop63():
+    """300 six-wide cameras in a loop, 3-wide landmarks (n = 10800, n_red = 1800, 15 tile rows; the arc length of this
+    width is 64 cameras, 3 tile rows; co-visibility +-8 cameras -- with +-12 the two separators leave no room for two arcs
+    of whole tiles and the natural order is kept): the camera order is accepted, camera-camera blocks in both senses
+    (tests/test_schur_fixtures_73_host.py asserts it)"""
+    return ring(300, 6, 3, half=8, seed=5, split=LOOP63_SPLIT)
+
+
 def _tiny_shards(dp, seed):
     """4 cameras, 2 landmarks each seen by two cameras, one camera-camera block: with 3 landmark shards rank 2 owns
     no landmark"""
@@ -214,7 +225,7 @@ def tiny_shards():
 GUIDED = {"edges63": edges63, "edges63_long": edges63_long, "edges32": edges32}
 MIS = {"mis66": mis66, "mis33": mis33}
 ALL = dict(GUIDED, **MIS)
-SHAPES = {"loop32": loop32, "tiny_shards": tiny_shards}   # (not edge fixtures: no pair-count spread)
+SHAPES = {"loop32": loop32, "loop63": loop63, "tiny_shards": tiny_shards}   # (not edge fixtures: no pair-count spread)
 
 
 def make(name):

@@ -10,9 +10,12 @@ import parity
 import schur_fixtures_73 as fx73
 
 K_MAX = 17
-K_WIDE = {"edges32": 129}   # the one fixture that also runs two passes of 128 columns
+K_WIDE = {"edges32": 129, "loop32": 129}   # the fixtures that also run two passes of 128 columns (loop32: SCHEDULE_FIXTURES)
 FIXTURES = ["tiny_shards", "edges32", "edges63", "edges63_long", "edges73", "edges73_aligned", "loop73"]
-COND_MAX = 1e6   # below it the 1e-10 floor of the parity criterion is above the reference's own error (cond * eps^2)
+# tests/test_gpu_solve_again_schedules.py: the three dissected loops (6 x 3, 7 x 3, 3 x 2), the open chain in its natural
+# order with unlisted tiles, and the pair-count spread
+SCHEDULE_FIXTURES = ["loop63", "loop73", "loop32", "chain73", "edges63"]
+COND_MAX = 1e6  # below it the 1e-10 floor of the parity criterion is above the reference's own error (cond * eps^2)
 
 _CACHE = {}
 

@@ -1,6 +1,6 @@
 """Host-only: the 7 x 3 fixtures of the Schur stage (tests/schur_fixtures_73.py) against the edges they exist for, as
 the host plan sees them -- the sibling of test_schur_ref.py::test_guided_fixture_reaches_its_edges -- and the shapes of
-fx.ring (loop73, loop32, chain73) and tiny_shards against the conditions the GPU tests of the camera order, the clear by
+fx.ring (loop73, loop32, loop63, chain73) and tiny_shards against the conditions the GPU tests of the camera order, the clear by
 tiles and the split API rely on: order accepted, tiles left unlisted, camera-camera blocks in both senses, the split pair
 reversed, a shard without landmarks. No GPU needed."""
 import numpy as np
@@ -68,7 +68,8 @@ def test_fixture_reaches_its_edges(name):
 
 
 # ---- the shapes of fx.ring: what the GPU tests of the camera order, the clear by tiles and the empty shard rely on -------
-LOOPS = [("loop73", 7, 3, 330, 19, fx73.LOOP73_SPLIT), ("loop32", 3, 2, 300, 8, fx.LOOP32_SPLIT)]
+LOOPS = [("loop73", 7, 3, 330, 19, fx73.LOOP73_SPLIT), ("loop32", 3, 2, 300, 8, fx.LOOP32_SPLIT),
+         ("loop63", 6, 3, 300, 15, fx.LOOP63_SPLIT)]
 
 
 @pytest.mark.parametrize("name,dp,dl,nc,tile_rows,split", LOOPS, ids=[c[0] for c in LOOPS])
@@ -82,7 +83,7 @@ def test_loop_has_its_order_accepted_with_blocks_in_both_senses(name, dp, dl, nc
     print(name, "largest landmark condition %.2f, natural %s, chosen %s" % (conds.max(), natural, chosen))
     assert used and chosen["path"] < natural["path"] == tile_rows, "the camera order of the loop is not accepted"
     al = 128 // np.gcd(128, dp)
-    assert al == 128, "the arc length of this width is 128 cameras (64 for 6-wide cameras)"
+    assert al == (64 if dp == 6 else 128), "the arc length of this width is 128 cameras (64 for 6-wide cameras)"
     assert np.array_equal(order[:al], np.arange(al)), "arc A is not the first whole arc length of cameras"
     words = api.schur_tile_mask_host(lam)
     assert len(words) == tile_rows

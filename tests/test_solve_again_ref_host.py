@@ -7,7 +7,7 @@
     Lambda = [A U; U^T C], Lambda^-1 e = [x_c; C^-1 (e_l - U^T x_c)], x_c = S^-1 (e_c - U C^-1 e_l) -- from the longdouble
     S, C^-1 and U of tests/schur_ref.py and a longdouble Gauss-Jordan solve with S; tiny_shards checks that route against
     the dense one.
-  - every fixture of the GPU tests has cond(Lambda) < 1e6: the refined solutions are then exact to ~cond eps^2 < 1e-25
+  - every fixture of the GPU tests (sar.FIXTURES and sar.SCHEDULE_FIXTURES) has cond(Lambda) < 1e6: the refined solutions are then exact to ~cond eps^2 < 1e-25
     relative, far below the 1e-10 floor of the criterion."""
 import numpy as np
 import pytest
@@ -102,7 +102,7 @@ def test_covariance_from_refined_unit_columns_matches_the_longdouble_inverse(nam
     assert float(np.abs(cov - cov.T).max()) <= bound * float(np.abs(cov).max())
 
 
-@pytest.mark.parametrize("name", sar.FIXTURES)
+@pytest.mark.parametrize("name", sar.FIXTURES + [n for n in sar.SCHEDULE_FIXTURES if n not in sar.FIXTURES])
 def test_every_fixture_of_the_gpu_tests_is_well_conditioned(name):
     cond = sar.condition(name)
     print("%s: cond(Lambda) = %.3e" % (name, cond))
