@@ -314,31 +314,16 @@ static void launch_gemm(hipStream_t s, int64_t M, int64_t N, int K, const double
 // of the consumer on its stream: the kernel boundaries are the release and the acquire (no fences inside the
 // compute kernels), and a waiter holds one wave slot, never the slots the producer still needs (a consumer
 // that polled in its own prologue would park hundreds of workgroups on the CUs of the kernel it waits for).
-// Every wait is bounded: on a timeout (100 MHz wall clock) the abort word is set, all later waits fall
-// through and the host reports the failure.
+// Every wait is bounded (spp_wait.h).
 struct FlagWait {
 	const int *flag; // nullptr: no wait
 	int value;
-	int *abort;
-	long long timeout_ticks;
+	WaitBound bound;
 };
 
 __device__ __forceinline__ void flag_spin(const FlagWait &fw)
 {
-	const long long t0 = wall_clock64();
-	for(int it = 0;; ++ it) {
-		if(__hip_atomic_load(fw.flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == fw.value)
-			return;
-		if((it & 15) == 15) {
-			if(__hip_atomic_load(fw.abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)
-				return;
-			if(wall_clock64() - t0 > fw.timeout_ticks) {
-				__hip_atomic_store(fw.abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-				return;
-			}
-		}
-		__builtin_amdgcn_s_sleep(2);
-	}
+	bounded_wait<2, 16>(fw.bound, 1, [&]() { return wait_ld(fw.flag) == fw.value; });
 }
 
 __global__ void flag_signal_kernel(int *flag, int value)
@@ -510,7 +495,7 @@ void tinv_finish_kernel(double *__restrict__ tinv_all)
 // --------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(POTRF_THREADS)
 void update_potrf_kernel(int64_t M, int64_t N, const double *P, int64_t ld, double *C, int nA, int target, int do_potrf,
-	int n_valid, int has_rhs, double *tinv, int *info, int64_t k0_next, int *counter, int *abort, long long timeout_ticks)
+	int n_valid, int has_rhs, double *tinv, int *info, int64_t k0_next, int *counter, WaitBound bound)
 {
 	extern __shared__ double sm[];
 	const int b = (int)blockIdx.x, tid = threadIdx.x;
@@ -527,36 +512,15 @@ void update_potrf_kernel(int64_t M, int64_t N, const double *P, int64_t ld, doub
 			rem -= cnt;
 		}
 		gemm_tn_staged_tile<32, 32, 16, 16, 0, 0>((int64_t)rem * 32, (int64_t)j * 32, M, N, P, ld, P, ld, C, ld, sm);
-		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-		__syncthreads();
-		if(tid == 0) {
-			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-			__hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		}
+		publish_add(counter);
 		return;
 	}
 	if(do_potrf && b == nA) {
 		__shared__ int go;
 		if(tid == 0) {
-			const long long t0 = wall_clock64();
-			int ok = 1;
-			for(int it = 0; __hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target; ++ it) { // monotonic counter: its value after this launch's nA producers
-				if((it & 15) == 15) {
-					if(__hip_atomic_load(abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-						ok = 0;
-						break;
-					}
-					if(wall_clock64() - t0 > timeout_ticks) {
-						__hip_atomic_store(abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-						ok = 0;
-						break;
-					}
-				}
-				__builtin_amdgcn_s_sleep(1);
-			}
-			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+			// monotonic counter: its value after this launch's nA producers
+			const int ok = bounded_wait<1, 16>(bound, 1, [&]() { return wait_ld(counter) >= target; });
+			acquire_by_lane();
 			go = ok;
 		}
 		__syncthreads();
@@ -642,7 +606,10 @@ void trsv_back_kernel(const double *__restrict__ R, int64_t ld, int64_t k0, int 
 
 // The timeout word of the backward-substitution chains is page-locked host memory (DenseWork::h_chain_err): a workgroup that
 // gives up stores there itself, with a system-scope vector store, so no copy of the word sits on the stream behind every
-// solve. The host looks at it after a synchronization (dense_chain_check).
+// solve. The host looks at it after a synchronization (dense_chain_check). Inside the launch the waits look at a word in
+// device memory instead (spp_wait.h, the tagged kind: info[1], never reset -- the tag is the solve's epoch in
+// trsv_back_chain_kernel, the low word of its check constant K in trsv_back_chain2_kernel, both non-zero): the mapped host
+// word is never polled.
 __device__ __forceinline__ void chain_raise(int *err)
 {
 	__hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -653,11 +620,11 @@ __device__ __forceinline__ void chain_raise(int *err)
 // kernel launches. Workgroup b applies x_k to its rows for k = last .. b+1
 // as the x_k are published (flag[k] == epoch of this solve), then solves its diagonal block with the
 // stored inverse, publishes x_b and exits. Every wait depends only on workgroups with a larger index, which never
-// wait on smaller ones: no cycle. The spin is BOUNDED: on timeout the workgroup raises `err`, publishes
-// nothing and exits -- the ones below it time out the same way -- so the grid always drains.
+// wait on smaller ones: no cycle. The wait is BOUNDED (spp_wait.h): a workgroup that gives up raises `err`, publishes
+// nothing and exits -- the ones below it find the abort word at their next bound check -- so the grid always drains.
 __global__ __launch_bounds__(256)
 void trsv_back_chain_kernel(const double *__restrict__ R, int64_t ld, int64_t n, int nblk,
-	const double *__restrict__ tinv_all, const double *__restrict__ y, double *xout, int *flags, int epoch, int *err)
+	const double *__restrict__ tinv_all, const double *__restrict__ y, double *xout, int *flags, int epoch, WaitBound bound, int *err)
 {
 	__shared__ double xs[NB];
 	__shared__ double part[2][NB];
@@ -687,18 +654,12 @@ void trsv_back_chain_kernel(const double *__restrict__ R, int64_t ld, int64_t n,
 		load_tile(nblk - 1);
 	double acc = (h == 0 && r0 + r < n) ? y[r0 + r] : 0.0; // each row is split over two threads (64 columns each)
 	for(int k = nblk - 1; k > b; -- k) {
-		if(tid == 0) {
-			int spins = 0;
-			// relaxed polling by ONE thread: an ACQUIRE load at agent scope invalidates the XCD's L2 on
-			// every poll (40 pollers thrash the caches of the workgroups that stream R), and 128 threads
-			// polling the data itself (x_k preset to a NaN pattern) was 2x slower than flag + fence;
-			// x_k is read with agent-scope atomic loads, which go to the coherent level on their own
-			while(__hip_atomic_load(&flags[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != epoch && spins < (1 << 22)) {
-				__builtin_amdgcn_s_sleep(1);
-				++ spins;
-			}
-			ok = spins < (1 << 22);
-		}
+		// relaxed polling by ONE thread: an ACQUIRE load at agent scope invalidates the XCD's L2 on
+		// every poll (40 pollers thrash the caches of the workgroups that stream R), and 128 threads
+		// polling the data itself (x_k preset to a NaN pattern) was 2x slower than flag + fence;
+		// x_k is read with agent-scope atomic loads, which go to the coherent level on their own
+		if(tid == 0)
+			ok = bounded_wait<1, 16, true>(bound, epoch, [&]() { return wait_ld(&flags[k]) == epoch; });
 		__syncthreads();
 		if(!ok) {
 			if(tid == 0)
@@ -765,7 +726,8 @@ void trsv_back_chain_kernel(const double *__restrict__ R, int64_t ld, int64_t n,
 // simply read again. So the producer never drains its stores and the consumer needs no second, dependent load.
 // Dispatch order = chain, then helpers from the last block row down: a workgroup only ever waits for data that
 // workgroups dispatched before it produce without waiting for a later one (helper b needs x_k, k > b + 1, which need
-// helpers > b + 1 only), so progress does not depend on how many workgroups are resident. Spins are bounded (err).
+// helpers > b + 1 only), so progress does not depend on how many workgroups are resident. Waits are bounded (spp_wait.h):
+// a helper that gives up hands nothing over and exits, the chain goes on with garbage, so every workgroup still drains.
 // --------------------------------------------------------------------------------------------------
 struct TrsvPay { double v; unsigned long long c; };
 
@@ -838,7 +800,7 @@ __device__ __forceinline__ void tile_dot(double2 &a, const TileRegs<NW> &t, cons
 template <int NW, bool MFORM>
 __global__ __launch_bounds__(64 * NW)
 void trsv_back_chain2_kernel(const double *__restrict__ R, int64_t ld, int64_t n, int nblk,
-	const double *__restrict__ tinv_all, const double *__restrict__ mbuf, double *y, TrsvPay *xpay, TrsvPay *wpay, unsigned long long K, int *err)
+	const double *__restrict__ tinv_all, const double *__restrict__ mbuf, double *y, TrsvPay *xpay, TrsvPay *wpay, unsigned long long K, WaitBound bound, int *err)
 {
 	__shared__ double xs[2][NB];   // chain: x_b in xs[b & 1] ; helper: xs[0 / 1] = the x_k being applied
 	__shared__ double zs[NB];
@@ -846,7 +808,8 @@ void trsv_back_chain2_kernel(const double *__restrict__ R, int64_t ld, int64_t n
 	__shared__ int ok[2];
 	constexpr int L = 1; // tiles right of the diagonal the chain applies itself (two measured slower: the chain is bound by what it fetches)
 	const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6); // (wave: a scalar -- column bases stay in scalar registers)
-	constexpr int SPIN_MAX = 1 << 22;
+	const int tag = (int)(unsigned)K; // this solve in the abort word: K is an odd multiple of an odd constant, its low word odd
+	auto pay_ok = [&](const double v, const unsigned long long c) { return ((unsigned long long)__double_as_longlong(v) ^ c) == K; };
 	auto part_sum = [&](const int row) {
 		double s = 0;
 #pragma unroll
@@ -873,17 +836,14 @@ void trsv_back_chain2_kernel(const double *__restrict__ R, int64_t ld, int64_t n
 			if(tid < 64) { // one wave polls the payload of x_k: two elements per lane
 				const TrsvPay *src = xpay + (size_t)k * NB + 2 * tid;
 				double v0 = 0, v1 = 0;
-				int spins = 0;
-				for(;;) {
+				const bool got = bounded_wait<2, 16, true>(bound, tag, [&]() {
 					const bool g0 = pay_load(src, v0, K), g1 = pay_load(src + 1, v1, K);
-					if(__all(g0 && g1) || ++ spins >= SPIN_MAX)
-						break;
-					__builtin_amdgcn_s_sleep(2);
-				}
+					return __all(g0 && g1) != 0;
+				});
 				xk[2 * tid] = v0;
 				xk[2 * tid + 1] = v1;
 				if(tid == 0)
-					ok[slot] = spins < SPIN_MAX;
+					ok[slot] = got;
 			}
 			lds_barrier();
 			if(!ok[slot]) {
@@ -968,14 +928,14 @@ void trsv_back_chain2_kernel(const double *__restrict__ R, int64_t ld, int64_t n
 			fetch_m(b - 2, t);
 			lds_barrier();
 			if(tid < NB) {
-				int spins = 0;
-				while(((unsigned long long)__double_as_longlong(uv) ^ uc) != K && spins < SPIN_MAX) {
-					__builtin_amdgcn_s_sleep(1);
-					ask_u(b, uv, uc);
-					++ spins;
-				}
-				if(spins >= SPIN_MAX)
-					chain_raise(err);
+				bool asked = true; // u_b was asked for one hop ago: the first test needs no load
+				if(!bounded_wait<1, 16, true>(bound, tag, [&]() {
+					if(!asked)
+						ask_u(b, uv, uc);
+					asked = false;
+					return pay_ok(uv, uc);
+				}))
+					chain_raise(err); // (the hop goes on with garbage: every workgroup still drains)
 				const double xr = uv - part_sum(tid);
 				xs[b & 1][tid] = xr;
 				pay_store(xpay + (size_t)b * NB + tid, xr, K);
@@ -1037,13 +997,13 @@ void trsv_back_chain2_kernel(const double *__restrict__ R, int64_t ld, int64_t n
 		// B: z = w_b - sum. w_b was asked for one hop ago; read again until the pair is consistent (the helper is
 		// normally far ahead)
 		if(tid < NB) {
-			int spins = 0;
-			while(((unsigned long long)__double_as_longlong(wv) ^ wc) != K && spins < SPIN_MAX) {
-				__builtin_amdgcn_s_sleep(1);
-				ask_w(b, wv, wc);
-				++ spins;
-			}
-			if(spins >= SPIN_MAX)
+			bool asked = true;
+			if(!bounded_wait<1, 16, true>(bound, tag, [&]() {
+				if(!asked)
+					ask_w(b, wv, wc);
+				asked = false;
+				return pay_ok(wv, wc);
+			}))
 				chain_raise(err); // (the hop goes on with garbage: every workgroup still drains)
 			zs[tid] = wv - part_sum(tid);
 		}
@@ -1154,8 +1114,8 @@ void dense_set_padding(spp_ctx *ctx, double *d_A, int64_t ld, int64_t n)
 // --------------------------------------------------------------------------------------------------
 // host drivers
 // --------------------------------------------------------------------------------------------------
-// info[0]: first failing pivot + 1, info[1]: free (the backward-substitution chain's timeout word is host memory,
-// DenseWork::h_chain_err), info[2]: abort flag of
+// info[0]: first failing pivot + 1, info[1]: abort word of the backward-substitution chains' waits (tagged by the solve:
+// never reset, a stale value means nothing; what the host reads is DenseWork::h_chain_err), info[2]: abort flag of
 // the device-flag hand-offs and the streamed launch (stays set until the host has seen it; TAIL_ABORT_TIMEOUT: a wait of
 // the streamed launch gave up), info[3]: abort flag of the sparse path's
 // dependency-driven launches -- zeroed once, when the buffer is created
@@ -1367,8 +1327,7 @@ static void dense_factor_lookahead(spp_ctx *ctx, double *d_A, int64_t ld, int64_
 	const size_t nints = (la_counter_ints(a.nsteps, a.nt) + 3) & ~(size_t)3;
 	dw.la_cnt.reserve(nints);
 	a.cnt = dw.la_cnt.p;
-	a.abort = dw.info.p + 2;
-	a.timeout_ticks = WAIT_TICKS_DEFAULT;
+	a.bound = {dw.info.p + 2, WAIT_TICKS_DEFAULT};
 	a.bulk_acquire = sw.la_bulk_acquire;
 	a.use444 = sw.tile_444;
 	static uint64_t bulk_attr_seen = 0;
@@ -1459,7 +1418,7 @@ static void flag_signal(hipStream_t st, int *flag, int value)
 
 static FlagWait make_flag_wait(spp_ctx *ctx, const int *flag, int value, long long timeout_ticks = WAIT_TICKS_DEFAULT)
 {
-	return FlagWait{flag, value, ctx->dense.info.p + 2, timeout_ticks};
+	return FlagWait{flag, value, {ctx->dense.info.p + 2, timeout_ticks}};
 }
 
 static void flag_wait(spp_ctx *ctx, hipStream_t st, const int *flag, int value, long long timeout_ticks)
@@ -1589,8 +1548,7 @@ static bool launch_dense_tail(spp_ctx *ctx, double *d_A, int64_t ld, int64_t row
 	a.pub = dw.tail_pub.p;
 	a.epoch = dw.tail_epoch;
 	a.info = dw.info.p;
-	a.abort = dw.info.p + 2;
-	a.timeout_ticks = sw.tail_timeout_ticks;
+	a.bound = {dw.info.p + 2, sw.tail_timeout_ticks};
 	static int launches = 0;
 	DevBuf<long long> trace;
 	a.trace = nullptr;
@@ -1800,7 +1758,7 @@ static void dense_factor_steps_enqueue(spp_ctx *ctx, double *d_A, int64_t ld, in
 		hipLaunchKernelGGL(update_potrf_kernel, dim3((unsigned)(nA + do_potrf + nbi * nbj)), dim3(POTRF_THREADS),
 			POTRF_LDS_DOUBLES * sizeof(double), s, m, N, d_A + kp0 + r0 * ld, ld, d_A + r0 + r0 * ld, nA, dw.fuse_expect[slot], do_potrf,
 			n_valid, (has_rhs && n_valid < NB) ? 1 : 0, dw.tinv_all.p + (size_t)(kn >= 0 ? kn : 0) * NB * NB, dw.info.p, kn0,
-			dw.fuse_cnt.p + slot, dw.info.p + 2, WAIT_TICKS_DEFAULT);
+			dw.fuse_cnt.p + slot, WaitBound{dw.info.p + 2, WAIT_TICKS_DEFAULT});
 		return true;
 	};
 	auto potrf_and_panel = [&](int64_t k, bool potrf_done = false) {
@@ -1929,7 +1887,9 @@ void dense_chain_check(spp_ctx *ctx)
 {
 	if(ctx->dense.h_chain_err && *ctx->dense.h_chain_err) {
 		*ctx->dense.h_chain_err = 0;
-		throw Error(SPP_E_HIP, "backward substitution: a workgroup of the chain kernel timed out waiting for its predecessor");
+		ctx->dense.chain_disabled = true;
+		throw Error(SPP_E_HIP, "backward substitution: a workgroup of the chain kernel timed out waiting for its predecessor; "
+			"the following calls launch per block row");
 	}
 }
 
@@ -2081,7 +2041,9 @@ void dense_potrs_upper(spp_ctx *ctx, const double *d_R, int64_t n, int64_t ld, d
 	}
 	// both chain kernels tell one solve from the next by a kernel argument (epoch / check constant): a captured
 	// launch would replay it stale -- inside a stream capture the substitution is a launch per block row
-	const int use_chain = capturing(s) ? 0 : switches().trsv_chain;
+	const int use_chain = (capturing(s) || ctx->dense.chain_disabled) ? 0 : switches().trsv_chain;
+	ensure_info(ctx);
+	const WaitBound bound{ctx->dense.info.p + 1, switches().chain_timeout_ticks};
 	if(use_chain == 2 && nblk > 1 && nblk <= 4096) {
 		DenseWork &dw = ctx->dense;
 		const size_t need = (size_t)nblk * NB * 4; // x and w, two words per element
@@ -2103,10 +2065,10 @@ void dense_potrs_upper(spp_ctx *ctx, const double *d_R, int64_t n, int64_t ld, d
 				SPP_HIP_CHECK(hipFuncSetAttribute((const void*)trsv_m_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TRSVM_LDS_DOUBLES * (int)sizeof(double)));
 			hipLaunchKernelGGL(trsv_m_kernel, dim3((unsigned)nblk - 1, 8), dim3(1024), TRSVM_LDS_DOUBLES * sizeof(double), s, d_R, ld, n, dw.tinv_all.p, dw.trsv_m.p);
 			hipLaunchKernelGGL((trsv_back_chain2_kernel<8, true>), dim3((unsigned)nblk + 1), dim3(512), 0, s,
-				d_R, ld, n, (int)nblk, dw.tinv_all.p, dw.trsv_m.p, d_b, xpay, wpay, K, dw.d_chain_err);
+				d_R, ld, n, (int)nblk, dw.tinv_all.p, dw.trsv_m.p, d_b, xpay, wpay, K, bound, dw.d_chain_err);
 		} else
 			hipLaunchKernelGGL((trsv_back_chain2_kernel<8, false>), dim3((unsigned)nblk + 1), dim3(512), 0, s,
-				d_R, ld, n, (int)nblk, dw.tinv_all.p, (const double*)nullptr, d_b, xpay, wpay, K, dw.d_chain_err);
+				d_R, ld, n, (int)nblk, dw.tinv_all.p, (const double*)nullptr, d_b, xpay, wpay, K, bound, dw.d_chain_err);
 		SPP_HIP_CHECK(hipGetLastError());
 		return;
 	}
@@ -2121,7 +2083,7 @@ void dense_potrs_upper(spp_ctx *ctx, const double *d_R, int64_t n, int64_t ld, d
 		chain_err_ensure(dw);
 		++ dw.epoch;
 		hipLaunchKernelGGL(trsv_back_chain_kernel, dim3((unsigned)nblk), dim3(256), 0, s, d_R, ld, n, (int)nblk,
-			dw.tinv_all.p, d_b, dw.xtmp.p, dw.flags.p, (int)dw.epoch, dw.d_chain_err);
+			dw.tinv_all.p, d_b, dw.xtmp.p, dw.flags.p, (int)dw.epoch, bound, dw.d_chain_err);
 		SPP_HIP_CHECK(hipGetLastError());
 		SPP_HIP_CHECK(hipMemcpyAsync(d_b, dw.xtmp.p, n * sizeof(double), hipMemcpyDeviceToDevice, s));
 		return;

@@ -5,6 +5,7 @@
 #pragma once
 #include "spp_internal.h"
 #include "spp_tiles.h"
+#include "spp_wait.h"
 
 // The fp64 MFMA form used by the tile products is v_mfma_f64_16x16x4 (2048 flop). Measured on MI355X with the operand
 // pattern of a real tile product (tools/mfma_rate2.hip: a register outer product, distinct operand registers per

@@ -21,8 +21,8 @@
 // launch, no stream event, nothing of the bulk side (the window keeps the chain two steps ahead of what it needs from the
 // bulk launches). Every dependency points to a task that is EARLIER in the order (step, potrf < b1 < c1 < b2 < c2 < d <
 // bulk), every executor (workgroup of the chain kernel, the bulk stream) runs its tasks in that order: the smallest
-// unfinished task is always runnable, so there is no cycle. All waits are bounded by the 100 MHz wall clock (abort word ->
-// every later wait falls through -> the host reports the failure and returns to the event schedule).
+// unfinished task is always runnable, so there is no cycle. All waits are bounded (spp_wait.h; the host returns to the
+// event schedule).
 //
 // Visibility (MI355X_MICROARCH.md, inter-workgroup hand-offs): everything the chain kernel publishes is stored
 // write-through (agent-scope atomic = sc1 stores), every storing wave drains (s_waitcnt vmcnt(0)), the workgroup barrier,
@@ -42,9 +42,8 @@ struct LaArgs {
 	double *tinv_all;
 	int *info;
 	int *cnt;            // counters of this factorization (zeroed by a memset in front of the launch)
-	int *abort;
-	long long timeout_ticks;
-	int bulk_acquire;    // 1: bulk workgroups run an agent-scope acquire behind their poll
+	WaitBound bound;     // of every wait (spp_wait.h)
+	int bulk_acquire;   // 1: bulk workgroups run an agent-scope acquire behind their poll
 	int use444;          // whole tiles of the bulk update by the v_mfma_f64_4x4x4_4b kernel (spp_dense_444.h)
 	long long *trace;    // optional: wall-clock stamps (SPP_LA_TRACE)
 };
@@ -93,9 +92,7 @@ constexpr int LA_LDS_DOUBLES = (NB + 16) * FS_STRIDE + 8; // the inverse (128 co
 static_assert(LA_LDS_DOUBLES >= POTRF_LDS_DOUBLES && LA_LDS_DOUBLES >= (32 + 32) * FS_STRIDE, "chain kernel LDS");
 static_assert(LA_LDS_DOUBLES * 8 <= 160 * 1024, "chain kernel LDS exceeds a CU");
 
-__device__ __forceinline__ int la_ld(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// Wait until cnt[i0] >= t0 and cnt[i1] >= t1 (an index < 0: no condition). ONE lane polls (relaxed, s_sleep), runs the
+// Wait until cnt[i0] >= t0 and cnt[i1] >= t1 (an index < 0: no condition). ONE lane polls (bounded_wait), runs the
 // agent-scope acquire and waits for it; the barrier holds the other waves' loads behind it. `phase` alternates the status
 // word so that a second wait cannot overwrite a status some wave has not read yet. Returns false after an abort / timeout.
 __device__ __forceinline__ bool la_wait(const LaArgs &a, int i0, int t0, int i1, int t1, double *sm, int &phase)
@@ -103,28 +100,12 @@ __device__ __forceinline__ bool la_wait(const LaArgs &a, int i0, int t0, int i1,
 	int *okw = (int*)(sm + LA_LDS_DOUBLES - 2) + (phase & 1) * 2;
 	phase ^= 1;
 	if(threadIdx.x == 0) {
-		int ok = 1;
-		const long long tb = wall_clock64();
-		for(int it = 0;; ++ it) {
-			const bool r0 = i0 < 0 || la_ld(a.cnt + i0) >= t0;
-			const bool r1 = i1 < 0 || la_ld(a.cnt + i1) >= t1;
-			if(r0 && r1)
-				break;
-			if((it & 15) == 15) {
-				if(la_ld(a.abort) != 0) {
-					ok = 0;
-					break;
-				}
-				if(wall_clock64() - tb > a.timeout_ticks) {
-					__hip_atomic_store(a.abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-					ok = 0;
-					break;
-				}
-			}
-			__builtin_amdgcn_s_sleep(1);
-		}
-		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+		const int ok = bounded_wait<1, 16>(a.bound, 1, [&]() {
+			const bool r0 = i0 < 0 || wait_ld(a.cnt + i0) >= t0;
+			const bool r1 = i1 < 0 || wait_ld(a.cnt + i1) >= t1;
+			return r0 && r1;
+		});
+		acquire_by_lane();
 		*okw = ok;
 	}
 	__syncthreads();
@@ -255,15 +236,9 @@ __device__ __forceinline__ void la_potrf_role(const LaArgs &a, double *sm)
 		la_potrf_step(a.A + k0 + k0 * a.ld, a.ld, (int)nv, (a.has_rhs && nv < NB) ? 1 : 0,
 			a.tinv_all + (size_t)k * NB * NB, a.info, k0, sm);
 		LA_TRACE(8 * k + 2);
-		if(LA_POTRF_STORE == 0) {
-			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-			__syncthreads();
-			if(threadIdx.x == 0) {
-				__builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-				asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-				__hip_atomic_fetch_add(a.cnt + la_potrf_done(a, k), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-			}
-		} else
+		if(LA_POTRF_STORE == 0)
+			publish_add(a.cnt + la_potrf_done(a, k));
+		else
 			la_publish(a, la_potrf_done(a, k));
 		LA_TRACE(8 * k + 1);
 	}
@@ -484,27 +459,10 @@ void la_bulk_kernel(const LaArgs a, const int k, const int nr, const int nc, con
 	const int gi = k + 1 + ri, gj = k + 1 + rj;
 	// the two row-panel pieces this tile multiplies: every 16-column slab of R(k, gi) and R(k, gj) solved
 	if(threadIdx.x == 0) {
-		int ok = 1;
 		const int i0 = la_col_cnt(a, k, gi), t0 = la_nslabs(a, gi), i1 = la_col_cnt(a, k, gj), t1 = la_nslabs(a, gj);
-		const long long tb = wall_clock64();
-		for(int it = 0; la_ld(a.cnt + i0) < t0 || la_ld(a.cnt + i1) < t1; ++ it) {
-			if((it & 15) == 15) {
-				if(la_ld(a.abort) != 0) {
-					ok = 0;
-					break;
-				}
-				if(wall_clock64() - tb > a.timeout_ticks) {
-					__hip_atomic_store(a.abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-					ok = 0;
-					break;
-				}
-			}
-			__builtin_amdgcn_s_sleep(2);
-		}
-		if(a.bulk_acquire) {
-			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-		}
+		const int ok = bounded_wait<2, 16>(a.bound, 1, [&]() { return !(wait_ld(a.cnt + i0) < t0 || wait_ld(a.cnt + i1) < t1); });
+		if(a.bulk_acquire)
+			acquire_by_lane();
 		ok_s = ok;
 	}
 	__syncthreads();

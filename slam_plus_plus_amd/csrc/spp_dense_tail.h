@@ -23,7 +23,7 @@
 // with a smaller index, which never waits for a larger one -- progress does not depend on residency. With a tile mask a
 // set E of trailing tile rows may be numbered in front of all others (tail_order_table, spp_tile_plan.cpp): no tile outside
 // E waits for one of E, and the host uses E only when E and the live tiles outside it are resident together. Every wait
-// is bounded (abort word).
+// is bounded (spp_wait.h).
 // Summation order per tile: its steps in the order of the launch's step list, row tiles ascending -- fixed, bit-
 // reproducible. The list is k ascending, except where the caller of a whole factorization hands over a step order
 // (TailArgs::sorder, tail_step_order in spp_tile_plan.cpp: by the depth of the step's diagonal tile): two chains of steps
@@ -54,8 +54,8 @@ struct TailArgs {
 	double *dbuf;        // [Tr][8][256]: inverse 16 x 16 diagonal tiles as they are published
 	int *pub;            // [Tr][Tc]: (epoch << 4) | row tiles published
 	int epoch;
-	int *info, *abort;   // abort word: 1 = a diagonal block is not positive definite (info[0] says which), TAIL_ABORT_TIMEOUT = a wait gave up
-	long long timeout_ticks;
+	int *info;
+	WaitBound bound;     // abort word: 1 = a diagonal block is not positive definite (info[0] says which), TAIL_ABORT_TIMEOUT = a wait gave up
 	long long *trace;    // debugging (SPP_TAIL_TRACE): per tile row 8 wall-clock stamps
 	const int *order;    // workgroup -> tile (i << 16 | j), a topological order of the nonzero tiles (see the host side)
 	// rowbits[k + 1], bit j: tile (k, j) of the region is nonzero after symbolic fill (region tile indices); rowbits[0]
@@ -138,26 +138,13 @@ void dense_tail_kernel(const TailArgs a)
 	// bounded wait by one lane: counters p (and q) of this epoch at least `need`; returns how many row tiles are out
 	auto wait_pub = [&](const int *p, const int *q, const int need) -> int {
 		if(tid == 0) {
-			const long long t0 = wall_clock64();
-			int got = -1;
-			for(;;) {
-				const int v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-				const int w = q ? __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : v;
-				const int cv = ((v >> 4) == a.epoch) ? (v & 15) : 0, cw = ((w >> 4) == a.epoch) ? (w & 15) : 0;
-				const int c = cv < cw ? cv : cw;
-				if(c >= need) {
-					got = c;
-					break;
-				}
-				if(__hip_atomic_load(a.abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-					break;
-				if(wall_clock64() - t0 > a.timeout_ticks) {
-					__hip_atomic_store(a.abort, TAIL_ABORT_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-					break;
-				}
-				__builtin_amdgcn_s_sleep(1);
-			}
-			st[1] = got;
+			int c = 0;
+			const bool ok = bounded_wait<1, 1>(a.bound, TAIL_ABORT_TIMEOUT, [&]() {
+				const int v = wait_ld(p);
+				c = pub_count(v, q ? wait_ld(q) : v);
+				return c >= need;
+			});
+			st[1] = ok ? c : -1;
 		}
 		lds_barrier();
 		const int got = st[1];
@@ -361,7 +348,7 @@ void dense_tail_kernel(const TailArgs a)
 		pb.flag = a.pub + ti * a.Tc + ti;
 		pb.base = tag;
 		pb.dbuf = a.dbuf + (size_t)ti * 8 * 256;
-		pb.abort = a.abort;
+		pb.abort = a.bound.abort;
 		potrf_diag_body<false, 1, 2, true>(a.A + i0 + i0 * a.ld, a.ld, n_valid, (a.has_rhs && n_valid < NB) ? 1 : 0,
 			a.tinv + (size_t)ti * NB * NB, a.info, i0, sm, pb, pre_first ? 1 : 0);
 		stamp(2);

@@ -373,6 +373,7 @@ struct DenseWork {
 	uint64_t epoch = 0;            // solves so far (backward-substitution chains tell one solve from the next by it)
 	int *h_chain_err = nullptr;    // timeout word of the chain kernels: page-locked, mapped host memory they store into on their error path alone (dense_chain_check)
 	int *d_chain_err = nullptr;    // ... its device address
+	bool chain_disabled = false;   // a chain kernel timed out on this ctx: later backward substitutions launch per block row
 	hipStream_t aux = nullptr;     // lookahead stream: potrf_diag + trsm of the next panel
 	hipEvent_t ev[2] = {nullptr, nullptr};
 	// device-flag hand-offs between the chain stream and the bulk stream (dense_factor_steps_enqueue):

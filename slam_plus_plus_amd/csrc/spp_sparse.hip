@@ -1179,8 +1179,7 @@ void front_bwd_kernel(const int32_t *__restrict__ level_fronts, FrontArgs fa)
 // flag behind an agent-scope release. A front starts the moment its own children are done; the critical path is the
 // heaviest root-to-leaf chain of fronts, not the sum over the levels of the slowest front of each.
 // Progress: workgroups are dispatched in block order, so every producer a resident workgroup waits for is resident or
-// finished. Every wait is bounded all the same (wall clock -> abort word -> every later wait falls through -> the host
-// reports the failure and goes back to the level-by-level launches).
+// finished. Every wait is bounded all the same (spp_wait.h; the host goes back to the level-by-level launches).
 // Flags hold the epoch of the solve that last finished the front: no clearing between solves.
 // --------------------------------------------------------------------------------------------------
 struct DagArgs {
@@ -1191,8 +1190,7 @@ struct DagArgs {
 	int epoch;
 	int level_limit;          // fronts of levels >= level_limit are handled by launches of their own (no flags)
 	int level_first;          // factorization: the fronts of levels < level_first were finished by earlier launches
-	int *abort;
-	long long timeout_ticks;
+	WaitBound bound;          // of every wait (spp_wait.h)
 	// big fronts: a team of workgroups each (consecutive blocks)
 	const int32_t *rank;       // per block: rank inside its front's team
 	const int32_t *front_team; // per front: team size (1: a single workgroup)
@@ -1203,33 +1201,9 @@ struct DagArgs {
 	long long *trace;          // debugging (SPP_DAG_TRACE): per block wall-clock stamps start / children done / end
 };
 
-__device__ __forceinline__ bool dag_wait(const int *flag, int value, int *abort, long long timeout_ticks)
+__device__ __forceinline__ bool dag_wait(const DagArgs &da, const int front)
 {
-	const long long t0 = wall_clock64();
-	for(int it = 0; __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != value; ++ it) {
-		if((it & 15) == 15) {
-			if(__hip_atomic_load(abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)
-				return false;
-			if(wall_clock64() - t0 > timeout_ticks) {
-				__hip_atomic_store(abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-				return false;
-			}
-		}
-		__builtin_amdgcn_s_sleep(1);
-	}
-	return true;
-}
-
-// the workgroup's stores are complete and visible device-wide, then the flag
-__device__ __forceinline__ void dag_publish(int *flag, int value)
-{
-	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-	__syncthreads();
-	if(threadIdx.x == 0) {
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-		__hip_atomic_store(flag, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-	}
+	return bounded_wait<1, 16>(da.bound, 1, [&]() { return wait_ld(da.done + front) == da.epoch; });
 }
 
 // ---- big fronts inside the dependency-driven launch: a TEAM of workgroups per front -------------------------------
@@ -1241,29 +1215,13 @@ __device__ __forceinline__ void dag_publish(int *flag, int value)
 // products of the dense factor), with a barrier of the team -- a monotonic counter in device memory behind an
 // agent-scope release, an acquire behind the wait -- between the phases. Fronts of one level run side by side, the
 // part of the assembly that needs no child runs ahead of the wait for the children.
-__device__ __forceinline__ void team_barrier(int *counter, int target, int *abort, long long timeout_ticks)
+__device__ __forceinline__ void team_barrier(int *counter, int target, const WaitBound &bound)
 {
-	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-	__syncthreads();
-	if(threadIdx.x == 0) {
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+	publish([&]() {
 		__hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		const long long t0 = wall_clock64();
-		for(int it = 0; __hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target < 0; ++ it) {
-			if((it & 15) == 15) {
-				if(__hip_atomic_load(abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)
-					break;
-				if(wall_clock64() - t0 > timeout_ticks) {
-					__hip_atomic_store(abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-					break;
-				}
-			}
-			__builtin_amdgcn_s_sleep(1);
-		}
-		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-	}
+		bounded_wait<1, 16>(bound, 1, [&]() { return wait_ld(counter) - target >= 0; });
+		acquire_by_lane();
+	});
 	__syncthreads();
 }
 
@@ -1287,7 +1245,7 @@ __device__ __noinline__ void team_update_tile(int64_t m0, int64_t n0, int64_t nr
 
 template <class WaitFn>
 __device__ __forceinline__ void bigfront_team_body(const int s, const int rank, const int G, const FrontArgs &fa,
-	int *bar, const int bar_base, double *tinv, int *abort, long long timeout_ticks, double *sm, const WaitFn &wait_children)
+	int *bar, const int bar_base, double *tinv, const WaitBound &bound, double *sm, const WaitFn &wait_children)
 {
 	__shared__ int jrange[2];
 	const int h = fa.front_h[s], w = fa.front_w[s], ld = fa.front_ld[s], pad = fa.front_pad[s];
@@ -1359,7 +1317,7 @@ __device__ __forceinline__ void bigfront_team_body(const int s, const int rank, 
 		__syncthreads();
 	}
 	int nbar = 0;
-	team_barrier(bar, bar_base + G * (++ nbar), abort, timeout_ticks);
+	team_barrier(bar, bar_base + G * (++ nbar), bound);
 	// ---- partial factorization, 128 pivots per step
 	const int nsteps = (w + pad) / NB;
 	for(int j = 0; j < nsteps; ++ j) {
@@ -1370,7 +1328,7 @@ __device__ __forceinline__ void bigfront_team_body(const int s, const int rank, 
 			n_valid = n_valid < 0 ? 0 : (n_valid > NB ? NB : n_valid);
 			team_potrf(F + k0 + (int64_t)k0 * ld, ld, n_valid, tv, fa.info, (int64_t)k0, sm);
 		}
-		team_barrier(bar, bar_base + G * (++ nbar), abort, timeout_ticks);
+		team_barrier(bar, bar_base + G * (++ nbar), bound);
 		const int nright = hp - k1; // columns right of the diagonal block (the slot column included)
 		double *P = F + k0 + (int64_t)k1 * ld;
 		// row panel R_kj = (R_kk^-1)^T F_kj in place, 16 columns per tile (eight waves; the other eight idle)
@@ -1378,7 +1336,7 @@ __device__ __forceinline__ void bigfront_team_body(const int s, const int rank, 
 			team_panel_tile((int64_t)sl * 16, nright, tv, P, ld, sm);
 			__syncthreads(); // the LDS panels are staged anew by the next tile
 		}
-		team_barrier(bar, bar_base + G * (++ nbar), abort, timeout_ticks);
+		team_barrier(bar, bar_base + G * (++ nbar), bound);
 		// trailing update F[k1.., k1..] -= P^T P, upper 64 x 64 blocks
 		{
 			const int nb64 = (nright + 63) >> 6, ntile = nb64 * (nb64 + 1) / 2;
@@ -1394,7 +1352,7 @@ __device__ __forceinline__ void bigfront_team_body(const int s, const int rank, 
 				__syncthreads();
 			}
 		}
-		team_barrier(bar, bar_base + G * (++ nbar), abort, timeout_ticks);
+		team_barrier(bar, bar_base + G * (++ nbar), bound);
 	}
 }
 
@@ -1412,32 +1370,6 @@ void front_dag_kernel(DagArgs da, FrontArgs fa)
 		return; // (a barrier does not wait for waves that have ended)
 	if(da.trace && tid == 0)
 		da.trace[8 * blockIdx.x] = wall_clock64();
-	if(cls == 4) {
-		const int G = da.front_team[s], rank = da.rank[blockIdx.x];
-		auto wait_kids = [&]() {
-			if(tid == 0) {
-				if(da.trace)
-					da.trace[8 * blockIdx.x + 1] = wall_clock64();
-				for(int cq = fa.child_ptr[s]; cq < fa.child_ptr[s + 1]; ++ cq) {
-					const int c = fa.child_list[cq];
-					if(da.front_level[c] >= da.level_first && !dag_wait(da.done + c, da.epoch, da.abort, da.timeout_ticks))
-						break;
-				}
-				__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-				asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-				if(da.trace)
-					da.trace[8 * blockIdx.x + 2] = wall_clock64();
-			}
-		};
-		const int nbar = 1 + 3 * ((fa.front_w[s] + fa.front_pad[s]) / NB);
-		bigfront_team_body(s, rank, G, fa, da.team_bar + s, da.solve_index * G * nbar, da.tinv + da.front_tinv[s], da.abort,
-			da.timeout_ticks, fsm, wait_kids);
-		if(rank == 0) // (every member released its stores in the last barrier of the team)
-			dag_publish(da.done + s, da.epoch);
-		if(da.trace && tid == 0)
-			da.trace[8 * blockIdx.x + 3] = wall_clock64();
-		return;
-	}
 	// the children's flags are awaited inside the body, after the part of the assembly that does not need them
 	auto wait_children = [&]() {
 		if(tid == 0) {
@@ -1445,15 +1377,24 @@ void front_dag_kernel(DagArgs da, FrontArgs fa)
 				da.trace[8 * blockIdx.x + 1] = wall_clock64();
 			for(int cq = fa.child_ptr[s]; cq < fa.child_ptr[s + 1]; ++ cq) {
 				const int c = fa.child_list[cq];
-				if(da.front_level[c] >= da.level_first && !dag_wait(da.done + c, da.epoch, da.abort, da.timeout_ticks))
+				if(da.front_level[c] >= da.level_first && !dag_wait(da, c))
 					break; // aborted: the front is computed from garbage and discarded by the host
 			}
-			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+			acquire_by_lane();
 			if(da.trace)
 				da.trace[8 * blockIdx.x + 2] = wall_clock64();
 		}
 	};
+	if(cls == 4) {
+		const int G = da.front_team[s], rank = da.rank[blockIdx.x];
+		const int nbar = 1 + 3 * ((fa.front_w[s] + fa.front_pad[s]) / NB);
+		bigfront_team_body(s, rank, G, fa, da.team_bar + s, da.solve_index * G * nbar, da.tinv + da.front_tinv[s], da.bound, fsm, wait_children);
+		if(rank == 0) // (every member released its stores in the last barrier of the team)
+			publish_store(da.done + s, da.epoch);
+		if(da.trace && tid == 0)
+			da.trace[8 * blockIdx.x + 3] = wall_clock64();
+		return;
+	}
 	if(cls == 0)
 		front_body<32, 64, false>(s, fa, fsm, wait_children);
 	else if(cls == 1)
@@ -1462,7 +1403,7 @@ void front_dag_kernel(DagArgs da, FrontArgs fa)
 		front_body<128, 512, false>(s, fa, fsm, wait_children);
 	else
 		front_body<MID_FRONT_MAX, 1024, true>(s, fa, fsm, wait_children);
-	dag_publish(da.done + s, da.epoch);
+	publish_store(da.done + s, da.epoch);
 	if(da.trace && tid == 0)
 		da.trace[8 * blockIdx.x + 3] = wall_clock64();
 }
@@ -1482,9 +1423,8 @@ void front_bwd_dag_kernel(DagArgs da, FrontArgs fa)
 		if(threadIdx.x == 0) {
 			const int p = da.front_parent[s];
 			if(p >= 0 && da.front_level[p] < da.level_limit) // (ancestors above the limit were finished by earlier launches)
-				dag_wait(da.done + p, da.epoch, da.abort, da.timeout_ticks);
-			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+				dag_wait(da, p);
+			acquire_by_lane();
 		}
 		__syncthreads();
 	};
@@ -1492,7 +1432,7 @@ void front_bwd_dag_kernel(DagArgs da, FrontArgs fa)
 		front_bwd_body<1024, 8>(s, fa, tri, part, vl, wait_parent);
 	else
 		front_bwd_body<FT, 4>(s, fa, tri, part, vl, wait_parent);
-	dag_publish(da.done + s, da.epoch);
+	publish_store(da.done + s, da.epoch);
 }
 
 __global__ void gather_perm_kernel(int64_t n, const int32_t *__restrict__ perm, const double *__restrict__ src,
@@ -1587,8 +1527,7 @@ static void sparse_enqueue(spp_ctx *ctx, const double *d_vals, double *d_rhs)
 	da.front_level = sp->front_level.p;
 	da.done = sp->dag_done.p;
 	da.level_limit = sp->dag_level_limit;
-	da.abort = ctx->dense.info.p + 3;
-	da.timeout_ticks = switches().dag_timeout_ticks;
+	da.bound = {ctx->dense.info.p + 3, switches().dag_timeout_ticks};
 	da.epoch = 0;
 	da.level_first = 0;
 	da.list = nullptr;

@@ -51,6 +51,7 @@ struct Switches {
 	int tail_trace;           // SPP_TAIL_TRACE (off): n: the n-th launch prints per tile row when its diagonal tile had all updates, was factored, and when the first panel tile started / ended
 	int trsv_chain;           // SPP_TRSV_CHAIN (2): 2: the chain inside one workgroup, 1: a workgroup per hop (round 2), 0: a launch per hop (round 1)
 	int trsv_mform;           // SPP_TRSV_MFORM (1): 0: the chain applies R_{b, b+1} and Tinv_b itself (two tiles per hop)
+	long long chain_timeout_ticks; // SPP_CHAIN_TIMEOUT_TICKS (5e7 = 0.5 s): bound of a wait inside the backward-substitution chain kernels (tests: a tiny value forces the timeout and the fallback to a launch per block row)
 	int trsm_fused;           // SPP_TRSM_FUSED (1): multi-column solves on the kept factor: one launch per step, every updating workgroup forms X_J itself; 0: two launches per step (X_J stored, then the updates read it). Same bits either way
 
 	// ---- Schur complement (spp_schur_plan.cpp, spp_schur.hip)
@@ -128,6 +129,7 @@ inline Switches parse_switches()
 	w.tail_trace = env_int("SPP_TAIL_TRACE", 0);
 	w.trsv_chain = env_int("SPP_TRSV_CHAIN", 2);
 	w.trsv_mform = env_int("SPP_TRSV_MFORM", 1);
+	w.chain_timeout_ticks = env_i64("SPP_CHAIN_TIMEOUT_TICKS", WAIT_TICKS_DEFAULT);
 	w.trsm_fused = env_int("SPP_TRSM_FUSED", 1);
 
 	w.sacc_ulm = env_int("SPP_SACC_ULM", 1) != 0;

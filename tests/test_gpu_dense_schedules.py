@@ -84,7 +84,7 @@ VARIANTS = [  # (tag, environment, expected DENSE_STREAMED, same R as the defaul
     ("mform0", {"SPP_TRSV_MFORM": "0"}, DEFAULT_PATH, "all", False),
 ]
 SWITCHES = ["SPP_DENSE_SCHED", "SPP_TAIL_ORDER_BETA", "SPP_DENSE_TAIL", "SPP_TAIL_ROWS", "SPP_FUSED", "SPP_TILE_444",
-            "SPP_DENSE_LA", "SPP_TRSV_CHAIN", "SPP_TRSV_MFORM", "SPP_TAIL_TIMEOUT_TICKS"]
+            "SPP_DENSE_LA", "SPP_TRSV_CHAIN", "SPP_TRSV_MFORM", "SPP_TAIL_TIMEOUT_TICKS", "SPP_CHAIN_TIMEOUT_TICKS"]
 
 
 def _child(code, args, env_extra, timeout):
@@ -154,3 +154,53 @@ def test_timed_out_streamed_launch_falls_back_to_the_per_step_schedule():
     the following factorizations on the context take the per-step schedule and are right"""
     r = _child(TIMEOUT_CHILD % ROOT, [], {"SPP_TAIL_TIMEOUT_TICKS": "1"}, 180)
     assert r.returncode == 0 and "TIMEOUT OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+
+
+CHAIN_TIMEOUT_CHILD = r"""
+import hashlib, sys
+import numpy as np
+sys.path.insert(0, %r)
+from slam_plus_plus_amd import api
+n = 640   # five block rows: two is the smallest size at which a workgroup of the one-hop-per-workgroup chain waits at all,
+          # three the smallest for a helper of the one-workgroup chain; five leaves several waiters
+rng = np.random.default_rng(5)
+V = rng.standard_normal((n, 64))
+A = V @ V.T / 64
+A[np.diag_indices(n)] += 1.0 + rng.random(n)
+b = rng.standard_normal(n)
+ctx = api.Context(0, 0)
+dA = api.DeviceArray.from_host(ctx, A.reshape(-1))
+db = api.DeviceArray.from_host(ctx, b)
+if sys.argv[1] == "timeout":
+    st = ctx.lib.spp_dense_posv(ctx.h, dA.ptr, n, n, db.ptr)
+    msg = ctx.last_error()
+    assert st == -3, (st, msg)   # SPP_E_HIP
+    assert "backward substitution" in msg and "launch per block row" in msg, msg
+    print("first call:", msg)
+for rep in range(2):
+    dA.upload(A.reshape(-1))
+    db.upload(b)
+    assert ctx._check(ctx.lib.spp_dense_posv(ctx.h, dA.ptr, n, n, db.ptr)) == 0
+    x = db.download()
+    res = np.abs(A @ x - b).max() / np.abs(b).max()
+    print("residual %%.3e" %% res)
+    assert res < 1e-12, res
+    print("X " + hashlib.sha256(x.tobytes()).hexdigest())
+print("CHAIN TIMEOUT OK")
+"""
+
+
+def test_timed_out_chain_falls_back_to_a_launch_per_block_row():
+    """SPP_CHAIN_TIMEOUT_TICKS=1 makes the first wait inside a backward-substitution chain kernel that is not satisfied at
+    once give up (a bounded wait the kernel handles, spp_wait.h): the call fails with an error that names the backward
+    substitution and the fallback, and the following solves on the context launch per block row -- right, and bit for bit
+    what SPP_TRSV_CHAIN=0 gives"""
+    def xs(env, mode):
+        r = _child(CHAIN_TIMEOUT_CHILD % ROOT, [mode], env, 120)
+        assert r.returncode == 0 and "CHAIN TIMEOUT OK" in r.stdout, "%s\n%s%s" % (env, r.stdout[-3000:], r.stderr[-3000:])
+        print(env, r.stdout)
+        return [ln for ln in r.stdout.splitlines() if ln.startswith("X ")]
+    ref = xs({"SPP_TRSV_CHAIN": "0"}, "plain")
+    assert len(ref) == 2 and ref[0] == ref[1]
+    for env in ({}, {"SPP_TRSV_MFORM": "0"}, {"SPP_TRSV_CHAIN": "1"}):   # one child at a time
+        assert xs(dict(env, SPP_CHAIN_TIMEOUT_TICKS="1"), "timeout") == ref, env
