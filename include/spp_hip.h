@@ -252,6 +252,26 @@ int spp_sparse_marginals_device(spp_ctx *ctx, int64_t n_sel, const int64_t *h_ve
  * sharded ctx, SPP_E_BADARG for a null pointer. */
 int spp_sparse_sigma_device(spp_ctx *ctx, double *d_sigma);
 
+/* ---- covariance blocks on Lambda's pattern from the kept DENSE SCHUR factor: bundle adjustment ----
+ * Blocks of Sigma = Lambda^-1 on the stored pattern of Lambda from the factor spp_factor_solve_device left in
+ * SPP_MODE_SCHUR (SPP_INFO_FACTOR_KEPT): a covariance per camera and per point and the cross block of every observation,
+ * the job of the reference's CSchurComplement_Marginals::Schur_Marginals (include/slam/BAMarginals.h:563-583, "block
+ * diagonal of the covariance matrix from a Schur-complemented system").
+ * d_sigma: SPP_INFO_NVALS doubles in the layout of vals: the block of Sigma at (i, j) stands where Lambda's stored block
+ * (i, j) stands (each block column-major; an observation block stored landmark row first holds Sigma[l, c]). Diagonal
+ * blocks are exactly symmetric. Every double of d_sigma is written exactly once.
+ * Z = S^-1 is formed whole from R and the block inverses (three launches per 128-row block row, about two thirds of a
+ * factorization's flops per n^3), then Sigma[c, l] = -(sum_j Z[c, c_j] U_j) C_l^-1 and
+ * Sigma[l, l] = C_l^-1 - C_l^-1 sum_i U_i^T Sigma[c_i, l] per landmark; no solve per column.
+ * d_vals: the contract of spp_solve_device (the values the factor was made from: U and C are read from them).
+ * STREAM-ORDERED on the ctx stream; no host synchronisation after the first call, which allocates the workspace (ld x ld
+ * doubles for Z; spp_free_memory frees it) and lists the camera-camera blocks. It keeps the factor and writes nothing into
+ * S or the block inverses. Refusals, each checked by the test of spp_solve_device before anything is touched (the ctx
+ * stays usable): SPP_E_STATE without a kept factor; SPP_E_UNSUPPORTED in the sparse mode, SPP_MODE_SCHUR_SPARSE,
+ * SPP_MODE_SCHUR_MIS, on a sharded ctx and for cameras of more than one width; SPP_E_BADARG for a null pointer.
+ * (spp_sparse_sigma_device keeps answering SPP_E_UNSUPPORTED in the Schur modes.) */
+int spp_schur_sigma_device(spp_ctx *ctx, const double *d_vals, double *d_sigma);
+
 /* split form for multi-GPU: (1) each rank forms its partial Schur complement and
  * reduced rhs into d_S_rhs = [S (ld x ld, column-major, upper blocks) | rhs (ld)] ; (2) the caller
  * all-reduces that buffer (RCCL); (3) every rank factors S, solves and back-substitutes its own
@@ -601,6 +621,14 @@ int spp_dense_posv(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, double *d_b
  * same bits), then B (n x nrhs, column-major, ldb >= n) <- X by the multi-column solves of the kept-factor path
  * (spp_solve_device); returns the factor's status (B untouched after SPP_NOT_POSDEF) */
 int spp_dense_posv_multi(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, double *d_B, int64_t ldb, int64_t nrhs);
+/* the inverse from the factor: A is factored as by spp_dense_potrf_upper (A <- R with the same bits), then Z (n x n,
+ * column-major, ldz >= n) <- A^-1, whole and exactly symmetric, by the block recursion of spp_schur_sigma_device on the
+ * kept upper factor; nothing of Z outside its n x n is written. Returns the factor's status (Z untouched after
+ * SPP_NOT_POSDEF) */
+int spp_dense_potri(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, double *d_Z, int64_t ldz);
+/* NOT FOR USERS -- a timing entry (tools/schur_sigma_time.py): the first step of spp_schur_sigma_device alone, Z = S^-1
+ * into the ctx's workspace, nothing else written; needs the kept factor and refuses as spp_schur_sigma_device does */
+int spp_schur_sigma_dense_device(spp_ctx *ctx);
 /* the same with the tile structure of A given: words[i], bit j set = the 128 x 128 tile (i, j), i <= j, of A may be nonzero
  * (nwords = ceil(n / 128); nwords = 0: every tile). The call adds the diagonal tiles and the right-hand side's tile column
  * and closes the pattern under elimination; the streamed factorization then skips the tiles that stay zero. A tile

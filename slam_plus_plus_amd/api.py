@@ -31,6 +31,7 @@ EXPORTS = [
     "spp_create", "spp_destroy", "spp_free_memory", "spp_last_error", "spp_host_staging", "spp_set_stream", "spp_synchronize",
     "spp_analyze", "spp_set_shard", "spp_get_info", "spp_get_ordering", "spp_sparse_fronts", "spp_factor_solve",
     "spp_factor_solve_device", "spp_solve_device", "spp_marginals_device", "spp_sparse_solve_device", "spp_sparse_marginals_device", "spp_sparse_sigma_device",
+    "spp_schur_sigma_device", "spp_dense_potri", "spp_schur_sigma_dense_device",
     "spp_schur_buffer_size", "spp_schur_form", "spp_schur_finish",
     "spp_schur_packed_size", "spp_schur_pack", "spp_schur_unpack",
     "spp_assemble_analyze", "spp_assemble_get_structure", "spp_assemble_device", "spp_assemble_set_edge_weights",
@@ -87,6 +88,9 @@ def load_library():
         "spp_sparse_solve_device": (cint, [vp, vp, i64, i64]),
         "spp_sparse_marginals_device": (cint, [vp, i64, vp, vp]),
         "spp_sparse_sigma_device": (cint, [vp, vp]),
+        "spp_schur_sigma_device": (cint, [vp, vp, vp]),
+        "spp_schur_sigma_dense_device": (cint, [vp]),
+        "spp_dense_potri": (cint, [vp, vp, i64, i64, vp, i64]),
         "spp_schur_buffer_size": (cint, [vp, _c_i64p]),
         "spp_schur_form": (cint, [vp, vp, vp, vp]),
         "spp_schur_finish": (cint, [vp, vp, vp, vp]),
@@ -644,8 +648,11 @@ class Context:
     def sparse_block_diagonal(self):
         """the diagonal blocks of Sigma = Lambda^-1, one (d_v, d_v) array per vertex v, sliced out of sparse_sigma()
         through blk_off of the analyzed BlockCSC; each exactly symmetric"""
+        return self._block_diagonal(self.sparse_sigma())
+
+    def _block_diagonal(self, sigma):
+        """the diagonal blocks of a value array in the layout of vals, one per vertex"""
         keep = self._keep
-        sigma = self.sparse_sigma()
         col_ptr, row_idx, blk_off, dim = (np.asarray(a) for a in (keep.col_ptr, keep.row_idx, keep.blk_off, keep.dim))
         out = []
         for v in range(dim.size):
@@ -654,6 +661,30 @@ class Context:
             d = int(dim[v])
             out.append(sigma[int(blk_off[p]):int(blk_off[p]) + d * d].reshape((d, d), order="F").copy())
         return out
+
+    def schur_sigma_device(self, d_vals, d_sigma):
+        """the blocks of Sigma = Lambda^-1 on the stored pattern of Lambda into d_sigma (device pointer, NVALS doubles in the
+        layout of vals) from the kept dense Schur factor (info("FACTOR_KEPT")); d_vals must be the values that factor was
+        made from. Stream-ordered."""
+        return self._check(self.lib.spp_schur_sigma_device(self.h, d_vals, d_sigma))
+
+    def schur_sigma(self, d_vals):
+        """schur_sigma_device into a host array of NVALS doubles: the block of Sigma at (i, j) where vals holds Lambda's"""
+        d_sigma = DeviceArray(self, max(1, self.info("NVALS")))
+        try:
+            self.schur_sigma_device(d_vals, d_sigma.ptr)
+            return d_sigma.download()[:self.info("NVALS")]
+        finally:
+            d_sigma.free()
+
+    def schur_block_diagonal(self, d_vals):
+        """the diagonal blocks of Sigma = Lambda^-1 -- a covariance per camera and per point --, one (d_v, d_v) array per
+        vertex v, sliced out of schur_sigma() through blk_off of the analyzed BlockCSC; each exactly symmetric"""
+        return self._block_diagonal(self.schur_sigma(d_vals))
+
+    def dense_potri(self, d_A, n, ld, d_Z, ldz):
+        """Z <- A^-1, whole and symmetric, by the dense factor and the block recursion on it (unit tests); returns the status"""
+        return self._check(self.lib.spp_dense_potri(self.h, d_A, int(n), int(ld), d_Z, int(ldz)))
 
     def dense_posv_multi(self, d_A, n, ld, d_B, ldb, nrhs):
         """A X = B for nrhs columns by the dense factor and the multi-column solves (unit tests); returns the status"""

@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libspp_hip.so")
-SOURCES = ["spp_api.cpp", "spp_symbolic.cpp", "spp_tile_plan.cpp", "spp_schur_plan.cpp", "spp_dense.hip", "spp_schur.hip", "spp_solve_again.hip", "spp_sparse.hip", "spp_sparse_solve.hip", "spp_sparse_sigma.hip",
+SOURCES = ["spp_api.cpp", "spp_symbolic.cpp", "spp_tile_plan.cpp", "spp_schur_plan.cpp", "spp_dense.hip", "spp_schur.hip", "spp_solve_again.hip", "spp_schur_sigma.hip", "spp_sparse.hip", "spp_sparse_solve.hip", "spp_sparse_sigma.hip",
            "spp_assemble.hip", "spp_assemble3.hip", "spp_geometry.hip"]
 
 

@@ -803,6 +803,30 @@ int spp_marginals_device(spp_ctx *ctx, const double *d_vals, int64_t n_sel, cons
 	SPP_CATCH(ctx)
 }
 
+int spp_schur_sigma_device(spp_ctx *ctx, const double *d_vals, double *d_sigma)
+{
+	if(!ctx || !d_vals || !d_sigma)
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	require_kept_factor(ctx, "spp_schur_sigma_device");
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	schur_sigma(ctx, d_vals, d_sigma);
+	return SPP_OK;
+	SPP_CATCH(ctx)
+}
+
+int spp_schur_sigma_dense_device(spp_ctx *ctx)
+{
+	if(!ctx)
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	require_kept_factor(ctx, "spp_schur_sigma_dense_device");
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	schur_sigma(ctx, nullptr, nullptr, true);
+	return SPP_OK;
+	SPP_CATCH(ctx)
+}
+
 // what spp_sparse_solve_device, spp_sparse_marginals_device and spp_sparse_sigma_device check before they touch anything
 static void require_kept_sparse_factor(const spp_ctx *ctx, const char *who)
 {
@@ -1389,6 +1413,32 @@ int spp_dense_posv_multi(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, doubl
 	int ret = dense_potrf_upper(ctx, tmp.p, n, ldp, true);
 	if(ret == SPP_OK)
 		dense_potrs_multi(ctx, tmp.p, n, ldp, d_B, ldb, nrhs);
+	SPP_HIP_CHECK(hipMemcpy2DAsync(d_A, ld * sizeof(double), tmp.p, ldp * sizeof(double), n * sizeof(double), n,
+		hipMemcpyDeviceToDevice, ctx->stream));
+	SPP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+	return ret;
+	SPP_CATCH(ctx)
+}
+
+// the factorization of spp_dense_potrf_upper, then the full symmetric inverse from the kept factor into Z (n x n, ldz >= n);
+// A <- R with the bits spp_dense_potrf_upper leaves
+int spp_dense_potri(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, double *d_Z, int64_t ldz)
+{
+	if(!ctx || !d_A || !d_Z || n <= 0 || ld < n || ldz < n)
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	drop_kept_factors(ctx);
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	const int64_t ldp = ((n + 1 + DENSE_NB - 1) / DENSE_NB) * DENSE_NB;
+	DevBuf<double> tmp;
+	tmp.reserve((size_t)ldp * ldp);
+	SPP_HIP_CHECK(hipMemsetAsync(tmp.p, 0, (size_t)ldp * ldp * sizeof(double), ctx->stream));
+	SPP_HIP_CHECK(hipMemcpy2DAsync(tmp.p, ldp * sizeof(double), d_A, ld * sizeof(double), n * sizeof(double), n,
+		hipMemcpyDeviceToDevice, ctx->stream));
+	dense_set_padding(ctx, tmp.p, ldp, n);
+	int ret = dense_potrf_upper(ctx, tmp.p, n, ldp, true);
+	if(ret == SPP_OK)
+		dense_potri_upper(ctx, tmp.p, n, ldp, d_Z, ldz);
 	SPP_HIP_CHECK(hipMemcpy2DAsync(d_A, ld * sizeof(double), tmp.p, ldp * sizeof(double), n * sizeof(double), n,
 		hipMemcpyDeviceToDevice, ctx->stream));
 	SPP_HIP_CHECK(hipStreamSynchronize(ctx->stream));

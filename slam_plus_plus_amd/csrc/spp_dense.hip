@@ -2270,3 +2270,4 @@ double microbench_update(spp_ctx *ctx, int64_t m, int iters)
 
 } // namespace spp
 #include "spp_dense_trsm.h" // k right-hand sides against the kept factor: a launch per block row and direction
+#include "spp_dense_potri.h" // the full inverse from the kept factor: three launches per block row

@@ -283,6 +283,12 @@ struct SchurPlan : SchurDims {
 	// the last spp_factor_solve_device left a factor a further solve may use (dense S in the own buffer, unsharded, SPP_OK):
 	// R in S, the whole block inverses in dense.tinv_all. Cleared on entry of every call that rewrites any of it (SPP_INFO_FACTOR_KEPT)
 	bool factor_kept = false;
+	// spp_schur_sigma_device (spp_schur_sigma.hip), made on its first call for this plan: Z = S^-1 (ld x ld, both triangles) and
+	// the stored camera-camera blocks of Lambda as (offset in vals, row camera's position, column camera's position)
+	DevBuf<double> sigma_Z;
+	DevBuf<int64_t> sigma_cc;
+	std::vector<int64_t> sigma_cc_host;
+	int64_t sigma_ncc = -1;        // -1: the list has not been made
 	int async_last = 0;            // ... of the last schur_finish: 1 = it returned on the factor's status with the stream still running (SPP_SOLVE_ASYNC), 0 = it drained the stream (SPP_INFO_SOLVE_ASYNC)
 	void release_all();
 };
@@ -601,6 +607,11 @@ void schur_solve_again(spp_ctx *ctx, const double *d_vals, double *d_B, int64_t 
 typedef std::function<void(double *d_B, int64_t ldb, int64_t nrhs)> KeptSolve;
 void kept_marginals(spp_ctx *ctx, const char *who, int64_t n_sel, const int64_t *h_vertices, double *d_cov, const KeptSolve &solve);
 
+// ---- spp_schur_sigma.hip ----
+// the blocks of Lambda^-1 on the stored pattern of Lambda (the layout of vals) from the kept dense Schur factor;
+// dense_only: form Z = S^-1 in the plan's workspace and stop (what tools/schur_sigma_time.py times as the dense part)
+void schur_sigma(spp_ctx *ctx, const double *d_vals, double *d_sigma, bool dense_only = false);
+
 // ---- spp_sparse_solve.hip ----
 // Lambda X = B in place for nrhs columns (n rows in Lambda's numbering, leading dimension ldb) against the fronts the last
 // sparse factorization left in the plan
@@ -628,6 +639,8 @@ void dense_potrs_upper(spp_ctx *ctx, const double *d_R, int64_t n, int64_t ld, d
 // R^T R X = B in place for nrhs columns against the factor and the block inverses of the last factorization (spp_dense_trsm.h)
 void dense_potrs_multi(spp_ctx *ctx, const double *d_R, int64_t n, int64_t ld, double *d_B, int64_t ldb, int64_t nrhs);
 void dense_tinv_complete(spp_ctx *ctx); // the stored block inverses in their whole form (no-op when they are)
+// Z (n x n, leading dimension ldz, both triangles, exactly symmetric) <- (R^T R)^-1 against the same (spp_dense_potri.h)
+void dense_potri_upper(spp_ctx *ctx, const double *d_R, int64_t n, int64_t ld, double *d_Z, int64_t ldz);
 void dense_aux_park(int device, hipStream_t s); // hands the bulk stream of a closing context to the next one
 void dense_factor_steps(spp_ctx *ctx, double *d_A, int64_t ld, int64_t n, int64_t rows, int64_t ncols,
 	int64_t nsteps, bool has_rhs);

@@ -1,5 +1,6 @@
 // spp_schur_dev.h -- device-side pieces of the landmark elimination that more than one translation unit uses
-// (spp_schur.hip, spp_solve_again.hip): the negated inverse of a landmark block and the fetch of a pose-landmark block.
+// (spp_schur.hip, spp_solve_again.hip, spp_schur_sigma.hip): the negated inverse of a landmark block and the fetch of a
+// pose-landmark block.
 #pragma once
 #include "spp_internal.h"
 
@@ -66,6 +67,19 @@ __device__ __forceinline__ void cinv_block(const double *__restrict__ m, double 
 			for(int j = 0; j < DL; ++ j)
 				o[i + DL * j] = -b[i][j];
 	}
+}
+
+// -(C^-1) of landmark l: stored by the plan (cinv), or formed from the block itself where the plan keeps none
+template <int DL>
+__device__ __forceinline__ void sa_neg_cinv(const double *__restrict__ cinv, const int64_t *__restrict__ lm_coff,
+	const double *__restrict__ vals, int64_t l, double *Ci)
+{
+	if(cinv) {
+#pragma unroll
+		for(int e = 0; e < DL * DL; ++ e)
+			Ci[e] = cinv[l * DL * DL + e];
+	} else
+		cinv_block<DL>(vals + lm_coff[l], Ci);
 }
 
 // pose-landmark block of Lambda as DP x DL column-major; (offset << 1) | transposed flag

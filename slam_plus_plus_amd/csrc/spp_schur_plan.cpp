@@ -33,6 +33,7 @@ void SchurPlan::release_all()
 	pair_a.release(); pair_b.release(); multi_blk.release(); multi_ptr.release(); cinv.release(); lfac.release();
 	W.release(); Up.release(); xw.release(); partial.release(); S.release();
 	pose_block.clear(); lm_block.clear(); is_lm.clear(); tile_mask.clear(); step_order.clear();
+	sigma_Z.release(); sigma_cc.release(); sigma_cc_host.clear(); sigma_ncc = -1;
 }
 
 // Guided ordering is possible when there are exactly two block widths and the blocks of the

@@ -20,19 +20,6 @@ namespace spp {
 
 constexpr int SA_QB = 8; // columns of B a wave (step 2) / a thread (step 4) carries at once: U is fetched once for them
 
-// -(C^-1) of landmark l: stored by the plan (cinv), or formed from the block itself where the plan keeps none
-template <int DL>
-__device__ __forceinline__ void sa_neg_cinv(const double *__restrict__ cinv, const int64_t *__restrict__ lm_coff,
-	const double *__restrict__ vals, int64_t l, double *Ci)
-{
-	if(cinv) {
-#pragma unroll
-		for(int e = 0; e < DL * DL; ++ e)
-			Ci[e] = cinv[l * DL * DL + e];
-	} else
-		cinv_block<DL>(vals + lm_coff[l], Ci);
-}
-
 // ---- step 1: one thread per (landmark, group of SA_QB columns): the inverse is formed once for them ----------------------
 template <int DL>
 __global__ __launch_bounds__(256)
