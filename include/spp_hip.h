@@ -130,6 +130,7 @@ int spp_set_shard(spp_ctx *ctx, int rank, int world_size);
 #define SPP_INFO_SOLVE_ASYNC    23 /* what the last spp_factor_solve_device / spp_schur_finish did (SPP_SOLVE_ASYNC): 1 it returned when the factor's status was known, the solves and the back-substitution still running on the stream; 0 it drained the stream (profiling on, stream capture, sparse reduced system, sparse mode, the switch at 0) */
 #define SPP_INFO_FACTOR_KEPT    24 /* 1: the ctx holds a factor spp_solve_device / spp_marginals_device may use: the last spp_factor_solve_device returned SPP_OK in SPP_MODE_SCHUR with a dense reduced system, unsharded, and nothing has rewritten it since; 0 otherwise (needs no analysis) */
 #define SPP_INFO_SPARSE_FACTOR_KEPT 25 /* 1: the ctx holds a sparse factor spp_sparse_solve_device / spp_sparse_marginals_device may use: the last spp_factor_solve_device returned SPP_OK in SPP_MODE_SPARSE, unsharded, and no call that drops it has been entered since; 0 otherwise (needs no analysis). SPP_INFO_FACTOR_KEPT stays 0 in the sparse mode */
+#define SPP_INFO_SCHUR_SPARSE_FACTOR_KEPT 26 /* 1: the ctx holds a factor spp_schur_sparse_solve_device / spp_schur_sparse_marginals_device / spp_schur_sparse_sigma_device may use: the last spp_factor_solve_device returned SPP_OK in SPP_MODE_SCHUR_SPARSE, unsharded, and no call that drops it has been entered since; 0 otherwise (needs no analysis). The two words above stay 0 in this mode */
 int spp_get_info(const spp_ctx *ctx, int what, int64_t *out);
 /* elimination order chosen by the analysis: order[k] = source block column eliminated k-th */
 int spp_get_ordering(const spp_ctx *ctx, int64_t *h_order);
@@ -271,6 +272,48 @@ int spp_sparse_sigma_device(spp_ctx *ctx, double *d_sigma);
  * SPP_MODE_SCHUR_MIS, on a sharded ctx and for cameras of more than one width; SPP_E_BADARG for a null pointer.
  * (spp_sparse_sigma_device keeps answering SPP_E_UNSUPPORTED in the Schur modes.) */
 int spp_schur_sigma_device(spp_ctx *ctx, const double *d_vals, double *d_sigma);
+
+/* ---- the same three jobs on the kept factor of a SPARSE reduced system: SPP_MODE_SCHUR_SPARSE ----
+ * The mode SPP_MODE_AUTO picks beyond 16384 reduced rows, and long landmark-SLAM trajectories analyzed in it. After SPP_OK
+ * of spp_factor_solve_device R (S = R^T R) sits in the fronts of the sparse plan made from S's pattern
+ * (SPP_INFO_SCHUR_SPARSE_FACTOR_KEPT); Lambda's values are the caller's. The six calls above keep answering
+ * SPP_E_UNSUPPORTED in this mode, and keep this factor.
+ * spp_schur_sparse_solve_device: Lambda X = B for nrhs further right-hand sides, the steps of spp_solve_device with the
+ * camera panel solved by the multifrontal substitutions of spp_sparse_solve_device. d_B: n x nrhs, column-major, leading
+ * dimension ldb >= n, rows in Lambda's numbering, overwritten by X; nothing outside its n rows and nrhs columns is
+ * written. CONTRACT: d_vals must hold the values that were factored, unchanged (U and C are read from them). Column j of
+ * the result has the same bits whatever the other columns hold, wherever it stands and however many columns the call
+ * carries; two runs give the same bits.
+ * STREAM-ORDERED on the ctx stream; no host synchronisation after the first call, which allocates the panels. d_vals and
+ * d_B must stay allocated until the stream has passed the call.
+ * The factor is kept by SPP_OK of spp_factor_solve_device / spp_factor_solve in SPP_MODE_SCHUR_SPARSE (also SPP_MODE_AUTO
+ * resolving to it), unsharded, and dropped on entry of every call that drops the two factors above: any factor / solve,
+ * spp_schur_form / spp_schur_finish, spp_dense_*, spp_analyze and the spp_assemble_analyze* calls, spp_set_shard,
+ * spp_free_memory. The three calls here keep it.
+ * Refusals, each checked before anything is touched (the ctx stays usable):
+ * SPP_E_STATE: no kept factor -- never solved, the last solve returned SPP_NOT_POSDEF, or a later call dropped it.
+ * SPP_E_UNSUPPORTED: SPP_MODE_SPARSE, SPP_MODE_SCHUR with a dense reduced system, SPP_MODE_SCHUR_MIS, a sharded ctx, block
+ * widths other than {6,3}, {3,2}, {7,3}.
+ * SPP_E_BADARG: a null pointer, nrhs < 1, ldb < n. */
+int spp_schur_sparse_solve_device(spp_ctx *ctx, const double *d_vals, double *d_B, int64_t ldb, int64_t nrhs);
+/* Joint covariance of chosen vertices, worded as spp_marginals_device: d_cov (m x m, column-major, m = sum of their widths)
+ * <- E^T Lambda^-1 E of the n_sel vertices h_vertices (cameras and landmarks in any mix and order, each at most once); one
+ * m-column spp_schur_sparse_solve_device of unit columns built on the device, the upper triangle computed and mirrored:
+ * exactly symmetric. Workspace: n x m doubles. Keeping and refusals as above; SPP_E_BADARG also for n_sel < 1, a vertex out
+ * of range or listed twice. NOT FOR STREAM CAPTURE: the call waits for the ctx stream once on entry. */
+int spp_schur_sparse_marginals_device(spp_ctx *ctx, const double *d_vals, int64_t n_sel, const int64_t *h_vertices, double *d_cov);
+/* Blocks of Sigma = Lambda^-1 on the stored pattern of Lambda, worded as spp_schur_sigma_device. d_sigma: SPP_INFO_NVALS
+ * doubles in the layout of vals; every double is written exactly once; diagonal blocks are exactly symmetric; an observation
+ * block stored landmark row first holds Sigma[l, c].
+ * The blocks of Z = S^-1 on the stored pattern of S come from the selected inversion of spp_sparse_sigma_device on the
+ * kept fronts -- that pattern holds a block for every two cameras that share a landmark, which is every block the landmark
+ * formulas of spp_schur_sigma_device read -- then Sigma[c, l] = -(sum_j Z[c, c_j] U_j) C_l^-1 and Sigma[l, l] as there; the
+ * camera blocks are copies of Z's. No solve per column, no dense n_red x n_red array.
+ * STREAM-ORDERED on the ctx stream; no host synchronisation after the first call, which allocates the workspaces (as many
+ * doubles as the fronts hold, and as many as S's value array; spp_free_memory frees them). It keeps the factor and writes
+ * nothing into S's buffer, the fronts or the plan. Keeping and refusals as for spp_schur_sparse_solve_device;
+ * SPP_E_BADARG for a null pointer. */
+int spp_schur_sparse_sigma_device(spp_ctx *ctx, const double *d_vals, double *d_sigma);
 
 /* split form for multi-GPU: (1) each rank forms its partial Schur complement and
  * reduced rhs into d_S_rhs = [S (ld x ld, column-major, upper blocks) | rhs (ld)] ; (2) the caller
@@ -629,6 +672,10 @@ int spp_dense_potri(spp_ctx *ctx, double *d_A, int64_t n, int64_t ld, double *d_
 /* NOT FOR USERS -- a timing entry (tools/schur_sigma_time.py): the first step of spp_schur_sigma_device alone, Z = S^-1
  * into the ctx's workspace, nothing else written; needs the kept factor and refuses as spp_schur_sigma_device does */
 int spp_schur_sigma_dense_device(spp_ctx *ctx);
+/* NOT FOR USERS -- a timing entry (tools/schur_sparse_again_time.py): the first step of spp_schur_sparse_sigma_device alone,
+ * the blocks of Z = S^-1 on S's stored pattern into the ctx's workspace, nothing else written; needs the kept factor and
+ * refuses as spp_schur_sparse_sigma_device does */
+int spp_schur_sparse_sigma_inverse_device(spp_ctx *ctx);
 /* the same with the tile structure of A given: words[i], bit j set = the 128 x 128 tile (i, j), i <= j, of A may be nonzero
  * (nwords = ceil(n / 128); nwords = 0: every tile). The call adds the diagonal tiles and the right-hand side's tile column
  * and closes the pattern under elimination; the streamed factorization then skips the tiles that stay zero. A tile

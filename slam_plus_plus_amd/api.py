@@ -23,7 +23,7 @@ FLAG_PROFILE = 1
 INFO = dict(MODE=0, N=1, NNZB=2, NVALS=3, FACTOR_NNZ=4, FACTOR_FLOPS=5, N_REDUCED=6, N_POSES=7,
             N_LANDMARKS=8, SCHUR_PAIRS=9, N_OBS=10, SOLVE_BYTES=11, N_SUPERNODES=12, N_LEVELS=13, S_LD=14, S_NNZB=15, DENSE_STREAMED=16,
             LM_STREAM=17, BS_GROUPS=18, SCHUR_SIDE=19, S_CLEAR=20, S_DEVICE_PTR=21, ASM_HUB_CHUNK=22, SOLVE_ASYNC=23, FACTOR_KEPT=24,
-            SPARSE_FACTOR_KEPT=25)
+            SPARSE_FACTOR_KEPT=25, SCHUR_SPARSE_FACTOR_KEPT=26)
 PHASES = ["permute", "schur_inv", "schur_gemm", "schur_rhs", "factor", "trisolve", "backsubst", "assemble", "total"]
 
 # every symbol include/spp_hip.h declares (tests/test_abi.py checks the .so exports them all)
@@ -32,6 +32,8 @@ EXPORTS = [
     "spp_analyze", "spp_set_shard", "spp_get_info", "spp_get_ordering", "spp_sparse_fronts", "spp_factor_solve",
     "spp_factor_solve_device", "spp_solve_device", "spp_marginals_device", "spp_sparse_solve_device", "spp_sparse_marginals_device", "spp_sparse_sigma_device",
     "spp_schur_sigma_device", "spp_dense_potri", "spp_schur_sigma_dense_device",
+    "spp_schur_sparse_solve_device", "spp_schur_sparse_marginals_device", "spp_schur_sparse_sigma_device",
+    "spp_schur_sparse_sigma_inverse_device",
     "spp_schur_buffer_size", "spp_schur_form", "spp_schur_finish",
     "spp_schur_packed_size", "spp_schur_pack", "spp_schur_unpack",
     "spp_assemble_analyze", "spp_assemble_get_structure", "spp_assemble_device", "spp_assemble_set_edge_weights",
@@ -90,6 +92,10 @@ def load_library():
         "spp_sparse_sigma_device": (cint, [vp, vp]),
         "spp_schur_sigma_device": (cint, [vp, vp, vp]),
         "spp_schur_sigma_dense_device": (cint, [vp]),
+        "spp_schur_sparse_solve_device": (cint, [vp, vp, vp, i64, i64]),
+        "spp_schur_sparse_marginals_device": (cint, [vp, vp, i64, vp, vp]),
+        "spp_schur_sparse_sigma_device": (cint, [vp, vp, vp]),
+        "spp_schur_sparse_sigma_inverse_device": (cint, [vp]),
         "spp_dense_potri": (cint, [vp, vp, i64, i64, vp, i64]),
         "spp_schur_buffer_size": (cint, [vp, _c_i64p]),
         "spp_schur_form": (cint, [vp, vp, vp, vp]),
@@ -681,6 +687,40 @@ class Context:
         """the diagonal blocks of Sigma = Lambda^-1 -- a covariance per camera and per point --, one (d_v, d_v) array per
         vertex v, sliced out of schur_sigma() through blk_off of the analyzed BlockCSC; each exactly symmetric"""
         return self._block_diagonal(self.schur_sigma(d_vals))
+
+    def schur_sparse_solve_device(self, d_vals, d_B, nrhs, ldb=None):
+        """Lambda X = B for nrhs columns (device pointer d_B, column-major, leading dimension ldb, default n) against the
+        factor of the sparse reduced system the last successful factor_solve_device left in MODE_SCHUR_SPARSE
+        (info("SCHUR_SPARSE_FACTOR_KEPT")); d_vals must be the values that call factored. Stream-ordered: B is complete
+        behind synchronize() / a download."""
+        if ldb is None:
+            ldb = self.info("N")
+        return self._check(self.lib.spp_schur_sparse_solve_device(self.h, d_vals, d_B, int(ldb), int(nrhs)))
+
+    def schur_sparse_marginals(self, d_vals, vertices):
+        """joint covariance E^T Lambda^-1 E of the given vertices (block columns of Lambda, each at most once, any mix of
+        cameras and landmarks) from the kept factor of the sparse reduced system, as an (m, m) numpy array; exactly symmetric"""
+        return self._marginals(vertices, lambda k, v, cov: self.lib.spp_schur_sparse_marginals_device(self.h, d_vals, k, v, cov))
+
+    def schur_sparse_sigma_device(self, d_vals, d_sigma):
+        """the blocks of Sigma = Lambda^-1 on the stored pattern of Lambda into d_sigma (device pointer, NVALS doubles in the
+        layout of vals) from the kept factor of the sparse reduced system (info("SCHUR_SPARSE_FACTOR_KEPT")); d_vals must be
+        the values that factor was made from. Stream-ordered."""
+        return self._check(self.lib.spp_schur_sparse_sigma_device(self.h, d_vals, d_sigma))
+
+    def schur_sparse_sigma(self, d_vals):
+        """schur_sparse_sigma_device into a host array of NVALS doubles: the block of Sigma at (i, j) where vals holds Lambda's"""
+        d_sigma = DeviceArray(self, max(1, self.info("NVALS")))
+        try:
+            self.schur_sparse_sigma_device(d_vals, d_sigma.ptr)
+            return d_sigma.download()[:self.info("NVALS")]
+        finally:
+            d_sigma.free()
+
+    def schur_sparse_block_diagonal(self, d_vals):
+        """the diagonal blocks of Sigma = Lambda^-1 -- a covariance per camera and per point --, one (d_v, d_v) array per
+        vertex v, sliced out of schur_sparse_sigma() through blk_off of the analyzed BlockCSC; each exactly symmetric"""
+        return self._block_diagonal(self.schur_sparse_sigma(d_vals))
 
     def dense_potri(self, d_A, n, ld, d_Z, ldz):
         """Z <- A^-1, whole and symmetric, by the dense factor and the block recursion on it (unit tests); returns the status"""

@@ -84,6 +84,7 @@ void dom_end(spp_ctx *ctx, double flops)
 static inline void drop_kept_factors(spp_ctx *ctx)
 {
 	ctx->schur.factor_kept = false;
+	ctx->schur.sparse_factor_kept = false;
 	ctx->sparse_factor_kept = false;
 }
 
@@ -428,7 +429,8 @@ int spp_get_info(const spp_ctx *ctx, int what, int64_t *out)
 	if(!ctx || !out)
 		return SPP_E_BADARG;
 	if(ctx->mode < 0 && what != SPP_INFO_NNZB && what != SPP_INFO_NVALS && what != SPP_INFO_N && what != SPP_INFO_DENSE_STREAMED &&
-	   what != SPP_INFO_ASM_HUB_CHUNK && what != SPP_INFO_FACTOR_KEPT && what != SPP_INFO_SPARSE_FACTOR_KEPT)
+	   what != SPP_INFO_ASM_HUB_CHUNK && what != SPP_INFO_FACTOR_KEPT && what != SPP_INFO_SPARSE_FACTOR_KEPT &&
+	   what != SPP_INFO_SCHUR_SPARSE_FACTOR_KEPT)
 		return SPP_E_STATE;
 	switch(what) {
 	case SPP_INFO_MODE: *out = (ctx->mode != SPP_MODE_SCHUR) ? ctx->mode : ctx->schur.mis ? SPP_MODE_SCHUR_MIS :
@@ -458,6 +460,7 @@ int spp_get_info(const spp_ctx *ctx, int what, int64_t *out)
 	case SPP_INFO_ASM_HUB_CHUNK: *out = ASM_HUB_CHUNK; break;
 	case SPP_INFO_FACTOR_KEPT: *out = (ctx->mode == SPP_MODE_SCHUR && ctx->schur.factor_kept) ? 1 : 0; break;
 	case SPP_INFO_SPARSE_FACTOR_KEPT: *out = (ctx->mode == SPP_MODE_SPARSE && ctx->sparse_factor_kept) ? 1 : 0; break;
+	case SPP_INFO_SCHUR_SPARSE_FACTOR_KEPT: *out = (ctx->mode == SPP_MODE_SCHUR && ctx->schur.sparse_factor_kept) ? 1 : 0; break;
 	default: return SPP_E_BADARG;
 	}
 	return SPP_OK;
@@ -764,6 +767,9 @@ int spp_factor_solve_device(spp_ctx *ctx, const double *d_vals, double *d_rhs)
 		ctx->shard_world == 1;
 	// the sparse mode: every supernode's pivot rows of R stay in the plan's fronts until the next factorization
 	ctx->sparse_factor_kept = ret == SPP_OK && ctx->mode == SPP_MODE_SPARSE && ctx->shard_world == 1;
+	// the sparse reduced system: R (S = R^T R) stays in the same fronts, Lambda's values are the caller's
+	ctx->schur.sparse_factor_kept = ret == SPP_OK && ctx->mode == SPP_MODE_SCHUR && ctx->schur.sparse_S && !ctx->schur.mis &&
+		ctx->shard_world == 1;
 	return ret;
 	SPP_CATCH(ctx)
 }
@@ -870,6 +876,70 @@ int spp_sparse_sigma_device(spp_ctx *ctx, double *d_sigma)
 	require_kept_sparse_factor(ctx, "spp_sparse_sigma_device");
 	SPP_HIP_CHECK(hipSetDevice(ctx->device));
 	sparse_sigma(ctx, d_sigma);
+	return SPP_OK;
+	SPP_CATCH(ctx)
+}
+
+// what spp_schur_sparse_solve_device, spp_schur_sparse_marginals_device and spp_schur_sparse_sigma_device check before they
+// touch anything
+static void require_kept_schur_sparse_factor(const spp_ctx *ctx, const char *who)
+{
+	SPP_REQUIRE(ctx->mode >= 0, SPP_E_STATE, std::string(who) + ": no kept factor (call spp_analyze and spp_factor_solve_device first)");
+	SPP_REQUIRE(ctx->mode == SPP_MODE_SCHUR && ctx->schur.sparse_S && !ctx->schur.mis && ctx->shard_world == 1 && ctx->sparse,
+		SPP_E_UNSUPPORTED, std::string(who) + ": only SPP_MODE_SCHUR_SPARSE, unsharded, keeps the factor of a sparse reduced system "
+		"(the dense Schur mode: spp_solve_device, the sparse mode: spp_sparse_solve_device)");
+	const int dp = ctx->schur.dp, dl = ctx->schur.dl;
+	SPP_REQUIRE((dp == 6 && dl == 3) || (dp == 3 && dl == 2) || (dp == 7 && dl == 3), SPP_E_UNSUPPORTED,
+		std::string(who) + ": block widths not instantiated ({6,3}, {3,2}, {7,3})");
+	SPP_REQUIRE(ctx->schur.sparse_factor_kept, SPP_E_STATE, std::string(who) + ": no kept factor (the last spp_factor_solve_device failed, or a later call dropped it)");
+}
+
+int spp_schur_sparse_solve_device(spp_ctx *ctx, const double *d_vals, double *d_B, int64_t ldb, int64_t nrhs)
+{
+	if(!ctx || !d_vals || !d_B || nrhs < 1)
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	require_kept_schur_sparse_factor(ctx, "spp_schur_sparse_solve_device");
+	SPP_REQUIRE(ldb >= ctx->st.n, SPP_E_BADARG, "spp_schur_sparse_solve_device: ldb < n");
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	schur_sparse_solve_again(ctx, d_vals, d_B, ldb, nrhs);
+	return SPP_OK;
+	SPP_CATCH(ctx)
+}
+
+int spp_schur_sparse_marginals_device(spp_ctx *ctx, const double *d_vals, int64_t n_sel, const int64_t *h_vertices, double *d_cov)
+{
+	if(!ctx || !d_vals || !h_vertices || !d_cov || n_sel < 1)
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	require_kept_schur_sparse_factor(ctx, "spp_schur_sparse_marginals_device");
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	kept_marginals(ctx, "spp_schur_sparse_marginals_device", n_sel, h_vertices, d_cov,
+		[&](double *d_B, int64_t ldb, int64_t nrhs) { schur_sparse_solve_again(ctx, d_vals, d_B, ldb, nrhs); });
+	return SPP_OK;
+	SPP_CATCH(ctx)
+}
+
+int spp_schur_sparse_sigma_device(spp_ctx *ctx, const double *d_vals, double *d_sigma)
+{
+	if(!ctx || !d_vals || !d_sigma)
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	require_kept_schur_sparse_factor(ctx, "spp_schur_sparse_sigma_device");
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	schur_sparse_sigma(ctx, d_vals, d_sigma);
+	return SPP_OK;
+	SPP_CATCH(ctx)
+}
+
+int spp_schur_sparse_sigma_inverse_device(spp_ctx *ctx)
+{
+	if(!ctx)
+		return SPP_E_BADARG;
+	SPP_TRY(ctx)
+	require_kept_schur_sparse_factor(ctx, "spp_schur_sparse_sigma_inverse_device");
+	SPP_HIP_CHECK(hipSetDevice(ctx->device));
+	schur_sparse_sigma(ctx, nullptr, nullptr, true);
 	return SPP_OK;
 	SPP_CATCH(ctx)
 }

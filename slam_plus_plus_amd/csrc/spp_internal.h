@@ -289,7 +289,14 @@ struct SchurPlan : SchurDims {
 	DevBuf<int64_t> sigma_cc;
 	std::vector<int64_t> sigma_cc_host;
 	int64_t sigma_ncc = -1;        // -1: the list has not been made
-	int async_last = 0;            // ... of the last schur_finish: 1 = it returned on the factor's status with the stream still running (SPP_SOLVE_ASYNC), 0 = it drained the stream (SPP_INFO_SOLVE_ASYNC)
+	// the last spp_factor_solve_device left the factor of the SPARSE reduced system in the fronts of the sparse plan (sparse_S, no
+	// independent-set cut, unsharded, SPP_OK); set and cleared where factor_kept is (SPP_INFO_SCHUR_SPARSE_FACTOR_KEPT)
+	bool sparse_factor_kept = false;
+	// spp_schur_sparse_sigma_device (spp_schur_sparse_sigma.hip), made on its first call for this plan: the blocks of Z = S^-1
+	// on the stored pattern of S (s_st.nvals doubles in the layout sblk_voff indexes) and S's block-CSC lists
+	DevBuf<double> sigma_Zb;
+	DevBuf<int64_t> sigma_scol, sigma_srow; // s_st.col_ptr [nc + 1], s_st.row_idx [n_sblk]
+	int async_last = 0;           // ... of the last schur_finish: 1 = it returned on the factor's status with the stream still running (SPP_SOLVE_ASYNC), 0 = it drained the stream (SPP_INFO_SOLVE_ASYNC)
 	void release_all();
 };
 
@@ -601,6 +608,8 @@ void schur_pack(spp_ctx *ctx, double *S, double *packed, bool pack);
 // ---- spp_solve_again.hip ----
 // Lambda X = B in place for nrhs columns (n rows in Lambda's numbering, leading dimension ldb) against the kept factor
 void schur_solve_again(spp_ctx *ctx, const double *d_vals, double *d_B, int64_t ldb, int64_t nrhs);
+// the same against the kept factor of the sparse reduced system: the camera panel goes through sparse_solve_again
+void schur_sparse_solve_again(spp_ctx *ctx, const double *d_vals, double *d_B, int64_t ldb, int64_t nrhs);
 // E^T Lambda^-1 E of the selected vertices (block columns of Lambda), m x m, exactly symmetric, on whichever kept factor
 // `solve` works: solve(d_B, ldb, nrhs) is Lambda X = B in place on the ctx's stream. `who` names the entry point in the
 // error texts.
@@ -621,6 +630,15 @@ void sparse_solve_again(spp_ctx *ctx, double *d_B, int64_t ldb, int64_t nrhs);
 // the blocks of Lambda^-1 on the stored pattern of Lambda (the layout of vals) from the fronts the last sparse
 // factorization left in the plan
 void sparse_sigma(spp_ctx *ctx, double *d_sigma);
+// its two halves: the recursion down the assembly tree into the plan's second arena, and the gather of the stored blocks
+// of the factored matrix out of that arena into `dst` (the layout of that matrix's value array)
+void sparse_sigma_arena(spp_ctx *ctx);
+void sparse_sigma_gather(spp_ctx *ctx, double *dst);
+
+// ---- spp_schur_sparse_sigma.hip ----
+// the blocks of Lambda^-1 on the stored pattern of Lambda (the layout of vals) from the kept factor of the sparse reduced
+// system; inverse_only: the blocks of Z = S^-1 into the plan's workspace and stop (tools/schur_sparse_again_time.py)
+void schur_sparse_sigma(spp_ctx *ctx, const double *d_vals, double *d_sigma, bool inverse_only = false);
 
 // ---- spp_dense.hip ----
 constexpr int DENSE_NB = 128;

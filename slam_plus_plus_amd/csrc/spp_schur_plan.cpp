@@ -34,6 +34,7 @@ void SchurPlan::release_all()
 	W.release(); Up.release(); xw.release(); partial.release(); S.release();
 	pose_block.clear(); lm_block.clear(); is_lm.clear(); tile_mask.clear(); step_order.clear();
 	sigma_Z.release(); sigma_cc.release(); sigma_cc_host.clear(); sigma_ncc = -1;
+	sigma_Zb.release(); sigma_scol.release(); sigma_srow.release();
 }
 
 // Guided ordering is possible when there are exactly two block widths and the blocks of the

@@ -5,7 +5,8 @@
 // inverses in dense.tinv_all; Lambda's values are the caller's. With Lambda = [A U; U^T C] (cameras | landmarks):
 //     1  B_l <- C_l^-1 B_l                                       every landmark
 //     2  P_c <- B_c - sum_o U_o B_l(o)                            per camera, its observations in cam_obs order
-//     3  P   <- S^-1 P                                            dense_potrs_multi (spp_dense_trsm.h)
+//     3  P   <- S^-1 P                                            dense_potrs_multi (spp_dense_trsm.h); with a sparse reduced
+//                                                                 system sparse_solve_again on the kept fronts (section 34)
 //     4  B_l <- B_l - C_l^-1 sum_o U_o^T P_c(o)                   per landmark, its observers in lm_ptr order
 //     5  B_c <- P_c
 // in place on B (n x k in Lambda's row numbering), at most 128 columns per pass through the one camera panel P (ld x 128,
@@ -177,12 +178,13 @@ void sa_cam_scatter_kernel(int64_t nc, int kc, const int64_t *__restrict__ pose_
 	B[pose_rbase[e / DP] + e % DP + (int64_t)q * ldb] = P[e + (int64_t)q * ldp];
 }
 
-template <int DP, int DL>
-static void solve_again_t(spp_ctx *ctx, const double *d_vals, double *d_B, int64_t ldb, int64_t nrhs)
+// `reduced(P, ld, kc)` is step 3 on the camera panel (n_red rows in the plan's camera order, kc <= 128 columns, leading
+// dimension ld): dense_potrs_multi on the dense S, sparse_solve_again on the fronts of the sparse one.
+template <int DP, int DL, class Reduced>
+static void solve_again_t(spp_ctx *ctx, const double *d_vals, double *d_B, int64_t ldb, int64_t nrhs, int64_t ld, const Reduced &reduced)
 {
 	SchurPlan &sp = ctx->schur;
 	hipStream_t s = ctx->stream;
-	const int64_t ld = sp.ld;
 	SPP_REQUIRE(sp.n_red == sp.nc * DP, SPP_E_UNSUPPORTED, "solve on the kept factor: cameras of one width only");
 	ctx->again_panel.reserve((size_t)ld * DENSE_NB);
 	double *P = ctx->again_panel.p;
@@ -197,7 +199,7 @@ static void solve_again_t(spp_ctx *ctx, const double *d_vals, double *d_B, int64
 		if(sp.nc) {
 			hipLaunchKernelGGL((sa_cam_panel_kernel<DP, DL>), dim3((unsigned)((sp.nc + 3) / 4), qg), dim3(256), 0, s,
 				sp.nc, kc, sp.cam_ptr.p, sp.cam_obs.p, sp.obs_lm.p, sp.obs_off.p, sp.lm_rbase.p, sp.pose_rbase.p, d_vals, B, ldb, P, ld);
-			dense_potrs_multi(ctx, sp.S.p, sp.n_red, ld, P, ld, kc);
+			reduced(P, ld, kc);
 		}
 		if(sp.nl && sp.no)
 			hipLaunchKernelGGL((sa_lm_back_kernel<DP, DL>), dim3((unsigned)((sp.nl + 255) / 256), qg), dim3(256), 0, s,
@@ -209,13 +211,29 @@ static void solve_again_t(spp_ctx *ctx, const double *d_vals, double *d_B, int64
 	SPP_HIP_CHECK(hipGetLastError());
 }
 
-void schur_solve_again(spp_ctx *ctx, const double *d_vals, double *d_B, int64_t ldb, int64_t nrhs)
+template <class Reduced>
+static void solve_again_widths(spp_ctx *ctx, const double *d_vals, double *d_B, int64_t ldb, int64_t nrhs, int64_t ld, const Reduced &reduced)
 {
 	const int dp = ctx->schur.dp, dl = ctx->schur.dl;
-	if(dp == 6 && dl == 3) solve_again_t<6, 3>(ctx, d_vals, d_B, ldb, nrhs);
-	else if(dp == 3 && dl == 2) solve_again_t<3, 2>(ctx, d_vals, d_B, ldb, nrhs);
-	else if(dp == 7 && dl == 3) solve_again_t<7, 3>(ctx, d_vals, d_B, ldb, nrhs);
+	if(dp == 6 && dl == 3) solve_again_t<6, 3>(ctx, d_vals, d_B, ldb, nrhs, ld, reduced);
+	else if(dp == 3 && dl == 2) solve_again_t<3, 2>(ctx, d_vals, d_B, ldb, nrhs, ld, reduced);
+	else if(dp == 7 && dl == 3) solve_again_t<7, 3>(ctx, d_vals, d_B, ldb, nrhs, ld, reduced);
 	else throw Error(SPP_E_UNSUPPORTED, "solve on the kept factor: block widths not instantiated ({6,3}, {3,2}, {7,3})");
+}
+
+void schur_solve_again(spp_ctx *ctx, const double *d_vals, double *d_B, int64_t ldb, int64_t nrhs)
+{
+	SchurPlan &sp = ctx->schur;
+	solve_again_widths(ctx, d_vals, d_B, ldb, nrhs, sp.ld,
+		[&](double *P, int64_t ld, int kc) { dense_potrs_multi(ctx, sp.S.p, sp.n_red, ld, P, ld, kc); });
+}
+
+// The sparse reduced system: the panel's rows are the numbering of s_st, the matrix the sparse plan
+// was made from; sparse_solve_again applies that plan's own permutation inside. Its passes are as wide as this one's.
+void schur_sparse_solve_again(spp_ctx *ctx, const double *d_vals, double *d_B, int64_t ldb, int64_t nrhs)
+{
+	solve_again_widths(ctx, d_vals, d_B, ldb, nrhs, std::max<int64_t>(ctx->schur.n_red, 1),
+		[&](double *P, int64_t ld, int kc) { sparse_solve_again(ctx, P, ld, kc); });
 }
 
 // ---- covariances ---------------------------------------------------------------------------------------------------

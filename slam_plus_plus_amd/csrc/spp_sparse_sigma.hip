@@ -202,6 +202,13 @@ void sg_gather_kernel(const int64_t *__restrict__ front_off, const int32_t *__re
 
 void sparse_sigma(spp_ctx *ctx, double *d_sigma)
 {
+	sparse_sigma_arena(ctx);
+	sparse_sigma_gather(ctx, d_sigma);
+}
+
+// steps 1 - 3 down the assembly tree: Z_s of every front into the arena sigma_z
+void sparse_sigma_arena(spp_ctx *ctx)
+{
 	SparsePlan *sp = ctx->sparse;
 	SPP_REQUIRE(sp, SPP_E_STATE, "sparse plan missing");
 	hipStream_t s = ctx->stream;
@@ -264,9 +271,19 @@ void sparse_sigma(spp_ctx *ctx, double *d_sigma)
 			hipLaunchKernelGGL(sg_mirror_kernel<false>, dim3(n_hi, (unsigned)lv[4]), dim3(SG_NT), 0, s, d_hi, Z);
 		}
 	}
+	SPP_HIP_CHECK(hipGetLastError());
+}
+
+// the assembly map backwards, out of the arena sparse_sigma_arena filled: every stored block of the factored matrix has
+// one entry, so every double of dst (the layout of that matrix's value array) is written once
+void sparse_sigma_gather(spp_ctx *ctx, double *dst)
+{
+	SparsePlan *sp = ctx->sparse;
+	SPP_REQUIRE(sp && sp->sigma_z.p, SPP_E_STATE, "sparse plan or its arena of Z missing");
+	const int64_t ns = sp->n_snodes;
 	if(ns > 0)
-		hipLaunchKernelGGL(sg_gather_kernel, dim3((unsigned)ns), dim3(SG_NT), 0, s, sp->front_off.p, sp->front_w.p, sp->front_ld.p,
-			sp->front_pad.p, sp->asm_ptr.p, sp->asm_src.p, sp->asm_dst.p, sp->asm_shape.p, Z, d_sigma);
+		hipLaunchKernelGGL(sg_gather_kernel, dim3((unsigned)ns), dim3(SG_NT), 0, ctx->stream, sp->front_off.p, sp->front_w.p,
+			sp->front_ld.p, sp->front_pad.p, sp->asm_ptr.p, sp->asm_src.p, sp->asm_dst.p, sp->asm_shape.p, sp->sigma_z.p, dst);
 	SPP_HIP_CHECK(hipGetLastError());
 }
 
